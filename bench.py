@@ -6,6 +6,8 @@
       started plainly it re-launches itself as `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
       127.0.0.1 --master-port <free port> bench.py <same arguments>` and rank 0 prints the one JSON line.
   python bench.py --workload flight ...                 closed-loop flights (warm-started control periods), see flight_main()
+  python bench.py ... --full                            the default workload plus everything beyond its headline (below)
+  python bench.py ... --dump-outputs DIR                also writes what the last timed step returned, DIR/<name>.npy
 
 One "step" = one pass of the hot path over one batch of synthetic scenes resident in HBM: for every scene a fresh
 depth frame (build the obstacle + edge KD indices) and one control step (<= 3 outer passes of {dual KD queries, pack P,
@@ -18,14 +20,16 @@ amk_shard_gather).  The steps are kept in flight by the C ABI's amk_pipeline_* (
 is that host).  Every in-flight step owns its own frames (distinct clouds: the working set
 is `streams` x 169 MB, far beyond the 256 MiB Infinity Cache).
 
-Besides the contract's fields the JSON line carries
+A plain run sets up, warms up, times --steps steps and prints the contract's fields and the configuration.  With --full the
+JSON line of the default workload also carries what takes runs or checks of its own:
   parity      |u - u*|_inf and (J - J*)/J* of the GPU solve on the committed fixtures of the three BASELINE sizes
               (tests/golden/mpc_parity_golden.npz: converged optima, SURVEY.md section 8(d) gate) and the check of one
               in-flight slot's controls / flags of the timed workload against the CPU oracle (same scenes);
   roofline    SURVEY 8(d)'s ruler: frac = frac_hbm_8d = steps/s x algorithmic bytes per scene-step / 8 TB/s (the whole step), and beside
               it frac_valu_issue + dominant_kernel: what the dominant kernel (mpc_solve_kernel, a serial interior-point solve per
               wavefront, not HBM-bound) fills of the chip's VALU issue slots; roofline_hbm = that kernel's own bytes / launch duration;
-  roofline_kd_build   the HBM-bound kernel of the step.
+  roofline_kd_build   the HBM-bound kernel of the step;
+  cpu_baseline, kernels_single_stream, hbm_peak_measured_gbs, value_steady_state (when --steps < --steady-steps).
 """
 import argparse
 import ctypes as C
@@ -211,6 +215,27 @@ def fixture_parity(torch, precision):
     out["ok"] = bool(all(out[c]["converged"] == out[c]["scenes"] and out[c]["du_max"] <= 1e-3 and
                          out[c]["frac_x_within_1e-3"] >= 0.98 for c in ("C1", "C2", "C5")))
     return out
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, outputs):
+    """--dump-outputs: one step's results (dict of arrays with the scene as the leading axis) as DIR/<name>.npy in float64
+    (flags are small integers: exact).  Above DUMP_MAX_BYTES in all, a fixed seeded sample of scenes is written, and its
+    scene indices as scene_index.npy."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    out = {k: np.asarray(v, dtype=np.float64) for k, v in outputs.items()}
+    S = len(next(iter(out.values())))
+    per_scene = sum(a.nbytes for a in out.values()) // S
+    keep = min(S, (DUMP_MAX_BYTES - 8 * S) // per_scene)
+    if keep < S:
+        idx = np.sort(np.random.default_rng(0).choice(S, keep, replace=False))
+        out = {k: a[idx] for k, a in out.items()}
+        out["scene_index"] = idx.astype(np.float64)
+    for k, a in out.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(a))
 
 
 # ------------------------------------------------------------------------------------------------
@@ -520,7 +545,17 @@ def main():
     ap.add_argument("--dry-run", action="store_true",
                     help="launch path only (CPU, gloo): ranks rendezvous, partition the scenes, exchange a gather-shaped buffer and "
                          "rank 0 prints a JSON line without a value -- what tests/test_bench_launch.py runs without a GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="default workload: also measure and check what the headline does not need -- the HBM copy probe's figure, the "
+                         "per-kernel HIP-event timings in the timed region, the steady-state run (--steady-steps), single-launch "
+                         "kernel times, the roofline blocks, the fixture parity gate, the CPU baseline and the check of the timed "
+                         "scenes against the CPU oracle (--no-cpu-baseline / --no-parity leave those out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="default workload: after the timed steps, write what the last timed step returned to its caller (u, "
+                         "x0array, flags, ref_path of its S scenes) as DIR/<name>.npy, float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.dump_outputs and (args.workload != "cold" or args.dry_run):
+        ap.error("--dump-outputs: the default (cold) workload only")
     if args.config == "yaml":
         args.points, args.T, args.K = 3072, 1.0, 3
         if args.workload == "flight":
@@ -563,7 +598,9 @@ def main():
     dev = torch.device("cuda", local_rank)
     lib = capi.load()
     # SURVEY 8(d) / BASELINE.md 3: the achievable HBM rate beside the vendor peak, before the pipeline's buffers exist
-    hbm_measured = measured_hbm_peak(torch, lib) if rank == 0 and not args.dry_run else None
+    # Runs in a plain run too, unreported: it is also the device warm-up every headline of this benchmark was measured after
+    # (without it the timed region is 2.5 % slower, same box, 2000 steps)
+    hbm_measured = measured_hbm_peak(torch, lib) if rank == 0 else None
     collective = dist is not None   # the exchange step runs whenever a process group exists (RCCL also at world 1)
 
     prm = synth.MpcParams(T=args.T, K=args.K)
@@ -610,7 +647,8 @@ def main():
         if args.solve_budget is not None:
             pl.mpc(i).set_solve_budget(args.solve_budget, args.budget_rounds)
     slots = [Frames(i) for i in range(nframes)]
-    max_rows = max(args.steps, args.steady_steps if args.steps < args.steady_steps else 0, nframes, args.warmup, 64)
+    run_steady = args.full and args.steps < args.steady_steps   # the timed region is then mostly ramp-up / drain of the slots
+    max_rows = max(args.steps, args.steady_steps if run_steady else 0, nframes, args.warmup, 64)
     u_sweep = torch.zeros((max_rows, S, 4), dtype=torch.float64, device=dev)   # the sweep's controls, one row per step
     sh = None
     rccl_info = None
@@ -685,8 +723,9 @@ def main():
 
     def timed(steps):
         t0 = time.perf_counter()
+        ticket = None
         for j in range(steps):
-            one_step(j)
+            ticket = one_step(j)
         t_enq = time.perf_counter() - t0   # host time in submit(): enqueue + back-pressure waits on busy slots
         if diag_streams is None:
             pl.drain()
@@ -704,7 +743,7 @@ def main():
         barrier()
         t_all = time.perf_counter() - t0
         phases["submit_s"], phases["drain_s"], phases["gather_s"], phases["barrier_s"] = t_enq, t_drain - t_enq, t_gather - t_drain, t_all - t_gather
-        return t_all, t_enq
+        return t_all, t_enq, ticket
 
     gather_bufs = {}
     phases = {}
@@ -731,22 +770,28 @@ def main():
     for j in range(args.warmup):
         one_step(j)
     barrier()
-    for k_ in (args.steps, args.steady_steps):   # the gather's receive buffers exist before the clock starts
+    for k_ in (args.steps, args.steady_steps) if run_steady else (args.steps,):   # the gather's receive buffers exist before the clock starts
         if collective:
             u_gather(k_)
-    lib.amk__timing_enable(1)              # HIP events around the solve and build kernels, on their launch stream
-    dt, t_enq = timed(args.steps)
+    if args.full:
+        lib.amk__timing_enable(1)          # HIP events around the solve and build kernels, on their launch stream
+    dt, t_enq, last_ticket = timed(args.steps)
     timed_phases = {k: round(v, 5) for k, v in phases.items()}
-    ms = (C.c_double * 8)(); cnt = (C.c_int * 8)()
-    capi.check(lib.amk__timing_collect(ms, cnt), "timing")
-    lib.amk__timing_enable(0)
+    if args.full:
+        ms = (C.c_double * 8)(); cnt = (C.c_int * 8)()
+        capi.check(lib.amk__timing_collect(ms, cnt), "timing")
+        lib.amk__timing_enable(0)
+    if args.dump_outputs and rank == 0:   # before anything else runs on the last step's slot
+        if last_ticket is None:
+            sys.exit("bench.py: --dump-outputs needs the pipeline's outputs (not with AMK_BENCH_SKIP=build|step)")
+        dump_outputs(args.dump_outputs, pl.outputs(last_ticket))
     dt = max_over_ranks(dt)
 
     flags = np.concatenate([pl.outputs(t)["flags"] for t in range(nframes)]) if diag_streams is None else np.zeros((1, 4), np.int32)
     solves = float(flags[:, 1].mean()); ipm_iters = float(flags[:, 3].mean())
     steady = None
-    if args.steps < args.steady_steps:     # the timed region above is mostly ramp-up / drain of the in-flight slots
-        dts, _ = timed(args.steady_steps)
+    if run_steady:
+        dts, _, _ = timed(args.steady_steps)
         dts = max_over_ranks(dts)
         steady = S * world * args.steady_steps / dts
     # The kernels' OWN durations: a pass with ONE step on the chip at a time (submit, wait, submit, ...), every kernel class
@@ -756,7 +801,7 @@ def main():
     # other launches in flight occupy, which is why that figure is reported separately as in_flight_submit_to_complete_ms.
     lone = None
     ticket_of_frames0 = None
-    if rank == 0 and diag_streams is None:
+    if rank == 0 and args.full and diag_streams is None:
         lib.amk__timing_enable(2)
         reps = 6   # always the frames of in-flight slot 0 = the scenes of `bench.py --streams 1` (the committed rocprof trace)
         for j in range(reps):   # one LAUNCH at a time: the `gang` steps that share it (frames 0 .. gang-1), then wait
@@ -772,7 +817,7 @@ def main():
         lone = {KCLASS[i]: {"avg_launch_us": round(1e3 * ms1[i] / cnt1[i], 2), "launches_per_step": cnt1[i] / (reps * gang)}
                 for i in range(8) if cnt1[i] and KCLASS[i]}
     chk = None   # frame set 0's controls and flags for the CPU check, taken before anything else runs on that slot
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and diag_streams is None:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and diag_streams is None:
         if ticket_of_frames0 is None:   # (no single-launch pass ran: run frame set 0 once more)
             ticket_of_frames0 = one_step(0, frames=0)
         pl.wait(ticket_of_frames0)
@@ -792,7 +837,7 @@ def main():
                      for i in range(8) if cnt2[i]}
 
     parity, cpu = None, None
-    if rank == 0 and not args.no_parity:
+    if rank == 0 and args.full and not args.no_parity:
         parity = {"fixtures": fixture_parity(torch, args.precision)}
     if chk is not None:
         sl = slots[0]
@@ -805,59 +850,6 @@ def main():
     if rank == 0:
         total_scenes = S * world * args.steps
         value = total_scenes / dt
-        step_bytes = alg_bytes_per_step(n, ne, N, prm.K)
-        alg_launch = solve_alg_bytes(N, prm.K) * S * gang
-        build_alg = 28 * S * gang * (n + ne)            # 12 B read + 16 B written per point; ONE launch builds the obstacle and the edge index (amk_kd_build_pair)
-        inflight_solve_ms = ms[5] / max(cnt[5], 1)
-        inflight_build_ms = ms[7] / max(cnt[7], 1)
-        solve_us = lone["mpc_solve_kernel"]["avg_launch_us"] if lone else None
-        build_us = lone["kd_build_kernel"]["avg_launch_us"] if lone else None
-        prof = {}
-        for key, fname in (("traffic", "pmc_traffic"), ("issue", "pmc_solve_issue"), ("kt1", "kernel_stats_streams1"),
-                           ("kt20", "kernel_stats")):
-            fpath = os.path.join(ROOT, "profiles", f"{PROFILE_TAG}_{fname}.json")
-            if os.path.exists(fpath):
-                prof[key] = json.load(open(fpath))
-        traffic = build_traffic = traffic_src = None
-        tj = prof.get("traffic")
-        if tj:   # PMC passes cannot run inside this process: reuse the committed rocprofv3 result of the same command
-            m = tj.get("_meta", {})
-            if (m.get("scenes_per_gpu"), m.get("gang", 1), m.get("points"), m.get("horizon"), m.get("K")) == (S, gang, n, N, prm.K):
-                kk = tj["kernels"].get(f"mpc_solve_kernel<{N}>"); kb = tj["kernels"].get("kd_build_kernel")
-                traffic = round(kk["hbm_bytes_per_launch_x2"]) if kk else None
-                build_traffic = round(kb["hbm_bytes_per_launch_x2"]) if kb else None
-                traffic_src = f"profiles/{PROFILE_TAG}_pmc_traffic.json (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE, KiB, separate passes)"
-
-        def rocprof_us(which, kernel):
-            k = (prof.get(which) or {}).get("kernels", {}).get(kernel)
-            return k["avg_us"] if k else None
-        # what bounds the dominant kernel (SQ counters of the committed profile): VALU issue slots.  Live part: how many
-        # solves the timed region ran per second; committed part: VALU instructions per wave-solve (a property of the
-        # kernel on this workload, profiles/r04_pmc_solve_issue.json), 4 issue cycles each on one of 1024 SIMDs.
-        issue = prof.get("issue")
-        valu_per_solve = issue["valu_instructions_per_wave_solve"] if issue else None
-        solves_per_s = value * solves
-        # issue cycles one VALU instruction of this kernel holds a SIMD for, MEASURED (SQ_ACTIVE_INST_VALU / SQ_INSTS_VALU of the
-        # committed profile: 4.27, the fp64 share of the mix; a wave64 fp32 instruction would be 4 on paper, an fp64 FMA 4+)
-        valu_cpi = (issue["frac_of_wave_time_issuing_valu"] * issue["wave_cycles_per_wave"] / valu_per_solve) if valu_per_solve else None
-        valu_frac_timed = (solves_per_s * valu_per_solve * valu_cpi / (N_CU * N_SIMD * CLOCK_GHZ * 1e9)) if valu_per_solve else None
-        hbm_8d_gbs = value / max(world, 1) * step_bytes / 1e9      # per GPU: SURVEY 8(d)'s bytes per scene-step x this GPU's steps/s
-        hbm = lambda nbytes, us: None if not us else round(nbytes / (us * 1e-6) / 1e9, 2)
-        frac = lambda gbs: None if gbs is None else round(gbs / HBM_PEAK_GBS, 6)
-        fracm = lambda gbs: None if gbs is None or not hbm_measured else round(gbs / hbm_measured, 6)   # against the measured copy rate
-        roof_solve_hbm = {
-            "bound": "hbm", "kernel": f"mpc_solve_kernel<{N}>", "alg_bytes_per_launch": alg_launch,
-            "avg_launch_us": solve_us, "achieved": hbm(alg_launch, solve_us), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": frac(hbm(alg_launch, solve_us)), "frac_of_measured_copy": fracm(hbm(alg_launch, solve_us)),
-            "traffic": traffic, "traffic_source": traffic_src,
-            "rocprof_avg_us_same_command": rocprof_us("kt1", f"mpc_solve_kernel<{N}>"),
-            "in_flight_submit_to_complete_ms": round(inflight_solve_ms, 4), "in_flight_launches": cnt[5],
-            "in_flight_rocprof_avg_us": rocprof_us("kt20", f"mpc_solve_kernel<{N}>"),
-            "note": "HBM view of the dominant kernel, kept because the contract asks for bytes / launch duration: the kernel "
-                    "moves 4 MB per launch and is nowhere near this roofline by construction (a serial interior-point solve "
-                    "per wavefront).  avg_launch_us: HIP events on the launch stream with one step on the chip at a time "
-                    "(= rocprofv3's kernel duration of `bench.py --streams 1`, profiles/); in_flight_*: the same events in "
-                    "the timed region, where they also contain the wait for CUs held by the other steps in flight"}
         line = {
             "metric": f"MPC steps/sec ({n // 1000}k-pt cloud, N={N}, {prm.K} obstacle constraints)",
             "value": round(value, 1), "unit": "MPC steps/s", "n_gpus": world, "steps": args.steps,
@@ -867,8 +859,6 @@ def main():
                                                    "step cross PCIe from pinned host memory inside the timed region"}
                if args.inputs == "host" else {}),
             "scaling": "weak", "vs_baseline": None, "dtype": "f64" if args.precision == 64 else "f32", "data": "synthetic",
-            "value_steady_state": round(steady, 1) if steady else None,
-            "value_steady_state_steps": args.steady_steps if steady else None,
             "config": {"workload": f"BASELINE configs[1] batched as configs[2]: {S} scenes/GPU x ({n}-pt obstacle "
                                    f"cloud + {ne}-pt edge cloud, N={N}, K={prm.K}), fresh frame + zero warm start "
                                    f"every step, every in-flight step on its own frames", "scenes_per_gpu": S, "points": n,
@@ -889,72 +879,130 @@ def main():
                        "rccl": rccl_info if collective else "no process group (single GPU, plain run): RCCL not used",
                        "multi_gpu_measured": "no N > 1 line has been measured by this project (no multi-GPU node was available to it "
                                              "in any round); per-rank files: gpurun_out/bench_ranks/"},
-            "roofline": {"bound": "hbm",
-                         "what": "SURVEY 8(d)'s ruler for the WHOLE step: algorithmic bytes per scene-step (every input read once, every "
-                                 "output written once) x steps/s of this GPU, against the vendor's HBM peak.  The path is not HBM-bound: its "
-                                 "dominant kernel is a serial interior-point solve per wavefront (frac_valu_issue, dominant_kernel below)",
-                         "alg_bytes_per_scene_step": step_bytes,
-                         "achieved": round(hbm_8d_gbs, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(hbm_8d_gbs / HBM_PEAK_GBS, 5), "frac_hbm_8d": round(hbm_8d_gbs / HBM_PEAK_GBS, 5),
-                         "frac_of_measured_copy": fracm(hbm_8d_gbs),
-                         "frac_valu_issue": None if valu_frac_timed is None else round(valu_frac_timed, 4),
-                         "valu_issue_cycles_per_instruction_measured": None if valu_cpi is None else round(valu_cpi, 3),
-                         "kernel": f"mpc_solve_kernel<{N}>",
-                         "traffic": traffic,
-                         "dominant_kernel": {
-                             "kernel": f"mpc_solve_kernel<{N}>", "bound": "valu-issue / dependent fp64 + LDS latency at 2 waves per SIMD (neither HBM nor MFMA)",
-                             "hbm_alg_bytes_per_launch": alg_launch, "avg_launch_us": solve_us,
-                             "hbm_achieved_gbs": hbm(alg_launch, solve_us), "hbm_frac": frac(hbm(alg_launch, solve_us)),
-                             "hbm_traffic_per_launch": traffic,
-                             "valu_issue_achieved_gcycles_per_s": None if valu_frac_timed is None else round(valu_frac_timed * N_CU * N_SIMD * CLOCK_GHZ, 1),
-                             "valu_issue_peak_gcycles_per_s": round(N_CU * N_SIMD * CLOCK_GHZ, 1),
-                             "frac_valu_issue": None if valu_frac_timed is None else round(valu_frac_timed, 4),
-                             "frac_valu_issue_at_saturation_solves_only": issue.get("valu_issue_util_at_saturation") if issue else None,
-                             "lds_array_frac_at_saturation": issue.get("lds_array_util_at_saturation (conflict level of the lone wave)") if issue else None,
-                             "valu_instructions_per_wave_solve": valu_per_solve, "solves_per_s_timed_region": round(solves_per_s, 1)},
-                         "note": "frac = frac_hbm_8d = steps/s x alg_bytes_per_scene_step / 8 TB/s.  frac_valu_issue = (solves/s of the timed "
-                                 "region) x (VALU instructions per wave-solve, SQ_INSTS_VALU of the committed profile) x (measured issue cycles "
-                                 "per VALU instruction, SQ_ACTIVE_INST_VALU / SQ_INSTS_VALU) / (1024 SIMDs x 2.4 GHz): the share of the chip's "
-                                 "VALU issue slots the dominant kernel fills while the builds and searches of the other steps share the CUs; "
-                                 "frac_valu_issue_at_saturation_solves_only is the same quantity with nothing but solves resident "
-                                 "(tools/experiments/ms_parts.py).  What stops it below 1: two waves per SIMD (180 VGPRs and 17.8 KB of LDS per scene; a third wave was measured to buy nothing, DESIGN 5: "
-                                 "per scene) cannot cover ~32-cycle dependent fp64 issue and LDS round trips "
-                                 f"(profiles/{PROFILE_TAG}_pmc_solve_issue.md, DESIGN.md section 5)"},
-            "roofline_hbm": roof_solve_hbm,
-            "roofline_solve_issue": issue,
-            "roofline_kd_build": {"bound": "hbm", "kernel": "kd_build_kernel (one launch: obstacle + edge index of every scene)",
-                                  "alg_bytes_per_launch": build_alg, "avg_launch_us": build_us,
-                                  "achieved": hbm(build_alg, build_us), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                  "frac": frac(hbm(build_alg, build_us)), "frac_of_measured_copy": fracm(hbm(build_alg, build_us)),
-                                  "traffic": build_traffic,
-                                  "alg_bytes_per_launch_survey_8d": 12 * S * gang * (n + ne),
-                                  "frac_survey_8d": frac(hbm(12 * S * gang * (n + ne), build_us)),
-                                  "frac_survey_8d_of_measured_copy": fracm(hbm(12 * S * gang * (n + ne), build_us)),
-                                  "rocprof_avg_us_same_command": rocprof_us("kt1", "kd_build_kernel"),
-                                  "in_flight_submit_to_complete_ms": round(inflight_build_ms, 4), "in_flight_launches": cnt[7],
-                                  "in_flight_rocprof_avg_us": rocprof_us("kt20", "kd_build_kernel"),
-                                  "note": "the HBM-heavy kernel: 28 B per point (12 read, 16 written as an (x, y, z, index) bucket "
-                                          "record), both trees of a frame in one launch (grid.y = tree); avg_launch_us with one step "
-                                          "on the chip at a time.  frac_survey_8d is the same duration against SURVEY 8(d)'s own accounting "
-                                          "(inputs read once: 12 B per point; the survey's K1 budgeted a 4-byte permutation, 16 B per point): "
-                                          "the 16-byte record is this design's choice -- it makes every search a run of contiguous records "
-                                          "instead of a gather through a permutation (DESIGN.md section 4)"},
-            "roofline_whole_step": {"alg_bytes_per_scene_step": step_bytes,
-                                    "achieved": round(value * step_bytes / 1e9, 2), "unit": "GB/s",
-                                    "frac": round(value * step_bytes / 1e9 / HBM_PEAK_GBS, 5),
-                                    "frac_of_measured_copy": fracm(value * step_bytes / 1e9)},
-            "hbm_peak_vendor_gbs": HBM_PEAK_GBS,
-            "hbm_peak_measured_gbs": None if not hbm_measured else round(hbm_measured, 1),
-            "hbm_peak_measured_how": "float4 device copy of 1 GiB (amk__hbm_copy_probe, csrc/probe.hip): bytes read + bytes written "
-                                     "over the copy's duration, best of 20 launch shapes -- 18 persistent ones (2 / 4 / 8 loads in flight per "
-                                     "thread, plain / non-temporal, 8 / 16 / 32 blocks per CU) and one 16-byte element per thread on a grid as large "
-                                     "as the data, plain / non-temporal stores (the shape that reaches the guide's 6.29 TB/s: "
-                                     f"profiles/r06_hbm_probe_shapes.txt) -- 10 repetitions each, HIP events; every HBM fraction of "
-                                     "this line is given against the vendor peak (frac) and against this figure (frac_of_measured_copy)",
-            "kernels_single_stream": lone,
-            "parity": parity,
-            "cpu_baseline": cpu,
         }
+        if args.full:
+            step_bytes = alg_bytes_per_step(n, ne, N, prm.K)
+            alg_launch = solve_alg_bytes(N, prm.K) * S * gang
+            build_alg = 28 * S * gang * (n + ne)            # 12 B read + 16 B written per point; ONE launch builds the obstacle and the edge index (amk_kd_build_pair)
+            inflight_solve_ms = ms[5] / max(cnt[5], 1)
+            inflight_build_ms = ms[7] / max(cnt[7], 1)
+            solve_us = lone["mpc_solve_kernel"]["avg_launch_us"] if lone else None
+            build_us = lone["kd_build_kernel"]["avg_launch_us"] if lone else None
+            prof = {}
+            for key, fname in (("traffic", "pmc_traffic"), ("issue", "pmc_solve_issue"), ("kt1", "kernel_stats_streams1"),
+                               ("kt20", "kernel_stats")):
+                fpath = os.path.join(ROOT, "profiles", f"{PROFILE_TAG}_{fname}.json")
+                if os.path.exists(fpath):
+                    prof[key] = json.load(open(fpath))
+            traffic = build_traffic = traffic_src = None
+            tj = prof.get("traffic")
+            if tj:   # PMC passes cannot run inside this process: reuse the committed rocprofv3 result of the same command
+                m = tj.get("_meta", {})
+                if (m.get("scenes_per_gpu"), m.get("gang", 1), m.get("points"), m.get("horizon"), m.get("K")) == (S, gang, n, N, prm.K):
+                    kk = tj["kernels"].get(f"mpc_solve_kernel<{N}>"); kb = tj["kernels"].get("kd_build_kernel")
+                    traffic = round(kk["hbm_bytes_per_launch_x2"]) if kk else None
+                    build_traffic = round(kb["hbm_bytes_per_launch_x2"]) if kb else None
+                    traffic_src = f"profiles/{PROFILE_TAG}_pmc_traffic.json (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE, KiB, separate passes)"
+
+            def rocprof_us(which, kernel):
+                k = (prof.get(which) or {}).get("kernels", {}).get(kernel)
+                return k["avg_us"] if k else None
+            # what bounds the dominant kernel (SQ counters of the committed profile): VALU issue slots.  Live part: how many
+            # solves the timed region ran per second; committed part: VALU instructions per wave-solve (a property of the
+            # kernel on this workload, profiles/r04_pmc_solve_issue.json), 4 issue cycles each on one of 1024 SIMDs.
+            issue = prof.get("issue")
+            valu_per_solve = issue["valu_instructions_per_wave_solve"] if issue else None
+            solves_per_s = value * solves
+            # issue cycles one VALU instruction of this kernel holds a SIMD for, MEASURED (SQ_ACTIVE_INST_VALU / SQ_INSTS_VALU of the
+            # committed profile: 4.27, the fp64 share of the mix; a wave64 fp32 instruction would be 4 on paper, an fp64 FMA 4+)
+            valu_cpi = (issue["frac_of_wave_time_issuing_valu"] * issue["wave_cycles_per_wave"] / valu_per_solve) if valu_per_solve else None
+            valu_frac_timed = (solves_per_s * valu_per_solve * valu_cpi / (N_CU * N_SIMD * CLOCK_GHZ * 1e9)) if valu_per_solve else None
+            hbm_8d_gbs = value / max(world, 1) * step_bytes / 1e9      # per GPU: SURVEY 8(d)'s bytes per scene-step x this GPU's steps/s
+            hbm = lambda nbytes, us: None if not us else round(nbytes / (us * 1e-6) / 1e9, 2)
+            frac = lambda gbs: None if gbs is None else round(gbs / HBM_PEAK_GBS, 6)
+            fracm = lambda gbs: None if gbs is None or not hbm_measured else round(gbs / hbm_measured, 6)   # against the measured copy rate
+            roof_solve_hbm = {
+                "bound": "hbm", "kernel": f"mpc_solve_kernel<{N}>", "alg_bytes_per_launch": alg_launch,
+                "avg_launch_us": solve_us, "achieved": hbm(alg_launch, solve_us), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": frac(hbm(alg_launch, solve_us)), "frac_of_measured_copy": fracm(hbm(alg_launch, solve_us)),
+                "traffic": traffic, "traffic_source": traffic_src,
+                "rocprof_avg_us_same_command": rocprof_us("kt1", f"mpc_solve_kernel<{N}>"),
+                "in_flight_submit_to_complete_ms": round(inflight_solve_ms, 4), "in_flight_launches": cnt[5],
+                "in_flight_rocprof_avg_us": rocprof_us("kt20", f"mpc_solve_kernel<{N}>"),
+                "note": "HBM view of the dominant kernel, kept because the contract asks for bytes / launch duration: the kernel "
+                        "moves 4 MB per launch and is nowhere near this roofline by construction (a serial interior-point solve "
+                        "per wavefront).  avg_launch_us: HIP events on the launch stream with one step on the chip at a time "
+                        "(= rocprofv3's kernel duration of `bench.py --streams 1`, profiles/); in_flight_*: the same events in "
+                        "the timed region, where they also contain the wait for CUs held by the other steps in flight"}
+            line.update({
+                "value_steady_state": round(steady, 1) if steady else None,
+                "value_steady_state_steps": args.steady_steps if steady else None,
+                "roofline": {"bound": "hbm",
+                             "what": "SURVEY 8(d)'s ruler for the WHOLE step: algorithmic bytes per scene-step (every input read once, every "
+                                     "output written once) x steps/s of this GPU, against the vendor's HBM peak.  The path is not HBM-bound: its "
+                                     "dominant kernel is a serial interior-point solve per wavefront (frac_valu_issue, dominant_kernel below)",
+                             "alg_bytes_per_scene_step": step_bytes,
+                             "achieved": round(hbm_8d_gbs, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                             "frac": round(hbm_8d_gbs / HBM_PEAK_GBS, 5), "frac_hbm_8d": round(hbm_8d_gbs / HBM_PEAK_GBS, 5),
+                             "frac_of_measured_copy": fracm(hbm_8d_gbs),
+                             "frac_valu_issue": None if valu_frac_timed is None else round(valu_frac_timed, 4),
+                             "valu_issue_cycles_per_instruction_measured": None if valu_cpi is None else round(valu_cpi, 3),
+                             "kernel": f"mpc_solve_kernel<{N}>",
+                             "traffic": traffic,
+                             "dominant_kernel": {
+                                 "kernel": f"mpc_solve_kernel<{N}>", "bound": "valu-issue / dependent fp64 + LDS latency at 2 waves per SIMD (neither HBM nor MFMA)",
+                                 "hbm_alg_bytes_per_launch": alg_launch, "avg_launch_us": solve_us,
+                                 "hbm_achieved_gbs": hbm(alg_launch, solve_us), "hbm_frac": frac(hbm(alg_launch, solve_us)),
+                                 "hbm_traffic_per_launch": traffic,
+                                 "valu_issue_achieved_gcycles_per_s": None if valu_frac_timed is None else round(valu_frac_timed * N_CU * N_SIMD * CLOCK_GHZ, 1),
+                                 "valu_issue_peak_gcycles_per_s": round(N_CU * N_SIMD * CLOCK_GHZ, 1),
+                                 "frac_valu_issue": None if valu_frac_timed is None else round(valu_frac_timed, 4),
+                                 "frac_valu_issue_at_saturation_solves_only": issue.get("valu_issue_util_at_saturation") if issue else None,
+                                 "lds_array_frac_at_saturation": issue.get("lds_array_util_at_saturation (conflict level of the lone wave)") if issue else None,
+                                 "valu_instructions_per_wave_solve": valu_per_solve, "solves_per_s_timed_region": round(solves_per_s, 1)},
+                             "note": "frac = frac_hbm_8d = steps/s x alg_bytes_per_scene_step / 8 TB/s.  frac_valu_issue = (solves/s of the timed "
+                                     "region) x (VALU instructions per wave-solve, SQ_INSTS_VALU of the committed profile) x (measured issue cycles "
+                                     "per VALU instruction, SQ_ACTIVE_INST_VALU / SQ_INSTS_VALU) / (1024 SIMDs x 2.4 GHz): the share of the chip's "
+                                     "VALU issue slots the dominant kernel fills while the builds and searches of the other steps share the CUs; "
+                                     "frac_valu_issue_at_saturation_solves_only is the same quantity with nothing but solves resident "
+                                     "(tools/experiments/ms_parts.py).  What stops it below 1: two waves per SIMD (180 VGPRs and 17.8 KB of LDS per scene; a third wave was measured to buy nothing, DESIGN 5: "
+                                     "per scene) cannot cover ~32-cycle dependent fp64 issue and LDS round trips "
+                                     f"(profiles/{PROFILE_TAG}_pmc_solve_issue.md, DESIGN.md section 5)"},
+                "roofline_hbm": roof_solve_hbm,
+                "roofline_solve_issue": issue,
+                "roofline_kd_build": {"bound": "hbm", "kernel": "kd_build_kernel (one launch: obstacle + edge index of every scene)",
+                                      "alg_bytes_per_launch": build_alg, "avg_launch_us": build_us,
+                                      "achieved": hbm(build_alg, build_us), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                      "frac": frac(hbm(build_alg, build_us)), "frac_of_measured_copy": fracm(hbm(build_alg, build_us)),
+                                      "traffic": build_traffic,
+                                      "alg_bytes_per_launch_survey_8d": 12 * S * gang * (n + ne),
+                                      "frac_survey_8d": frac(hbm(12 * S * gang * (n + ne), build_us)),
+                                      "frac_survey_8d_of_measured_copy": fracm(hbm(12 * S * gang * (n + ne), build_us)),
+                                      "rocprof_avg_us_same_command": rocprof_us("kt1", "kd_build_kernel"),
+                                      "in_flight_submit_to_complete_ms": round(inflight_build_ms, 4), "in_flight_launches": cnt[7],
+                                      "in_flight_rocprof_avg_us": rocprof_us("kt20", "kd_build_kernel"),
+                                      "note": "the HBM-heavy kernel: 28 B per point (12 read, 16 written as an (x, y, z, index) bucket "
+                                              "record), both trees of a frame in one launch (grid.y = tree); avg_launch_us with one step "
+                                              "on the chip at a time.  frac_survey_8d is the same duration against SURVEY 8(d)'s own accounting "
+                                              "(inputs read once: 12 B per point; the survey's K1 budgeted a 4-byte permutation, 16 B per point): "
+                                              "the 16-byte record is this design's choice -- it makes every search a run of contiguous records "
+                                              "instead of a gather through a permutation (DESIGN.md section 4)"},
+                "roofline_whole_step": {"alg_bytes_per_scene_step": step_bytes,
+                                        "achieved": round(value * step_bytes / 1e9, 2), "unit": "GB/s",
+                                        "frac": round(value * step_bytes / 1e9 / HBM_PEAK_GBS, 5),
+                                        "frac_of_measured_copy": fracm(value * step_bytes / 1e9)},
+                "hbm_peak_vendor_gbs": HBM_PEAK_GBS,
+                "hbm_peak_measured_gbs": None if not hbm_measured else round(hbm_measured, 1),
+                "hbm_peak_measured_how": "float4 device copy of 1 GiB (amk__hbm_copy_probe, csrc/probe.hip): bytes read + bytes written "
+                                         "over the copy's duration, best of 20 launch shapes -- 18 persistent ones (2 / 4 / 8 loads in flight per "
+                                         "thread, plain / non-temporal, 8 / 16 / 32 blocks per CU) and one 16-byte element per thread on a grid as large "
+                                         "as the data, plain / non-temporal stores (the shape that reaches 6.29 TB/s: "
+                                         f"profiles/r06_hbm_probe_shapes.txt) -- 10 repetitions each, HIP events; every HBM fraction of "
+                                         "this line is given against the vendor peak (frac) and against this figure (frac_of_measured_copy)",
+                "kernels_single_stream": lone,
+                "parity": parity,
+                "cpu_baseline": cpu,
+            })
         if breakdown:
             line["kernel_breakdown"] = breakdown
         print(json.dumps(line), flush=True)

@@ -127,6 +127,49 @@ def load_ref(strict=True):
     return lib
 
 
+class RefAnswers:
+    """The reference's own answers for one cloud, as tests/golden/make_kd_ref_golden.py stored them from oracle/_ref: size(),
+    search() and search_raw() with KdHandle's results, for the stored queries only.  The tests compare against these, so
+    they need the reference only to make the file, not to run."""
+
+    def __init__(self, G, prefix, xyz):
+        self.G, self.p = G, prefix
+        self.q = G[prefix + ".queries"]
+        assert np.array_equal(np.nansum(np.asarray(xyz, np.float64), axis=0), G[prefix + ".cloud_sum"]), \
+            f"{prefix}: the cloud differs from the one the answers were stored for"
+
+    def size(self):
+        return int(self.G[self.p + ".size"])
+
+    def _row(self, q):
+        hit = np.flatnonzero((self.q == np.asarray(q, np.float64)).all(axis=1))
+        assert len(hit), f"{self.p}: no stored answer for the query {q}"
+        return hit[0]
+
+    def _answer(self, q, n, kind):
+        i, key = self._row(q), f"{self.p}.n{n}.{kind}"
+        c = self.G[key + ".cnt"][i]
+        pts = self.G[key + ".pts"][i, :c] if key + ".pts" in self.G.files else None
+        return self.G[key + ".idx"][i, :c], self.G[key + ".d2"][i, :c], pts
+
+    def search(self, q, n):
+        return self._answer(q, n, "search")
+
+    def search_raw(self, q, n):
+        return self._answer(q, n, "raw")[:2]
+
+
+REF_GOLDEN = os.path.join(ROOT, "tests", "golden", "kd_ref_golden.npz")
+_REF_G = None
+
+
+def ref_answers(prefix, xyz):
+    global _REF_G
+    if _REF_G is None:
+        _REF_G = np.load(REF_GOLDEN)
+    return RefAnswers(_REF_G, prefix, xyz)
+
+
 def kd_oracle(xyz, stride=None):
     return KdHandle(load_oracle(), "kdo", xyz, stride)
 

@@ -18,12 +18,3 @@ def oracle():
     from tests import _oracle
     return _oracle.load_oracle()
 
-
-@pytest.fixture(scope="session")
-def ref_kd():
-    """oracle/_ref: the reference's nanoflann header compiled in place (strict-IEEE build)."""
-    from tests import _oracle
-    lib = _oracle.load_ref(strict=True)
-    if lib is None:
-        pytest.skip("oracle/_ref not built (needs /root/reference at build time)")
-    return lib

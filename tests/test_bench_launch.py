@@ -64,3 +64,24 @@ def test_under_a_launcher_the_world_size_wins(tmp_path):
     out = json.loads(lines[0])
     assert out["n_gpus"] == 3 and out["gather_ok"] and out["padded_scenes_per_rank"] == 7
     _check_rccl_block_and_rank_files(out, str(tmp_path), 3)
+
+
+def test_dump_outputs_keeps_a_seeded_sample_within_the_byte_budget(tmp_path, monkeypatch):
+    """--dump-outputs above its byte budget: the same seeded sample of scenes (and their indices) on every call, all float64."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(3)
+    outputs = {"u": rng.standard_normal((1000, 4)), "flags": rng.integers(0, 9, (1000, 4)).astype(np.int32)}
+    bench.dump_outputs(str(tmp_path / "all"), outputs)
+    assert np.array_equal(np.load(tmp_path / "all" / "flags.npy"), outputs["flags"])
+    assert not (tmp_path / "all" / "scene_index.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 20000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), outputs)
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("u", "flags", "scene_index")}
+    assert sum(a.nbytes for a in got.values()) <= 20000 and all(a.dtype == np.float64 for a in got.values())
+    idx = got["scene_index"].astype(int)
+    assert len(idx) == len(got["u"]) > 100 and np.all(np.diff(idx) > 0)
+    assert np.array_equal(got["u"], outputs["u"][idx]) and np.array_equal(got["flags"], outputs["flags"][idx])
+    for n in got:
+        assert np.array_equal(got[n], np.load(tmp_path / "b" / f"{n}.npy"))

@@ -331,17 +331,9 @@ def test_tie_flags_mark_every_query_whose_indices_may_differ_from_nanoflann(torc
             kd.close()
 
 
-def test_nanoflann_tie_order_mode(torch_cuda, oracle):
-    """amk_kd_set_tie_order(AMK_TIES_NANOFLANN): the handle builds the reference's own tree on the device and answers by
-    nanoflann's own traversal -- index lists (not only distances) identical to the reference on tie-heavy clouds:
-    integer lattice, triplicated points, a quantised two-wall depth lattice, a planar cloud, plus random / tiny / NaN-x
-    clouds; node counts equal the oracle's tree (the oracle is pinned to the reference header, tests/test_kd_oracle.py,
-    and the reference itself is consulted directly when oracle/_ref is present)."""
-    import ctypes as C
-    torch = torch_cuda
-    from avoid_mpc_amd import capi
-    from avoid_mpc_amd.host import KdBatch
-    lib = capi.load()
+def _tie_order_cases():
+    """-> [(name, cloud, queries)] of test_nanoflann_tie_order_mode (tests/golden/make_kd_ref_golden.py stores the reference's
+    answers to the same queries)."""
     rng = np.random.default_rng(8)
     g = np.stack(np.meshgrid(np.arange(10), np.arange(10), np.arange(10), indexing="ij"), -1).reshape(-1, 3).astype(np.float32)
     u, v = np.meshgrid(np.arange(64), np.arange(48))
@@ -358,16 +350,33 @@ def test_nanoflann_tie_order_mode(torch_cuda, oracle):
     clouds = dict(grid=g, lattice=lattice, dup=dup, planar=planar, random=rng.uniform(-5, 5, (5000, 3)).astype(np.float32),
                   tiny=rng.uniform(-1, 1, (7, 3)).astype(np.float32), nanx=nanx, eleven=rng.uniform(-1, 1, (11, 3)).astype(np.float32),
                   geo=geo, geo_neg=geo_neg, geo_mix=geo_mix)
-    differ_default = 0
+    cases = []
     for name, c in clouds.items():
-        t = _oracle.kd_oracle(c)
-        tr = _oracle.kd_ref(c)
         pts = c[~np.isnan(c[:, 0])]
         qs = np.concatenate([pts[rng.integers(0, len(pts), 24)].astype(np.float64),
                              pts[rng.integers(0, len(pts), 24)].astype(np.float64) + 0.5,
                              rng.uniform(-6, 6, (16, 3))])
         if name.startswith("geo"):   # (the shifted queries above are meaningless at 3^39: query at the points and between them)
             qs = np.concatenate([pts.astype(np.float64)[:40], 0.5 * (pts[:-1] + pts[1:]).astype(np.float64)[:24]])
+        cases.append((name, c, qs))
+    return cases
+
+
+def test_nanoflann_tie_order_mode(torch_cuda, oracle):
+    """amk_kd_set_tie_order(AMK_TIES_NANOFLANN): the handle builds the reference's own tree on the device and answers by
+    nanoflann's own traversal -- index lists (not only distances) identical to the reference on tie-heavy clouds:
+    integer lattice, triplicated points, a quantised two-wall depth lattice, a planar cloud, plus random / tiny / NaN-x
+    clouds; node counts equal the oracle's tree (the oracle is pinned to the reference header, tests/test_kd_oracle.py),
+    index lists equal the reference's own answers (tests/golden/kd_ref_golden.npz)."""
+    import ctypes as C
+    torch = torch_cuda
+    from avoid_mpc_amd import capi
+    from avoid_mpc_amd.host import KdBatch
+    lib = capi.load()
+    differ_default = 0
+    for name, c, qs in _tie_order_cases():
+        t = _oracle.kd_oracle(c)
+        tr = _oracle.ref_answers("tie." + name, c)
         kd = KdBatch(1, len(c))
         assert lib.amk_kd_set_tie_order(kd.h, 1) == 0 and lib.amk_kd_set_tie_order(kd.h, 7) == capi.AMK_ERR_UNSUPPORTED
         kd.build(torch.from_numpy(c[None].copy()).cuda())
@@ -386,9 +395,7 @@ def test_nanoflann_tie_order_mode(torch_cuda, oracle):
                 assert np.array_equal(idx[i][:cnt[i]], ia), (name, k, i, idx[i], ia)
                 assert np.array_equal(d2[i][:cnt[i]].view(np.int64), da.view(np.int64))
                 assert np.array_equal(pt[i][:cnt[i]], pa)
-                if tr is not None:
-                    ir = tr.search(q, k)[0]
-                    assert np.array_equal(idx[i][:cnt[i]], ir), (name, k, i)
+                assert np.array_equal(idx[i][:cnt[i]], tr.search(q, k)[0]), (name, k, i)
                 differ_default += not np.array_equal(t.bruteforce(q, k)[0][:len(ia)], ia)
         kd.close()
     assert differ_default > 50     # the default (lowest-index) policy does differ on these clouds: the mode matters

@@ -1,5 +1,6 @@
 """Pins the C restatement of the KD path (oracle/kd_oracle.c) against the reference's own
-nanoflann header compiled in place (oracle/_ref) and against the committed golden vectors."""
+nanoflann header compiled in place (oracle/_ref): its answers on these clouds and queries are stored in
+tests/golden/kd_ref_golden.npz (tests/golden/make_kd_ref_golden.py), so the tests run without the reference."""
 import numpy as np
 import pytest
 
@@ -21,18 +22,41 @@ def _clouds():
     return out
 
 
-@pytest.mark.parametrize("name", list(_clouds().keys()))
-@pytest.mark.parametrize("k", [1, 3, 8])
-def test_restatement_equals_reference(name, k, oracle, ref_kd):
-    cloud = _clouds()[name]
-    a = _oracle.kd_oracle(cloud)
-    b = _oracle.kd_ref(cloud)
+def _queries(name, cloud):
     rng = np.random.default_rng(7)
     lo, hi = cloud.min(0) - 1.0, cloud.max(0) + 1.0
     qs = rng.uniform(lo, hi, (200, 3))
     qs[:20] = cloud[rng.integers(0, len(cloud), 20)]                     # queries on data points
     if name == "grid_ties":
         qs[20:40] = rng.integers(0, 9, (20, 3)) + 0.5                    # equidistant to 8 corners
+    return qs
+
+
+def _nan_x_cloud():
+    rng = np.random.default_rng(2)
+    cloud = rng.uniform(-1, 1, (50, 3)).astype(np.float32)
+    cloud[[3, 17, 40], 0] = np.nan                                       # dropped (kd_tree_two.h:99)
+    return cloud
+
+
+def _nan_y_cloud_and_queries():
+    rng = np.random.default_rng(3)
+    cloud = rng.uniform(-1, 1, (50, 3)).astype(np.float32)
+    cloud[5, 1] = np.nan                                                 # kept: only x is tested (:99)
+    return cloud, rng.uniform(-1, 1, (20, 3))
+
+
+def _fma_cloud_and_queries():
+    return synth.make_cloud(20000, 5)[0], np.random.default_rng(9).uniform([0, -8, 0], [30, 8, 4], (300, 3))
+
+
+@pytest.mark.parametrize("name", list(_clouds().keys()))
+@pytest.mark.parametrize("k", [1, 3, 8])
+def test_restatement_equals_reference(name, k, oracle):
+    cloud = _clouds()[name]
+    a = _oracle.kd_oracle(cloud)
+    b = _oracle.ref_answers(name, cloud)
+    qs = _queries(name, cloud)
     for q in qs:
         ia, da, pa = a.search(q, k)
         ib, db, pb = b.search(q, k)
@@ -43,11 +67,9 @@ def test_restatement_equals_reference(name, k, oracle, ref_kd):
         assert np.array_equal(ra[0], rb[0]) and np.array_equal(ra[1], rb[1])
 
 
-def test_nan_x_filter_and_count_quirk(oracle, ref_kd):
-    rng = np.random.default_rng(2)
-    cloud = rng.uniform(-1, 1, (50, 3)).astype(np.float32)
-    cloud[[3, 17, 40], 0] = np.nan                                       # dropped (kd_tree_two.h:99)
-    a, b = _oracle.kd_oracle(cloud), _oracle.kd_ref(cloud)
+def test_nan_x_filter_and_count_quirk(oracle):
+    cloud = _nan_x_cloud()
+    a, b = _oracle.kd_oracle(cloud), _oracle.ref_answers("nan_x", cloud)
     assert a.size() == b.size() == 47
     q = np.array([0.1, 0.2, 0.3])
     for n in (1, 8, 46, 47, 48, 60):
@@ -62,22 +84,20 @@ def test_nan_x_filter_and_count_quirk(oracle, ref_kd):
             assert len(ia) == n
 
 
-def test_nan_y_is_kept(oracle, ref_kd):
-    rng = np.random.default_rng(3)
-    cloud = rng.uniform(-1, 1, (50, 3)).astype(np.float32)
-    cloud[5, 1] = np.nan                                                 # kept: only x is tested (:99)
-    a, b = _oracle.kd_oracle(cloud), _oracle.kd_ref(cloud)
+def test_nan_y_is_kept(oracle):
+    cloud, qs = _nan_y_cloud_and_queries()
+    a, b = _oracle.kd_oracle(cloud), _oracle.ref_answers("nan_y", cloud)
     assert a.size() == b.size() == 50
-    for q in rng.uniform(-1, 1, (20, 3)):
+    for q in qs:
         ia, da, _ = a.search(q, 8)
         ib, db, _ = b.search(q, 8)
         assert np.array_equal(ia, ib) and np.array_equal(da.view(np.int64), db.view(np.int64))
         assert 5 not in ia                                               # NaN distance never inserted
 
 
-def test_empty_cloud(oracle, ref_kd):
+def test_empty_cloud(oracle):
     cloud = np.zeros((0, 3), np.float32)
-    a, b = _oracle.kd_oracle(cloud), _oracle.kd_ref(cloud)
+    a, b = _oracle.kd_oracle(cloud), _oracle.ref_answers("empty", cloud)
     assert a.size() == b.size() == 0
     assert len(a.search(np.zeros(3), 3)[0]) == 0 and len(b.search(np.zeros(3), 3)[0]) == 0
 
@@ -95,12 +115,8 @@ def test_bruteforce_agrees_when_no_ties(oracle):
 def test_fma_build_of_reference_same_indices(oracle):
     """The reference's own flags (-O3 -march=native) contract the distance into FMAs: index lists
     must not change (SURVEY.md appendix C finding 3)."""
-    fast = _oracle.load_ref(strict=False)
-    if fast is None:
-        pytest.skip("oracle/_ref not built")
-    cloud = synth.make_cloud(20000, 5)[0]
+    cloud, qs = _fma_cloud_and_queries()
     a = _oracle.kd_oracle(cloud)
-    b = _oracle.kd_ref(cloud, strict=False)
-    rng = np.random.default_rng(9)
-    for q in rng.uniform([0, -8, 0], [30, 8, 4], (300, 3)):
+    b = _oracle.ref_answers("fma", cloud)
+    for q in qs:
         assert np.array_equal(a.search(q, 8)[0], b.search(q, 8)[0])

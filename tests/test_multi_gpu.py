@@ -33,7 +33,7 @@ needs_two = pytest.mark.skipif(_n_devices() < 2, reason="needs two GPUs on the b
 
 def _bench(gpus, rank_dir, extra=()):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1", AMK_BENCH_RANK_DIR=str(rank_dir))
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "16", "--warmup", "4",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--full", "--steps", "16", "--warmup", "4",
                         "--steady-steps", "0", "--no-cpu-baseline", *extra], capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

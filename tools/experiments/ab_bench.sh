@@ -10,7 +10,7 @@ done
 for r in $(seq 1 ${REPS:-3}); do
   for v in A B; do
     cp /tmp/ab/lib$v.so avoid_mpc_amd/libavoid_mpc_amd.so
-    echo "$v: $(python bench.py ${BENCH_ARGS:---steps 512} --no-cpu-baseline --no-parity --steady-steps 0 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'])")"
+    echo "$v: $(python bench.py --full ${BENCH_ARGS:---steps 512} --no-cpu-baseline --no-parity --steady-steps 0 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'])")"
   done
 done
 python -m avoid_mpc_amd.build --force > /dev/null 2>&1

@@ -6,7 +6,7 @@ rocprofv3 -L > $O/avail.txt 2>&1
 grep -i -o "SQC_ICACHE[A-Z_]*\|SQ_IFETCH[A-Z_]*\|SQ_WAIT_IFETCH[A-Z_]*\|SQ_INST_LEVEL[A-Z_]*\|SQC_TC_INST[A-Z_]*\|SQ_WAVE[A-Z_]*IFETCH[A-Z_]*" $O/avail.txt | sort -u > $O/names.txt
 cat $O/names.txt
 for G in 1 4; do
-rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/g$G -o p -- python bench.py --steps 8 --warmup 2 --streams 1 --gang $G --no-cpu-baseline --no-parity --steady-steps 0 > /dev/null 2>> $O/err.txt
+rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/g$G -o p -- python bench.py --full --steps 8 --warmup 2 --streams 1 --gang $G --no-cpu-baseline --no-parity --steady-steps 0 > /dev/null 2>> $O/err.txt
 done
 python - <<'P'
 import csv, glob, collections

@@ -7,7 +7,7 @@ for cfg in "" "-DAMK_BUILD_THREADS=256 -DAMK_TILE_P=16 -DAMK_STAGE_RECORDS=768";
   AMK_HIPCC_FLAGS="$cfg" python -m avoid_mpc_amd.build --force > /dev/null 2>&1
   echo "== build flags: [$cfg]"
   AMK_REPS=128 python tools/experiments/ms_parts.py 2>/dev/null | grep -E "build-only|build\+3"
-  python bench.py --no-cpu-baseline --no-parity 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('cold', round(d['value']))"
-  python bench.py --workload flight --no-cpu-baseline --no-parity 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('flight', round(d['value']))"
+  python bench.py --full --no-cpu-baseline --no-parity 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('cold', round(d['value']))"
+  python bench.py --full --workload flight --no-cpu-baseline --no-parity 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('flight', round(d['value']))"
 done
 python -m avoid_mpc_amd.build --force > /dev/null 2>&1

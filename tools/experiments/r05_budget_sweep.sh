@@ -10,9 +10,9 @@ d=json.loads(sys.stdin.read().strip().splitlines()[-1]); c=d.get('config',{}); f
 print(d['value'], 'steady', d.get('value_steady_state'), 'it/step', c.get('ipm_iters_per_step', f.get('ipm_iters_per_step')))"; }
 for cfg in "0 0" "30 0" "24 0" "16 0" "12 0" "8 0" "24 1" "16 1" "16 3" "12 3" "8 4" "6 6"; do
   set -- $cfg
-  echo "cold budget $1 rounds $2: $(python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-parity --solve-budget $1 --budget-rounds $2 2>/dev/null | val)"
+  echo "cold budget $1 rounds $2: $(python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-parity --solve-budget $1 --budget-rounds $2 2>/dev/null | val)"
 done | tee $out/budget_cold.txt
 for cfg in "0 0" "16 0" "8 0"; do
   set -- $cfg
-  echo "flight budget $1 rounds $2: $(python bench.py --workload flight --no-parity --no-cpu-baseline --solve-budget $1 --budget-rounds $2 2>/dev/null | val)"
+  echo "flight budget $1 rounds $2: $(python bench.py --full --workload flight --no-parity --no-cpu-baseline --solve-budget $1 --budget-rounds $2 2>/dev/null | val)"
 done | tee $out/budget_flight.txt

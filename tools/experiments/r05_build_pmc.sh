@@ -1,7 +1,7 @@
 # SQ counters of the index build and the step's search kernel (cold step, one stream): what inside a CU bounds them?
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r05bpmc; rm -rf $O; mkdir -p $O
-CMD="python bench.py --steps 8 --warmup 2 --streams 1 --no-cpu-baseline --no-parity --steady-steps 0"
+CMD="python bench.py --full --steps 8 --warmup 2 --streams 1 --no-cpu-baseline --no-parity --steady-steps 0"
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_INSTS_VALU SQ_INSTS_LDS --kernel-trace --output-format csv -d $O/a -o a -- $CMD > /dev/null 2> $O/err_a.txt
 rocprofv3 --pmc SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU SQ_WAVES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE TA_BUSY_avr GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/b -o b -- $CMD > /dev/null 2> $O/err_b.txt
 python - <<PY

@@ -4,11 +4,11 @@ cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 B="--workload flight --keyframes 100 --points 3072 --T 1.0 --K 3 --no-parity --no-cpu-baseline --periods 120"
 B0="--workload flight --points 3072 --T 1.0 --K 3 --no-parity --no-cpu-baseline --periods 120"
 O=gpurun_out/r05kf3; mkdir -p $O
-python bench.py $B --streams 8 --gang 4 --scenes 8 > $O/host_B_8x4_s8.json 2> $O/err.txt
-python bench.py $B0 --streams 8 --gang 4 --scenes 8 > $O/host_B0_8x4_s8.json 2>> $O/err.txt
-python bench.py $B --streams 8 --gang 8 > $O/B_8x8.json 2>> $O/err.txt
-python bench.py $B --streams 12 --gang 4 > $O/B_12x4.json 2>> $O/err.txt
-python bench.py $B --streams 16 --gang 2 > $O/B_16x2.json 2>> $O/err.txt
+python bench.py --full $B --streams 8 --gang 4 --scenes 8 > $O/host_B_8x4_s8.json 2> $O/err.txt
+python bench.py --full $B0 --streams 8 --gang 4 --scenes 8 > $O/host_B0_8x4_s8.json 2>> $O/err.txt
+python bench.py --full $B --streams 8 --gang 8 > $O/B_8x8.json 2>> $O/err.txt
+python bench.py --full $B --streams 12 --gang 4 > $O/B_12x4.json 2>> $O/err.txt
+python bench.py --full $B --streams 16 --gang 2 > $O/B_16x2.json 2>> $O/err.txt
 python - <<PY
 import json, glob
 for f in sorted(glob.glob("$O/*.json")):

@@ -1,7 +1,7 @@
 # keyframe flights on sensor-like frames (nothing behind the vehicle) against 360-degree clouds: rate, map size, parity
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r05kfs; mkdir -p $O; : > $O/err.txt
-run() { tag=$1; shift; timeout 900 python bench.py "$@" > $O/s.json 2>> $O/err.txt; python - <<PY
+run() { tag=$1; shift; timeout 900 python bench.py --full "$@" > $O/s.json 2>> $O/err.txt; python - <<PY
 import json
 d = json.loads([l for l in open("$O/s.json").read().splitlines() if l.startswith("{")][-1])
 p = (d.get("parity") or {}).get("flights_vs_cpu_oracle") or {}

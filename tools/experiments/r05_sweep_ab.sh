@@ -6,8 +6,8 @@ O=gpurun_out/r05sweep; mkdir -p $O; : > $O/err.txt
 A="--workload flight --keyframes 3 --no-parity --no-cpu-baseline --streams 10 --gang 2"
 B="--workload flight --keyframes 100 --points 3072 --T 1.0 --K 3 --no-parity --no-cpu-baseline --periods 120 --streams 12 --gang 4"
 for v in 1 2; do
-  timeout 600 python bench.py $A > $O/A.json 2>> $O/err.txt
-  timeout 600 python bench.py $B > $O/B.json 2>> $O/err.txt
+  timeout 600 python bench.py --full $A > $O/A.json 2>> $O/err.txt
+  timeout 600 python bench.py --full $B > $O/B.json 2>> $O/err.txt
   python - <<PY
 import json
 for r in "AB":
@@ -15,7 +15,7 @@ for r in "AB":
     print("run $v regime", r, d["value"], d["flight"]["x_final_mean_m"], d["flight"]["solves_per_step"])
 PY
 done
-timeout 900 rocprofv3 --kernel-trace --stats -d $O/kt -o kt -- python bench.py $A --streams 1 > /dev/null 2>> $O/err.txt
+timeout 900 rocprofv3 --kernel-trace --stats -d $O/kt -o kt -- python bench.py --full $A --streams 1 > /dev/null 2>> $O/err.txt
 db=$(find $O/kt -name "*.db" | head -1); python tools/rocprof_summary.py $db | grep -v "at::native\|Cijk\|rocprim" | head -12 | tee $O/kernel_stats_A.md
 find $O -name "*.db" -size +6M -delete; find $O -name "*.csv" -size +4M -delete
 tail -3 $O/err.txt

@@ -1,7 +1,7 @@
 # SQ / cache counters of the sweep's mark kernel (regime A, one stream), two passes
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=gpurun_out/r05swpmc; rm -rf $O; mkdir -p $O
-CMD="python bench.py --workload flight --keyframes 3 --streams 1 --gang 2 --periods 20 --no-parity --no-cpu-baseline"
+CMD="python bench.py --full --workload flight --keyframes 3 --streams 1 --gang 2 --periods 20 --no-parity --no-cpu-baseline"
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES --kernel-trace --output-format csv -d $O/a -o a -- $CMD > /dev/null 2> $O/err_a.txt
 rocprofv3 --pmc TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TA_BUSY_avr GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $O/b -o b -- $CMD > /dev/null 2> $O/err_b.txt
 python - <<PY

@@ -11,13 +11,13 @@ import json
 d=json.load(open('avoid_mpc_amd/kernel_resources.json'))
 print("tiles $T recs $R:", [v for k,v in d.items() if 'sweep_mark' in k])
 PY
-  timeout 600 python bench.py $A > $O/A.json 2>> $O/err.txt
+  timeout 600 python bench.py --full $A > $O/A.json 2>> $O/err.txt
   python - <<PY
 import json
 d = json.loads([l for l in open("$O/A.json").read().splitlines() if l.startswith("{")][-1])
 print("tiles $T recs $R regime A", d["value"], d["flight"]["x_final_mean_m"])
 PY
-  rm -rf $O/kt; timeout 900 rocprofv3 --kernel-trace --stats -d $O/kt -o kt -- python bench.py $A --streams 1 > /dev/null 2>> $O/err.txt
+  rm -rf $O/kt; timeout 900 rocprofv3 --kernel-trace --stats -d $O/kt -o kt -- python bench.py --full $A --streams 1 > /dev/null 2>> $O/err.txt
   db=$(find $O/kt -name "*.db" | head -1); python tools/rocprof_summary.py $db | grep "sweep_mark"
 done
 rm -rf $O/kt

@@ -9,11 +9,11 @@ cd /tmp && export TMPDIR=/tmp; cd $ROOTD
 OUT=gpurun_out/$TAG; mkdir -p $OUT; : > $OUT/err.txt
 A="--workload flight --keyframes 3 --no-parity --no-cpu-baseline"
 B="--workload flight --keyframes 100 --points 3072 --T 1.0 --K 3 --no-parity --no-cpu-baseline"
-timeout 600 python bench.py $A --streams 10 --gang 2 > $OUT/A_10x2.json 2>> $OUT/err.txt
-timeout 600 python bench.py $B --streams 4 --gang 2 --periods 120 > $OUT/B_4x2.json 2>> $OUT/err.txt
-timeout 600 python bench.py $B --streams 8 --gang 4 --periods 120 > $OUT/B_8x4.json 2>> $OUT/err.txt
-timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/ktA -o kt -- python bench.py $A --streams 1 --gang 2 --periods 24 > /dev/null 2>> $OUT/err.txt
-timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/ktB -o kt -- python bench.py $B --streams 1 --gang 2 --periods 120 > /dev/null 2>> $OUT/err.txt
+timeout 600 python bench.py --full $A --streams 10 --gang 2 > $OUT/A_10x2.json 2>> $OUT/err.txt
+timeout 600 python bench.py --full $B --streams 4 --gang 2 --periods 120 > $OUT/B_4x2.json 2>> $OUT/err.txt
+timeout 600 python bench.py --full $B --streams 8 --gang 4 --periods 120 > $OUT/B_8x4.json 2>> $OUT/err.txt
+timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/ktA -o kt -- python bench.py --full $A --streams 1 --gang 2 --periods 24 > /dev/null 2>> $OUT/err.txt
+timeout 900 rocprofv3 --kernel-trace --stats -d $OUT/ktB -o kt -- python bench.py --full $B --streams 1 --gang 2 --periods 120 > /dev/null 2>> $OUT/err.txt
 for r in A B; do
   db=$(find $OUT/kt$r -name "*.db" | head -1)
   [ -n "$db" ] && python tools/rocprof_summary.py $db > $OUT/kernel_stats_kf_$r.md
