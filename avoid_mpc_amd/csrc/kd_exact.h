@@ -1074,6 +1074,11 @@ __device__ __forceinline__ int exact_knn_wave(const ExactTree &T, double qx, dou
 
 }  // namespace amk
 
+// host side: the batch pointers of a handle's bucketed index (amk_common.h: amk_kd)
+inline amk::GridPtrs grid_ptrs(const amk_kd *kd) {
+    return amk::GridPtrs{kd->gpt.p, kd->cell_start.p, kd->gparams.p, kd->cap, kd->ntiles};
+}
+
 // host side: the batch pointers of a handle whose reference-shaped tree exists (amk_common.h: amk_kd)
 inline amk::ExactPtrs amk_exact_ptrs(amk_kd *kd) {
     amk::ExactPtrs ep;

@@ -623,7 +623,7 @@ extern "C" int amk_kd_keyframe_sweep(amk_kd *keyframe, amk_kd *current, double t
         AMK_HIP(keyframe->flags.alloc((size_t)S * keyframe->cap));
         AMK_HIP(keyframe->sweep_cnt.alloc((size_t)S * 2));
     }
-    const amk::GridPtrs cur{current->gpt.p, current->cell_start.p, current->gparams.p, current->cap, current->ntiles};
+    const amk::GridPtrs cur = grid_ptrs(current);
     {   // the key frame's points are the queries and are compacted in place: they must exist in index order
         const int st = ensure_soa(keyframe, stream);
         if (st != AMK_OK) return st;
@@ -1017,7 +1017,7 @@ int kd_sweep_mapped(amk_kd *pool, int n_rows, const int *d_kf_list, const int *d
     int st = pool_planes(pool);
     if (st != AMK_OK) return st;
     if (!pool->flags.p) AMK_HIP(pool->flags.alloc((size_t)pool->n_scenes * pool->cap));
-    const amk::GridPtrs cur{pool->gpt.p, pool->cell_start.p, pool->gparams.p, pool->cap, pool->ntiles};
+    const amk::GridPtrs cur = grid_ptrs(pool);
     if (pool->max_points > 0 && g_sweep_target) {   // the current frames once more, as fine hashed grids (one per sweep row)
         const int nb = sweep_buckets(pool->max_points);
         if (pool->sw_rows < n_rows) {
@@ -1350,9 +1350,8 @@ int amk_kd_search(amk_kd *kd, const double *d_queries, int n_queries, int k, int
     if (!kd || !d_queries || n_queries <= 0 || k <= 0) return AMK_ERR_INVALID_ARG;
     if (k > AMK_MAX_K || n_queries > AMK_MAX_QUERIES) return AMK_ERR_UNSUPPORTED;
     if (kd->mode == 0) {
-        const amk::GridPtrs gpt{kd->gpt.p, kd->cell_start.p, kd->gparams.p, kd->cap, kd->ntiles};
         const int blocks = (kd->n_scenes + 7) / 8 * 8 * ((n_queries + 3) / 4);
-        hipLaunchKernelGGL(kd_grid_search_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, gpt, kd->size.p,
+        hipLaunchKernelGGL(kd_grid_search_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, grid_ptrs(kd), kd->size.p,
                            kd->n_scenes, d_queries, n_queries, k, d_indices, d_sqdist, d_pts, d_counts);
         AMK_HIP(hipGetLastError());
         if (kd->tie_order && kd->ex_valid) {  // nanoflann's own traversal where its tree is available (and current)
@@ -1387,9 +1386,8 @@ int amk_kd_tie_flags(amk_kd *kd, const double *d_queries, int query_stride, int 
                      void *stream) {
     if (!kd || !d_queries || !d_tie_flags || n_queries <= 0 || k <= 0 || query_stride < 3) return AMK_ERR_INVALID_ARG;
     if (k + 1 > AMK_MAX_K || n_queries > AMK_MAX_QUERIES) return AMK_ERR_UNSUPPORTED;
-    const amk::GridPtrs gpt{kd->gpt.p, kd->cell_start.p, kd->gparams.p, kd->cap, kd->ntiles};
     const int blocks = (kd->n_scenes + 7) / 8 * 8 * ((n_queries + 3) / 4);
-    hipLaunchKernelGGL(kd_tie_flags_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, gpt, kd->size.p, kd->n_scenes,
+    hipLaunchKernelGGL(kd_tie_flags_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, grid_ptrs(kd), kd->size.p, kd->n_scenes,
                        d_queries, query_stride, n_queries, k, d_tie_flags);
     AMK_HIP(hipGetLastError());
     return AMK_OK;

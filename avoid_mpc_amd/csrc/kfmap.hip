@@ -19,7 +19,7 @@
 // insertion), the deque is a list of slot numbers, a popped keyframe's slot becomes free.  The deque never holds more than
 // max_frame_count + 1 keyframes (the pop loop runs before the insertion), so a free slot always exists.  Scenes are
 // independent: their deques differ in length, the step sees a per-scene frame map (absent frames = empty clouds).
-#include "kd_grid.h"
+#include "kd_exact.h"
 #include "mpc_handle.h"
 
 #include <cstdio>
@@ -350,8 +350,7 @@ extern "C" {
 int amk_kfmap_update(amk_kfmap *m, void *stream_) {
     if (!m) return AMK_ERR_INVALID_ARG;
     hipStream_t stream = (hipStream_t)stream_;
-    const GridPtrs pool{m->obs->gpt.p, m->obs->cell_start.p, m->obs->gparams.p, m->obs->cap, m->obs->ntiles};
-    hipLaunchKernelGGL(kf_pop_kernel, dim3(m->S), dim3(64), 0, stream, m->S, m->P, pool, m->obs->size.p, m->cur_slot.p, m->kf_n.p,
+    hipLaunchKernelGGL(kf_pop_kernel, dim3(m->S), dim3(64), 0, stream, m->S, m->P, grid_ptrs(m->obs), m->obs->size.p, m->cur_slot.p, m->kf_n.p,
                        m->kf_slots.p, m->need.p, m->Twc.p, m->tinv.p, m->prm.max_frame_count, m->prm.depth_min, m->kf_list.p,
                        m->cur_list.p);
     AMK_HIP(hipGetLastError());

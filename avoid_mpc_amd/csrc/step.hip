@@ -13,8 +13,7 @@
 // The multi-frame map (keyframes, PtIsInFrame fast path, per-frame merge) is step_frames.hip.
 #include <type_traits>
 
-#include "kd_exact.h"
-#include "mpc_handle.h"
+#include "step_common.h"
 
 using namespace amk;
 
@@ -71,11 +70,8 @@ __global__ __launch_bounds__(512) void step_scan_kernel(const float *__restrict_
         if (lane < k) {
             const int li = ws->li[qq][lane];
             const bool ok = li != kNoIndex;
-            out_d2[row * k + lane] = ok ? ws->ld[qq][lane] : DBL_MAX;
-            float *o = out_pts + (row * k + lane) * 3;
-            o[0] = ok ? xs[li] : 0.f;
-            o[1] = ok ? ys[li] : 0.f;
-            o[2] = ok ? zs[li] : 0.f;
+            store_nbr(out_pts, out_d2, row * k + lane, ok, ws->ld[qq][lane], ok ? xs[li] : 0.f, ok ? ys[li] : 0.f,
+                      ok ? zs[li] : 0.f);
         }
     }
 }
@@ -112,59 +108,8 @@ __global__ __launch_bounds__(256) void step_knn_grid_kernel(GridPtrs gobs, GridP
     if (lane < k) {
         const bool ok = li != kNoIndex;
         const float4 rec = gs.pt[lpos];  // the neighbour's coordinates (lpos = 0 for an empty slot: a valid address)
-        if (is_edge) {
-            edge_d2[s] = ok ? ld : DBL_MAX;
-            edge_pt[3 * s + 0] = ok ? rec.x : 0.f;
-            edge_pt[3 * s + 1] = ok ? rec.y : 0.f;
-            edge_pt[3 * s + 2] = ok ? rec.z : 0.f;
-        } else {
-            const size_t row = (size_t)s * N + q;
-            knn_d2[row * K + lane] = ok ? ld : DBL_MAX;
-            float *o = knn_pts + (row * K + lane) * 3;
-            o[0] = ok ? rec.x : 0.f;
-            o[1] = ok ? rec.y : 0.f;
-            o[2] = ok ? rec.z : 0.f;
-        }
-    }
-}
-
-// Handles in AMK_TIES_NANOFLANN mode: the same raw results by nanoflann's own traversal of its own tree (kd_exact.h), one
-// WAVEFRONT per (scene, query), overwriting what step_knn_grid_kernel wrote wherever the tree is available.  With exact ties
-// (quantised edge clouds) this is what keeps the snapped edge point and the neighbour SET equal to the reference's.
-__global__ __launch_bounds__(256) void step_knn_exact_kernel(ExactPtrs eobs, ExactPtrs eedge, int use_obs, int use_edge,
-                                                             int n_scenes, const double *__restrict__ ref_path, int N, int K,
-                                                             float *__restrict__ knn_pts, double *__restrict__ knn_d2,
-                                                             float *__restrict__ edge_pt, double *__restrict__ edge_d2,
-                                                             const int *__restrict__ done) {
-    __shared__ ExactWaveStack stacks[4];
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)  /* wave-uniform: keeps what derives from it in SGPRs */, lane = threadIdx.x & 63;
-    const int t = blockIdx.x * 4 + w;
-    const int nq = N + 1;
-    if (t >= n_scenes * nq) return;
-    const int s = t / nq, q = t - s * nq;
-    if (done[s]) return;
-    const bool is_edge = q == N;
-    if (is_edge ? !use_edge : !use_obs) return;
-    const double *qp = ref_path + ((size_t)s * N + (is_edge ? 0 : q)) * SD;
-    const ExactTree T = is_edge ? eedge.scene(s) : eobs.scene(s);
-    const int k = is_edge ? 1 : K;
-    double rd;
-    int ri;
-    const int got = exact_knn_wave(T, qp[0], qp[1], qp[2], k, rd, ri, &stacks[w]);
-    if (got < 0) return;
-    if (lane < k) {
-        const int j = lane;
-        const bool ok = j < got;
-        const float px = ok ? T.x[ri] : 0.f, py = ok ? T.y[ri] : 0.f, pz = ok ? T.z[ri] : 0.f;
-        if (is_edge) {
-            edge_d2[s] = ok ? rd : DBL_MAX;
-            edge_pt[3 * s + 0] = px; edge_pt[3 * s + 1] = py; edge_pt[3 * s + 2] = pz;
-        } else {
-            const size_t row = (size_t)s * N + q;
-            knn_d2[row * K + j] = ok ? rd : DBL_MAX;
-            float *o = knn_pts + (row * K + j) * 3;
-            o[0] = px; o[1] = py; o[2] = pz;
-        }
+        if (is_edge) store_nbr(edge_pt, edge_d2, s, ok, ld, rec.x, rec.y, rec.z);
+        else store_nbr(knn_pts, knn_d2, ((size_t)s * N + q) * K + lane, ok, ld, rec.x, rec.y, rec.z);
     }
 }
 
@@ -219,8 +164,6 @@ __device__ __forceinline__ void plan_scene(int s, GridPtrs gpt, ExactPtrs eobs,
             if (lane < K) {
                 const int li = GRID ? gli : sli;
                 const bool ok = li != kNoIndex;
-                knn_d2[(size_t)s * N * K + lane] = ok ? (GRID ? gld : sld) : DBL_MAX;
-                float *o = knn_pts + ((size_t)s * N * K + lane) * 3;
                 float nx = 0.f, ny = 0.f, nz = 0.f;
                 if (GRID) {
                     const float4 rec = gs.pt[glpos];
@@ -228,26 +171,9 @@ __device__ __forceinline__ void plan_scene(int s, GridPtrs gpt, ExactPtrs eobs,
                 } else if (ok) {
                     nx = xs[li]; ny = ys[li]; nz = zs[li];
                 }
-                o[0] = ok ? nx : 0.f;
-                o[1] = ok ? ny : 0.f;
-                o[2] = ok ? nz : 0.f;
+                store_nbr(knn_pts, knn_d2, (size_t)s * N * K + lane, ok, GRID ? gld : sld, nx, ny, nz);
             }
-            if (EXACT) {  // AMK_TIES_NANOFLANN: the re-query by the reference's own traversal (lane 0), as above
-                __shared__ double xr[AMK_MAX_K];
-                __shared__ int xi[AMK_MAX_K], xgot;
-                __shared__ ExactStackStorage xstack;  // LDS, not scratch: one lane walks the tree
-                const ExactTree T = eobs.scene(s);
-                if (lane == 0) xgot = exact_knn_thread(T, ex, ey, ez, K, xr, xi, xstack.view());
-                __syncthreads();
-                if (xgot >= 0 && lane < K) {
-                    const bool ok = lane < xgot;
-                    knn_d2[(size_t)s * N * K + lane] = ok ? xr[lane] : DBL_MAX;
-                    float *o = knn_pts + ((size_t)s * N * K + lane) * 3;
-                    o[0] = ok ? T.x[xi[lane]] : 0.f;
-                    o[1] = ok ? T.y[xi[lane]] : 0.f;
-                    o[2] = ok ? T.z[xi[lane]] : 0.f;
-                }
-            }
+            if constexpr (EXACT) exact_requery(eobs.scene(s), ex, ey, ez, K, knn_pts, knn_d2, (size_t)s * N);
             if (lane == 0) {
                 p1[0] = ex;
                 p1[1] = ey;
@@ -258,8 +184,7 @@ __device__ __forceinline__ void plan_scene(int s, GridPtrs gpt, ExactPtrs eobs,
     if (lane == 0) flags[4 * s + 0] = is_safety;
 }
 
-// ProcessWaypoints' padding and needReplan (:216-231), the early exit (:333-335) and GetRefStates
-// (:236-257); called by the one wavefront that owns scene s.
+// pack_ref_states (step_common.h) for the one wavefront that owns scene s
 __device__ __forceinline__ void pack_scene(int s, const int *__restrict__ sizes_obs, int N, int K, int nref,
                                                           int iter, int max_iter, double speed, double T,
                                                           double safety_distance,
@@ -270,40 +195,15 @@ __device__ __forceinline__ void pack_scene(int s, const int *__restrict__ sizes_
                                                           const double *__restrict__ knn_d2,
                                                           double *__restrict__ ref_states, int *__restrict__ done,
                                                           const int *__restrict__ flags) {
-    const int lane = threadIdx.x;
     // iter < 0: the scene's own pass counter (the solves it has finished this step, flags[1]) -- with an iteration budget on the
     // solve (amk_mpc_set_solve_budget) the scenes of a launch are no longer in the same pass
     if (iter < 0) iter = flags[4 * s + 1];
     // QueryNearest through either path returns K points iff the cloud holds more than K, else none
     // (FrameKDMap.cpp:298,339-345 + kd_tree_two.h:119-124)
     const int cnt = sizes_obs[s] > K ? K : 0;
-    bool need = false;
-    if (lane < N) need = (cnt == 0) || (sqrt(knn_d2[((size_t)s * N + lane) * K]) <= safety_distance);
-    const bool need_replan = __ballot(need) != 0ull;
-    if (!need_replan && iter > 0 && flags[4 * s + 0]) {  // :333-335
-        if (lane == 0) done[s] = 1;
-        return;
-    }
-    double *P = ref_states + (size_t)s * nref;
-    const double *sq = state_quad + ((size_t)s * max_iter + iter) * SD;
-    const double *rp = ref_path + (size_t)s * N * SD;
-    if (lane < SD) P[lane] = sq[lane];
-    for (int e = lane; e < SD * N; e += 64) P[SD + e] = rp[e];
-    for (int e = lane; e < 3 * K * N; e += 64) {
-        const int j = (e / 3) % K;
-        P[SD + SD * N + e] = (j < cnt) ? (double)knn_pts[(size_t)s * N * K * 3 + e] : 10000.0;  // :223-226
-    }
-    if (lane < SD) {
-        const double *last = rp + (N - 1) * SD;
-        double v = last[lane];
-        if (lane == 0) {
-            double dX = speed * T - fmax(0., last[0] - pos_x[s]);
-            dX = fmax(0., dX);
-            v += dX;
-        }
-        if (lane == 1) v = 0.;
-        P[SD + SD * N + 3 * K * N + lane] = v;
-    }
+    pack_ref_states(threadIdx.x, kWave, s, N, K, nref, iter, max_iter, speed, T, safety_distance, flags[4 * s + 0],
+                    [cnt](int) { return cnt; }, state_quad, pos_x, ref_path + (size_t)s * N * SD, knn_pts, knn_d2,
+                    ref_states, done);
 }
 
 // PlanWapionts, then ProcessWaypoints' bookkeeping + GetRefStates, for scene s = blockIdx.x (one wavefront): the
@@ -332,6 +232,10 @@ __global__ __launch_bounds__(kWave) void step_plan_pack_kernel(
 
 }  // namespace
 
+void amk::launch_step_begin(int S, int *done, int *flags, double *u, hipStream_t stream) {
+    hipLaunchKernelGGL(step_begin_kernel, dim3((S + 255) / 256), dim3(256), 0, stream, S, done, flags, u);
+}
+
 // Internal (tools/experiments, bench.py AMK_BENCH_SKIP): leave kernel classes out of amk_step_batch to see what each costs
 // with the others in flight -- bit 0 queries, bit 1 plan/pack, bit 2 solves.  Results are garbage while set.
 static int g_diag_skip = 0;
@@ -343,21 +247,13 @@ extern "C" int amk_step_batch(amk_kd *obstacle, amk_kd *edge, amk_mpc *mpc, cons
     if (!obstacle || !edge || !mpc || !prm || !d_state_quad || !d_pos_x || !d_ref_path || !d_u || !d_flags)
         return AMK_ERR_INVALID_ARG;
     if (obstacle->n_scenes != mpc->S || edge->n_scenes != mpc->S) return AMK_ERR_INVALID_ARG;
-    if (prm->mpc_max_iter < 1 || prm->mpc_max_iter > AMK_MAX_OUTER_ITER || mpc->K < 1) return AMK_ERR_INVALID_ARG;
+    if (!step_params_ok(mpc, prm)) return AMK_ERR_INVALID_ARG;
     hipStream_t stream = (hipStream_t)stream_;
     const int N = mpc->N, K = mpc->K;
-    if (!mpc->done.p) {
-        const size_t Sa = mpc->S;
-        AMK_HIP(mpc->knn_pts.alloc(Sa * N * K * 3));
-        AMK_HIP(mpc->knn_d2.alloc(Sa * N * K));
-        AMK_HIP(mpc->edge_pt.alloc(Sa * 3));
-        AMK_HIP(mpc->edge_d2.alloc(Sa));
-        AMK_HIP(mpc->ref_states.alloc(Sa * mpc->nref));
-        AMK_HIP(mpc->done.alloc(Sa));
-    }
+    if (int st = ensure_step_workspace(mpc); st != AMK_OK) return st;
     const int S = mpc->launch_scenes();   // (amk_pipeline: a gang that is not full runs its leading scenes only)
     { TimedLaunch tl(KC_BEGIN, stream);
-    hipLaunchKernelGGL(step_begin_kernel, dim3((S + 255) / 256), dim3(256), 0, stream, S, mpc->done.p, d_flags, d_u); }
+    launch_step_begin(S, mpc->done.p, d_flags, d_u, stream); }
     int qpw, groups, wpb;
     scan_geometry(N, qpw, groups, wpb);
     const int bps = (groups + wpb - 1) / wpb;
@@ -368,11 +264,14 @@ extern "C" int amk_step_batch(amk_kd *obstacle, amk_kd *edge, amk_mpc *mpc, cons
         if (st == AMK_OK) st = amk__kd_ensure_soa(edge, stream_);
         if (st != AMK_OK) return st;
     }
-    const GridPtrs gobs{obstacle->gpt.p, obstacle->cell_start.p, obstacle->gparams.p, obstacle->cap, obstacle->ntiles};
-    const GridPtrs gedge{edge->gpt.p, edge->cell_start.p, edge->gparams.p, edge->cap, edge->ntiles};
+    const GridPtrs gobs = grid_ptrs(obstacle), gedge = grid_ptrs(edge);
     // handles in AMK_TIES_NANOFLANN mode (their reference-shaped trees were built by amk_kd_build)
-    const int ex_obs = use_grid && obstacle->tie_order && obstacle->ex_valid, ex_edge = use_grid && edge->tie_order && edge->ex_valid;
-    const ExactPtrs eobs = ex_obs ? amk_exact_ptrs(obstacle) : ExactPtrs{}, eedge = ex_edge ? amk_exact_ptrs(edge) : ExactPtrs{};
+    ExactPair ex{};
+    ex.use_obs = use_grid && obstacle->tie_order && obstacle->ex_valid;
+    ex.use_edge = use_grid && edge->tie_order && edge->ex_valid;
+    if (ex.use_obs) ex.obs = amk_exact_ptrs(obstacle);
+    if (ex.use_edge) ex.edge = amk_exact_ptrs(edge);
+    const FrameBufs out{mpc->knn_pts.p, mpc->knn_d2.p, mpc->edge_pt.p, mpc->edge_d2.p};
     // Rounds.  Plain schedule (no budget): round r IS pass r of every scene still in the loop, mpc_max_iter rounds.  With an
     // iteration budget B (amk_mpc_set_solve_budget) a solve launch of the first `budget_rounds` rounds ends after B iterations per
     // scene; a scene that is not finished by then pauses (done[s] = 2), sits out the next round's queries and packing, and is
@@ -393,10 +292,9 @@ extern "C" int amk_step_batch(amk_kd *obstacle, amk_kd *edge, amk_mpc *mpc, cons
             hipLaunchKernelGGL(step_knn_grid_kernel, dim3(S8 * ((N + 4) / 4)), dim3(256), 0, stream, gobs, gedge, S,
                                d_ref_path, N, K, mpc->knn_pts.p, mpc->knn_d2.p, mpc->edge_pt.p, mpc->edge_d2.p,
                                mpc->done.p);
-            if (ex_obs || ex_edge)
-                hipLaunchKernelGGL(step_knn_exact_kernel, dim3((S * (N + 1) + 3) / 4), dim3(256), 0, stream, eobs, eedge, ex_obs,
-                                   ex_edge, S, d_ref_path, N, K, mpc->knn_pts.p, mpc->knn_d2.p, mpc->edge_pt.p,
-                                   mpc->edge_d2.p, mpc->done.p);
+            if (ex.use_obs || ex.use_edge)
+                hipLaunchKernelGGL(step_knn_exact_kernel<ExactPair>, dim3((S * (N + 1) + 3) / 4), dim3(256), 0, stream, ex, S,
+                                   d_ref_path, N, K, out, mpc->done.p);
         } else {
         { TimedLaunch tl(KC_SCAN_OBS, stream);
         hipLaunchKernelGGL(step_scan_kernel<5>, dim3(S8 * bps), dim3(wpb * kWave), scan_lds_bytes<5>(wpb), stream,
@@ -410,8 +308,8 @@ extern "C" int amk_step_batch(amk_kd *obstacle, amk_kd *edge, amk_mpc *mpc, cons
         if (!(g_diag_skip & 2)) { TimedLaunch tl(KC_PLAN, stream);
         auto plan_kernel = step_plan_pack_kernel<false, true>;
         if (!use_grid) plan_kernel = step_plan_pack_kernel<false, false>;
-        else if (ex_obs) plan_kernel = step_plan_pack_kernel<true, true>;
-        hipLaunchKernelGGL(plan_kernel, dim3(S), dim3(kWave), 0, stream, gobs, eobs, obstacle->x.p,
+        else if (ex.use_obs) plan_kernel = step_plan_pack_kernel<true, true>;
+        hipLaunchKernelGGL(plan_kernel, dim3(S), dim3(kWave), 0, stream, gobs, ex.obs, obstacle->x.p,
                            obstacle->y.p, obstacle->z.p, obstacle->cap, obstacle->size.p, obstacle->pmax.p, edge->size.p, N,
                            K, mpc->nref, per_scene ? -1 : iter, prm->mpc_max_iter, prm->speed, mpc->T, prm->safety_distance, d_state_quad,
                            d_pos_x, d_ref_path, mpc->knn_pts.p, mpc->knn_d2.p, mpc->edge_pt.p, mpc->edge_d2.p,
@@ -429,7 +327,7 @@ extern "C" int amk_step_batch_host(amk_kd *obstacle, amk_kd *edge, amk_mpc *mpc,
                                    const double *h_state_quad, const double *h_pos_x, double *h_ref_path, double *h_u,
                                    double *h_x0array, int *h_flags) {
     if (!mpc || !prm || !h_state_quad || !h_pos_x || !h_ref_path || !h_u || !h_flags) return AMK_ERR_INVALID_ARG;
-    if (prm->mpc_max_iter < 1 || prm->mpc_max_iter > AMK_MAX_OUTER_ITER) return AMK_ERR_INVALID_ARG;
+    if (!step_params_ok(mpc, prm)) return AMK_ERR_INVALID_ARG;
     const size_t S = mpc->S, N = mpc->N, mi = prm->mpc_max_iter;
     if (mpc->sh_sq.n < S * mi * SD) AMK_HIP(mpc->sh_sq.alloc(S * AMK_MAX_OUTER_ITER * SD));
     if (!mpc->sh_ref.p) {

@@ -18,9 +18,8 @@
 //                                 reference point, padding, needReplan, early exit, GetRefStates
 //   mpc_solve_kernel              Solve + refill of the reference path (mpc_solve.hip)
 // Frames whose handles are in AMK_TIES_NANOFLANN mode are queried by nanoflann's own traversal of its own tree
-// (kd_exact.h): step_knn_frames_exact_kernel overwrites the raw results, the snap re-query follows suit.
-#include "kd_exact.h"
-#include "mpc_handle.h"
+// (kd_exact.h): step_knn_exact_kernel (step_common.h) overwrites the raw results, the snap re-query follows suit.
+#include "step_common.h"
 
 using namespace amk;
 
@@ -47,18 +46,6 @@ struct FrameSet {  // kernel argument: where every frame's indices live
         const int m = scene_of(f, s);
         return m < 0 ? 0 : (fmap ? size_edge[0] : size_edge[f])[m];
     }
-};
-
-struct FrameBufs {  // per-frame raw query results, frame-major
-    float *knn_pts;   // [F][S][N][K][3]
-    double *knn_d2;   // [F][S][N][K]
-    float *edge_pt;   // [F][S][3]
-    double *edge_d2;  // [F][S]
-};
-
-struct FrameExact {  // lives in device memory (too large for the kernel argument segment next to FrameSet)
-    ExactPtrs obs[AMK_MAX_FRAMES], edge[AMK_MAX_FRAMES];
-    int use_obs[AMK_MAX_FRAMES], use_edge[AMK_MAX_FRAMES];
 };
 
 // PtIsInFrame (FrameKDMap.cpp:215-231): Twc rigid, its inverse is [R' | -R' t]
@@ -133,58 +120,9 @@ __global__ __launch_bounds__(256) void step_knn_frames_kernel(FrameSet fs, int n
         if (lane < k) {
             const bool ok = li != kNoIndex;
             const float4 rec = gs.pt[lpos];
-            if (is_edge) {
-                const size_t o = (size_t)f * n_scenes + s;
-                fb.edge_d2[o] = ok ? ld : DBL_MAX;
-                fb.edge_pt[3 * o + 0] = ok ? rec.x : 0.f;
-                fb.edge_pt[3 * o + 1] = ok ? rec.y : 0.f;
-                fb.edge_pt[3 * o + 2] = ok ? rec.z : 0.f;
-            } else {
-                const size_t row = ((size_t)f * n_scenes + s) * N + q;
-                fb.knn_d2[row * K + lane] = ok ? ld : DBL_MAX;
-                float *o = fb.knn_pts + (row * K + lane) * 3;
-                o[0] = ok ? rec.x : 0.f;
-                o[1] = ok ? rec.y : 0.f;
-                o[2] = ok ? rec.z : 0.f;
-            }
-        }
-    }
-}
-
-// one THREAD per (frame, scene, query): the same raw results by the reference's traversal, where the frame has its tree
-__global__ __launch_bounds__(256) void step_knn_frames_exact_kernel(const FrameExact *__restrict__ fe, int n_scenes,
-                                                                    const double *__restrict__ ref_path, int N, int K,
-                                                                    FrameBufs fb, const int *__restrict__ done) {
-    __shared__ ExactWaveStack stacks[4];
-    const int f = blockIdx.y;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)  /* wave-uniform: keeps what derives from it in SGPRs */, lane = threadIdx.x & 63;
-    const int t = blockIdx.x * 4 + w;
-    const int nq = N + 1;
-    if (t >= n_scenes * nq) return;
-    const int s = t / nq, q = t - s * nq;
-    if (done[s]) return;
-    const bool is_edge = q == N;
-    if (is_edge ? !fe->use_edge[f] : !fe->use_obs[f]) return;
-    const double *qp = ref_path + ((size_t)s * N + (is_edge ? 0 : q)) * SD;
-    const ExactTree T = is_edge ? fe->edge[f].scene(s) : fe->obs[f].scene(s);
-    const int k = is_edge ? 1 : K;
-    double rd;
-    int ri;
-    const int got = exact_knn_wave(T, qp[0], qp[1], qp[2], k, rd, ri, &stacks[w]);
-    if (got < 0) return;
-    if (lane < k) {
-        const int j = lane;
-        const bool ok = j < got;
-        const float px = ok ? T.x[ri] : 0.f, py = ok ? T.y[ri] : 0.f, pz = ok ? T.z[ri] : 0.f;
-        if (is_edge) {
             const size_t o = (size_t)f * n_scenes + s;
-            fb.edge_d2[o] = ok ? rd : DBL_MAX;
-            fb.edge_pt[3 * o + 0] = px; fb.edge_pt[3 * o + 1] = py; fb.edge_pt[3 * o + 2] = pz;
-        } else {
-            const size_t row = ((size_t)f * n_scenes + s) * N + q;
-            fb.knn_d2[row * K + j] = ok ? rd : DBL_MAX;
-            float *o = fb.knn_pts + (row * K + j) * 3;
-            o[0] = px; o[1] = py; o[2] = pz;
+            if (is_edge) store_nbr(fb.edge_pt, fb.edge_d2, o, ok, ld, rec.x, rec.y, rec.z);
+            else store_nbr(fb.knn_pts, fb.knn_d2, (o * N + q) * K + lane, ok, ld, rec.x, rec.y, rec.z);
         }
     }
 }
@@ -302,30 +240,15 @@ __global__ __launch_bounds__(4 * kWave) void step_merge_plan_pack_kernel(
                 const GridScene gs = fs.obs_scene(f, mf);
                 grid_knn(gs, ex, ey, ez, K, gld, gli, glpos, &wl[w]);
                 if (lane < K) {
-                    const bool ok = gli != kNoIndex;
                     const float4 rec = gs.pt[glpos];
-                    const size_t row = ((size_t)f * S + s) * N;
-                    fb.knn_d2[row * K + lane] = ok ? gld : DBL_MAX;
-                    float *o = fb.knn_pts + (row * K + lane) * 3;
-                    o[0] = ok ? rec.x : 0.f; o[1] = ok ? rec.y : 0.f; o[2] = ok ? rec.z : 0.f;
+                    store_nbr(fb.knn_pts, fb.knn_d2, ((size_t)f * S + s) * N * K + lane, gli != kNoIndex, gld, rec.x, rec.y,
+                              rec.z);
                 }
             }
             if constexpr (EXACT) {   // (nw == 1: the barriers below are this wavefront's own)
                 __syncthreads();
-                if (mf >= 0 && fe->use_obs[f]) {  // AMK_TIES_NANOFLANN frame: the re-query by the reference's traversal (lane 0)
-                    __shared__ double xr[AMK_MAX_K];
-                    __shared__ int xi[AMK_MAX_K], xgot;
-                    __shared__ ExactStackStorage xstack;  // LDS, not scratch: one lane walks the tree
-                    const ExactTree T = fe->obs[f].scene(s);
-                    if (lane == 0) xgot = exact_knn_thread(T, ex, ey, ez, K, xr, xi, xstack.view());
-                    __syncthreads();
-                    if (xgot >= 0 && lane < K) {
-                        const bool ok = lane < xgot;
-                        const size_t row = ((size_t)f * S + s) * N;
-                        fb.knn_d2[row * K + lane] = ok ? xr[lane] : DBL_MAX;
-                        float *o = fb.knn_pts + (row * K + lane) * 3;
-                        o[0] = ok ? T.x[xi[lane]] : 0.f; o[1] = ok ? T.y[xi[lane]] : 0.f; o[2] = ok ? T.z[xi[lane]] : 0.f;
-                    }
+                if (mf >= 0 && fe->use_obs[f]) {  // AMK_TIES_NANOFLANN frame
+                    exact_requery(fe->obs[f].scene(s), ex, ey, ez, K, fb.knn_pts, fb.knn_d2, ((size_t)f * S + s) * N);
                     __syncthreads();
                 }
             }
@@ -434,44 +357,8 @@ __global__ __launch_bounds__(4 * kWave) void step_merge_plan_pack_kernel(
     }
     __threadfence_block();
     __syncthreads();
-    // ---- padding, needReplan (:216-231), early exit (:333-335), GetRefStates (:236-257)
-    bool need = false;
-    if (lane < N) need = (cntq[lane] == 0) || (sqrt(knn_d2[((size_t)s * N + lane) * K]) <= safety_distance);
-    const bool need_replan = __ballot(need) != 0ull;   // (every wavefront evaluates the same rows: one decision per workgroup)
-    if (!need_replan && iter > 0 && is_safety) {
-        if (tid == 0) done[s] = 1;
-        return;
-    }
-    double *P = ref_states + (size_t)s * nref;
-    const double *sq = state_quad + ((size_t)s * max_iter + iter) * SD;
-    if (tid < SD) P[tid] = sq[tid];
-    for (int e = tid; e < SD * N; e += nthr) P[SD + e] = rp[e];
-    for (int e = tid; e < 3 * K * N; e += nthr) {
-        const int i = e / (3 * K), jj = (e / 3) % K;
-        P[SD + SD * N + e] = (jj < cntq[i]) ? (double)knn_pts[(size_t)s * N * K * 3 + e] : 10000.0;
-    }
-    if (tid < SD) {
-        const double *last = rp + (N - 1) * SD;
-        double v = last[tid];
-        if (tid == 0) {
-            double dX = speed * T - fmax(0., last[0] - pos_x[s]);
-            dX = fmax(0., dX);
-            v += dX;
-        }
-        if (tid == 1) v = 0.;
-        P[SD + SD * N + 3 * K * N + tid] = v;
-    }
-}
-
-__global__ void step_frames_begin_kernel(int S, int *__restrict__ done, int *__restrict__ flags, double *__restrict__ u) {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= S) return;
-    done[s] = 0;
-    flags[4 * s + 0] = 1;
-    flags[4 * s + 1] = 0;
-    flags[4 * s + 2] = -1;
-    flags[4 * s + 3] = 0;
-    u[4 * s + 0] = u[4 * s + 1] = u[4 * s + 2] = u[4 * s + 3] = 0.0;
+    pack_ref_states(tid, nthr, s, N, K, nref, iter, max_iter, speed, T, safety_distance, is_safety,
+                    [&](int i) { return cntq[i]; }, state_quad, pos_x, rp, knn_pts, knn_d2, ref_states, done);
 }
 
 }  // namespace
@@ -485,17 +372,7 @@ static int run_frames(const FrameSet &fs, amk_kd *const *obstacle, amk_kd *const
                       const amk_frame_camera *cam, amk_mpc *mpc, const amk_step_params *prm, const double *d_state_quad,
                       const double *d_pos_x, double *d_ref_path, double *d_u, double *d_x0array, int *d_flags, hipStream_t stream) {
     const int N = mpc->N, K = mpc->K, F = fs.n;
-    {
-        const size_t S = mpc->S;
-        if (!mpc->done.p) {
-            AMK_HIP(mpc->knn_pts.alloc(S * N * K * 3));
-            AMK_HIP(mpc->knn_d2.alloc(S * N * K));
-            AMK_HIP(mpc->edge_pt.alloc(S * 3));
-            AMK_HIP(mpc->edge_d2.alloc(S));
-            AMK_HIP(mpc->ref_states.alloc(S * mpc->nref));
-            AMK_HIP(mpc->done.alloc(S));
-        }
-    }
+    if (int st = ensure_step_workspace(mpc); st != AMK_OK) return st;
     const int Sall = mpc->S;
     if (mpc->mf_frames < F) {   // sized ONCE for the largest map of its kind (AMK_MAX_FRAMES handles; a keyframe map: its own
         // 1 + max_frame_count): a map that gains a keyframe between two calls must not free a buffer an earlier call's kernels
@@ -554,7 +431,7 @@ static int run_frames(const FrameSet &fs, amk_kd *const *obstacle, amk_kd *const
     else if (need_cpl <= 1) merge_kernel = step_merge_plan_pack_kernel<false, 1>;
     else if (need_cpl <= 2) merge_kernel = step_merge_plan_pack_kernel<false, 2>;
     else if (need_cpl <= 4) merge_kernel = step_merge_plan_pack_kernel<false, 4>;
-    hipLaunchKernelGGL(step_frames_begin_kernel, dim3((S + 255) / 256), dim3(256), 0, stream, S, mpc->done.p, d_flags, d_u);
+    launch_step_begin(S, mpc->done.p, d_flags, d_u, stream);
     const int S8 = (S + 7) / 8 * 8;
     const int fc = 8;   // map mode: frames of the first chunk of search blocks (the chunks double: 8, 16, 32, ...)
     int n_chunks = 1;
@@ -567,8 +444,8 @@ static int run_frames(const FrameSet &fs, amk_kd *const *obstacle, amk_kd *const
             hipLaunchKernelGGL(step_knn_frames_kernel<false>, dim3(S8 * ((N + 4) / 4), F), dim3(256), 0, stream, fs, S, d_ref_path,
                                N, K, fb, mpc->done.p, 1, d_Twc, c);
         if (any_exact)
-            hipLaunchKernelGGL(step_knn_frames_exact_kernel, dim3((S * (N + 1) + 3) / 4, F), dim3(256), 0, stream, fe_dev, S,
-                               d_ref_path, N, K, fb, mpc->done.p);
+            hipLaunchKernelGGL(step_knn_exact_kernel<const FrameExact *>, dim3((S * (N + 1) + 3) / 4, F), dim3(256), 0, stream,
+                               fe_dev, S, d_ref_path, N, K, fb, mpc->done.p);
         hipLaunchKernelGGL(merge_kernel, dim3(S), dim3(any_exact ? kWave : 4 * kWave), 0, stream, fs, fe_dev, fb, S, d_Twc, c, N, K, mpc->nref,
                            iter, prm->mpc_max_iter, prm->speed, mpc->T, prm->safety_distance, d_state_quad, d_pos_x,
                            d_ref_path, mpc->knn_pts.p, mpc->knn_d2.p, mpc->ref_states.p, mpc->done.p, d_flags);
@@ -587,7 +464,7 @@ extern "C" int amk_step_batch_frames(amk_kd *const *obstacle, amk_kd *const *edg
         return AMK_ERR_INVALID_ARG;
     if (d_Twc && !cam) return AMK_ERR_INVALID_ARG;
     if (n_frames > AMK_MAX_FRAMES) return AMK_ERR_UNSUPPORTED;
-    if (prm->mpc_max_iter < 1 || prm->mpc_max_iter > AMK_MAX_OUTER_ITER || mpc->K < 1) return AMK_ERR_INVALID_ARG;
+    if (!step_params_ok(mpc, prm)) return AMK_ERR_INVALID_ARG;
     const int S = mpc->S, F = n_frames;
     FrameSet fs{};
     fs.n = F;
@@ -596,8 +473,8 @@ extern "C" int amk_step_batch_frames(amk_kd *const *obstacle, amk_kd *const *edg
     for (int f = 0; f < F; ++f) {
         if (!obstacle[f] || !edge[f] || obstacle[f]->n_scenes != S || edge[f]->n_scenes != S) return AMK_ERR_INVALID_ARG;
         if (obstacle[f]->mode != 0 || edge[f]->mode != 0) return AMK_ERR_UNSUPPORTED;  // bucketed indices only
-        fs.obs[f] = GridPtrs{obstacle[f]->gpt.p, obstacle[f]->cell_start.p, obstacle[f]->gparams.p, obstacle[f]->cap, obstacle[f]->ntiles};
-        fs.edge[f] = GridPtrs{edge[f]->gpt.p, edge[f]->cell_start.p, edge[f]->gparams.p, edge[f]->cap, edge[f]->ntiles};
+        fs.obs[f] = grid_ptrs(obstacle[f]);
+        fs.edge[f] = grid_ptrs(edge[f]);
         fs.size_obs[f] = obstacle[f]->size.p;
         fs.size_edge[f] = edge[f]->size.p;
     }
@@ -615,13 +492,13 @@ int step_batch_map(amk_kd *obs_pool, amk_kd *edge_pool, int n_frames, const int 
         return AMK_ERR_INVALID_ARG;
     if (d_Twc && !cam) return AMK_ERR_INVALID_ARG;
     if (n_frames > AMK_MAX_MAP_FRAMES || n_frames * mpc->K > 64 * 128) return AMK_ERR_UNSUPPORTED;
-    if (prm->mpc_max_iter < 1 || prm->mpc_max_iter > AMK_MAX_OUTER_ITER || mpc->K < 1) return AMK_ERR_INVALID_ARG;
+    if (!step_params_ok(mpc, prm)) return AMK_ERR_INVALID_ARG;
     FrameSet fs{};
     fs.n = n_frames;
     fs.fmap = d_fmap;
     fs.S = mpc->S;
-    fs.obs[0] = GridPtrs{obs_pool->gpt.p, obs_pool->cell_start.p, obs_pool->gparams.p, obs_pool->cap, obs_pool->ntiles};
-    fs.edge[0] = GridPtrs{edge_pool->gpt.p, edge_pool->cell_start.p, edge_pool->gparams.p, edge_pool->cap, edge_pool->ntiles};
+    fs.obs[0] = grid_ptrs(obs_pool);
+    fs.edge[0] = grid_ptrs(edge_pool);
     fs.size_obs[0] = obs_pool->size.p;
     fs.size_edge[0] = edge_pool->size.p;
     return run_frames(fs, nullptr, nullptr, d_Twc, cam, mpc, prm, d_state_quad, d_pos_x, d_ref_path, d_u, d_x0array, d_flags, stream);
