@@ -10,8 +10,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libavoid_mpc_amd.so")
 
 AMK_OK, AMK_ERR_INVALID_ARG, AMK_ERR_HIP, AMK_ERR_NO_DEVICE, AMK_ERR_UNSUPPORTED, AMK_ERR_TIMEOUT = 0, 1, 2, 3, 4, 5   # include/avoid_mpc_amd.h
-AMK_TIES_LOWEST_INDEX, AMK_TIES_NANOFLANN = 0, 1
+AMK_TIES_LOWEST_INDEX, AMK_TIES_NANOFLANN, AMK_TIES_AUTO = 0, 1, 2
 AMK_EXACT_OFF, AMK_EXACT_IN_USE, AMK_EXACT_GAVE_UP, AMK_EXACT_TOO_DEEP = -1, 0, 1, 2   # amk_kd_exact_status
+AMK_EXACT_NOT_NEEDED = 3   # AMK_TIES_AUTO only: no query of the scene has tied since the last build
 AMK_MAX_K = 64
 AMK_MAX_QUERIES = 64
 AMK_MAX_HORIZON = 32

@@ -85,6 +85,9 @@ int kd_build_mapped_gang(amk_kd *obs_pool, amk_kd *edge_pool, int n_frames, int 
                          const int *d_out_scene, hipStream_t stream);
 int kd_sweep_mapped(amk_kd *pool, int n_rows, const int *d_kf_list, const int *d_cur_list, double th_dist, int th_count,
                     int *d_outliers, int *d_rebuilt, hipStream_t stream);
+// kd_index.hip, AMK_TIES_AUTO: the lazy build of the reference-shaped trees of up to two handles (null: none) in two launches --
+// a workgroup returns at once unless its scene's `need` word is raised and its tree is not built yet (see amk_kd::au_state)
+int kd_auto_build(amk_kd *a, amk_kd *b, hipStream_t stream);
 }  // namespace amk
 
 // ------------------------------------------------------------------------------------------------
@@ -114,6 +117,16 @@ struct amk_kd {
     amk::DevBuf<float> ex_pc;   // [3][S][cap] the coordinates in vAcc_ order (leaves are contiguous runs)
     amk::DevBuf<int> ex_feat, ex_child, ex_nn;
     amk::DevBuf<double> ex_low, ex_high, ex_nbbox, ex_root;
+    // AMK_TIES_AUTO: the same tree, built on the device for the scenes where a query tied, by the searches that saw the tie.
+    // Every index build clears au_state on its stream, so a tree never answers for a cloud it was not built from.
+    int au_active = 0;            // host flag: the last index build ran in AMK_TIES_AUTO and cleared au_state for the cloud held
+    amk::DevBuf<int> au_state;    // [3][S] need (a query of the scene tied), built (its tree belongs to the cloud held), requery_tied
+                                  // (the control step's re-query of the snapped reference point tied in this pass)
+    amk::DevBuf<int> au_rowflag;  // [S][AMK_MAX_QUERIES] tie flag of every (scene, query) row of the search / step pass in flight
+    int *au_need() const { return au_state.p; }
+    int *au_built() const { return au_state.p + n_scenes; }
+    int *au_requery() const { return au_state.p + 2 * (size_t)n_scenes; }
+    bool auto_on() const { return tie_order == AMK_TIES_AUTO && au_active && mode == 0; }
     amk::DevBuf<unsigned char> flags; // [S][cap] keyframe sweep: 1 = outlier
     amk::DevBuf<int> sweep_cnt;       // [S][2]   {outliers, rebuilt}
     // the keyframe map's pool only (kd_sweep_mapped): the sweep's target, per sweep ROW -- the current frame's points once more, sorted

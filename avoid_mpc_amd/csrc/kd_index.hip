@@ -197,7 +197,7 @@ static BuildArgs build_args(amk_kd *kd, const float *d_xyz, int point_stride, lo
 // writes them itself (coalesced) instead of kd_records_to_soa_kernel scattering them from the records afterwards.  Returns
 // whether `a` now asks for them (false: allocation failed or not wanted -- ensure_soa makes them on demand as before).
 static bool build_writes_soa(amk_kd *kd, BuildArgs &a, size_t so = 0) {
-    if (!kd->tie_order || kd->cap <= 0) return false;
+    if (kd->tie_order != AMK_TIES_NANOFLANN || kd->cap <= 0) return false;   // (AMK_TIES_AUTO makes them per scene, on demand)
     if (!kd->x.p || !kd->y.p || !kd->z.p) {   // (a failed allocation leaves what it got: ensure_soa retries the rest)
         const size_t tot = (size_t)kd->n_scenes * kd->cap;
         if ((!kd->x.p && kd->x.alloc(tot) != hipSuccess) || (!kd->y.p && kd->y.alloc(tot) != hipSuccess) ||
@@ -429,7 +429,7 @@ __global__ __launch_bounds__(256) void kd_exact_search_kernel(amk::ExactPtrs ep,
 static amk::ExactPtrs exact_ptrs(amk_kd *kd) { return amk_exact_ptrs(kd); }
 
 // builds the reference's tree of every scene from the index-ordered planes (made on demand from the bucket records)
-static int exact_build(amk_kd *kd, hipStream_t stream) {
+static int exact_alloc(amk_kd *kd) {
     const size_t S = kd->n_scenes;
     if (!kd->ex_vind.p) {
         kd->ex_max_nodes = kd->cap / 2 + 64;  // ~0.29 nodes per point with 10-point leaves; more = pathological data
@@ -440,13 +440,199 @@ static int exact_build(amk_kd *kd, hipStream_t stream) {
         AMK_HIP(kd->ex_child.alloc(nc)); AMK_HIP(kd->ex_low.alloc(nc)); AMK_HIP(kd->ex_high.alloc(nc));
         AMK_HIP(kd->ex_nbbox.alloc(nc * 6)); AMK_HIP(kd->ex_root.alloc(S * 6)); AMK_HIP(kd->ex_nn.alloc(S));
     }
-    const int st = ensure_soa(kd, stream);
+    return AMK_OK;
+}
+static int exact_build(amk_kd *kd, hipStream_t stream) {
+    int st = exact_alloc(kd);
+    if (st == AMK_OK) st = ensure_soa(kd, stream);
     if (st != AMK_OK) return st;
     hipLaunchKernelGGL(kd_exact_build_top_kernel, dim3(kd->n_scenes), dim3(amk::kExactTopThreads), 0, stream, exact_ptrs(kd), kd->size.p);
     hipLaunchKernelGGL(kd_exact_build_kernel, dim3(kd->n_scenes), dim3(amk::kExactThreads), 0, stream, exact_ptrs(kd),
                        kd->size.p, g_exact_queue_cap);
     AMK_HIP(hipGetLastError());
     kd->ex_valid = 1;
+    return AMK_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// opt-in AMK_TIES_AUTO: the same tree, but only for the scenes where a query tied, and only the tied queries go through it
+// ------------------------------------------------------------------------------------------------
+// kd_grid_search_kernel with one more candidate and the tie test of kd_tie_flags_kernel on the k + 1: the first k are stored
+// as there (the k + 1 nearest in (distance, index) order begin with the k nearest in that order), the row's flag says whether
+// nanoflann's list may differ, and a flagged row raises its scene's `need` word for the lazy build behind this launch.
+__global__ __launch_bounds__(256) void kd_grid_search_auto_kernel(amk::GridPtrs gpt, const int *__restrict__ sizes, int n_scenes,
+                                                                  const double *__restrict__ queries, int n_queries,
+                                                                  int k, int *__restrict__ out_idx,
+                                                                  double *__restrict__ out_d2,
+                                                                  float *__restrict__ out_pts, int *__restrict__ out_cnt,
+                                                                  int *__restrict__ rowflag, int *__restrict__ need) {
+    __shared__ amk::GridWaveLds wl[4];
+    const int bps = (n_queries + 3) / 4;  // blocks per scene
+    const int xcd = blockIdx.x & 7;
+    const int j = blockIdx.x >> 3;
+    const int s = (j / bps) * 8 + xcd;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)  /* wave-uniform: keeps what derives from it in SGPRs */, lane = threadIdx.x & 63;
+    const int q = (j % bps) * 4 + w;
+    if (s >= n_scenes || q >= n_queries) return;
+    const size_t row = (size_t)s * n_queries + q;
+    const double *qp = queries + row * 3;
+    double ld;
+    int li, lpos;
+    const amk::GridScene gs = gpt.scene(s);
+    amk::grid_knn(gs, qp[0], qp[1], qp[2], k + 1, ld, li, lpos, &wl[w]);
+    const int size = sizes[s];
+    const int cnt = size < k ? size : (size > k ? k : 0);  // kd_tree_two.h:119-124
+    const double ld_next = __shfl_down(ld, 1);
+    const int li_next = __shfl_down(li, 1);
+    const bool tie = lane < cnt && li != amk::kNoIndex && li_next != amk::kNoIndex && ld == ld_next;
+    const bool any = __ballot(tie) != 0ull;
+    if (lane == 0) {
+        rowflag[row] = any;
+        if (any) need[s] = 1;   // (every wavefront that raises it stores the same value)
+        if (out_cnt) out_cnt[row] = cnt;
+    }
+    if (lane < k) {
+        const bool ok = lane < cnt && li != amk::kNoIndex;
+        const int idx = ok ? li : -1;
+        if (out_idx) out_idx[row * k + lane] = idx;
+        if (out_d2) out_d2[row * k + lane] = ok ? ld : DBL_MAX;
+        if (out_pts) {
+            const float4 rec = gs.pt[lpos];  // lpos = 0 for empty slots: a valid address
+            float *o = out_pts + (row * k + lane) * 3;
+            o[0] = ok ? rec.x : 0.f;
+            o[1] = ok ? rec.y : 0.f;
+            o[2] = ok ? rec.z : 0.f;
+        }
+    }
+}
+
+// The lazy build, for up to two handles per launch (blockIdx.y; the control step passes its obstacle and edge handle).  A
+// workgroup returns at once unless a query of its scene tied (need) and the scene's tree does not belong to the current cloud
+// yet (built); launched unconditionally behind every search, so the host never learns whether anything tied.
+struct AutoBuildArgs {
+    amk::ExactPtrs ep[2];
+    const float4 *gp[2];
+    float *x[2], *y[2], *z[2];
+    const int *sizes[2], *need[2];
+    int *built[2];
+};
+// the scene's index-ordered planes from its bucket records (kd_records_to_soa_kernel for one scene: the index build does not
+// write them in this mode, which would be 12 bytes per point stored for nothing on the untied path), then exact_build_top.
+// The scatter is what a tied scene pays over AMK_TIES_NANOFLANN, whose index build writes the planes coalesced: +0.29 ms per
+// 256 x 50 k-point build.  (Measured and not kept: the scatter as a kernel of its own -- 12 blocks per scene in dispatch order
+// 0.15 ms SLOWER, 16 or 64 blocks per scene pinned to the XCD s % 8 0.09 ms faster, which leaves 0.2 ms and costs every lazy
+// build one more launch that returns at once on the untied path: profiles/tie_auto_cost.txt.)
+__global__ __launch_bounds__(amk::kExactTopThreads) void kd_auto_build_top_kernel(const AutoBuildArgs a) {
+    const int s = blockIdx.x, h = blockIdx.y;
+    if (!a.need[h][s] || a.built[h][s]) return;   // (block-uniform)
+    const int cap = a.ep[h].cap, n = a.sizes[h][s];
+    const size_t base = (size_t)s * cap;
+    const float4 *gp = a.gp[h] + base;
+    float *xs = a.x[h] + base, *ys = a.y[h] + base, *zs = a.z[h] + base;
+    const float qnan = __builtin_nanf("");
+    for (int i = threadIdx.x; i < cap; i += amk::kExactTopThreads) {
+        if (i < n) {
+            const float4 r = gp[i];
+            const int idx = __float_as_int(r.w);   // < n: the padding stores below touch other elements
+            xs[idx] = r.x; ys[idx] = r.y; zs[idx] = r.z;
+        } else {
+            xs[i] = qnan; ys[i] = qnan; zs[i] = qnan;
+        }
+    }
+    __threadfence_block();
+    __syncthreads();   // the planes are read back by the tree build
+    amk::exact_build_top(a.ep[h].scene(s), n);
+}
+// exact_build_rest; the tree now belongs to the cloud held (also a tree that was given up: n_nodes = -1 says so)
+__global__ __launch_bounds__(amk::kExactThreads) void kd_auto_build_rest_kernel(const AutoBuildArgs a, int qcap) {
+    const int s = blockIdx.x, h = blockIdx.y;
+    if (!a.need[h][s] || a.built[h][s]) return;   // (block-uniform)
+    amk::exact_build_rest(a.ep[h].scene(s), a.sizes[h][s], qcap);
+    if (threadIdx.x == 0) a.built[h][s] = 1;
+}
+
+// kd_exact_search_kernel for the rows the search flagged, in the scenes whose tree is built
+__global__ __launch_bounds__(256) void kd_exact_search_auto_kernel(amk::ExactPtrs ep, const int *__restrict__ sizes, int n_scenes,
+                                                                   const double *__restrict__ queries, int n_queries, int k,
+                                                                   int *__restrict__ out_idx, double *__restrict__ out_d2,
+                                                                   float *__restrict__ out_pts, int *__restrict__ out_cnt,
+                                                                   const int *__restrict__ rowflag, const int *__restrict__ built) {
+    __shared__ amk::ExactWaveStack stacks[4];
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)  /* wave-uniform: keeps what derives from it in SGPRs */, lane = threadIdx.x & 63;
+    const size_t row = (size_t)blockIdx.x * 4 + w;
+    if (row >= (size_t)n_scenes * n_queries) return;
+    const int s = (int)(row / n_queries);
+    if (!rowflag[row] || !built[s]) return;   // (wave-uniform)
+    const amk::ExactTree T = ep.scene(s);
+    const double *qp = queries + row * 3;
+    const int size = sizes[s];
+    double rd;
+    int ri;
+    const int got = amk::exact_knn_wave(T, qp[0], qp[1], qp[2], k, rd, ri, &stacks[w]);
+    if (got < 0) return;
+    const int cnt = size < k ? size : (size > k ? k : 0);  // kd_tree_two.h:119-124
+    if (out_cnt && lane == 0) out_cnt[row] = cnt;
+    if (lane < k) {
+        const int j = lane;
+        const bool ok = j < cnt && j < got;
+        const int idx = ok ? ri : -1;
+        if (out_idx) out_idx[row * k + j] = idx;
+        if (out_d2) out_d2[row * k + j] = ok ? rd : DBL_MAX;
+        if (out_pts) {
+            float *o = out_pts + (row * k + j) * 3;
+            o[0] = ok ? T.x[idx] : 0.f;
+            o[1] = ok ? T.y[idx] : 0.f;
+            o[2] = ok ? T.z[idx] : 0.f;
+        }
+    }
+}
+
+// The mode's device memory: everything AMK_TIES_NANOFLANN holds plus the three words per scene and the row flags.  Called by
+// amk_kd_set_tie_order(AUTO) -- never by a search or a step.
+static int auto_alloc(amk_kd *kd) {
+    const size_t S = kd->n_scenes, tot = S * (size_t)kd->cap;
+    int st = exact_alloc(kd);
+    if (st != AMK_OK) return st;
+    if (!kd->x.p) AMK_HIP(kd->x.alloc(tot));
+    if (!kd->y.p) AMK_HIP(kd->y.alloc(tot));
+    if (!kd->z.p) AMK_HIP(kd->z.alloc(tot));
+    if (!kd->au_rowflag.p) {
+        AMK_HIP(kd->au_rowflag.alloc(S * AMK_MAX_QUERIES));
+        AMK_HIP(hipMemset(kd->au_rowflag.p, 0, sizeof(int) * S * AMK_MAX_QUERIES));
+    }
+    if (!kd->au_state.p) {
+        AMK_HIP(kd->au_state.alloc(3 * S));
+        AMK_HIP(hipMemset(kd->au_state.p, 0, sizeof(int) * 3 * S));
+    }
+    return AMK_OK;
+}
+// Called by EVERY index build of a handle, behind its launch: whatever trees the handle holds describe the previous cloud.
+static int auto_reset(amk_kd *kd, hipStream_t stream) {
+    kd->au_active = 0;
+    if (kd->tie_order != AMK_TIES_AUTO) return AMK_OK;
+    if (!kd->au_state.p) return AMK_ERR_INVALID_ARG;   // (amk_kd_set_tie_order allocated it)
+    AMK_HIP(hipMemsetAsync(kd->au_state.p, 0, sizeof(int) * 3 * (size_t)kd->n_scenes, stream));
+    kd->au_active = 1;
+    return AMK_OK;
+}
+static void auto_build_entry(AutoBuildArgs &a, int h, amk_kd *kd) {
+    a.ep[h] = amk_exact_ptrs(kd);
+    a.gp[h] = kd->gpt.p;
+    a.x[h] = kd->x.p; a.y[h] = kd->y.p; a.z[h] = kd->z.p;
+    a.sizes[h] = kd->size.p; a.need[h] = kd->au_need();
+    a.built[h] = kd->au_built();
+}
+int amk::kd_auto_build(amk_kd *a, amk_kd *b, hipStream_t stream) {
+    if (!a) { a = b; b = nullptr; }
+    if (!a) return AMK_OK;
+    if (b && b->n_scenes != a->n_scenes) return AMK_ERR_INVALID_ARG;
+    AutoBuildArgs args{};
+    auto_build_entry(args, 0, a);
+    if (b) auto_build_entry(args, 1, b);
+    const dim3 grid(a->n_scenes, b ? 2 : 1);
+    hipLaunchKernelGGL(kd_auto_build_top_kernel, grid, dim3(amk::kExactTopThreads), 0, stream, args);
+    hipLaunchKernelGGL(kd_auto_build_rest_kernel, grid, dim3(amk::kExactThreads), 0, stream, args, g_exact_queue_cap);
+    AMK_HIP(hipGetLastError());
     return AMK_OK;
 }
 
@@ -617,6 +803,8 @@ __global__ __launch_bounds__(kCompactThreads) void kd_sweep_compact_kernel(
 extern "C" int amk_kd_keyframe_sweep(amk_kd *keyframe, amk_kd *current, double th_dist, int th_count, int *d_outliers,
                                      int *d_rebuilt, void *stream_) {
     if (!keyframe || !current || keyframe == current || keyframe->n_scenes != current->n_scenes) return AMK_ERR_INVALID_ARG;
+    // (the sweep compacts the keyframe's cloud in place: a lazily built tree would go stale -- header)
+    if (keyframe->tie_order == AMK_TIES_AUTO || current->tie_order == AMK_TIES_AUTO) return AMK_ERR_UNSUPPORTED;
     hipStream_t stream = (hipStream_t)stream_;
     const int S = keyframe->n_scenes;
     if (!keyframe->flags.p) {
@@ -642,7 +830,7 @@ extern "C" int amk_kd_keyframe_sweep(amk_kd *keyframe, amk_kd *current, double t
     keyframe->async_pending = 1;
     AMK_HIP(hipGetLastError());
     keyframe->ex_valid = 0;   // a rebuilt keyframe's old tree describes another cloud
-    if (keyframe->tie_order) return exact_build(keyframe, stream);  // (the planes are valid: the sweep compacted them)
+    if (keyframe->tie_order == AMK_TIES_NANOFLANN) return exact_build(keyframe, stream);  // (the planes are valid: the sweep compacted them)
     return AMK_OK;
 }
 
@@ -1190,7 +1378,8 @@ int amk_kd_build(amk_kd *kd, const float *d_xyz, int point_stride, long long sce
         kd->async_pending = 1;
     }
     AMK_HIP(hipGetLastError());
-    if (kd->tie_order) return exact_build(kd, (hipStream_t)stream);
+    if (const int st = auto_reset(kd, (hipStream_t)stream); st != AMK_OK) return st;
+    if (kd->tie_order == AMK_TIES_NANOFLANN) return exact_build(kd, (hipStream_t)stream);
     return AMK_OK;
 }
 
@@ -1214,11 +1403,13 @@ int amk_kd_build_pair(amk_kd *obstacle, const float *d_xyz, const int *d_counts,
         }
     }
     AMK_HIP(hipGetLastError());
-    for (amk_kd *kd : {obstacle, edge})
-        if (kd->tie_order) {
+    for (amk_kd *kd : {obstacle, edge}) {
+        if (const int st = auto_reset(kd, (hipStream_t)stream); st != AMK_OK) return st;
+        if (kd->tie_order == AMK_TIES_NANOFLANN) {
             const int st = exact_build(kd, (hipStream_t)stream);
             if (st != AMK_OK) return st;
         }
+    }
     return AMK_OK;
 }
 
@@ -1257,21 +1448,30 @@ int kd_build_gang(amk_kd *obstacle, amk_kd *edge, int n_frames, int frame_scenes
         }
     }
     AMK_HIP(hipGetLastError());
-    for (amk_kd *kd : {obstacle, edge})
-        if (kd->tie_order) {
+    for (amk_kd *kd : {obstacle, edge}) {
+        if (const int st = auto_reset(kd, stream); st != AMK_OK) return st;
+        if (kd->tie_order == AMK_TIES_NANOFLANN) {
             const int st = exact_build(kd, stream);
             if (st != AMK_OK) return st;
         }
+    }
     return AMK_OK;
 }
 }  // namespace amk
 extern "C" {
 
 // internal (tests): number of nodes of every scene's reference-shaped tree (-1: not available), after synchronising
+// A handle in AMK_TIES_AUTO: 0 for a scene whose tree has not been built for the current cloud (no tree, no nodes).
 int amk__kd_exact_nodes(amk_kd *kd, int *h_nodes) {
     if (!kd || !h_nodes || !kd->ex_nn.p) return AMK_ERR_INVALID_ARG;
     AMK_HIP(hipDeviceSynchronize());
     AMK_HIP(hipMemcpy(h_nodes, kd->ex_nn.p, sizeof(int) * kd->n_scenes, hipMemcpyDeviceToHost));
+    if (kd->tie_order == AMK_TIES_AUTO) {
+        std::vector<int> built((size_t)kd->n_scenes, 0);
+        if (kd->au_active) AMK_HIP(hipMemcpy(built.data(), kd->au_built(), sizeof(int) * kd->n_scenes, hipMemcpyDeviceToHost));
+        for (int s = 0; s < kd->n_scenes; ++s)
+            if (!built[s]) h_nodes[s] = 0;
+    }
     return AMK_OK;
 }
 
@@ -1307,10 +1507,38 @@ static __global__ __launch_bounds__(64) void kd_exact_status_kernel(int S, const
     status[s] = deepest > (unsigned)amk::kExactMaxDepth ? AMK_EXACT_TOO_DEEP : AMK_EXACT_IN_USE;
 }
 
+// the same for a handle in AMK_TIES_AUTO: a scene without a tree for the current cloud has not needed one
+static __global__ __launch_bounds__(64) void kd_auto_status_kernel(int S, const int *__restrict__ built, const int *__restrict__ n_nodes,
+                                                                   const int *__restrict__ feat, const int *__restrict__ child,
+                                                                   unsigned *__restrict__ scratch, int max_nodes, int cap,
+                                                                   int *__restrict__ status) {
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= S) return;
+    if (!built[s]) { status[s] = AMK_EXACT_NOT_NEEDED; return; }
+    const int nn = n_nodes[s];
+    if (nn < 0) { status[s] = AMK_EXACT_GAVE_UP; return; }
+    const int *f = feat + (size_t)s * max_nodes, *c = child + (size_t)s * max_nodes;
+    unsigned *d = scratch + (size_t)s * cap;
+    unsigned deepest = 0;
+    if (nn > 0) d[0] = 0;
+    for (int id = 0; id < nn; ++id) {
+        const unsigned dep = d[id];
+        if (f[id] >= 0) { d[c[id]] = dep + 1; d[c[id] + 1] = dep + 1; }
+        else deepest = dep > deepest ? dep : deepest;
+    }
+    status[s] = deepest > (unsigned)amk::kExactMaxDepth ? AMK_EXACT_TOO_DEEP : AMK_EXACT_IN_USE;
+}
+
 // Which index answers a handle's searches, per scene (header).  Stream-ordered.
 int amk_kd_exact_status(amk_kd *kd, int *d_status, void *stream) {
     if (!kd || !d_status) return AMK_ERR_INVALID_ARG;
-    if (!kd->tie_order || !kd->ex_valid || !kd->ex_nn.p) {   // the bucketed index answers everything: not a fallback
+    if (kd->tie_order == AMK_TIES_AUTO && kd->au_active) {
+        hipLaunchKernelGGL(kd_auto_status_kernel, dim3((kd->n_scenes + 63) / 64), dim3(64), 0, (hipStream_t)stream, kd->n_scenes,
+                           kd->au_built(), kd->ex_nn.p, kd->ex_feat.p, kd->ex_child.p, kd->ex_sa.p, kd->ex_max_nodes, kd->cap, d_status);
+        AMK_HIP(hipGetLastError());
+        return AMK_OK;
+    }
+    if (kd->tie_order != AMK_TIES_NANOFLANN || !kd->ex_valid || !kd->ex_nn.p) {   // the bucketed index answers everything: not a fallback
         AMK_HIP(hipMemsetAsync(d_status, 0xff, sizeof(int) * kd->n_scenes, (hipStream_t)stream));   // AMK_EXACT_OFF == -1
         return AMK_OK;
     }
@@ -1333,7 +1561,11 @@ int amk_kd_exact_status_host(amk_kd *kd, int *h_status) {   // synchronises
 
 int amk_kd_set_tie_order(amk_kd *kd, int mode) {
     if (!kd) return AMK_ERR_INVALID_ARG;
-    if (mode != AMK_TIES_LOWEST_INDEX && mode != AMK_TIES_NANOFLANN) return AMK_ERR_UNSUPPORTED;
+    if (mode != AMK_TIES_LOWEST_INDEX && mode != AMK_TIES_NANOFLANN && mode != AMK_TIES_AUTO) return AMK_ERR_UNSUPPORTED;
+    if (mode == AMK_TIES_AUTO) {   // the mode's memory, here and not on the search path (a failure leaves the handle as it was)
+        const int st = auto_alloc(kd);
+        if (st != AMK_OK) return st;
+    }
     kd->tie_order = mode;
     return AMK_OK;
 }
@@ -1349,12 +1581,27 @@ int amk_kd_search(amk_kd *kd, const double *d_queries, int n_queries, int k, int
                   float *d_pts, int *d_counts, void *stream) {
     if (!kd || !d_queries || n_queries <= 0 || k <= 0) return AMK_ERR_INVALID_ARG;
     if (k > AMK_MAX_K || n_queries > AMK_MAX_QUERIES) return AMK_ERR_UNSUPPORTED;
+    if (kd->mode == 0 && kd->tie_order == AMK_TIES_AUTO && k + 1 > AMK_MAX_K) return AMK_ERR_UNSUPPORTED;   // (amk_kd_tie_flags' rule)
+    if (kd->auto_on()) {
+        // bucketed search with tie detection, lazy build, re-answer of the tied rows: four launches whatever the data holds
+        const int blocks = (kd->n_scenes + 7) / 8 * 8 * ((n_queries + 3) / 4);
+        hipLaunchKernelGGL(kd_grid_search_auto_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, grid_ptrs(kd), kd->size.p,
+                           kd->n_scenes, d_queries, n_queries, k, d_indices, d_sqdist, d_pts, d_counts, kd->au_rowflag.p, kd->au_need());
+        AMK_HIP(hipGetLastError());
+        if (const int st = amk::kd_auto_build(kd, nullptr, (hipStream_t)stream); st != AMK_OK) return st;
+        const size_t rows = (size_t)kd->n_scenes * n_queries;
+        hipLaunchKernelGGL(kd_exact_search_auto_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
+                           exact_ptrs(kd), kd->size.p, kd->n_scenes, d_queries, n_queries, k, d_indices, d_sqdist, d_pts, d_counts,
+                           kd->au_rowflag.p, kd->au_built());
+        AMK_HIP(hipGetLastError());
+        return AMK_OK;
+    }
     if (kd->mode == 0) {
         const int blocks = (kd->n_scenes + 7) / 8 * 8 * ((n_queries + 3) / 4);
         hipLaunchKernelGGL(kd_grid_search_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, grid_ptrs(kd), kd->size.p,
                            kd->n_scenes, d_queries, n_queries, k, d_indices, d_sqdist, d_pts, d_counts);
         AMK_HIP(hipGetLastError());
-        if (kd->tie_order && kd->ex_valid) {  // nanoflann's own traversal where its tree is available (and current)
+        if (kd->tie_order == AMK_TIES_NANOFLANN && kd->ex_valid) {  // nanoflann's own traversal where its tree is available (and current)
             const size_t rows = (size_t)kd->n_scenes * n_queries;
             hipLaunchKernelGGL(kd_exact_search_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                                exact_ptrs(kd), kd->size.p, kd->n_scenes, d_queries, n_queries, k, d_indices, d_sqdist, d_pts,
@@ -1426,6 +1673,7 @@ int amk_kd_search_host(amk_kd *kd, const double *h_queries, int n_queries, int k
                        float *h_pts, int *h_counts) {
     if (!kd || !h_queries || n_queries <= 0 || k <= 0) return AMK_ERR_INVALID_ARG;
     if (k > AMK_MAX_K || n_queries > AMK_MAX_QUERIES) return AMK_ERR_UNSUPPORTED;
+    if (kd->mode == 0 && kd->tie_order == AMK_TIES_AUTO && k + 1 > AMK_MAX_K) return AMK_ERR_UNSUPPORTED;   // (before anything is staged)
     const size_t rows = (size_t)kd->n_scenes * n_queries;
     // one device block and one pinned host block: [queries | sqdist | indices | counts | pts]
     const size_t o_q = 0, o_d2 = o_q + rows * 3 * sizeof(double), o_idx = o_d2 + rows * k * sizeof(double),

@@ -247,6 +247,9 @@ int launch_gang(amk_pipeline *p, amk_pipeline::Slot &s) {
     const int G = p->gang, S = c.n_scenes, N = amk_mpc_horizon(s.mpc), mi = c.step.mpc_max_iter;
     const int filled = (int)s.open.size();
     if (filled > G || filled > AMK_PIPELINE_MAX_GANG) return AMK_ERR_INVALID_ARG;   // (submit() never stages more than a gang)
+    // AMK_TIES_AUTO on the slot's handles (amk_pipeline_kd) is for the single-frame step only (header): refused before anything is launched
+    if ((s.map || !s.open[0].kf_obstacle.empty()) && ((s.obstacle && s.obstacle->tie_order == AMK_TIES_AUTO) || (s.edge && s.edge->tie_order == AMK_TIES_AUTO)))
+        return AMK_ERR_UNSUPPORTED;
     hipStream_t st = s.stream;
     for (const auto &f : s.open)   // inputs produced on the caller's streams: ordered on the device, not by the host
         if (f.input_ready) AMK_HIP(hipStreamWaitEvent(st, f.input_ready, 0));

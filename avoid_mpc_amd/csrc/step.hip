@@ -114,7 +114,10 @@ __global__ __launch_bounds__(256) void step_knn_grid_kernel(GridPtrs gobs, GridP
 }
 
 // PlanWapionts (:259-281) for reference point 0; called by the one wavefront that owns scene s.
-template <bool EXACT, bool GRID>
+// AUTO (obstacle handle in AMK_TIES_AUTO mode, GRID only): the re-query of the snapped point asks for K + 1 neighbours and makes
+// the tie test of kd_tie_flags_kernel on them (raw results: every slot counts); a tie raises the scene's `need` word for the lazy
+// tree build behind this kernel and `requery_tied`, which has step_requery_pack_auto_kernel redo the re-query in that tree.
+template <bool EXACT, bool GRID, bool AUTO = false>
 __device__ __forceinline__ void plan_scene(int s, GridPtrs gpt, ExactPtrs eobs,
                                                           const float *__restrict__ X, const float *__restrict__ Y,
                                                           const float *__restrict__ Z, int cap,
@@ -125,7 +128,8 @@ __device__ __forceinline__ void plan_scene(int s, GridPtrs gpt, ExactPtrs eobs,
                                                           float *__restrict__ knn_pts, double *__restrict__ knn_d2,
                                                           const float *__restrict__ edge_pt,
                                                           const double *__restrict__ edge_d2,
-                                                          int *__restrict__ flags) {
+                                                          int *__restrict__ flags, int *__restrict__ need = nullptr,
+                                                          int *__restrict__ requery_tied = nullptr) {
     const int lane = threadIdx.x;
     const int size_o = sizes_obs[s];
     // GetNearestDistance (FrameKDMap.cpp:400-427): SearchForNearest(p, 1) -> no result unless the cloud
@@ -154,7 +158,13 @@ __device__ __forceinline__ void plan_scene(int s, GridPtrs gpt, ExactPtrs eobs,
             int sli = kNoIndex;
             double sld = DBL_MAX;
             if constexpr (GRID) {
-                grid_knn(gs, ex, ey, ez, K, gld, gli, glpos, &wl1_store);
+                grid_knn(gs, ex, ey, ez, AUTO ? K + 1 : K, gld, gli, glpos, &wl1_store);
+                if constexpr (AUTO) {
+                    const double ld_next = __shfl_down(gld, 1);
+                    const int li_next = __shfl_down(gli, 1);
+                    const bool tie = lane < K && gli != kNoIndex && li_next != kNoIndex && gld == ld_next;
+                    if (__ballot(tie) != 0ull && lane == 0) { need[s] = 1; requery_tied[s] = 1; }
+                }
             } else {
                 ScanLds<1> &ws1 = ws1_store;
                 q1[0] = ex; q1[1] = ey; q1[2] = ez;  // every lane stores the same values
@@ -230,6 +240,129 @@ __global__ __launch_bounds__(kWave) void step_plan_pack_kernel(
                knn_d2, ref_states, done, flags);
 }
 
+// ---- AMK_TIES_AUTO (either handle): the same pass with tie detection in the queries that answer it, the reference-shaped tree
+// built lazily on the device for the scenes where something tied, and only the tied rows answered again by its traversal.
+// Every launch is unconditional (the host never learns whether anything tied): where nothing did, they return at once.
+struct StepAuto {
+    int obs, edge;               // the handle is in AMK_TIES_AUTO (and its flags are current)
+    int eager_obs, eager_edge;   // the handle is in AMK_TIES_NANOFLANN with a current tree: every row goes through it, as in step_knn_exact_kernel
+    ExactPtrs tobs, tedge;
+    int *need_obs, *need_edge;
+    const int *built_obs, *built_edge;
+    int *row_obs;                // [S][N] tie flag of obstacle query (s, q) of this pass
+    int *row_edge;               // [S]    tie flag of the edge query
+    int *requery_tied;           // [S]    the re-query of the snapped point tied in this pass
+};
+
+// step_knn_grid_kernel with one more candidate and the tie test for the handles in AMK_TIES_AUTO (raw results, so every one of the
+// k slots counts -- there is no adaptor count rule here).  A kernel of its own: the default one keeps its 48 registers.
+__global__ __launch_bounds__(256) void step_knn_grid_auto_kernel(GridPtrs gobs, GridPtrs gedge, int n_scenes,
+                                                                 const double *__restrict__ ref_path, int N, int K,
+                                                                 float *__restrict__ knn_pts, double *__restrict__ knn_d2,
+                                                                 float *__restrict__ edge_pt, double *__restrict__ edge_d2,
+                                                                 const int *__restrict__ done, StepAuto au) {
+    __shared__ GridWaveLds wl[4];
+    const int nq = N + 1;
+    const int bps = (nq + 3) / 4;
+    const int xcd = blockIdx.x & 7;
+    const int j = blockIdx.x >> 3;
+    const int s = (j / bps) * 8 + xcd;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int q = (j % bps) * 4 + w;
+    if (s >= n_scenes || q >= nq || done[s]) return;
+    const bool is_edge = q == N;
+    const double *qp = ref_path + ((size_t)s * N + (is_edge ? 0 : q)) * SD;  // read in place from mRefPath
+    const int k = is_edge ? 1 : K;
+    const bool detect = is_edge ? au.edge : au.obs;   // (wave-uniform)
+    double ld;
+    int li, lpos;
+    const GridScene gs = is_edge ? gedge.scene(s) : gobs.scene(s);
+    grid_knn(gs, qp[0], qp[1], qp[2], detect ? k + 1 : k, ld, li, lpos, &wl[w]);
+    if (detect) {
+        const double ld_next = __shfl_down(ld, 1);
+        const int li_next = __shfl_down(li, 1);
+        const bool tie = lane < k && li != kNoIndex && li_next != kNoIndex && ld == ld_next;
+        const bool any = __ballot(tie) != 0ull;
+        if (lane == 0) {
+            if (is_edge) au.row_edge[s] = any;
+            else au.row_obs[(size_t)s * N + q] = any;
+            if (any) (is_edge ? au.need_edge : au.need_obs)[s] = 1;   // (every wavefront that raises it stores the same value)
+        }
+    }
+    if (lane < k) {
+        const bool ok = li != kNoIndex;
+        const float4 rec = gs.pt[lpos];  // the neighbour's coordinates (lpos = 0 for an empty slot: a valid address)
+        if (is_edge) store_nbr(edge_pt, edge_d2, s, ok, ld, rec.x, rec.y, rec.z);
+        else store_nbr(knn_pts, knn_d2, ((size_t)s * N + q) * K + lane, ok, ld, rec.x, rec.y, rec.z);
+    }
+}
+
+// step_knn_exact_kernel for a pair of handles of which at least one is in AMK_TIES_AUTO: of such a handle only the rows the
+// kernel above flagged, and only where the scene's tree is built; a handle in AMK_TIES_NANOFLANN every row, as there.
+__global__ __launch_bounds__(256) void step_knn_exact_auto_kernel(StepAuto au, int n_scenes, const double *__restrict__ ref_path,
+                                                                  int N, int K, FrameBufs fb, const int *__restrict__ done) {
+    __shared__ ExactWaveStack stacks[4];
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)  /* wave-uniform: keeps what derives from it in SGPRs */, lane = threadIdx.x & 63;
+    const int t = blockIdx.x * 4 + w;
+    const int nq = N + 1;
+    if (t >= n_scenes * nq) return;
+    const int s = t / nq, q = t - s * nq;
+    if (done[s]) return;
+    const bool is_edge = q == N;
+    if (is_edge ? au.edge : au.obs) {
+        const int flagged = is_edge ? au.row_edge[s] : au.row_obs[(size_t)s * N + q];
+        if (!flagged || !(is_edge ? au.built_edge : au.built_obs)[s]) return;
+    } else if (!(is_edge ? au.eager_edge : au.eager_obs)) {
+        return;
+    }
+    const double *qp = ref_path + ((size_t)s * N + (is_edge ? 0 : q)) * SD;
+    const ExactTree T = is_edge ? au.tedge.scene(s) : au.tobs.scene(s);
+    const int k = is_edge ? 1 : K;
+    double rd;
+    int ri;
+    const int got = exact_knn_wave(T, qp[0], qp[1], qp[2], k, rd, ri, &stacks[w]);
+    if (got < 0) return;
+    if (lane < k) {
+        const bool ok = lane < got;
+        const float px = ok ? T.x[ri] : 0.f, py = ok ? T.y[ri] : 0.f, pz = ok ? T.z[ri] : 0.f;
+        if (is_edge) store_nbr(fb.edge_pt, fb.edge_d2, s, ok, rd, px, py, pz);
+        else store_nbr(fb.knn_pts, fb.knn_d2, ((size_t)s * N + q) * K + lane, ok, rd, px, py, pz);
+    }
+}
+
+// Obstacle handle in AMK_TIES_AUTO: the two halves of step_plan_pack_kernel as two kernels, because the tree the snapped point's
+// re-query may need can only be built between them (the query point is computed by the first half).
+__global__ __launch_bounds__(kWave) void step_plan_auto_kernel(
+    GridPtrs gpt, const int *__restrict__ sizes_obs, const int *__restrict__ sizes_edge, int N, int K, double safety_distance,
+    double *__restrict__ ref_path, float *__restrict__ knn_pts, double *__restrict__ knn_d2, const float *__restrict__ edge_pt,
+    const double *__restrict__ edge_d2, const int *__restrict__ done, int *__restrict__ flags, int *__restrict__ need,
+    int *__restrict__ requery_tied) {
+    const int s = blockIdx.x;
+    if (done[s]) return;
+    if (threadIdx.x == 0) requery_tied[s] = 0;   // (raised again below by the same lane)
+    plan_scene<false, true, true>(s, gpt, ExactPtrs{}, nullptr, nullptr, nullptr, 0, sizes_obs, nullptr, sizes_edge, N, K,
+                                  safety_distance, ref_path, knn_pts, knn_d2, edge_pt, edge_d2, flags, need, requery_tied);
+}
+// ... the second half: where the re-query tied and the scene's tree is built, exact_requery at the snapped point (reference
+// point 0, where plan_scene left it), as step_plan_pack_kernel<true, true> makes it for every snap; then pack_scene.
+__global__ __launch_bounds__(kWave) void step_requery_pack_auto_kernel(
+    ExactPtrs eobs, const int *__restrict__ requery_tied, const int *__restrict__ built, const int *__restrict__ sizes_obs, int N,
+    int K, int nref, int iter, int max_iter, double speed, double T, double safety_distance,
+    const double *__restrict__ state_quad, const double *__restrict__ pos_x, const double *__restrict__ ref_path,
+    float *__restrict__ knn_pts, double *__restrict__ knn_d2, double *__restrict__ ref_states, int *__restrict__ done,
+    const int *__restrict__ flags) {
+    const int s = blockIdx.x;
+    if (done[s]) return;
+    if (requery_tied[s] && built[s]) {   // (block-uniform)
+        const double *p1 = ref_path + (size_t)s * N * SD;
+        exact_requery(eobs.scene(s), p1[0], p1[1], p1[2], K, knn_pts, knn_d2, (size_t)s * N);
+        __threadfence_block();
+        __syncthreads();
+    }
+    pack_scene(s, sizes_obs, N, K, nref, iter, max_iter, speed, T, safety_distance, state_quad, pos_x, ref_path, knn_pts,
+               knn_d2, ref_states, done, flags);
+}
+
 }  // namespace
 
 void amk::launch_step_begin(int S, int *done, int *flags, double *u, hipStream_t stream) {
@@ -250,6 +383,8 @@ extern "C" int amk_step_batch(amk_kd *obstacle, amk_kd *edge, amk_mpc *mpc, cons
     if (!step_params_ok(mpc, prm)) return AMK_ERR_INVALID_ARG;
     hipStream_t stream = (hipStream_t)stream_;
     const int N = mpc->N, K = mpc->K;
+    // AMK_TIES_AUTO on the obstacle handle asks the bucketed index for K + 1 neighbours (the rule of amk_kd_tie_flags)
+    if (obstacle->mode == 0 && edge->mode == 0 && obstacle->tie_order == AMK_TIES_AUTO && K + 1 > AMK_MAX_K) return AMK_ERR_UNSUPPORTED;
     if (int st = ensure_step_workspace(mpc); st != AMK_OK) return st;
     const int S = mpc->launch_scenes();   // (amk_pipeline: a gang that is not full runs its leading scenes only)
     { TimedLaunch tl(KC_BEGIN, stream);
@@ -267,10 +402,21 @@ extern "C" int amk_step_batch(amk_kd *obstacle, amk_kd *edge, amk_mpc *mpc, cons
     const GridPtrs gobs = grid_ptrs(obstacle), gedge = grid_ptrs(edge);
     // handles in AMK_TIES_NANOFLANN mode (their reference-shaped trees were built by amk_kd_build)
     ExactPair ex{};
-    ex.use_obs = use_grid && obstacle->tie_order && obstacle->ex_valid;
-    ex.use_edge = use_grid && edge->tie_order && edge->ex_valid;
+    ex.use_obs = use_grid && obstacle->tie_order == AMK_TIES_NANOFLANN && obstacle->ex_valid;
+    ex.use_edge = use_grid && edge->tie_order == AMK_TIES_NANOFLANN && edge->ex_valid;
     if (ex.use_obs) ex.obs = amk_exact_ptrs(obstacle);
     if (ex.use_edge) ex.edge = amk_exact_ptrs(edge);
+    // handles in AMK_TIES_AUTO mode (their trees are built by this step, on the device, where a query ties)
+    const bool au_obs = use_grid && obstacle->auto_on(), au_edge = use_grid && edge->auto_on();
+    StepAuto au{};
+    if (au_obs || au_edge) {
+        au.obs = au_obs; au.edge = au_edge; au.eager_obs = ex.use_obs; au.eager_edge = ex.use_edge;
+        if (au_obs || ex.use_obs) au.tobs = amk_exact_ptrs(obstacle);
+        if (au_edge || ex.use_edge) au.tedge = amk_exact_ptrs(edge);
+        if (au_obs) { au.need_obs = obstacle->au_need(); au.built_obs = obstacle->au_built(); au.row_obs = obstacle->au_rowflag.p;
+                      au.requery_tied = obstacle->au_requery(); }
+        if (au_edge) { au.need_edge = edge->au_need(); au.built_edge = edge->au_built(); au.row_edge = edge->au_rowflag.p; }
+    }
     const FrameBufs out{mpc->knn_pts.p, mpc->knn_d2.p, mpc->edge_pt.p, mpc->edge_d2.p};
     // Rounds.  Plain schedule (no budget): round r IS pass r of every scene still in the loop, mpc_max_iter rounds.  With an
     // iteration budget B (amk_mpc_set_solve_budget) a solve launch of the first `budget_rounds` rounds ends after B iterations per
@@ -287,6 +433,14 @@ extern "C" int amk_step_batch(amk_kd *obstacle, amk_kd *edge, amk_mpc *mpc, cons
     const bool per_scene = rounds != mi;
     for (int iter = 0; iter < rounds; ++iter) {
         if (g_diag_skip & 1) {
+        } else if (au_obs || au_edge) {
+            TimedLaunch tl(KC_SCAN_OBS, stream);
+            hipLaunchKernelGGL(step_knn_grid_auto_kernel, dim3(S8 * ((N + 4) / 4)), dim3(256), 0, stream, gobs, gedge, S,
+                               d_ref_path, N, K, mpc->knn_pts.p, mpc->knn_d2.p, mpc->edge_pt.p, mpc->edge_d2.p,
+                               mpc->done.p, au);
+            if (int st = kd_auto_build(au_obs ? obstacle : nullptr, au_edge ? edge : nullptr, stream); st != AMK_OK) return st;
+            hipLaunchKernelGGL(step_knn_exact_auto_kernel, dim3((S * (N + 1) + 3) / 4), dim3(256), 0, stream, au, S, d_ref_path,
+                               N, K, out, mpc->done.p);
         } else if (use_grid) {
             TimedLaunch tl(KC_SCAN_OBS, stream);
             hipLaunchKernelGGL(step_knn_grid_kernel, dim3(S8 * ((N + 4) / 4)), dim3(256), 0, stream, gobs, gedge, S,
@@ -305,7 +459,16 @@ extern "C" int amk_step_batch(amk_kd *obstacle, amk_kd *edge, amk_mpc *mpc, cons
                            edge->y.p, edge->z.p, edge->cap, edge->size.p, edge->pmax.p, S, d_ref_path, N, 1, 1,
                            mpc->edge_pt.p, mpc->edge_d2.p, mpc->done.p); }
         }
-        if (!(g_diag_skip & 2)) { TimedLaunch tl(KC_PLAN, stream);
+        if (!(g_diag_skip & 2) && au_obs) { TimedLaunch tl(KC_PLAN, stream);
+        hipLaunchKernelGGL(step_plan_auto_kernel, dim3(S), dim3(kWave), 0, stream, gobs, obstacle->size.p, edge->size.p, N, K,
+                           prm->safety_distance, d_ref_path, mpc->knn_pts.p, mpc->knn_d2.p, mpc->edge_pt.p, mpc->edge_d2.p,
+                           mpc->done.p, d_flags, obstacle->au_need(), obstacle->au_requery());
+        if (int st = kd_auto_build(obstacle, nullptr, stream); st != AMK_OK) return st;
+        hipLaunchKernelGGL(step_requery_pack_auto_kernel, dim3(S), dim3(kWave), 0, stream, au.tobs, obstacle->au_requery(),
+                           obstacle->au_built(), obstacle->size.p, N, K, mpc->nref, per_scene ? -1 : iter, prm->mpc_max_iter,
+                           prm->speed, mpc->T, prm->safety_distance, d_state_quad, d_pos_x, d_ref_path, mpc->knn_pts.p,
+                           mpc->knn_d2.p, mpc->ref_states.p, mpc->done.p, d_flags);
+        } else if (!(g_diag_skip & 2)) { TimedLaunch tl(KC_PLAN, stream);
         auto plan_kernel = step_plan_pack_kernel<false, true>;
         if (!use_grid) plan_kernel = step_plan_pack_kernel<false, false>;
         else if (ex.use_obs) plan_kernel = step_plan_pack_kernel<true, true>;

@@ -395,8 +395,8 @@ static int run_frames(const FrameSet &fs, amk_kd *const *obstacle, amk_kd *const
         std::vector<char> cur(sizeof(FrameExact), 0);
         FrameExact *h = reinterpret_cast<FrameExact *>(cur.data());
         for (int f = 0; f < F; ++f) {
-            h->use_obs[f] = obstacle[f]->tie_order && obstacle[f]->ex_valid;
-            h->use_edge[f] = edge[f]->tie_order && edge[f]->ex_valid;
+            h->use_obs[f] = obstacle[f]->tie_order == AMK_TIES_NANOFLANN && obstacle[f]->ex_valid;
+            h->use_edge[f] = edge[f]->tie_order == AMK_TIES_NANOFLANN && edge[f]->ex_valid;
             // bytewise copies of zero-filled structs: the table is compared bytewise below, padding included
             if (h->use_obs[f]) { const ExactPtrs t = amk_exact_ptrs(obstacle[f]); std::memcpy(&h->obs[f], &t, sizeof t); }
             if (h->use_edge[f]) { const ExactPtrs t = amk_exact_ptrs(edge[f]); std::memcpy(&h->edge[f], &t, sizeof t); }
@@ -473,6 +473,8 @@ extern "C" int amk_step_batch_frames(amk_kd *const *obstacle, amk_kd *const *edg
     for (int f = 0; f < F; ++f) {
         if (!obstacle[f] || !edge[f] || obstacle[f]->n_scenes != S || edge[f]->n_scenes != S) return AMK_ERR_INVALID_ARG;
         if (obstacle[f]->mode != 0 || edge[f]->mode != 0) return AMK_ERR_UNSUPPORTED;  // bucketed indices only
+        // (no lazily built trees on the multi-frame path -- header)
+        if (obstacle[f]->tie_order == AMK_TIES_AUTO || edge[f]->tie_order == AMK_TIES_AUTO) return AMK_ERR_UNSUPPORTED;
         fs.obs[f] = grid_ptrs(obstacle[f]);
         fs.edge[f] = grid_ptrs(edge[f]);
         fs.size_obs[f] = obstacle[f]->size.p;

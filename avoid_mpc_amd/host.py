@@ -42,12 +42,15 @@ class KdBatch:
     __del__ = close
 
     def set_tie_order(self, mode):
-        """capi.AMK_TIES_LOWEST_INDEX (default) or capi.AMK_TIES_NANOFLANN; takes effect at the next build."""
+        """capi.AMK_TIES_LOWEST_INDEX (default), capi.AMK_TIES_NANOFLANN (the reference's tree for every scene at every build) or
+        capi.AMK_TIES_AUTO (the same answers; the tree is built on the device only for scenes where a query ties, and only tied
+        queries go through it; search k + 1 <= AMK_MAX_K, single-frame step only).  Takes effect at the next build."""
         capi.check(self.lib.amk_kd_set_tie_order(self.h, int(mode)), "amk_kd_set_tie_order")
 
     def exact_status(self, stream=None):
         """amk_kd_exact_status: int32 device tensor [S] -- -1 mode off / 0 the reference-shaped tree answers / 1 its build gave up /
-        2 deeper than the traversal stack (1, 2: the bucketed index answers)."""
+        2 deeper than the traversal stack (1, 2: the bucketed index answers) / 3 (AMK_TIES_AUTO only) no query of the scene has tied
+        since the last build, so it has no tree and the bucketed index has given the reference's answers."""
         st = torch.empty(self.S, dtype=torch.int32, device="cuda")
         capi.check(self.lib.amk_kd_exact_status(self.h, capi.dptr(st), capi.stream_ptr(stream)), "amk_kd_exact_status")
         return st

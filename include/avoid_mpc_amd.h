@@ -105,9 +105,26 @@ int amk_kd_tie_flags(amk_kd *kd, const double *d_queries, int query_stride, int 
  * re-query then go through nanoflann's traversal too).  A scene whose tree would exceed the node capacity
  * (cap / 2 + 64) or a traversal depth of 48 -- pathological data -- keeps the bucketed index's answer.  The mode takes effect at the NEXT
  * build: a search between amk_kd_set_tie_order(NANOFLANN) and that build still answers from the bucketed index (the
- * handle tracks whether its exact tree belongs to the cloud it currently holds).                                        */
+ * handle tracks whether its exact tree belongs to the cloud it currently holds).
+ * AMK_TIES_AUTO: the answers of AMK_TIES_NANOFLANN at close to the default's price when ties are rare.  The bucketed index
+ * answers every query with k + 1 neighbours and tests the k + 1 for two equal squared distances (the test of amk_kd_tie_flags);
+ * only a scene with such a query gets the reference's tree -- built on the device, behind the search that saw the tie, once per
+ * cloud -- and only the tied queries are answered again by nanoflann's traversal.  Without a tie among the k + 1 nearest the
+ * two orders give the same list, so indices, sqdist, pts and counts equal those of AMK_TIES_NANOFLANN bit for bit (a scene
+ * whose tree is given up or too deep keeps the bucketed answer for its tied queries, as there).  Nothing synchronises with the
+ * host: the search enqueues the lazy build and the re-answer unconditionally, they return at once where nothing tied.  k + 1 <=
+ * AMK_MAX_K (else AMK_ERR_UNSUPPORTED).  The tree's memory is allocated by amk_kd_set_tie_order(AUTO), never by a search or a
+ * step; the mode takes effect at the NEXT build; every index build of the handle forgets the trees of the previous cloud.
+ * Searches of ONE handle in this mode share its tie flags and must not overlap on different streams.  amk_step_batch (and
+ * amk_pipeline_* without keyframes) honours the mode on either handle: the N obstacle queries, the edge query and the edge
+ * snap's re-query, in every pass, with the result of the same step in AMK_TIES_NANOFLANN mode (K + 1 <= AMK_MAX_K).  The
+ * multi-frame paths do NOT support it: amk_step_batch_frames with a handle in this mode, amk_kd_keyframe_sweep with either
+ * handle in it (the sweep compacts a cloud in place: a lazily built tree would go stale) and a pipeline slot with a keyframe
+ * map or keyframe handles whose amk_pipeline_kd handles are in it return AMK_ERR_UNSUPPORTED before launching anything;
+ * the keyframe map's own pool handles stay in the default mode.  A handle in scan mode ignores the mode.                  */
 #define AMK_TIES_LOWEST_INDEX 0
 #define AMK_TIES_NANOFLANN 1
+#define AMK_TIES_AUTO 2
 int amk_kd_set_tie_order(amk_kd *kd, int mode);
 /* Whether AMK_TIES_NANOFLANN holds for a scene: d_status[s] (device, [n_scenes], stream-ordered after the build it describes)
  *   AMK_EXACT_OFF      (-1) the mode is off, or no build has run since it was switched on: the bucketed index answers (by design)
@@ -116,12 +133,16 @@ int amk_kd_set_tie_order(amk_kd *kd, int mode);
  *                           the bucketed index answers -- same distances, equal distances in cloud-index order
  *   AMK_EXACT_TOO_DEEP ( 2) the tree exists but is deeper than the traversal stack (48 levels): queries that would descend past
  *                           it are answered by the bucketed index, the others by the tree
+ *   AMK_EXACT_NOT_NEEDED (3) AMK_TIES_AUTO only: no query of the scene has tied since the last build, so no tree exists and the
+ *                           bucketed index has answered everything -- which is the reference's answer.  In AMK_TIES_AUTO the
+ *                           values 0 / 1 / 2 describe the scenes whose tree has been built for the current cloud.
  * A caller that NEEDS the reference's index lists checks this after the build; 1 and 2 are pathological data (never seen on
  * depth-derived or synthetic clouds; tests force them with a shrunken ring and a geometric point sequence).              */
 #define AMK_EXACT_OFF (-1)
 #define AMK_EXACT_IN_USE 0
 #define AMK_EXACT_GAVE_UP 1
 #define AMK_EXACT_TOO_DEEP 2
+#define AMK_EXACT_NOT_NEEDED 3
 int amk_kd_exact_status(amk_kd *kd, int *d_status, void *stream);
 int amk_kd_exact_status_host(amk_kd *kd, int *h_status);   /* the same into host memory; synchronises the device */
 

@@ -65,9 +65,20 @@ public:
         if (kd_) amk_throw(amk_kd_set_tie_order(kd_, tie_order_), "amk_kd_set_tie_order");
     }
 
+    // Not in the reference: the tie order by name -- AMK_TIES_LOWEST_INDEX, AMK_TIES_NANOFLANN (= SetNanoflannTieOrder(true)) or
+    // AMK_TIES_AUTO: the reference's `indices` as well, but nanoflann's tree is built lazily, on the device, and only once a
+    // search of the current cloud meets two equal squared distances among its k + 1 nearest (k + 1 <= AMK_MAX_K then).
+    void SetTieOrder(int mode) {
+        if (kd_) amk_throw(amk_kd_set_tie_order(kd_, mode), "amk_kd_set_tie_order");
+        else if (mode != AMK_TIES_LOWEST_INDEX && mode != AMK_TIES_NANOFLANN && mode != AMK_TIES_AUTO) amk_throw(AMK_ERR_UNSUPPORTED, "amk_kd_set_tie_order");
+        tie_order_ = mode;
+    }
+
     // Not in the reference: whether SetNanoflannTieOrder(true) holds for the cloud the tree currently indexes --
     // AMK_EXACT_IN_USE (0): searches follow nanoflann's own tree; AMK_EXACT_GAVE_UP (1) / AMK_EXACT_TOO_DEEP (2): pathological
-    // data, the bucketed index answers (same distances, equal distances in index order); AMK_EXACT_OFF (-1): mode off / no build
+    // data, the bucketed index answers (same distances, equal distances in index order); AMK_EXACT_OFF (-1): mode off / no build;
+    // AMK_EXACT_NOT_NEEDED (3), after SetTieOrder(AMK_TIES_AUTO) only: no search of the current cloud has tied, so there is no
+    // tree and the bucketed index has given the reference's answers
     int NanoflannTieOrderStatus() const {
         int st = AMK_EXACT_OFF;
         if (kd_) amk_throw(amk_kd_exact_status_host(kd_, &st), "amk_kd_exact_status_host");
