@@ -48,7 +48,16 @@ constexpr int kGridParamDoubles = 8;  // bbmin[3], h, inv_h, gx, gy, gz
 // ------------------------------------------------------------------------------------------------
 // build: one block per scene over the compacted SoA planes
 // ------------------------------------------------------------------------------------------------
+// A point with a NaN or infinite coordinate is at no squared distance < DBL_MAX from any query: it goes to the trash bucket
+// and is never returned.  Every other point is at a finite fp64 distance from every float query (< 1.4e78) and must be
+// found, FLT_MAX included (the streaming scan of kd_device.h returns it: both modes answer alike).
 __device__ __forceinline__ bool finite3(float x, float y, float z) {
+    return fabsf(x) <= FLT_MAX && fabsf(y) <= FLT_MAX && fabsf(z) <= FLT_MAX;  // false for NaN and inf
+}
+// What a bounding box is taken over: the boxes start from +-3.0e38 as "empty", so a coordinate beyond that stays out of them (and
+// out of the grid's geometry: one such point would stretch the cells over the whole float range).  A point outside the box is
+// clamped into a boundary cell like any other point the sampled box missed.
+__device__ __forceinline__ bool boxable3(float x, float y, float z) {
     return fabsf(x) <= 3.0e38f && fabsf(y) <= 3.0e38f && fabsf(z) <= 3.0e38f;  // false for NaN and inf
 }
 
@@ -410,6 +419,18 @@ struct GridScene {
     int nt;                     // tiles: cell c = the runs [cs[t][c], cs[t][c + 1]) for t < nt
 };
 
+// Points of the scene's index with a non-finite coordinate (the trash bucket, bucket ncell of every tile).  A scene that was
+// never built has zeroed tables and geometry: 0.
+__device__ __forceinline__ int grid_trash_count(const GridScene &gs) {
+    const int ncell = (int)gs.gp[5] * (int)gs.gp[6] * (int)gs.gp[7];
+    int n = 0;
+    for (int t = 0; t < gs.nt; ++t) {
+        const int *cst = gs.cs + (size_t)t * (kGridMaxCells + 2);
+        n += cst[ncell + 1] - cst[ncell];
+    }
+    return n;
+}
+
 struct GridPtrs {  // the batch: what a kernel needs to find scene s
     const float4 *pt;
     const int *cs;
@@ -769,8 +790,12 @@ __device__ __forceinline__ double grid_nn1_thread(const GridScene &gs, double qx
 // the 50 k-point flight frames: 20-24 ms per 512-scene sweep with the ring walk once the vehicles fly among the cylinders,
 // where most keyframe points have their nearest current point in a NEIGHBOUR cell or none within th).  Leaves at the first point
 // within th (sqrt is monotone: the minimum is within th too).  Returns 1 = outlier, 0 = not (also when the index holds no
-// point with finite coordinates: the reference then has no result to test).  Same flags as `sqrt(grid_nn1_thread(...)) > th`
-// (tests/test_keyframe_gpu.py, test_kfmap_gpu.py).
+// point with finite coordinates: nothing is nearest, nothing was left behind).  A query with a NaN or infinite coordinate is
+// an outlier whenever the index holds a point with finite coordinates.  On finite queries the same flags as
+// `sqrt(grid_nn1_thread(...)) > th` (tests/test_keyframe_gpu.py, test_kfmap_gpu.py); grid_nn1_thread answers DBL_MAX for a NaN
+// query only.  The keyframe map's pool calls this too when it sweeps against the frames' own indices (kd_sweep_mapped with
+// g_sweep_target 0, an A/B setting): its hashed target (the default) treats non-finite keyframe points differently, and the map
+// is unspecified for such frames (header).
 #ifndef AMK_SWEEP_TILES
 #define AMK_SWEEP_TILES 2
 #endif
@@ -784,7 +809,10 @@ __device__ __forceinline__ int grid_outlier_thread(const GridScene &gs, double q
     const double h = gs.gp[3], inv_h = gs.gp[4];
     const int g[3] = {(int)gs.gp[5], (int)gs.gp[6], (int)gs.gp[7]};
     const double q[3] = {qx, qy, qz};
-    if (!(qx == qx && qy == qy && qz == qz)) return 0;
+    // a query with a NaN or infinite coordinate is within th of nothing (every distance is NaN or inf): no row is walked -- its
+    // cube's corners are not numbers that have a cell (inf - inf) --, the tail decides.  SearchForNearest(pt, 1) hands the
+    // reference DBL_MAX for such a point, which is farther than any th.
+    const bool qbad = !(fabs(qx) <= DBL_MAX && fabs(qy) <= DBL_MAX && fabs(qz) <= DBL_MAX);
     // (the cube is widened by a rounding allowance: a point whose computed distance is <= th may be th + 1 ulp away along one axis)
     const double r = th + 1e-9 * h + 1e-12 * (fabs(qx) + fabs(qy) + fabs(qz) + fabs(b[0]) + fabs(b[1]) + fabs(b[2]) + th);
     int lo[3], hi[3];
@@ -800,7 +828,7 @@ __device__ __forceinline__ int grid_outlier_thread(const GridScene &gs, double q
     const bool q_is_float = (double)qxf == qx && (double)qyf == qy && (double)qzf == qz;
     const float t2f = q_is_float ? (float)(t2 * (1.0 + 1e-5)) * (1.0f + 1e-6f) : __builtin_inff();
     // rows (iy, iz) of the cube, the query's OWN row first: that is where a point within th most likely lies, and the first one ends the walk
-    const int ny = hi[1] - lo[1] + 1, nrows = ny * (hi[2] - lo[2] + 1);
+    const int ny = hi[1] - lo[1] + 1, nrows = qbad ? 0 : ny * (hi[2] - lo[2] + 1);
     const int own = (cell_of(q[2], b[2], inv_h, g[2]) - lo[2]) * ny + (cell_of(q[1], b[1], inv_h, g[1]) - lo[1]);
     for (int r = 0; r < nrows; ++r) {
         {

@@ -116,7 +116,7 @@ __device__ __forceinline__ void sample_bbox_scene(int s, const float *__restrict
         if (i >= n) break;
         const float *p = src + (size_t)i * point_stride;
         const float px = p[0], py = p[1], pz = p[2];
-        if (amk::finite3(px, py, pz)) {
+        if (amk::boxable3(px, py, pz)) {
             bmn[0] = fminf(bmn[0], px); bmx[0] = fmaxf(bmx[0], px);
             bmn[1] = fminf(bmn[1], py); bmx[1] = fmaxf(bmx[1], py);
             bmn[2] = fminf(bmn[2], pz); bmx[2] = fmaxf(bmx[2], pz);
@@ -372,8 +372,20 @@ __global__ __launch_bounds__(256) void kd_tie_flags_kernel(amk::GridPtrs gpt, co
 // ------------------------------------------------------------------------------------------------
 // opt-in nanoflann tie order (kd_exact.h): the reference's own tree beside the bucketed index
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(amk::kExactTopThreads) void kd_exact_build_top_kernel(amk::ExactPtrs ep, const int *__restrict__ sizes) {
+// The guard of both builds: nanoflann's divideTree compares coordinates against split planes and is undefined on a NaN or an
+// infinity (the reference's own header ends with a segmentation fault on most clouds that keep such a point; some build and
+// then prune wrongly).  A scene whose bucketed index holds anything in its trash bucket does not start the build: its tree is
+// marked unavailable (amk_kd_exact_status: AMK_EXACT_GAVE_UP), the bucketed index answers.  Decided on the device, from
+// the index the build kernel has just written on the same stream.  Block-uniform.
+__device__ __forceinline__ bool exact_refused(const amk::GridScene &gs, const amk::ExactTree &T) {
+    if (amk::grid_trash_count(gs) == 0) return false;
+    if (threadIdx.x == 0) *T.n_nodes = -1;   // (exact_build_rest then finds nothing to do and leaves it at -1)
+    return true;
+}
+__global__ __launch_bounds__(amk::kExactTopThreads) void kd_exact_build_top_kernel(amk::ExactPtrs ep, amk::GridPtrs gpt,
+                                                                                   const int *__restrict__ sizes) {
     const int s = blockIdx.x;
+    if (exact_refused(gpt.scene(s), ep.scene(s))) return;
     amk::exact_build_top(ep.scene(s), sizes[s]);
 }
 __global__ __launch_bounds__(amk::kExactThreads) void kd_exact_build_kernel(amk::ExactPtrs ep, const int *__restrict__ sizes, int qcap) {
@@ -446,7 +458,8 @@ static int exact_build(amk_kd *kd, hipStream_t stream) {
     int st = exact_alloc(kd);
     if (st == AMK_OK) st = ensure_soa(kd, stream);
     if (st != AMK_OK) return st;
-    hipLaunchKernelGGL(kd_exact_build_top_kernel, dim3(kd->n_scenes), dim3(amk::kExactTopThreads), 0, stream, exact_ptrs(kd), kd->size.p);
+    hipLaunchKernelGGL(kd_exact_build_top_kernel, dim3(kd->n_scenes), dim3(amk::kExactTopThreads), 0, stream, exact_ptrs(kd),
+                       grid_ptrs(kd), kd->size.p);
     hipLaunchKernelGGL(kd_exact_build_kernel, dim3(kd->n_scenes), dim3(amk::kExactThreads), 0, stream, exact_ptrs(kd),
                        kd->size.p, g_exact_queue_cap);
     AMK_HIP(hipGetLastError());
@@ -511,6 +524,7 @@ __global__ __launch_bounds__(256) void kd_grid_search_auto_kernel(amk::GridPtrs 
 // yet (built); launched unconditionally behind every search, so the host never learns whether anything tied.
 struct AutoBuildArgs {
     amk::ExactPtrs ep[2];
+    amk::GridPtrs grid[2];
     const float4 *gp[2];
     float *x[2], *y[2], *z[2];
     const int *sizes[2], *need[2];
@@ -525,6 +539,7 @@ struct AutoBuildArgs {
 __global__ __launch_bounds__(amk::kExactTopThreads) void kd_auto_build_top_kernel(const AutoBuildArgs a) {
     const int s = blockIdx.x, h = blockIdx.y;
     if (!a.need[h][s] || a.built[h][s]) return;   // (block-uniform)
+    if (exact_refused(a.grid[h].scene(s), a.ep[h].scene(s))) return;   // (kd_auto_build_rest_kernel marks the scene built: GAVE_UP)
     const int cap = a.ep[h].cap, n = a.sizes[h][s];
     const size_t base = (size_t)s * cap;
     const float4 *gp = a.gp[h] + base;
@@ -617,6 +632,7 @@ static int auto_reset(amk_kd *kd, hipStream_t stream) {
 }
 static void auto_build_entry(AutoBuildArgs &a, int h, amk_kd *kd) {
     a.ep[h] = amk_exact_ptrs(kd);
+    a.grid[h] = grid_ptrs(kd);
     a.gp[h] = kd->gpt.p;
     a.x[h] = kd->x.p; a.y[h] = kd->y.p; a.z[h] = kd->z.p;
     a.sizes[h] = kd->size.p; a.need[h] = kd->au_need();
@@ -761,7 +777,7 @@ __global__ __launch_bounds__(kCompactThreads) void kd_sweep_compact_kernel(
                 xs[o] = px[e]; ys[o] = py[e]; zs[o] = pz[e];
                 ++o;
                 amax = fmaxf(amax, fmaxf(fabsf(px[e]), fmaxf(fabsf(py[e]), fabsf(pz[e]))));
-                if (amk::finite3(px[e], py[e], pz[e])) {
+                if (amk::boxable3(px[e], py[e], pz[e])) {
                     bmn[0] = fminf(bmn[0], px[e]); bmx[0] = fmaxf(bmx[0], px[e]);
                     bmn[1] = fminf(bmn[1], py[e]); bmx[1] = fmaxf(bmx[1], py[e]);
                     bmn[2] = fminf(bmn[2], pz[e]); bmx[2] = fmaxf(bmx[2], pz[e]);
@@ -854,8 +870,11 @@ __global__ __launch_bounds__(amk::kGridBuildThreads) void kd_grid_build_list_ker
 // once the frames are a forward-looking sensor's and every robot sweeps every period (profiles/r05_sweep_target.txt).  Here the
 // current frame of every sweep row is sorted once more into cubic cells of edge 2.5 th on a world-fixed lattice, hashed into
 // kSweepBuckets buckets (a bucket may hold several cells: more candidates, the same answer -- the distance test decides): the cube of
-// a query touches <= 2 cells per axis, ~5 points each on a surface.  Points with a non-finite coordinate stay out (they are
-// within th of nothing); their absence is what `finite == 0` reports.
+// a query touches <= 2 cells per axis, ~5 points each on a surface.  Points with a NaN, an infinite or a |coordinate| > 3.0e38
+// stay out (boxable3: the rule this grid was written and tested with); their absence is what `finite == 0` reports.  The map is
+// UNSPECIFIED for frames with such points (header): a keyframe point with an infinite coordinate passes the mark kernel's
+// `q == q` gate and is an outlier on a row's first sweep, one with a NaN never is, and on later sweeps of the row (the keyframe
+// taken from the previous generation's grid) neither is visited.  amk_kd_keyframe_sweep does not come here.
 // ------------------------------------------------------------------------------------------------
 constexpr int kSweepBuckets = 16384;   // at most: 64 KB of LDS histogram per build block; a pool of small frames takes fewer (sweep_buckets)
 constexpr int kSweepBuildThreads = 1024;
@@ -912,7 +931,7 @@ __global__ __launch_bounds__(kSweepBuildThreads) void kd_sweep_hash_build_kernel
     const int sc = cur_list[row];
     if (tid == 0) src[row] = sc;
     // the keyframe is the frame this row swept against last time: the mark kernel takes its points from that grid, which leaves out the
-    // points with a non-finite coordinate -- their flag is 0 (no outlier: within th of nothing, but SearchForNearest gives them no result)
+    // points with a non-finite coordinate -- their flag is 0 (not what amk_kd_keyframe_sweep decides for them: the map is unspecified there)
     if (src_prev[row] == kf)
         for (int i = tid; i < sizes[kf]; i += kSweepBuildThreads) flags[(size_t)kf * cap + i] = 0;
     const int n = sizes[sc];
@@ -933,7 +952,7 @@ __global__ __launch_bounds__(kSweepBuildThreads) void kd_sweep_hash_build_kernel
         }
 #pragma unroll
         for (int u = 0; u < U; ++u)
-            if (i0 + u * kSweepBuildThreads < n && amk::finite3(x[u], y[u], z[u]))
+            if (i0 + u * kSweepBuildThreads < n && amk::boxable3(x[u], y[u], z[u]))
                 atomicAdd(&hist[sweep_bucket(sweep_cell(x[u], inv_hf), sweep_cell(y[u], inv_hf), sweep_cell(z[u], inv_hf), nb)], 1);
     }
     __syncthreads();
@@ -966,7 +985,7 @@ __global__ __launch_bounds__(kSweepBuildThreads) void kd_sweep_hash_build_kernel
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int i = i0 + u * kSweepBuildThreads;
-            if (i < n && amk::finite3(x[u], y[u], z[u])) {
+            if (i < n && amk::boxable3(x[u], y[u], z[u])) {
                 const int pos = atomicAdd(&hist[sweep_bucket(sweep_cell(x[u], inv_hf), sweep_cell(y[u], inv_hf), sweep_cell(z[u], inv_hf), nb)], 1);
 #ifndef AMK_DIAG_NOSTORE   // (diagnostics: without the scatter the kernel takes 169 of its 458 us)
                 out[pos] = make_float4(x[u], y[u], z[u], __int_as_float(id[u]));

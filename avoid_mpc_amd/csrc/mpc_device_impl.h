@@ -859,7 +859,12 @@ __device__ __forceinline__ void solve_scene(real *sm, const LdsMap &L, int N, in
 #else
         adjoint_sweep(sm, L, N, prm_g);
 #endif
-        return J + box_errors(sm, L, nvar, SC_MU, o_s_max, acc, err);
+        const real phi = J + box_errors(sm, L, nvar, SC_MU, o_s_max, acc, err);
+        // A merit value that is not a number (a NaN in the state, the path or the neighbours) is not an optimality error of zero: the
+        // max-norms above drop NaNs (fmax), and the solve used to report status 0 after 0 iterations on such a problem.  With NaN errors
+        // no convergence test and no barrier update passes, and the solve ends as "failed" (status 1 or 2) like any other that finds no step.
+        if (!(phi == phi)) { err[0] = phi; err[1] = phi; }
+        return phi;
     };
     // starting barrier parameter: the duals start on the central path of whatever SC_MU is chosen, so mu_init is lowered
     // level by level while the start already solves that level's barrier problem to the accuracy at which the barrier

@@ -86,6 +86,32 @@ int amk_kd_sizes(amk_kd *kd, int *h_sizes, void *stream);
 int amk_kd_search(amk_kd *kd, const double *d_queries, int n_queries, int k, int *d_indices,
                   double *d_sqdist, float *d_pts, int *d_counts, void *stream);
 
+/* Non-finite coordinates (NaN, +-inf, values whose squared distance overflows) -- what amk_kd_build, amk_kd_build_pair,
+ * amk_kd_search, amk_kd_tie_flags and their host variants do with them; tests/test_nonfinite_gpu.py asserts every sentence.
+ *   * A point whose x is NaN is dropped by the build (as above).  EVERY other point is kept, keeps its index and counts in
+ *     amk_kd_sizes -- a NaN y or z and an infinity in any coordinate included, as in the reference (kd_tree_two.h:99 tests x).
+ *   * A kept point is USABLE for a query iff its squared distance, evaluated in fp64 as the adaptor does
+ *     (((qx - x)^2 + (qy - y)^2) + (qz - z)^2), is < DBL_MAX: false for NaN, for inf and for a sum that overflows (a query
+ *     coordinate of 1e200).  An unusable point is never returned, by the bucketed index and by the streaming scan alike, in
+ *     any tie order.  A finite float is usable for every float query (< 1.4e78): a coordinate of FLT_MAX is returned when
+ *     nothing is nearer.  A query at 1e150 is answered normally (squares near 1e300).
+ *   * d_counts follows the size rule above whatever is usable; the slots beyond the usable points hold -1 / DBL_MAX / (0,0,0).
+ *     So a query with a NaN or infinite coordinate gets `count` empty slots, and no tie flag.  This is the one place where
+ *     the choice changes control flow against the reference as restated: amk_step_batch re-plans when the nearest squared
+ *     distance of a reference point is within the safety distance, and an empty slot's DBL_MAX is not, where the restated
+ *     reference's 0.0 is -- a scene whose solve failed (NaN predicted states) makes 1 solve here, 3 in oracle/step_oracle.c.
+ *   * The reference differs in those slots: with zero-initialised result buffers it hands out index 0 / distance 0.0 /
+ *     point 0 in every slot the traversal did not fill and DBL_MAX in the last (oracle/_ref, recorded in tests/golden/
+ *     kd_ref_golden.npz; its own buffers are uninitialised, kd_tree_two.h:114-115).  And for a cloud that KEEPS a non-finite
+ *     point it has no behaviour at all: nanoflann's divideTree compares coordinates with split planes, and on most such
+ *     clouds the build ends in a segmentation fault (200 NaN y + 200 NaN z, 50 inf y / -inf z, 50 +inf x, all but five
+ *     NaN y, each in 3000 points), on others it builds and then prunes wrongly.  There this library's answer is the rule
+ *     above, whose plain restatement is tests/_oracle.py kd_brute_np.
+ *   * AMK_TIES_NANOFLANN / AMK_TIES_AUTO: a scene whose cloud keeps a point with a NaN or infinite coordinate does not get
+ *     the reference-shaped tree (decided on the device, per scene, at the point where the build would start):
+ *     amk_kd_exact_status reports AMK_EXACT_GAVE_UP, the bucketed index answers by the rule above, equal distances in
+ *     cloud-index order.  The other scenes of the batch are unaffected.                                                   */
+
 /* Tie visibility.  For every query: d_tie_flags[s][q] = 1 when, among the k + 1 nearest points, two are at exactly the same
  * squared distance (two returned neighbours, or the k-th returned one and the best rejected one), else 0.  nanoflann keeps
  * the first VISITED of equal distances (KNNResultSet::addPoint, nanoflann_two.hpp:219-246; traversal order), this library
@@ -152,7 +178,14 @@ int amk_kd_exact_status_host(amk_kd *kd, int *h_status);   /* the same into host
  * holds <= 1 point, kd_tree_two.h:119-124).  A scene with >= th_count outliers has its `keyframe` rebuilt
  * from them (InitializeNew(newCloud), order preserved) and d_rebuilt[s] = 1; otherwise `keyframe` is left
  * untouched and d_rebuilt[s] = 0.  d_outliers[s] = number of outliers (either may be NULL).
- * Both handles must hold the same number of scenes.                                               */
+ * Both handles must hold the same number of scenes.
+ * Non-finite coordinates (see amk_kd_search): a keyframe point without a usable neighbour in `current` -- its own coordinates
+ * NaN or infinite, or `current` without a point of finite coordinates -- has the nearest-neighbour distance DBL_MAX, as
+ * the reference's SearchForNearest(pt, 1) reports it; it is an outlier iff `current` holds a usable point at all (no frame
+ * to compare with leaves the keyframe alone).  Such outliers stay in the rebuilt keyframe like any other.
+ * This holds for amk_kd_keyframe_sweep only.  The keyframe MAP (amk_kfmap_*, and pipeline slots with one) is UNSPECIFIED for
+ * frames that hold a NaN, an infinite or a |coordinate| > 3.0e38: its sweep is not covered by this contract or by any test
+ * (whether such a keyframe point is flagged depends on the sweep target and on the row's history); feed it finite frames. */
 int amk_kd_keyframe_sweep(amk_kd *keyframe, amk_kd *current, double th_dist, int th_count,
                           int *d_outliers, int *d_rebuilt, void *stream);
 
@@ -232,7 +265,14 @@ int amk_mpc_set_precision(amk_mpc *mpc, int bits);
  *   d_info       [S][4] int       = {status (0 converged, 1 iteration cap, 2 regularisation overflow), iterations,
  *                                    regularisations, line-search failures}   (may be NULL)
  * The full primal solution is kept as the next call's warm start (.cpp:110,129).  The reference
- * never inspects the solver status (.cpp:116-122); neither does this function -- it reports it.  */
+ * never inspects the solver status (.cpp:116-122); neither does this function -- it reports it.
+ * A scene whose merit function is not a number (a NaN in d_ref_states) does not report status 0: NaN optimality errors pass
+ * no convergence test, the solve ends with status 1 or 2 and its u may be NaN.  Tested for a NaN in x_init and, on the path
+ * that existed before (infinite errors, the factorisation fails), for an infinity in an early and in the last reference
+ * state that a stage cost reads; other placements are not pinned.  A NaN among the neighbour points is NOT such a case: every
+ * comparison with it is false, its collision term never becomes active, and the solve converges as if the point were not
+ * there (status 0, as in the oracle).  Scenes do not share anything: the other scenes of the batch are
+ * bit-identical to a batch without the poisoned one (likewise in amk_step_batch).                                    */
 int amk_mpc_solve(amk_mpc *mpc, const double *d_ref_states, double *d_u, double *d_x0array,
                   int *d_info, int faster, void *stream);
 
@@ -613,6 +653,11 @@ int amk_depth_out_size(int rows, int cols, double resize_scale, int *out_w, int 
  *   d_Twb     [S][16] world <- body, row-major
  *   d_cloud   [S][W*H][point_stride] float32 out (point_stride 3 or 4: feeds amk_kd_build directly),
  *             cloud_scene_stride in floats;  d_counts [S] out: points written per scene.
+ * Invalid pixels: a float32 NaN (what 32FC1 frames mark invalid pixels with) passes the first range gate as in the
+ * reference (both comparisons are false), becomes a NaN inverse depth, spreads to every down-scaled pixel one of whose
+ * four taps reads it (also through a border tap of weight 0) and falls out at the second gate; +-inf, negative and
+ * denormal pixels fail the first gate like 0 (inverse depth 0).  No emitted coordinate is non-finite while the pose is
+ * finite; a NaN in d_Twb gives NaN coordinates (a NaN x is what amk_kd_build drops).
  * Arithmetic contract: DESIGN.md section 10 (float bilinear taps in OpenCV's order without FMA, double
  * back-projection and transform without FMA); bit-exact against oracle/depth_oracle.c.  Parity with OpenCV's
  * own resize and Eigen's -march=native products is unpinned (neither is in the image).                       */

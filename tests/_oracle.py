@@ -31,12 +31,22 @@ def build_oracle(force=False):
 class KdHandle:
     """One tree of either flavour (prefix 'kdo' = C restatement, 'ref_kd' = reference header)."""
 
-    def __init__(self, lib, prefix, xyz, stride=None):
+    def __init__(self, lib, prefix, xyz, stride=None, allow_nonfinite=False):
         xyz = np.ascontiguousarray(xyz, dtype=np.float32)
         if stride is None:
             stride = xyz.shape[1]
-        self.lib, self.p = lib, prefix
-        self.h = getattr(lib, prefix + "_create")(xyz.reshape(-1), xyz.shape[0], stride)
+        self.lib, self.p, self.h = lib, prefix, None
+        # A cloud that KEEPS a non-finite coordinate (NaN y / z, +-inf anywhere; NaN-x points are dropped) is refused, for both
+        # flavours: nanoflann's build is undefined on it, and the reference header and the restatement alike end the process with a
+        # segmentation fault on most such clouds.  allow_nonfinite: the one recorded cloud known to build (test_kd_oracle.py).
+        kept = xyz[~np.isnan(xyz[:, 0]), :3] if xyz.size else xyz
+        if not allow_nonfinite and not np.isfinite(kept).all():
+            raise ValueError("cloud keeps a point with a non-finite coordinate: the reference's tree is undefined on it "
+                             "(use _oracle.kd_brute_np for the expected answers)")
+        create = prefix + ("_create_unchecked" if allow_nonfinite and prefix == "kdo" else "_create")
+        self.h = getattr(lib, create)(xyz.reshape(-1), xyz.shape[0], stride)
+        if not self.h:
+            raise ValueError(prefix + "_create refused the cloud (kept non-finite coordinate)")
 
     def size(self):
         return getattr(self.lib, self.p + "_size")(self.h)
@@ -82,8 +92,9 @@ class KdHandle:
 
 
 def _decl_kd(lib, p):
-    getattr(lib, p + "_create").restype = C.c_void_p
-    getattr(lib, p + "_create").argtypes = [_f32p, C.c_int, C.c_int]
+    for create in ("_create", "_create_unchecked") if p == "kdo" else ("_create",):
+        getattr(lib, p + create).restype = C.c_void_p
+        getattr(lib, p + create).argtypes = [_f32p, C.c_int, C.c_int]
     getattr(lib, p + "_size").restype = C.c_int
     getattr(lib, p + "_size").argtypes = [C.c_void_p]
     getattr(lib, p + "_search").restype = C.c_int
@@ -142,7 +153,8 @@ class RefAnswers:
         return int(self.G[self.p + ".size"])
 
     def _row(self, q):
-        hit = np.flatnonzero((self.q == np.asarray(q, np.float64)).all(axis=1))
+        # (bit patterns: a NaN query finds its row, -0.0 is not 0.0)
+        hit = np.flatnonzero((self.q.view(np.int64) == np.ascontiguousarray(q, np.float64).view(np.int64)).all(axis=1))
         assert len(hit), f"{self.p}: no stored answer for the query {q}"
         return hit[0]
 
@@ -170,13 +182,36 @@ def ref_answers(prefix, xyz):
     return RefAnswers(_REF_G, prefix, xyz)
 
 
-def kd_oracle(xyz, stride=None):
-    return KdHandle(load_oracle(), "kdo", xyz, stride)
+def kd_oracle(xyz, stride=None, allow_nonfinite=False):
+    return KdHandle(load_oracle(), "kdo", xyz, stride, allow_nonfinite)
 
 
-def kd_ref(xyz, stride=None, strict=True):
+def kd_ref(xyz, stride=None, strict=True, allow_nonfinite=False):
     lib = load_ref(strict)
-    return None if lib is None else KdHandle(lib, "ref_kd", xyz, stride)
+    return None if lib is None else KdHandle(lib, "ref_kd", xyz, stride, allow_nonfinite)
+
+
+DBL_MAX = np.finfo(np.float64).max
+
+
+def kd_count_rule(size, k):
+    """KDTreeTwo::SearchForNearest's result count (kd_tree_two.h:119-124): by the SIZE of the filtered cloud."""
+    return size if size < k else (k if size > k else 0)
+
+
+def kd_brute_np(cloud, q, k):
+    """The plain reference of a search on ANY cloud, non-finite coordinates included (include/avoid_mpc_amd.h, "non-finite
+    coordinates"): NaN-x filter; squared distance in fp64 in the adaptor's order, ((q0-x)^2 + (q1-y)^2) + (q2-z)^2; a point is
+    usable iff that is < DBL_MAX (false for NaN, inf and overflow); order by (distance, index); the first min(count rule,
+    usable) entries.  cloud float32 [n, >= 3], q float64 [3] -> (indices int32, sqdist float64, size of the filtered cloud).
+    Equals kdo_bruteforce bit for bit on finite clouds (tests/test_kd_oracle.py)."""
+    cloud = np.asarray(cloud, np.float32)
+    c = cloud[~np.isnan(cloud[:, 0]), :3].astype(np.float64)
+    with np.errstate(all="ignore"):
+        d = ((q[0] - c[:, 0]) ** 2 + (q[1] - c[:, 1]) ** 2) + (q[2] - c[:, 2]) ** 2
+    ok = np.flatnonzero(d < DBL_MAX)
+    o = ok[np.lexsort((ok, d[ok]))][:kd_count_rule(len(c), k)]
+    return o.astype(np.int32), d[o], len(c)
 
 
 class MpcoOpts(C.Structure):

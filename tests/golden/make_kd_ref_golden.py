@@ -3,11 +3,16 @@ oracle/_ref; see oracle/ref_nanoflann.cpp and oracle/Makefile) on the clouds and
 test_nanoflann_tie_order_mode in tests/test_kd_gpu.py, read back by tests/_oracle.py RefAnswers.
 
 Run where the reference is present, after build():   python tests/golden/make_kd_ref_golden.py
+The answers to the hostile queries (test_kd_oracle._hostile_queries: NaN, +-inf, overflow) are recorded in a CHILD process, one
+per cloud: a crash of the reference on such an input is then a finding (the child's exit status is reported), not the end of
+this script.
 Per cloud (prefix): queries [Q, 3], cloud_sum (nansum over the points), size; per result count n and kind (search: indices,
 squared distances, points; raw: indices, squared distances) the answers padded to n columns with their counts.
 """
 import os
+import subprocess
 import sys
+import tempfile
 
 import numpy as np
 
@@ -18,8 +23,8 @@ from tests import test_kd_gpu as tg  # noqa: E402
 from tests import test_kd_oracle as to  # noqa: E402
 
 
-def record(out, prefix, cloud, queries, ns, strict=True, raw=False):
-    t = _oracle.kd_ref(cloud, strict=strict)
+def record(out, prefix, cloud, queries, ns, strict=True, raw=False, allow_nonfinite=False):
+    t = _oracle.kd_ref(cloud, strict=strict, allow_nonfinite=allow_nonfinite)
     assert t is not None, "oracle/_ref missing: build() with the reference present"
     queries = np.asarray(queries, np.float64).reshape(-1, 3)
     out[prefix + ".queries"] = queries
@@ -45,13 +50,33 @@ def record(out, prefix, cloud, queries, ns, strict=True, raw=False):
     t.close()
 
 
-def main():
+def record_hostile_in_child(out, name):
+    """hostile.<name>: the reference's answers for the hostile queries on the finite cloud <name>, made by a child process."""
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "hostile.npz")
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--hostile-child", name, path])
+        assert r.returncode == 0, f"the reference ended with status {r.returncode} on the hostile queries of {name}: a finding"
+        with np.load(path) as G:
+            out.update({k: G[k] for k in G.files})
+
+
+def hostile_child(name, path):
     out = {}
+    record(out, "hostile." + name, to._clouds()[name], to._hostile_queries()[1], (1, 3, 8), raw=True)
+    np.savez(path, **out)
+
+
+def main():
+    if len(sys.argv) == 4 and sys.argv[1] == "--hostile-child":
+        return hostile_child(sys.argv[2], sys.argv[3])
+    out = {}
+    for name in to.HOSTILE_CLOUDS:
+        record_hostile_in_child(out, name)
     for name, cloud in to._clouds().items():
         record(out, name, cloud, to._queries(name, cloud), (1, 3, 8), raw=True)
     record(out, "nan_x", to._nan_x_cloud(), [[0.1, 0.2, 0.3]], (1, 8, 46, 47, 48, 60))
     cloud, qs = to._nan_y_cloud_and_queries()
-    record(out, "nan_y", cloud, qs, (8,))
+    record(out, "nan_y", cloud, qs, (8,), allow_nonfinite=True)   # one NaN y among 50 points: known to build
     record(out, "empty", np.zeros((0, 3), np.float32), [[0.0, 0.0, 0.0]], (3,))
     cloud, qs = to._fma_cloud_and_queries()
     record(out, "fma", cloud, qs, (8,), strict=False)

@@ -58,6 +58,56 @@ def scene(rng, rows, cols, dtype):
     return d.astype(np.float32), 1.0
 
 
+def hostile_scene(rng, rows, cols, dtype):
+    """scene() with the invalid pixels real sensors produce.  float32 (32FC1 marks invalid pixels with NaN): 5 % NaN, 3 % +inf,
+    2 % -inf, 2 % negative, 1 % denormal, a 20 x 30 block of NaN (larger than any resize tap pair), NaN in the whole last row
+    and column (the border tap has weight 0 there and still multiplies the NaN).  uint16: 0 and 65535."""
+    img, p2m = scene(rng, rows, cols, dtype)
+    u = rng.random((rows, cols))
+    if dtype == np.uint16:
+        img[u < 0.05] = 0
+        img[(u >= 0.05) & (u < 0.10)] = 65535
+        img[rows // 3: rows // 3 + 20, cols // 4: cols // 4 + 30] = 65535
+        img[-1, :] = 65535; img[:, -1] = 0
+        return img, p2m
+    img[u < 0.05] = np.nan
+    img[(u >= 0.05) & (u < 0.08)] = np.inf
+    img[(u >= 0.08) & (u < 0.10)] = -np.inf
+    img[(u >= 0.10) & (u < 0.12)] = -rng.uniform(0.5, 30.0)
+    img[(u >= 0.12) & (u < 0.13)] = np.float32(1e-41)
+    img[rows // 3: rows // 3 + 20, cols // 4: cols // 4 + 30] = np.nan
+    img[-1, :] = np.nan; img[:, -1] = np.nan
+    return img, p2m
+
+
+@pytest.mark.parametrize("dtype", [np.uint16, np.float32])
+@pytest.mark.parametrize("shape,scale", [((480, 640), 10.0), ((97, 131), 4.0), ((60, 80), 2.5)])
+def test_c_equals_numpy_on_hostile_pixels(dtype, shape, scale):
+    """NaN, +-inf, negative and denormal float pixels, 0 / 65535 uint16 pixels: a NaN passes the first range gate (both of its
+    comparisons are false), becomes a NaN inverse depth, spreads through the bilinear taps, and falls out at the second gate.
+    The oracle equals its numpy twin -- the inverse-depth image bit for bit, NaNs included --, no emitted coordinate is
+    non-finite, and a frame of nothing but NaN gives an empty cloud and an empty edge cloud."""
+    rng = np.random.default_rng(hash((shape, scale, 5)) % 2**32)
+    img, p2m = hostile_scene(rng, *shape, dtype)
+    prm = dict(YAML, pixel2meter=p2m, resize_scale=scale,
+               Tbc=np.array([[0, 0, 1, 0.1], [-1, 0, 0, 0.0], [0, -1, 0, 0.05], [0, 0, 0, 1.0]]))
+    th = 0.3
+    Twb = np.array([[np.cos(th), -np.sin(th), 0, 3.0], [np.sin(th), np.cos(th), 0, -1.0], [0, 0, 1, 1.5], [0, 0, 0, 1]])
+    cloud, inv = _oracle.depth_oracle(img, prm, Twb)
+    with np.errstate(invalid="ignore", over="ignore"):
+        pts, small = np_process(img, prm, Twb)
+    assert inv.shape == small.shape and np.array_equal(inv.view(np.uint32), small.view(np.uint32))   # NaN == NaN by bits
+    assert (np.isnan(inv).sum() > 0) == (dtype == np.float32)
+    assert len(cloud) == len(pts) > 0
+    assert np.allclose(cloud, pts, rtol=0, atol=np.abs(pts).max() * 2e-7)
+    assert np.isfinite(cloud).all()
+    edge = _oracle.depth_edge_oracle(img, prm, Twb)[0]
+    assert len(edge) > 0 and np.isfinite(edge).all()
+    if dtype == np.float32:
+        blank = np.full(shape, np.nan, np.float32)
+        assert len(_oracle.depth_oracle(blank, prm, Twb)[0]) == 0 and len(_oracle.depth_edge_oracle(blank, prm, Twb)[0]) == 0
+
+
 @pytest.mark.parametrize("dtype", [np.uint16, np.float32])
 @pytest.mark.parametrize("shape,scale", [((480, 640), 10.0), ((97, 131), 4.0), ((48, 64), 1.0), ((60, 80), 2.5)])
 def test_c_equals_numpy(dtype, shape, scale):

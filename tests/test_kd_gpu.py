@@ -193,7 +193,7 @@ def test_points_outside_the_sampled_box_and_nan_runs(torch_cuda, oracle):
     out = np.arange(n)[np.arange(n) % 1024 >= 64][::97][:300]        # never a sampled position
     pts[out] = rng.uniform(-60, 60, (len(out), 3)).astype(np.float32)
     q = np.concatenate([rng.uniform([-6, -6, -1], [6, 6, 4], (40, 3)), pts[out[:12]].astype(np.float64) + 0.25,
-                        rng.uniform(-70, 70, (12, 3))])                # (a NaN query is undefined in the reference too)
+                        rng.uniform(-70, 70, (12, 3))])                # (NaN / inf queries and points: tests/test_nonfinite_gpu.py)
     pts[1000:1200, 0] = np.nan                                        # three full 64-point groups and two ragged ones
     pts[rng.choice(n, 500, replace=False), 0] = np.nan
     res = _gpu_search(torch_cuda, [pts], q[None], 8)

@@ -46,6 +46,22 @@ def _nan_y_cloud_and_queries():
     return cloud, rng.uniform(-1, 1, (20, 3))
 
 
+HOSTILE_CLOUDS = ("uniform5k", "corridor20k")   # the two finite clouds the reference's answers to hostile queries are stored for
+
+
+def _hostile_queries():
+    """Queries with a non-finite or overflowing coordinate -> (names, float64 [Q, 3]).  The squared distance of every point is
+    NaN (nan_*), inf (inf_*, big_*: 1e200 squared overflows) -- no point enters the result set -- or about 1e300 (huge_*: finite,
+    answered normally; all points tie unless the other two coordinates decide at 1e284 resolution); -0.0 is an ordinary query."""
+    nan, inf = np.nan, np.inf
+    cases = [("nan_x", (nan, 0.0, 1.0)), ("nan_y", (0.0, nan, 1.0)), ("nan_z", (3.0, 0.5, nan)), ("nan_all", (nan, nan, nan)),
+             ("inf_x", (inf, 0.0, 1.0)), ("ninf_x", (-inf, 0.0, 1.0)), ("inf_y", (2.0, inf, 1.0)), ("ninf_z", (2.0, 0.5, -inf)),
+             ("big_x", (1e200, 0.0, 0.0)), ("nbig_y", (1.0, -1e200, 0.5)), ("big_z", (1.0, 0.5, 1e200)),
+             ("huge_x", (1e150, 0.0, 0.0)), ("nhuge_z", (4.0, 0.25, -1e150)),
+             ("negzero", (-0.0, -0.0, -0.0)), ("negzero_x", (-0.0, 0.5, 1.0))]
+    return [c[0] for c in cases], np.array([c[1] for c in cases], np.float64)
+
+
 def _fma_cloud_and_queries():
     return synth.make_cloud(20000, 5)[0], np.random.default_rng(9).uniform([0, -8, 0], [30, 8, 4], (300, 3))
 
@@ -86,7 +102,8 @@ def test_nan_x_filter_and_count_quirk(oracle):
 
 def test_nan_y_is_kept(oracle):
     cloud, qs = _nan_y_cloud_and_queries()
-    a, b = _oracle.kd_oracle(cloud), _oracle.ref_answers("nan_y", cloud)
+    # (the one cloud with a kept non-finite coordinate that the reference is recorded on: it happens to build)
+    a, b = _oracle.kd_oracle(cloud, allow_nonfinite=True), _oracle.ref_answers("nan_y", cloud)
     assert a.size() == b.size() == 50
     for q in qs:
         ia, da, _ = a.search(q, 8)
@@ -120,3 +137,97 @@ def test_fma_build_of_reference_same_indices(oracle):
     b = _oracle.ref_answers("fma", cloud)
     for q in qs:
         assert np.array_equal(a.search(q, 8)[0], b.search(q, 8)[0])
+
+
+@pytest.mark.parametrize("name", HOSTILE_CLOUDS)
+def test_restatement_equals_reference_on_hostile_queries(name, oracle):
+    """NaN / +-inf / overflowing query coordinates on finite clouds: SearchForNearest still returns `count` entries by the size
+    rule; the slots the traversal did not fill hold what the reference's value-initialised result vectors hold (index 0,
+    distance 0.0, DBL_MAX in the last of the n) and its point 0.  All slots, bits.  (kdo_search used to copy them out of
+    uninitialised heap and index the cloud with them: segmentation fault.)"""
+    cloud = _clouds()[name]
+    a, b = _oracle.kd_oracle(cloud), _oracle.ref_answers("hostile." + name, cloud)
+    names, qs = _hostile_queries()
+    for nm, q in zip(names, qs):
+        for k in (1, 3, 8):
+            ia, da, pa = a.search(q, k)
+            ib, db, pb = b.search(q, k)
+            assert len(ia) == k and np.array_equal(ia, ib), (name, nm, k, ia, ib)
+            assert np.array_equal(da.view(np.int64), db.view(np.int64)), (name, nm, k, da, db)
+            assert np.array_equal(pa.view(np.int32), pb.view(np.int32)), (name, nm, k)
+            ra, rb = a.search_raw(q, k), b.search_raw(q, k)
+            assert np.array_equal(ra[0], rb[0]) and np.array_equal(ra[1].view(np.int64), rb[1].view(np.int64)), (name, nm, k)
+            if nm.startswith(("nan", "inf", "ninf", "big", "nbig")):     # no point at a distance < DBL_MAX: nothing found
+                assert len(ra[0]) == 0 and da[-1] == _oracle.DBL_MAX and not da[:-1].any() and not ia.any()
+            else:
+                assert len(ra[0]) == k
+
+
+def _poisoned(kind):
+    rng = np.random.default_rng(21)
+    c = rng.uniform(-10, 10, (3000, 3)).astype(np.float32)
+    if kind == "nan_y_nan_z":
+        c[100:300, 1] = np.nan; c[1000:1200, 2] = np.nan
+    elif kind == "inf_y_ninf_z":
+        c[::60, 1] = np.inf; c[7::60, 2] = -np.inf
+    elif kind == "inf_x":
+        c[::60, 0] = np.inf
+    elif kind == "all_but_five_nan_y":
+        c[5:, 1] = np.nan
+    elif kind == "nan_x_only":
+        c[::9, 0] = np.nan                                               # dropped, not kept: accepted
+    return c
+
+
+@pytest.mark.parametrize("kind", ["nan_y_nan_z", "inf_y_ninf_z", "inf_x", "all_but_five_nan_y"])
+def test_tree_refuses_a_cloud_with_a_kept_nonfinite_coordinate(kind, oracle):
+    """The four kinds of cloud on which the reference's build and the restatement's both ended the process with a segmentation
+    fault: kdo_create returns NULL, the wrappers of both flavours raise before any build runs."""
+    c = _poisoned(kind)
+    lib = _oracle.load_oracle()
+    assert lib.kdo_create(np.ascontiguousarray(c).reshape(-1), len(c), 3) is None
+    with pytest.raises(ValueError):
+        _oracle.kd_oracle(c)
+    with pytest.raises(ValueError):
+        _oracle.kd_ref(c) if _oracle.load_ref() is not None else _oracle.KdHandle(lib, "ref_kd", c)
+    assert _oracle.kd_oracle(_poisoned("nan_x_only")).size() == 3000 - len(range(0, 3000, 9))
+
+
+def _lattice_cloud():
+    return (np.round(synth.make_cloud(5000, 6)[0] * 20) / 20).astype(np.float32)   # 5 cm lattice: exact ties
+
+
+@pytest.mark.parametrize("name", ["corridor20k_5", "lattice5k"])
+def test_numpy_reference_equals_bruteforce_on_finite_clouds(name, oracle):
+    """_oracle.kd_brute_np (the expected values wherever a cloud keeps non-finite points and no tree exists) is the same
+    function as kdo_bruteforce where both are defined: indices and distance bits, ties included."""
+    cloud = synth.make_cloud(20000, 5)[0] if name == "corridor20k_5" else _lattice_cloud()
+    a = _oracle.kd_oracle(cloud)
+    rng = np.random.default_rng(13)
+    qs = rng.uniform([0, -8, 0], [30, 8, 4], (250, 3))
+    qs[:40] = cloud[rng.integers(0, len(cloud), 40)]
+    qs[40:140] = cloud[rng.integers(0, len(cloud), 100)] + 0.025         # lattice5k: cell centres, equidistant to the corners
+    tied = 0
+    for q in qs:
+        for k in (1, 8, 16):
+            i1, d1 = a.bruteforce(q, k)
+            i2, d2, size = _oracle.kd_brute_np(cloud, q, k)
+            assert size == a.size() and np.array_equal(i1, i2), (name, q, k)
+            assert np.array_equal(d1.view(np.int64), d2.view(np.int64)), (name, q, k)
+            tied += k == 16 and len(np.unique(d1)) < len(d1)
+    assert name != "lattice5k" or tied >= 30                             # the lattice does exercise the (distance, index) order
+
+
+def test_numpy_reference_on_hostile_clouds():
+    """Defined where the trees are not: fewer usable points than k -> that many entries; none -> none; a point at FLT_MAX is
+    usable (its fp64 squared distance is ~1e77); the size counts every kept point."""
+    q = np.array([0.5, 0.25, 1.0])
+    c = _poisoned("all_but_five_nan_y")
+    i, d, size = _oracle.kd_brute_np(c, q, 8)
+    assert size == 3000 and sorted(i.tolist()) == [0, 1, 2, 3, 4] and (np.diff(d) >= 0).all()
+    c[:, 2] = np.inf
+    i, d, size = _oracle.kd_brute_np(c, q, 8)
+    assert size == 3000 and len(i) == 0
+    c = _poisoned("nan_x_only"); c[1, 1] = np.finfo(np.float32).max; c[2, :] = 1e30
+    i, d, size = _oracle.kd_brute_np(c, q, 3000)
+    assert len(i) == size and i[-1] == 0 and 1e76 < d[-1] < 1e78 and i[-2] == 1   # (point 0 has a NaN x: indices shift by one)
