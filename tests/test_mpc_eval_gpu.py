@@ -38,12 +38,13 @@ def _points(cfg, S, seed):
     return prm, W, R
 
 
-@pytest.mark.parametrize("cfg", ["C1", "C2", "C5"])
-def test_eval_matches_oracle(cfg):
+def compare_eval_with_oracle(prm, W, R):
+    """amk_mpc_eval at the points (W, R) under prm against the oracle: f, grad_f, g, the Jacobian (CCS, pattern included) and
+    the Hessian of the Lagrangian's objective part (upper triangle, nothing outside the declared pattern).  -> worst relative
+    errors (f, grad_f, hess_l).  (prm.drag: the caller wraps the call in _oracle.oracle_drag.)"""
     import torch
     from avoid_mpc_amd.host import MpcBatch
-    S = 24
-    prm, W, R = _points(cfg, S, 5)
+    S = len(W)
     N, K = prm.N, prm.K
     nx, ng = 10 + 14 * N, 10 + 10 * N
     m = MpcBatch(prm.T, prm.dt, prm.K, S); m.configure(prm)
@@ -54,12 +55,15 @@ def test_eval_matches_oracle(cfg):
     jc, jr = m.sparsity("jac_g"); hc, hr = m.sparsity("hess_l")
     assert len(jr) == 10 + 39 * N and len(hr) == 25 * (N - 1) + 10 + 4 * N
     lib = _oracle.load_oracle()
+    worst = [0.0, 0.0, 0.0]
     for s in range(S):
         P = np.ascontiguousarray(np.concatenate([R[s], prm.gain, prm.tau, prm.weights, [prm.radius]]))
         w = np.ascontiguousarray(W[s])
         f = lib.mpco_nlp_f(w, P, N, K)
+        worst[0] = max(worst[0], abs(out["f"][s] - f) / abs(f))
         assert abs(out["f"][s] - f) <= RTOL * abs(f)
         g = np.zeros(nx); lib.mpco_nlp_grad_f(w, P, N, K, g)
+        worst[1] = max(worst[1], np.abs(out["grad_f"][s] - g).max() / np.abs(g).max())
         assert np.abs(out["grad_f"][s] - g).max() <= RTOL * np.abs(g).max()
         cg = np.zeros(ng); lib.mpco_nlp_g(w, P, N, K, prm.dt, cg)
         assert np.abs(out["g"][s] - cg).max() <= 1e-12 * max(1.0, np.abs(w).max())
@@ -84,12 +88,20 @@ def test_eval_matches_oracle(cfg):
             rows = hr[hc[col]:hc[col + 1]]
             assert np.all(np.diff(rows) > 0) and np.all(rows <= col)
             Hg[rows, col] = out["hess_l"][s][hc[col]:hc[col + 1]]
+        worst[2] = max(worst[2], np.abs(Hg - lam_f[s] * np.triu(Hd)).max() / np.abs(Hd).max())
         assert np.abs(Hg - lam_f[s] * np.triu(Hd)).max() <= RTOL * np.abs(Hd).max()
         # nothing of the Hessian falls outside the declared pattern
         mask = np.zeros((nx, nx), bool)
         for col in range(nx):
             mask[hr[hc[col]:hc[col + 1]], col] = True
         assert np.all(np.triu(Hd)[~mask] == 0)
+    return tuple(worst)
+
+
+@pytest.mark.parametrize("cfg", ["C1", "C2", "C5"])
+def test_eval_matches_oracle(cfg):
+    prm, W, R = _points(cfg, 24, 5)
+    compare_eval_with_oracle(prm, W, R)
 
 
 def test_eval_host_and_null_outputs():
