@@ -230,6 +230,8 @@ def load():
     sig["amk__kd_set_mode"] = (i, [vp, i])  # internal: 0 bucketed index, 1 streaming scan
     sig["amk__sweep_set_target"] = (None, [i])  # internal (tests, A/B): the pool's sweep against 1 a fine hashed grid of the current frame (default), 0 the frame's own index
     sig["amk__sweep_set_order"] = (None, [i])   # internal (tests, A/B): 1 keyframe points in last sweep's grid order where it is theirs (default), 0 record order
+    sig["amk__frames_force_wide"] = (None, [i])  # internal (tests): 1 the multi-frame step's merge re-reads its candidates every round whatever the map's size
+    sig["amk__mpc_ref_states"] = (i, [vp, vp, ll])  # internal (tests): host copy of the P vectors the last step's newest pass handed to the solve
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)
         if fn is None:

@@ -374,6 +374,16 @@ void amk::launch_step_begin(int S, int *done, int *flags, double *u, hipStream_t
 static int g_diag_skip = 0;
 extern "C" void amk__diag_skip(int mask) { g_diag_skip = mask; }
 
+// Internal (tests): host copy of the packed parameter vectors P the newest pass of the last step -- either path -- handed to the
+// solve: the first min(n, S nref) doubles of the workspace, after a device-wide wait.  No step has run yet: AMK_ERR_INVALID_ARG.
+extern "C" int amk__mpc_ref_states(amk_mpc *mpc, double *h_out, long long n) {
+    if (!mpc || !h_out || n < 0 || !mpc->ref_states.p) return AMK_ERR_INVALID_ARG;
+    AMK_HIP(hipDeviceSynchronize());
+    const long long have = (long long)mpc->S * mpc->nref;
+    AMK_HIP(hipMemcpy(h_out, mpc->ref_states.p, sizeof(double) * (size_t)(n < have ? n : have), hipMemcpyDeviceToHost));
+    return AMK_OK;
+}
+
 extern "C" int amk_step_batch(amk_kd *obstacle, amk_kd *edge, amk_mpc *mpc, const amk_step_params *prm,
                               const double *d_state_quad, const double *d_pos_x, double *d_ref_path, double *d_u,
                               double *d_x0array, int *d_flags, void *stream_) {

@@ -125,6 +125,7 @@ __device__ __forceinline__ void pack_ref_states(int tid, int nthr, int s, int N,
         const double *last = rp + (N - 1) * SD;
         double v = last[tid];
         if (tid == 0) {
+#pragma clang fp contract(off)   // the product rounded, then the difference, like the oracle's two operations: fused, the target's x differs in its last bit whenever speed * T is inexact
             double dX = speed * T - fmax(0., last[0] - pos_x[s]);
             dX = fmax(0., dX);
             v += dX;

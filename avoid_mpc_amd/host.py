@@ -251,6 +251,12 @@ class MpcBatch:
     def reset_warm_start(self, stream=None):
         capi.check(self.lib.amk_mpc_reset_warm_start(self.h, capi.stream_ptr(stream)), "reset_warm_start")
 
+    def ref_states(self):
+        """(tests) float64 [S, ref_len]: the P vectors the newest pass of the last control step handed to the solve (synchronises)."""
+        P = np.zeros((self.S, self.ref_len))
+        capi.check(self.lib.amk__mpc_ref_states(self.h, P.ctypes.data_as(C.c_void_p), P.size), "amk__mpc_ref_states")
+        return P
+
 
 class KfMap:
     """amk_kfmap: FrameKDMap's keyframe list for S scenes on the device (FrameKDMap.cpp:29-74,233-252,428-488)."""

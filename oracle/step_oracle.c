@@ -181,7 +181,8 @@ int stepo_run(void *kd_obs, void *kd_edge, void *mpc, int K, double speed, doubl
  * cam[7] = {fx, fy, cx, cy (already divided by the resize scale, :21-24), depth_max, width, height}; Twc row-major 4x4
  * (NULL: every point counts as inside the current frame).  The reference sorts the merged candidates with std::sort on
  * the squared distance alone (:371, FrameKDMap.h:52-54: equal distances in unspecified order); here ties keep the
- * earlier frame / earlier neighbour -- the rule of the product. */
+ * earlier frame / earlier neighbour -- the rule of the product.
+ * ref_log (optional, as in stepo_run): [mpc_max_iter][20+10N+3KN] the vecRefStates handed to each Solve. */
 static int pt_is_in_frame(const double *p, const double *T, const double *cam) {
     if (!T) return 1;
     /* Twc.inverse() * p for a rigid Twc: R'(p - t) */
@@ -257,7 +258,7 @@ static double mapf_nearest_distance(void **kds, int F, const double *p) {
 
 int stepo_run_frames(void **kd_obs, void **kd_edge, int F, const double *Twc, const double *cam, void *mpc, int K,
                      double speed, double T, double safety_distance, int mpc_max_iter, const double *state_quad,
-                     double pos_x, double *ref_path, double *u, double *x0array, int *flags) {
+                     double pos_x, double *ref_path, double *u, double *x0array, int *flags, double *ref_log) {
     const int N = mpco_horizon(mpc);
     const int nref = 20 + 10 * N + 3 * K * N;
     double *ref_states = (double *)malloc(sizeof(double) * nref);
@@ -301,6 +302,7 @@ int stepo_run_frames(void **kd_obs, void **kd_edge, int F, const double *Twc, co
             tg[0] += dX;
             tg[1] = 0.;
         }
+        if (ref_log) memcpy(ref_log + (size_t)nref * iter, ref_states, sizeof(double) * nref);
         { const int st = mpco_Solve(mpc, ref_states, u, x0, iter == 0);
           if (st > status) status = st; }
         iters += mpco_last_info(mpc)[1];

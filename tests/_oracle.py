@@ -374,7 +374,7 @@ def step_oracle_frames(kd_obs_frames, kd_edge_frames, mpc, prm, state_quad, pos_
     lib = load_oracle()
     lib.stepo_run_frames.restype = C.c_int
     lib.stepo_run_frames.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
-                                     C.c_double, C.c_double, C.c_int, _f64p, C.c_double, _f64p, _f64p, _f64p, _i32p]
+                                     C.c_double, C.c_double, C.c_int, _f64p, C.c_double, _f64p, _f64p, _f64p, _i32p, _f64p]
     F = len(kd_obs_frames)
     oa = (C.c_void_p * F)(*[k.h for k in kd_obs_frames]); ea = (C.c_void_p * F)(*[k.h for k in kd_edge_frames])
     N, K = mpc.N, mpc.K
@@ -382,11 +382,12 @@ def step_oracle_frames(kd_obs_frames, kd_edge_frames, mpc, prm, state_quad, pos_
     T = np.ascontiguousarray(Twc, np.float64).reshape(-1) if Twc is not None else None
     cm = np.ascontiguousarray(cam, np.float64) if cam is not None else None
     sq = np.ascontiguousarray(state_quad, np.float64)
+    log = np.zeros((prm.max_iter, 20 + 10 * N + 3 * K * N))
     lib.stepo_run_frames(oa, ea, F, T.ctypes.data_as(C.c_void_p) if T is not None else None,
                          cm.ctypes.data_as(C.c_void_p) if cm is not None else None, mpc.h, K, prm.speed, prm.T,
                          prm.safety_distance, prm.max_iter, sq.reshape(-1), float(pos_x), ref_path.reshape(-1), u,
-                         x0.reshape(-1), flags)
-    return dict(u=u, x0array=x0, flags=flags)
+                         x0.reshape(-1), flags, log.reshape(-1))
+    return dict(u=u, x0array=x0, flags=flags, ref_log=log)
 
 
 # ---- depth image -> cloud (oracle/depth_oracle.c) ------------------------------------------------

@@ -85,15 +85,21 @@ def test_exact_distance_ties_between_frames():
     Lattice clouds (0.25 m) cut into disjoint frames at x = 6: frame 0 holds x >= 6, frame 1 x < 6; reference points sit on
     the 0.125 m lattice and one of them exactly on the cut, so (5.75, y, z) of frame 1 and (6.25, y, z) of frame 0 tie.  The
     reference merges with an unstable std::sort on the distance alone (FrameKDMap.cpp:371); this library and the oracle
-    keep the EARLIER frame first.  The test first proves that such ties occur among the K nearest of the merged lists, then
-    compares the whole step (which points entered P decides the solve)."""
+    keep the EARLIER frame first.  A reference point merges only when the current frame is small or the point is outside the
+    current image: the camera's depth_max of 5 m (2 m behind the start) puts the points beyond x = 3, the one on the cut included,
+    out of range -- without a camera frame 0 alone (thousands of points) answers every query and no tie ever reaches a merge.
+    The test first proves that such ties occur among the K nearest of the rows that MERGE, then compares the whole step (which
+    points entered P decides the solve)."""
     import torch
+    from avoid_mpc_amd import capi
     from avoid_mpc_amd.host import KdBatch, MpcBatch, step_batch_frames
+    from tests import _frames_cases as fc
+    Twc, cam = fc.TWC_AXIS, fc.TIES_CAM
     prm = synth.MpcParams(T=0.66, K=8)
     S = 8
     scenes = [synth.make_scene(20000, 1900 + i, prm) for i in range(S)]
     spans = [(6.0, 1e9), (-1e9, 6.0)]
-    ties = 0
+    ties = merged_rows = 0
     for sc in scenes:
         sc["cloud"] = np.unique((np.round(sc["cloud"] * 4) / 4).astype(np.float32), axis=0)
         sc["edge"] = np.unique((np.round(sc["edge"] * 4) / 4).astype(np.float32), axis=0)
@@ -104,12 +110,16 @@ def test_exact_distance_ties_between_frames():
            [sc["edge"][(sc["edge"][:, 0] >= a) & (sc["edge"][:, 0] < b)] for sc in scenes]) for a, b in spans]
     for s, sc in enumerate(scenes):   # how many reference points see an inter-frame tie inside their merged K nearest
         t0, t1 = _oracle.kd_oracle(fr[0][0][s]), _oracle.kd_oracle(fr[1][0][s])
+        assert t0.size() > prm.K and t1.size() > prm.K
         for p in sc["ref_path"][:, :3]:
+            if fc.in_frame(p, Twc, cam):
+                continue   # answered by frame 0 alone
+            merged_rows += 1
             (i0, d0, p0), (i1, d1, p1) = t0.search(p, prm.K), t1.search(p, prm.K)
             kth = np.sort(np.concatenate([d0, d1]))[prm.K - 1]
             common = np.intersect1d(d0[d0 <= kth], d1[d1 <= kth])
             ties += len(common) > 0
-    assert ties >= 8, ties
+    assert ties >= 8 and merged_rows >= S * prm.N // 2, (ties, merged_rows)
     kd_o, kd_e = [], []
     for f in range(2):
         for lst, out in ((fr[f][0], kd_o), (fr[f][1], kd_e)):
@@ -122,7 +132,8 @@ def test_exact_distance_ties_between_frames():
     sq = np.stack([_oracle.scene_state_quads(sc, prm) for sc in scenes])
     ref = torch.from_numpy(np.stack([sc["ref_path"] for sc in scenes])).cuda()
     pos_x = torch.from_numpy(np.array([sc["pos"][0] for sc in scenes])).cuda()
-    out = step_batch_frames(kd_o, kd_e, mpc, prm, torch.from_numpy(sq).cuda(), pos_x, ref)   # no camera: every frame is searched
+    out = step_batch_frames(kd_o, kd_e, mpc, prm, torch.from_numpy(sq).cuda(), pos_x, ref,
+                            Twc=torch.from_numpy(np.repeat(Twc[None], S, 0).copy()).cuda(), cam=capi.FrameCamera(*cam))
     torch.cuda.synchronize()
     u, x0, flags, rp = out["u"].cpu().numpy(), out["x0array"].cpu().numpy(), out["flags"].cpu().numpy(), ref.cpu().numpy()
     worst = 0.0
@@ -131,8 +142,8 @@ def test_exact_distance_ties_between_frames():
         ke = [_oracle.kd_oracle(fr[f][1][s]) for f in range(2)]
         m = _oracle.MpcOracle(prm.T, prm.dt, prm.K); m.configure(prm)
         r_ref = sc["ref_path"].copy()
-        r = _oracle.step_oracle_frames(ko, ke, m, prm, sq[s], sc["pos"][0], r_ref, None, None)
+        r = _oracle.step_oracle_frames(ko, ke, m, prm, sq[s], sc["pos"][0], r_ref, Twc, cam)
         assert np.array_equal(flags[s], r["flags"]), (s, flags[s], r["flags"])
         worst = max(worst, np.abs(u[s] - r["u"]).max(), np.abs(x0[s] - r["x0array"]).max(), np.abs(rp[s] - r_ref).max())
-    print(f"inter-frame ties at {ties} reference points; worst |gpu - oracle| = {worst:.3e}")
+    print(f"inter-frame ties at {ties} of {merged_rows} reference points that merge; worst |gpu - oracle| = {worst:.3e}")
     assert worst <= TOL
