@@ -232,6 +232,7 @@ def load():
     sig["amk__sweep_set_order"] = (None, [i])   # internal (tests, A/B): 1 keyframe points in last sweep's grid order where it is theirs (default), 0 record order
     sig["amk__frames_force_wide"] = (None, [i])  # internal (tests): 1 the multi-frame step's merge re-reads its candidates every round whatever the map's size
     sig["amk__mpc_ref_states"] = (i, [vp, vp, ll])  # internal (tests): host copy of the P vectors the last step's newest pass handed to the solve
+    sig["amk__kfmap_slots_host"] = (i, [vp, vp, vp, vp, vp, vp])  # internal (tests): cur_slot [S], kf_n [S], kf_slots [S][P], fmap [F][S], need [S] of a keyframe map
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)
         if fn is None:

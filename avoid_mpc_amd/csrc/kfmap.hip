@@ -396,4 +396,18 @@ int amk_kfmap_state_host(amk_kfmap *m, int *h_n_keyframes, int *h_n_query_frames
     return AMK_OK;
 }
 
+// Internal (tests only, not in the public header): the raw bookkeeping -- cur_slot [S], kf_n [S], kf_slots [S][P], fmap [F][S] and
+// need [S] as the kernels left them (any pointer may be NULL).  Synchronises the device.
+int amk__kfmap_slots_host(amk_kfmap *m, int *h_cur_slot, int *h_kf_n, int *h_kf_slots, int *h_fmap, int *h_need) {
+    if (!m) return AMK_ERR_INVALID_ARG;
+    AMK_HIP(hipDeviceSynchronize());
+    const size_t S = m->S;
+    if (h_cur_slot) AMK_HIP(hipMemcpy(h_cur_slot, m->cur_slot.p, sizeof(int) * S, hipMemcpyDeviceToHost));
+    if (h_kf_n) AMK_HIP(hipMemcpy(h_kf_n, m->kf_n.p, sizeof(int) * S, hipMemcpyDeviceToHost));
+    if (h_kf_slots) AMK_HIP(hipMemcpy(h_kf_slots, m->kf_slots.p, sizeof(int) * S * m->P, hipMemcpyDeviceToHost));
+    if (h_fmap) AMK_HIP(hipMemcpy(h_fmap, m->fmap.p, sizeof(int) * S * m->F, hipMemcpyDeviceToHost));
+    if (h_need) AMK_HIP(hipMemcpy(h_need, m->need.p, sizeof(int) * S, hipMemcpyDeviceToHost));
+    return AMK_OK;
+}
+
 }  // extern "C"

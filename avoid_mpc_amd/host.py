@@ -309,6 +309,18 @@ class KfMap:
                                                  out.ctypes.data_as(C.c_void_p), sz.ctypes.data_as(C.c_void_p)), "amk_kfmap_state_host")
         return dict(n_keyframes=nk, n_query_frames=nq, last_outliers=out, frame_sizes=sz)
 
+    def reset(self, first_scene, n_scenes, stream=None):
+        capi.check(self.lib.amk_kfmap_reset(self.h, int(first_scene), int(n_scenes), capi.stream_ptr(stream)), "amk_kfmap_reset")
+
+    def slots(self):
+        """Internal (tests): the raw bookkeeping -> dict(cur_slot [S], kf_n [S], kf_slots [S, P], fmap [F, S], need [S]) (synchronises)"""
+        S, F = self.S, self.F
+        a = dict(cur_slot=np.zeros(S, np.int32), kf_n=np.zeros(S, np.int32), kf_slots=np.zeros((S, F + 1), np.int32),
+                 fmap=np.zeros((F, S), np.int32), need=np.zeros(S, np.int32))
+        capi.check(self.lib.amk__kfmap_slots_host(self.h, *[a[k].ctypes.data_as(C.c_void_p) for k in ("cur_slot", "kf_n", "kf_slots", "fmap", "need")]),
+                   "amk__kfmap_slots_host")
+        return a
+
 
 class Pipeline:
     """amk_pipeline: n_slots launches in flight, each slot = {HIP stream, obstacle + edge index, MPC batch, outputs};
