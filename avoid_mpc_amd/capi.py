@@ -36,6 +36,8 @@ SYMBOLS = [
     "amk_mpc_setup_weights", "amk_mpc_setup_tau", "amk_mpc_setup_gains", "amk_mpc_set_drag_coefficient", "amk_mpc_set_drone_radius",
     "amk_kfmap_pool_bytes", "amk_kfmap_create", "amk_kfmap_destroy", "amk_kfmap_reset", "amk_kfmap_scenes", "amk_kfmap_frames", "amk_kfmap_twc", "amk_kfmap_add_vertex",
     "amk_kfmap_update", "amk_kfmap_step", "amk_kfmap_state_host",
+    "amk_kfmap_query_nearest", "amk_kfmap_nearest_distance", "amk_kfmap_query_nearest_host", "amk_kfmap_nearest_distance_host",
+    "amk_kfmap_points_host", "amk_kd_query_frames", "amk_kd_nearest_distance_frames", "amk_kd_query_frames_host",
     "amk_mpc_set_drone_accel_limits", "amk_mpc_set_solver_options", "amk_mpc_set_solve_budget", "amk_mpc_set_precision", "amk_mpc_solve",
     "amk_mpc_get_warm_start", "amk_mpc_set_warm_start", "amk_mpc_reset_warm_start",
     "amk_mpc_solve_host", "amk_mpc_ng", "amk_mpc_jac_nnz", "amk_mpc_hess_nnz", "amk_mpc_jac_sparsity",
@@ -208,6 +210,14 @@ def load():
         "amk_kfmap_update": (i, [vp, vp]),
         "amk_kfmap_step": (i, [vp, vp, vp, C.POINTER(StepParams), vp, vp, vp, vp, vp, vp, vp]),
         "amk_kfmap_state_host": (i, [vp, vp, vp, vp, vp]),
+        "amk_kfmap_query_nearest": (i, [vp, C.POINTER(FrameCamera), vp, i, i, i, i, vp, vp, vp, vp, vp]),
+        "amk_kfmap_nearest_distance": (i, [vp, vp, i, i, vp, vp]),
+        "amk_kfmap_query_nearest_host": (i, [vp, C.POINTER(FrameCamera), vp, i, i, i, i, vp, vp, vp, vp]),
+        "amk_kfmap_nearest_distance_host": (i, [vp, vp, i, i, vp]),
+        "amk_kfmap_points_host": (i, [vp, i, vp, ll, vp, C.POINTER(ll)]),
+        "amk_kd_query_frames": (i, [vp, i, vp, C.POINTER(FrameCamera), vp, i, i, i, vp, vp, vp, vp, vp]),
+        "amk_kd_nearest_distance_frames": (i, [vp, i, vp, i, i, vp, vp]),
+        "amk_kd_query_frames_host": (i, [vp, i, vp, C.POINTER(FrameCamera), vp, i, i, i, vp, vp, vp, vp]),
         "amk_shard_scene_range": (i, [i, i, i, C.POINTER(i), C.POINTER(i)]),
         "amk_shard_unique_id": (i, [C.c_char_p]),
         "amk_shard_create": (i, [C.c_char_p, i, i, C.POINTER(vp)]),

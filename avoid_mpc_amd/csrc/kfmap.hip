@@ -23,12 +23,22 @@
 #include "mpc_handle.h"
 
 #include <cstdio>
+#include <functional>
 #include <vector>
 
 namespace amk {
 int step_batch_map(amk_kd *obs_pool, amk_kd *edge_pool, int n_frames, const int *d_fmap, const double *d_Twc,
                    const amk_frame_camera *cam, amk_mpc *mpc, const amk_step_params *prm, const double *d_state_quad,
                    const double *d_pos_x, double *d_ref_path, double *d_u, double *d_x0array, int *d_flags, hipStream_t stream);
+// map_query.hip: QueryNearest / GetNearestDistance over a pool, and the staging of their *_host variants
+int map_query_nearest(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_Twc, const amk_frame_camera *cam,
+                      const double *d_queries, int query_stride, int n_queries, int k, float *d_pts, double *d_sqdist, int *d_frame,
+                      int *d_counts, hipStream_t stream);
+int map_nearest_distance(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_queries, int query_stride,
+                         int n_queries, double *d_dist, hipStream_t stream);
+int map_query_host(int S, const double *h_queries, int query_stride, int n_queries, int k, const double *h_Twc, float *h_pts,
+                   double *h_sqdist, int *h_frame, int *h_counts, double *h_dist,
+                   const std::function<int(const double *, const double *, float *, double *, int *, int *, double *)> &launch);
 }
 
 struct amk_kfmap {
@@ -368,6 +378,72 @@ int amk_kfmap_step(amk_kfmap *m, const amk_frame_camera *cam, amk_mpc *mpc, cons
     if (!m || !mpc || mpc->S != m->S) return AMK_ERR_INVALID_ARG;
     return amk::step_batch_map(m->obs, m->edge, m->F, m->fmap.p, cam ? m->Twc.p : nullptr, cam, mpc, prm, d_state_quad, d_pos_x,
                                d_ref_path, d_u, d_x0array, d_flags, (hipStream_t)stream_);
+}
+
+// FrameKDMap::QueryNearest / GetNearestDistance over the map as it stands (map_query.hip); stream-ordered, no map state changes
+int amk_kfmap_query_nearest(amk_kfmap *m, const amk_frame_camera *cam, const double *d_queries, int query_stride, int n_queries, int k,
+                            int query_edge, float *d_pts, double *d_sqdist, int *d_frame, int *d_counts, void *stream) {
+    if (!m) return AMK_ERR_INVALID_ARG;
+    return amk::map_query_nearest(query_edge ? m->edge : m->obs, m->F, m->fmap.p, m->S, cam ? m->Twc.p : nullptr, cam, d_queries,
+                                  query_stride, n_queries, k, d_pts, d_sqdist, d_frame, d_counts, (hipStream_t)stream);
+}
+
+int amk_kfmap_nearest_distance(amk_kfmap *m, const double *d_queries, int query_stride, int n_queries, double *d_dist, void *stream) {
+    if (!m) return AMK_ERR_INVALID_ARG;
+    return amk::map_nearest_distance(m->obs, m->F, m->fmap.p, m->S, d_queries, query_stride, n_queries, d_dist, (hipStream_t)stream);
+}
+
+int amk_kfmap_query_nearest_host(amk_kfmap *m, const amk_frame_camera *cam, const double *h_queries, int query_stride, int n_queries,
+                                 int k, int query_edge, float *h_pts, double *h_sqdist, int *h_frame, int *h_counts) {
+    if (!m) return AMK_ERR_INVALID_ARG;
+    return amk::map_query_host(m->S, h_queries, query_stride, n_queries, k, nullptr, h_pts, h_sqdist, h_frame, h_counts, nullptr,
+                               [&](const double *dq, const double *, float *dp, double *dd, int *df, int *dc, double *) {
+                                   return amk_kfmap_query_nearest(m, cam, dq, query_stride, n_queries, k, query_edge, dp, dd, df, dc, nullptr);
+                               });
+}
+
+int amk_kfmap_nearest_distance_host(amk_kfmap *m, const double *h_queries, int query_stride, int n_queries, double *h_dist) {
+    if (!m || !h_dist) return AMK_ERR_INVALID_ARG;
+    return amk::map_query_host(m->S, h_queries, query_stride, n_queries, 1, nullptr, nullptr, nullptr, nullptr, nullptr, h_dist,
+                               [&](const double *dq, const double *, float *, double *, int *, int *, double *dd) {
+                                   return amk_kfmap_nearest_distance(m, dq, query_stride, n_queries, dd, nullptr);
+                               });
+}
+
+// FrameKDMap::GetPtCloud (:490-515) for one scene: the obstacle points of its query frames, in query-vector order, from the
+// pool's index-ordered planes (kd_index.hip: pool_planes -- written by every build, compacted by every sweep).  Synchronises.
+int amk_kfmap_points_host(amk_kfmap *m, int scene, float *h_xyz, long long capacity_points, int *h_frame_sizes, long long *n_points_out) {
+    if (!m || scene < 0 || scene >= m->S || capacity_points < 0 || (!h_xyz && capacity_points > 0)) return AMK_ERR_INVALID_ARG;
+    AMK_HIP(hipDeviceSynchronize());
+    const size_t S = m->S;
+    std::vector<int> fm((size_t)m->F), sz((size_t)m->F, -1);
+    AMK_HIP(hipMemcpy2D(fm.data(), sizeof(int), m->fmap.p + scene, sizeof(int) * S, sizeof(int), m->F, hipMemcpyDeviceToHost));
+    long long total = 0;
+    for (int f = 0; f < m->F; ++f) {
+        if (fm[f] < 0) continue;
+        AMK_HIP(hipMemcpy(&sz[f], m->obs->size.p + fm[f], sizeof(int), hipMemcpyDeviceToHost));
+        total += sz[f];
+    }
+    if (h_frame_sizes)   // -1 behind the scene's last frame (amk_kfmap_state_host's convention; the query vector has no holes: kf_insert_kernel)
+        for (int f = 0; f < m->F; ++f) h_frame_sizes[f] = sz[f];
+    if (n_points_out) *n_points_out = total;
+    if (!h_xyz && capacity_points == 0) return AMK_OK;   // the size probe
+    if (capacity_points < total) return AMK_ERR_INVALID_ARG;
+    if (total > 0 && !m->obs->x.p) return AMK_ERR_INVALID_ARG;   // (cannot occur: the planes are reserved at creation)
+    std::vector<float> plane;
+    long long o = 0;
+    for (int f = 0; f < m->F; ++f) {
+        const int n = sz[f];
+        if (n <= 0) continue;
+        plane.resize((size_t)n);
+        const float *src[3] = {m->obs->x.p, m->obs->y.p, m->obs->z.p};
+        for (int c = 0; c < 3; ++c) {
+            AMK_HIP(hipMemcpy(plane.data(), src[c] + (size_t)fm[f] * m->obs->cap, sizeof(float) * n, hipMemcpyDeviceToHost));
+            for (int i = 0; i < n; ++i) h_xyz[(size_t)(o + i) * 3 + c] = plane[i];
+        }
+        o += n;
+    }
+    return AMK_OK;
 }
 
 // Introspection (tests, diagnostics): per scene the number of keyframes, the number of frames of the query vector, the

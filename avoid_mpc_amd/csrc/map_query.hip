@@ -1,0 +1,284 @@
+// FrameKDMap's own queries over a MULTI-FRAME map, for a batch of scenes on gfx950, outside any control step:
+//   QueryNearest (AM/src/FrameKDMap.cpp:254-376)       amk_kfmap_query_nearest / amk_kd_query_frames
+//   GetNearestDistance (:378-427)                       amk_kfmap_nearest_distance / amk_kd_nearest_distance_frames
+// The rules are the ones the step applies to its reference points (step_frames.hip; written out in
+// include/avoid_mpc_amd.h, "The map's own queries"), answered here for any points, any k <= AMK_MAX_K and any
+// number of queries, from the map as it stands -- no amk_mpc, no staging of per-frame rows, no workspace.
+//
+// map_query_kernel: one wavefront per (scene, query).  It decides fast path or merge from the numbers the step uses (size of
+// frame 0, PtIsInFrame with contraction off), walks the frames its scene holds, runs grid_knn in every frame that contributes and
+// folds that frame's sorted k-list into a running sorted k-list held one entry per lane (distance, point, frame).  The fold is the
+// insertion grid_knn itself uses: the frame's entries are offered best first, an entry ranks behind every kept entry at the same or
+// a smaller distance (kept entries came from an earlier frame or are earlier neighbours of this one: the tie rule), and the
+// fold of a frame ends at its first entry that ranks behind the k-th kept one -- every later one is no nearer.  On a map whose
+// running list is full of near points a frame that holds nothing nearer costs ONE rank (a ballot and a population count).
+#include "step_common.h"
+
+#include <functional>
+
+using namespace amk;
+
+namespace {
+
+struct QueryFrames {  // kernel argument: the frames of ONE kind of cloud (obstacle or edge)
+    GridPtrs g[AMK_MAX_FRAMES];
+    const int *size[AMK_MAX_FRAMES];
+    int n;
+    // Map mode (kfmap.hip): every frame of every scene lives in ONE pool handle (g[0] / size[0]); frame f of scene s is pool
+    // scene fmap[f * S + s], or absent (< 0).  n may then exceed AMK_MAX_FRAMES.
+    const int *fmap;
+    int S;
+};
+
+__device__ __forceinline__ float wave_shr1_f32(float v) { return __int_as_float(wave_shr1_i32(__float_as_int(v))); }
+
+// DIST: GetNearestDistance -- the same walk with k = 1 and no fast path; out_dist = sqrt of the best squared distance
+template <bool MAP, bool DIST>
+__global__ __launch_bounds__(256) void map_query_kernel(QueryFrames qf, int n_scenes, const double *__restrict__ queries,
+                                                        int query_stride, int n_queries, int k_in,
+                                                        const double *__restrict__ Twc, amk_frame_camera cam,
+                                                        float *__restrict__ out_pts, double *__restrict__ out_d2,
+                                                        int *__restrict__ out_frame, int *__restrict__ out_cnt,
+                                                        double *__restrict__ out_dist) {
+    __shared__ GridWaveLds wl[4];
+    const int bps = (n_queries + 3) / 4;  // blocks per scene; scenes interleaved over the 8 XCDs like kd_grid_search_kernel
+    const int xcd = blockIdx.x & 7;
+    const int j = blockIdx.x >> 3;
+    const int s = (j / bps) * 8 + xcd;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)  /* wave-uniform: keeps what derives from it in SGPRs */, lane = threadIdx.x & 63;
+    const int q = (j % bps) * 4 + w;
+    if (s >= n_scenes || q >= n_queries) return;
+    const int k = DIST ? 1 : k_in;
+    const size_t row = (size_t)s * n_queries + q;
+    const double *qp = queries + row * query_stride;
+    const double qx = qp[0], qy = qp[1], qz = qp[2];
+    // frames this scene's map holds: the walk ends at its last present frame (step_merge_plan_pack_kernel's ballot)
+    int F = qf.n;
+    if (MAP) {
+        int hi = 0;
+        for (int f0 = 0; f0 < qf.n; f0 += 64) {
+            const int f = f0 + lane;
+            const unsigned long long b = __ballot(f < qf.n && qf.fmap[(size_t)f * qf.S + s] >= 0);
+            if (b) hi = f0 + 64 - __clzll((long long)b);
+        }
+        F = hi;
+    }
+    auto scene_of = [&](int f) { return MAP ? qf.fmap[(size_t)f * qf.S + s] : s; };
+    const GridPtrs pool = qf.g[0];   // (map mode: one set of pool pointers stays live over the loop)
+    const int *pool_size = qf.size[0];
+
+    double rd = DBL_MAX;             // the running list: lane i < k holds the i-th best (distance, point, frame) so far
+    float rx = 0.f, ry = 0.f, rz = 0.f;
+    int rf = -1, cnt = 0;
+    bool fast = false;
+    if (!DIST && F > 0) {            // QueryNearestWithCurFrame (:254-275, 339-345)
+        const int m0 = scene_of(0);
+        const int n0 = m0 < 0 ? 0 : (MAP ? pool_size : qf.size[0])[m0];
+        fast = n0 >= k && (!Twc || pt_in_frame(Twc + (size_t)s * 16, cam, qx, qy, qz));
+        if (fast) {
+            double ld;
+            int li, lpos;
+            const GridScene gs = (MAP ? pool : qf.g[0]).scene(m0);
+            grid_knn(gs, qx, qy, qz, k, ld, li, lpos, &wl[w]);
+            cnt = n0 > k ? k : 0;    // kd_tree_two.h:119-124: a cloud of exactly k points answers nothing
+            if (lane < cnt && li != kNoIndex) {
+                const float4 rec = gs.pt[lpos];
+                rd = ld; rx = rec.x; ry = rec.y; rz = rec.z; rf = 0;
+            }
+        }
+    }
+    if (!fast) {                     // QueryNearestThreadWorker over mVecQueryVector (:276-321) + sort by distance (:371-375)
+        for (int f = 0; f < F; ++f) {
+            const int m = scene_of(f);
+            if (m < 0) continue;     // (map mode: this scene's map has no frame f)
+            const int n = (MAP ? pool_size : qf.size[f])[m];
+            if (n <= k) continue;    // k' = min(k, size_f) results exist iff size_f > k'
+            double ld;
+            int li, lpos;
+            const GridScene gs = (MAP ? pool : qf.g[f]).scene(m);
+            grid_knn(gs, qx, qy, qz, k, ld, li, lpos, &wl[w]);
+            const float4 rec = gs.pt[lpos];   // (lpos = 0 for empty slots: a valid address)
+            const double nd = (lane < k && li != kNoIndex) ? ld : DBL_MAX;
+            for (int e = 0; e < k; ++e) {     // this frame's entries, best first
+                const double dc = readlane_f64(nd, e);
+                if (!(dc < DBL_MAX)) break;
+                // rank among the kept entries: behind every one at the same or a smaller distance
+                const int pos = __popcll(__ballot((lane < k) & (rd <= dc)));
+                if (pos >= k) break;          // (the entries behind it are no nearer)
+                const float cx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rec.x), e));
+                const float cy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rec.y), e));
+                const float cz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rec.z), e));
+                const double up_d = wave_shr1_f64(rd);
+                const float up_x = wave_shr1_f32(rx), up_y = wave_shr1_f32(ry), up_z = wave_shr1_f32(rz);
+                const int up_f = wave_shr1_i32(rf);
+                const bool above = lane > pos, here = lane == pos;   // selects, not branches
+                rd = here ? dc : (above ? up_d : rd);
+                rx = here ? cx : (above ? up_x : rx);
+                ry = here ? cy : (above ? up_y : ry);
+                rz = here ? cz : (above ? up_z : rz);
+                rf = here ? f : (above ? up_f : rf);
+            }
+        }
+        cnt = __popcll(__ballot((lane < k) & (rd < DBL_MAX)));
+    }
+    if (DIST) {
+        if (lane == 0) out_dist[row] = sqrt(rd);   // (no frame answered: sqrt(DBL_MAX), :381,426)
+        return;
+    }
+    if (lane == 0 && out_cnt) out_cnt[row] = cnt;
+    if (lane < k) {
+        const bool ok = rd < DBL_MAX;
+        const size_t o = row * k + lane;
+        if (out_d2) out_d2[o] = ok ? rd : DBL_MAX;
+        if (out_frame) out_frame[o] = ok ? rf : -1;
+        if (out_pts) {
+            out_pts[o * 3 + 0] = ok ? rx : 0.f;
+            out_pts[o * 3 + 1] = ok ? ry : 0.f;
+            out_pts[o * 3 + 2] = ok ? rz : 0.f;
+        }
+    }
+}
+
+template <bool DIST>
+int launch_query(const QueryFrames &qf, int S, const double *d_queries, int query_stride, int n_queries, int k, const double *d_Twc,
+                 const amk_frame_camera *cam, float *d_pts, double *d_sqdist, int *d_frame, int *d_counts, double *d_dist,
+                 hipStream_t stream) {
+    const long long blocks = (long long)((S + 7) / 8 * 8) * ((n_queries + 3) / 4);
+    if (blocks > 0x7fffffffll) return AMK_ERR_UNSUPPORTED;
+    amk_frame_camera c{};
+    if (cam) c = *cam;
+    auto kernel = qf.fmap ? map_query_kernel<true, DIST> : map_query_kernel<false, DIST>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, stream, qf, S, d_queries, query_stride, n_queries, k, d_Twc, c,
+                       d_pts, d_sqdist, d_frame, d_counts, d_dist);
+    AMK_HIP(hipGetLastError());
+    return AMK_OK;
+}
+
+int query_args_ok(const double *d_queries, int query_stride, int n_queries) {
+    return d_queries && query_stride >= 3 && n_queries >= 1;
+}
+
+// a caller's list of frame handles -> the kernel's argument (status: the header's rules, before anything is launched)
+int frames_of_handles(amk_kd *const *frames, int n_frames, QueryFrames &qf, int &S) {
+    if (!frames || n_frames < 1) return AMK_ERR_INVALID_ARG;
+    if (n_frames > AMK_MAX_FRAMES) return AMK_ERR_UNSUPPORTED;
+    for (int f = 0; f < n_frames; ++f)
+        if (!frames[f] || frames[f]->n_scenes != frames[0]->n_scenes) return AMK_ERR_INVALID_ARG;
+    qf = QueryFrames{};
+    qf.n = n_frames;
+    qf.fmap = nullptr;
+    qf.S = S = frames[0]->n_scenes;
+    for (int f = 0; f < n_frames; ++f) {
+        if (frames[f]->mode != 0 || frames[f]->tie_order != AMK_TIES_LOWEST_INDEX) return AMK_ERR_UNSUPPORTED;
+        qf.g[f] = grid_ptrs(frames[f]);
+        qf.size[f] = frames[f]->size.p;
+    }
+    return AMK_OK;
+}
+
+QueryFrames frames_of_pool(amk_kd *pool, int n_frames, const int *d_fmap, int S) {
+    QueryFrames qf{};
+    qf.n = n_frames;
+    qf.fmap = d_fmap;
+    qf.S = S;
+    qf.g[0] = grid_ptrs(pool);
+    qf.size[0] = pool->size.p;
+    return qf;
+}
+
+}  // namespace
+
+namespace amk {
+// The two queries over a keyframe map's pool (kfmap.hip): frame f of scene s = pool scene d_fmap[f * S + s] (< 0: absent).
+int map_query_nearest(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_Twc, const amk_frame_camera *cam,
+                      const double *d_queries, int query_stride, int n_queries, int k, float *d_pts, double *d_sqdist, int *d_frame,
+                      int *d_counts, hipStream_t stream) {
+    if (!pool || !d_fmap || n_frames < 1 || S < 1 || !query_args_ok(d_queries, query_stride, n_queries) || k < 1) return AMK_ERR_INVALID_ARG;
+    if (d_Twc && !cam) return AMK_ERR_INVALID_ARG;
+    if (k > AMK_MAX_K) return AMK_ERR_UNSUPPORTED;
+    return launch_query<false>(frames_of_pool(pool, n_frames, d_fmap, S), S, d_queries, query_stride, n_queries, k, d_Twc, cam, d_pts,
+                               d_sqdist, d_frame, d_counts, nullptr, stream);
+}
+
+int map_nearest_distance(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_queries, int query_stride,
+                         int n_queries, double *d_dist, hipStream_t stream) {
+    if (!pool || !d_fmap || n_frames < 1 || S < 1 || !query_args_ok(d_queries, query_stride, n_queries) || !d_dist) return AMK_ERR_INVALID_ARG;
+    return launch_query<true>(frames_of_pool(pool, n_frames, d_fmap, S), S, d_queries, query_stride, n_queries, 1, nullptr, nullptr,
+                              nullptr, nullptr, nullptr, nullptr, d_dist, stream);
+}
+
+// The *_host variants: queries (and poses) staged through device memory, `launch` enqueued on the null stream between two
+// device-wide waits (a build or an update enqueued on any stream is seen), results copied back.  Allocates per call: a
+// convenience for single-robot hosts and tests, not a hot path.  Any output may be NULL.
+int map_query_host(int S, const double *h_queries, int query_stride, int n_queries, int k, const double *h_Twc, float *h_pts,
+                   double *h_sqdist, int *h_frame, int *h_counts, double *h_dist,
+                   const std::function<int(const double *, const double *, float *, double *, int *, int *, double *)> &launch) {
+    if (S < 1 || !query_args_ok(h_queries, query_stride, n_queries) || k < 1) return AMK_ERR_INVALID_ARG;
+    if (k > AMK_MAX_K) return AMK_ERR_UNSUPPORTED;
+    const size_t rows = (size_t)S * n_queries, nq = (rows - 1) * query_stride + 3;
+    DevBuf<double> q, twc, d2, dist;
+    DevBuf<float> pts;
+    DevBuf<int> frame, counts;
+    AMK_HIP(q.alloc(nq));
+    AMK_HIP(hipMemcpy(q.p, h_queries, sizeof(double) * nq, hipMemcpyHostToDevice));
+    if (h_Twc) {
+        AMK_HIP(twc.alloc((size_t)S * 16));
+        AMK_HIP(hipMemcpy(twc.p, h_Twc, sizeof(double) * S * 16, hipMemcpyHostToDevice));
+    }
+    if (h_pts) AMK_HIP(pts.alloc(rows * k * 3));
+    if (h_sqdist) AMK_HIP(d2.alloc(rows * k));
+    if (h_frame) AMK_HIP(frame.alloc(rows * k));
+    if (h_counts) AMK_HIP(counts.alloc(rows));
+    if (h_dist) AMK_HIP(dist.alloc(rows));
+    AMK_HIP(hipDeviceSynchronize());
+    const int st = launch(q.p, twc.p, pts.p, d2.p, frame.p, counts.p, dist.p);
+    if (st != AMK_OK) return st;
+    AMK_HIP(hipDeviceSynchronize());
+    if (h_pts) AMK_HIP(hipMemcpy(h_pts, pts.p, sizeof(float) * rows * k * 3, hipMemcpyDeviceToHost));
+    if (h_sqdist) AMK_HIP(hipMemcpy(h_sqdist, d2.p, sizeof(double) * rows * k, hipMemcpyDeviceToHost));
+    if (h_frame) AMK_HIP(hipMemcpy(h_frame, frame.p, sizeof(int) * rows * k, hipMemcpyDeviceToHost));
+    if (h_counts) AMK_HIP(hipMemcpy(h_counts, counts.p, sizeof(int) * rows, hipMemcpyDeviceToHost));
+    if (h_dist) AMK_HIP(hipMemcpy(h_dist, dist.p, sizeof(double) * rows, hipMemcpyDeviceToHost));
+    return AMK_OK;
+}
+}  // namespace amk
+
+extern "C" {
+
+int amk_kd_query_frames(amk_kd *const *frames, int n_frames, const double *d_Twc, const amk_frame_camera *cam,
+                        const double *d_queries, int query_stride, int n_queries, int k, float *d_pts, double *d_sqdist,
+                        int *d_frame, int *d_counts, void *stream) {
+    if (!query_args_ok(d_queries, query_stride, n_queries) || k < 1) return AMK_ERR_INVALID_ARG;
+    if (d_Twc && !cam) return AMK_ERR_INVALID_ARG;
+    if (k > AMK_MAX_K) return AMK_ERR_UNSUPPORTED;
+    QueryFrames qf;
+    int S = 0;
+    if (const int st = frames_of_handles(frames, n_frames, qf, S); st != AMK_OK) return st;
+    return launch_query<false>(qf, S, d_queries, query_stride, n_queries, k, d_Twc, cam, d_pts, d_sqdist, d_frame, d_counts, nullptr,
+                               (hipStream_t)stream);
+}
+
+int amk_kd_nearest_distance_frames(amk_kd *const *frames, int n_frames, const double *d_queries, int query_stride, int n_queries,
+                                   double *d_dist, void *stream) {
+    if (!query_args_ok(d_queries, query_stride, n_queries) || !d_dist) return AMK_ERR_INVALID_ARG;
+    QueryFrames qf;
+    int S = 0;
+    if (const int st = frames_of_handles(frames, n_frames, qf, S); st != AMK_OK) return st;
+    return launch_query<true>(qf, S, d_queries, query_stride, n_queries, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_dist,
+                              (hipStream_t)stream);
+}
+
+int amk_kd_query_frames_host(amk_kd *const *frames, int n_frames, const double *h_Twc, const amk_frame_camera *cam,
+                             const double *h_queries, int query_stride, int n_queries, int k, float *h_pts, double *h_sqdist,
+                             int *h_frame, int *h_counts) {
+    if (h_Twc && !cam) return AMK_ERR_INVALID_ARG;
+    QueryFrames qf;
+    int S = 0;
+    if (const int st = frames_of_handles(frames, n_frames, qf, S); st != AMK_OK) return st;
+    return amk::map_query_host(S, h_queries, query_stride, n_queries, k, h_Twc, h_pts, h_sqdist, h_frame, h_counts, nullptr,
+                               [&](const double *dq, const double *dT, float *dp, double *dd, int *df, int *dc, double *) {
+                                   return amk_kd_query_frames(frames, n_frames, dT, cam, dq, query_stride, n_queries, k, dp, dd, df, dc, nullptr);
+                               });
+}
+
+}  // extern "C"

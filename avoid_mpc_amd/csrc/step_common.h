@@ -24,6 +24,21 @@ __device__ __forceinline__ void store_nbr(float *__restrict__ pts, double *__res
     o[2] = ok ? z : 0.f;
 }
 
+// PtIsInFrame (FrameKDMap.cpp:215-231): Twc rigid, its inverse is [R' | -R' t]
+__device__ __forceinline__ bool pt_in_frame(const double *__restrict__ T, const amk_frame_camera &cam, double px, double py,
+                                            double pz) {
+#pragma clang fp contract(off)   // every kernel that takes this decision for a point (the step's searches skip what its merge will not read; map_query.hip) gets the same bits
+    const double dx = px - T[3], dy = py - T[7], dz = pz - T[11];
+    const double x = T[0] * dx + T[4] * dy + T[8] * dz;
+    const double y = T[1] * dx + T[5] * dy + T[9] * dz;
+    const double z = T[2] * dx + T[6] * dy + T[10] * dz;
+    if (z > cam.depth_max || z < 0) return false;
+    const double u = cam.fx * x / z + cam.cx;
+    const double v = cam.fy * y / z + cam.cy;
+    if (u < 0 || u >= cam.width || v < 0 || v >= cam.height) return false;
+    return true;
+}
+
 // Where the AMK_TIES_NANOFLANN trees come from: one frame's two trees by value (the single-frame path: no table to upload,
 // its steps stay graph-capturable), or the device table of a frame list (too large for the kernel-argument segment next to
 // FrameSet; frame = blockIdx.y).

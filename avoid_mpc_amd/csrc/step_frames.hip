@@ -48,21 +48,6 @@ struct FrameSet {  // kernel argument: where every frame's indices live
     }
 };
 
-// PtIsInFrame (FrameKDMap.cpp:215-231): Twc rigid, its inverse is [R' | -R' t]
-__device__ __forceinline__ bool pt_in_frame(const double *__restrict__ T, const amk_frame_camera &cam, double px, double py,
-                                            double pz) {
-#pragma clang fp contract(off)   // two kernels take this decision for the same point (the searches skip what the merge will not read): same bits in both
-    const double dx = px - T[3], dy = py - T[7], dz = pz - T[11];
-    const double x = T[0] * dx + T[4] * dy + T[8] * dz;
-    const double y = T[1] * dx + T[5] * dy + T[9] * dz;
-    const double z = T[2] * dx + T[6] * dy + T[10] * dz;
-    if (z > cam.depth_max || z < 0) return false;
-    const double u = cam.fx * x / z + cam.cx;
-    const double v = cam.fy * y / z + cam.cy;
-    if (u < 0 || u >= cam.width || v < 0 || v >= cam.height) return false;
-    return true;
-}
-
 // blockIdx.y = the frame (a list of handles: every frame exists) or a chunk of consecutive frames (a keyframe map with room for
 // 101 frames holds ~6 on a flight, and a launch of 101 x S x (N + 4) / 4 blocks of which 94 % return at once is mostly dispatch)
 template <bool MAP>

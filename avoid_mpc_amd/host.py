@@ -258,11 +258,63 @@ class MpcBatch:
         return P
 
 
+def _stream_arg(stream):
+    """A torch stream, None (torch's current stream) or a raw hipStream_t (int / c_void_p, e.g. amk_pipeline_stream)."""
+    if isinstance(stream, C.c_void_p):
+        return stream
+    if isinstance(stream, int):
+        return C.c_void_p(stream)
+    return capi.stream_ptr(stream)
+
+
+def _check_queries(queries, S):
+    assert queries.dtype == torch.float64 and queries.dim() == 3 and queries.shape[0] == S and queries.shape[2] >= 3 and queries.shape[1] >= 1
+    return int(queries.shape[1]), int(queries.shape[2])
+
+
+def _query_out(S, Q, k, dev):
+    return dict(pts=torch.empty((S, Q, k, 3), dtype=torch.float32, device=dev), sqdist=torch.empty((S, Q, k), dtype=torch.float64, device=dev),
+                frame=torch.empty((S, Q, k), dtype=torch.int32, device=dev), counts=torch.empty((S, Q), dtype=torch.int32, device=dev))
+
+
+def query_frames(handles, queries, k, Twc=None, cam=None, stream=None, out=None):
+    """amk_kd_query_frames: FrameKDMap::QueryNearest over a list of KdBatch handles (obstacle OR edge, index 0 = current frame).
+    queries float64 [S, Q, >= 3]; Twc float64 [S, 4, 4] or None; cam: capi.FrameCamera.  -> dict(pts, sqdist, frame, counts)"""
+    F, S = len(handles), handles[0].S
+    Q, stride = _check_queries(queries, S)
+    if out is None:
+        out = _query_out(S, Q, int(k), queries.device)
+    ha = (C.c_void_p * F)(*[h.h for h in handles])
+    capi.check(capi.load().amk_kd_query_frames(ha, F, capi.dptr(Twc), C.byref(cam) if cam is not None else None, capi.dptr(queries), stride,
+                                               Q, int(k), capi.dptr(out["pts"]), capi.dptr(out["sqdist"]), capi.dptr(out["frame"]),
+                                               capi.dptr(out["counts"]), _stream_arg(stream)), "amk_kd_query_frames")
+    return out
+
+
+def nearest_distance_frames(handles, queries, stream=None, out=None):
+    """amk_kd_nearest_distance_frames: FrameKDMap::GetNearestDistance over a list of KdBatch handles -> float64 [S, Q]"""
+    F, S = len(handles), handles[0].S
+    Q, stride = _check_queries(queries, S)
+    if out is None:
+        out = torch.empty((S, Q), dtype=torch.float64, device=queries.device)
+    ha = (C.c_void_p * F)(*[h.h for h in handles])
+    capi.check(capi.load().amk_kd_nearest_distance_frames(ha, F, capi.dptr(queries), stride, Q, capi.dptr(out), _stream_arg(stream)),
+               "amk_kd_nearest_distance_frames")
+    return out
+
+
 class KfMap:
     """amk_kfmap: FrameKDMap's keyframe list for S scenes on the device (FrameKDMap.cpp:29-74,233-252,428-488)."""
 
-    def __init__(self, n_scenes, max_points, max_edge_points, max_frame_count, th_dist, th_count, depth_min, Tbc):
+    def __init__(self, n_scenes, max_points, max_edge_points, max_frame_count, th_dist, th_count, depth_min, Tbc, handle=None):
+        """handle: a borrowed amk_kfmap* (a pipeline slot's); it is then not destroyed by this object."""
         self.lib = capi.load()
+        self.owned = handle is None
+        if handle is not None:
+            self.h = handle if isinstance(handle, C.c_void_p) else C.c_void_p(handle)
+            self.S, self.F = self.lib.amk_kfmap_scenes(self.h), self.lib.amk_kfmap_frames(self.h)
+            self.max_points, self.max_edge_points = int(max_points), int(max_edge_points)
+            return
         p = capi.KfmapParams(int(max_frame_count), int(th_count), float(th_dist), float(depth_min),
                              (C.c_double * 16)(*[float(v) for v in np.asarray(Tbc, np.float64).reshape(-1)]))
         h = C.c_void_p()
@@ -272,7 +324,8 @@ class KfMap:
 
     def close(self):
         if getattr(self, "h", None):
-            self.lib.amk_kfmap_destroy(self.h)
+            if self.owned:
+                self.lib.amk_kfmap_destroy(self.h)
             self.h = None
 
     __del__ = close
@@ -300,6 +353,40 @@ class KfMap:
                                            capi.dptr(pos_x), capi.dptr(ref_path), capi.dptr(out["u"]), capi.dptr(out["x0array"]),
                                            capi.dptr(out["flags"]), capi.stream_ptr(stream)), "amk_kfmap_step")
         return out
+
+    def query_nearest(self, queries, k, cam=None, edge=False, stream=None, out=None):
+        """amk_kfmap_query_nearest: FrameKDMap::QueryNearest for queries float64 [S, Q, 3 | 10 | 14 ...] (the first three of every
+        row are read) over each scene's own query vector, from the map as it stands.  cam: capi.FrameCamera or None (every query
+        counts as inside the current frame); edge: the edge clouds.  stream: a torch stream or a raw hipStream_t (int).
+        -> dict(pts [S,Q,k,3] f32, sqdist [S,Q,k] f64, frame [S,Q,k] i32 (position in the query vector, -1 empty), counts [S,Q] i32)"""
+        Q, stride = _check_queries(queries, self.S)
+        if out is None:
+            out = _query_out(self.S, Q, int(k), queries.device)
+        capi.check(self.lib.amk_kfmap_query_nearest(self.h, C.byref(cam) if cam is not None else None, capi.dptr(queries), stride, Q, int(k),
+                                                    int(bool(edge)), capi.dptr(out["pts"]), capi.dptr(out["sqdist"]), capi.dptr(out["frame"]),
+                                                    capi.dptr(out["counts"]), _stream_arg(stream)), "amk_kfmap_query_nearest")
+        return out
+
+    def nearest_distance(self, queries, stream=None, out=None):
+        """amk_kfmap_nearest_distance: FrameKDMap::GetNearestDistance -> float64 [S, Q] (sqrt(DBL_MAX) where no frame answers)."""
+        Q, stride = _check_queries(queries, self.S)
+        if out is None:
+            out = torch.empty((self.S, Q), dtype=torch.float64, device=queries.device)
+        capi.check(self.lib.amk_kfmap_nearest_distance(self.h, capi.dptr(queries), stride, Q, capi.dptr(out), _stream_arg(stream)),
+                   "amk_kfmap_nearest_distance")
+        return out
+
+    def points(self, scene):
+        """amk_kfmap_points_host: FrameKDMap::GetPtCloud for one scene -> (xyz float32 [n, 3] in query-vector order, frame_sizes int32 [F],
+        -1 behind the scene's last frame) (synchronises)"""
+        sz = np.zeros(self.F, np.int32); n = C.c_longlong(0)
+        capi.check(self.lib.amk_kfmap_points_host(self.h, int(scene), None, 0, sz.ctypes.data_as(C.c_void_p), C.byref(n)),
+                   "amk_kfmap_points_host")   # the size probe
+        xyz = np.zeros((n.value, 3), np.float32)
+        if n.value:
+            capi.check(self.lib.amk_kfmap_points_host(self.h, int(scene), xyz.ctypes.data_as(C.c_void_p), n.value, sz.ctypes.data_as(C.c_void_p),
+                                                      C.byref(n)), "amk_kfmap_points_host")
+        return xyz, sz
 
     def state(self):
         """-> dict(n_keyframes [S], n_query_frames [S], last_outliers [S], frame_sizes [S, F]) (synchronises)"""
@@ -344,6 +431,7 @@ class Pipeline:
         self.N = self.lib.amk_mpc_horizon(self.lib.amk_pipeline_mpc(h, 0))
         self.gang = self.lib.amk_pipeline_gang(h)
         self._events = []
+        self._max_points = (int(max_points), int(max_edge_points))
         hs = n_scenes * self.gang   # scenes of a slot's handles
         self._mpc = [MpcBatch(prm.T, prm.dt, prm.K, hs, handle=self.lib.amk_pipeline_mpc(h, i)) for i in range(n_slots)]
         self._kd = [(KdBatch(hs, max_points, handle=self.lib.amk_pipeline_kd(h, i, 0)),
@@ -374,6 +462,37 @@ class Pipeline:
         capi.check(self.lib.amk_kfmap_state_host(h, nk.ctypes.data_as(C.c_void_p), nq.ctypes.data_as(C.c_void_p),
                                                  out.ctypes.data_as(C.c_void_p), sz.ctypes.data_as(C.c_void_p)), "amk_kfmap_state_host")
         return dict(n_keyframes=nk, n_query_frames=nq, last_outliers=out, frame_sizes=sz)
+
+    def kfmap(self, slot):
+        """The slot's keyframe map as a KfMap that borrows the handle (amk_pipeline_kfmap)."""
+        h = self.lib.amk_pipeline_kfmap(self.h, int(slot))
+        assert h, "the pipeline was created without keyframes"
+        return KfMap(0, self._max_points[0], self._max_points[1], 0, 0, 0, 0, None, handle=h)
+
+    def kfmap_query(self, slot, queries, k=None, cam=None, edge=False, after_wait=False):
+        """QueryNearest (k given) or GetNearestDistance (k None) on the slot's keyframe map, over its gang x n_scenes scenes.
+        Enqueued on the SLOT's stream, behind every launch the slot has been given so far (frames staged in an open gang are not in the
+        map yet: wait() first); torch's current stream is ordered on both sides -- the slot reads `queries` after the work queued on it
+        so far, and work queued on it afterwards sees the results.  after_wait=True: the caller has waited for the slot (wait / drain)
+        and the query runs on torch's current stream instead.  The slot's next launch must not overlap the query: order the next
+        submit's input_ready behind it (the default order_after_current_stream does)."""
+        m = self.kfmap(slot)
+        Q = int(queries.shape[1])   # (the outputs belong to torch's current stream, which waits for the slot below before it reuses them)
+        out = torch.empty((m.S, Q), dtype=torch.float64, device=queries.device) if k is None else _query_out(m.S, Q, int(k), queries.device)
+        run = (lambda st: m.nearest_distance(queries, stream=st, out=out)) if k is None else \
+              (lambda st: m.query_nearest(queries, k, cam=cam, edge=edge, stream=st, out=out))
+        if after_wait:
+            return run(None)
+        raw = self.lib.amk_pipeline_stream(self.h, int(slot))
+        ext = torch.cuda.ExternalStream(int(raw))
+        ext.wait_stream(torch.cuda.current_stream())
+        run(int(raw))
+        torch.cuda.current_stream().wait_stream(ext)
+        return out
+
+    def kfmap_points(self, slot, scene):
+        """GetPtCloud of one scene of the slot's keyframe map (synchronises the device) -> (xyz [n, 3], frame_sizes [F])."""
+        return self.kfmap(slot).points(scene)
 
     def mpc(self, slot):
         return self._mpc[slot]

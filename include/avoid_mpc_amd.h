@@ -534,6 +534,9 @@ int amk_pipeline_gang(const amk_pipeline *p);       /* frames per launch (>= 1) 
 amk_mpc *amk_pipeline_mpc(amk_pipeline *p, int slot);
 amk_kd *amk_pipeline_kd(amk_pipeline *p, int slot, int which /* 0 obstacle, 1 edge */);
 amk_kfmap *amk_pipeline_kfmap(amk_pipeline *p, int slot);   /* the slot's keyframe map (NULL without one), e.g. for amk_kfmap_state_host */
+/* ... and for the map's own queries (amk_kfmap_query_nearest / _nearest_distance / _points_host, below): enqueue them on
+ * amk_pipeline_stream(p, slot) -- behind every launch the slot was given; frames staged in an open gang are not in the map yet --
+ * or on any stream after amk_pipeline_wait / _wait_stream, and order the slot's next submit behind them (input_ready).          */
 void *amk_pipeline_stream(amk_pipeline *p, int slot);
 /* submit() hands back a ticket = position_in_gang * n_slots + slot (without a gang: the slot index, as before);
  * ticket % n_slots is the slot, for amk_pipeline_mpc / _kd / _stream.                                                    */
@@ -597,6 +600,64 @@ int amk_kfmap_step(amk_kfmap *map, const struct amk_frame_camera *cam, amk_mpc *
 /* Introspection (synchronises): per scene mKeyFrameMap.size(), mVecQueryVector.size(), the outliers of the last sweep and --
  * h_frame_sizes [S][amk_kfmap_frames()] or NULL -- the obstacle-cloud size of every query frame (-1 behind the scene's last). */
 int amk_kfmap_state_host(amk_kfmap *map, int *h_n_keyframes, int *h_n_query_frames, int *h_last_outliers, int *h_frame_sizes);
+
+/* The map's own queries: FrameKDMap::QueryNearest, GetNearestDistance and GetPtCloud (FrameKDMap.h:60-67) for any points,
+ * outside a control step.  They answer from the map as it stands, change no map state, need no amk_mpc and allocate nothing
+ * (the *_host variants stage through device memory they allocate per call).  A query is stream-ordered: enqueue it AFTER the
+ * amk_kfmap_add_vertex / amk_kfmap_update it should see (same stream, or ordered by an event), and do not let it overlap a LATER
+ * add_vertex / update / reset on another stream -- those rebuild the trees it reads.
+ *   d_queries   read at d_queries[(s * n_queries + q) * query_stride + {0,1,2}], s < amk_kfmap_scenes(): query_stride 3 = packed,
+ *               10 = the rows of mRefPath, 14 = the rows of x0array; n_queries >= 1 (no AMK_MAX_QUERIES cap), 1 <= k <= AMK_MAX_K
+ *               (k = 0: AMK_ERR_INVALID_ARG, k > AMK_MAX_K: AMK_ERR_UNSUPPORTED)
+ *   d_pts [S][n_queries][k][3], d_sqdist [S][n_queries][k], d_frame [S][n_queries][k] (the position in the query vector the
+ *   neighbour came from, 0 = current frame: what PtDists::isInKeyFrame carries), d_counts [S][n_queries], d_dist [S][n_queries];
+ *   each output of the k-NN query may be NULL
+ *   query_edge  != 0: the frames' edge clouds (QueryNearest(..., queryEdge = true)), else their obstacle clouds
+ *   cam         NULL: no frustum test, every query counts as inside the current frame (as amk_kfmap_step)
+ * QueryNearest, the rules of the step (amk_step_batch_frames):
+ *   fast path   taken when frame 0 exists, holds >= k points and the query passes PtIsInFrame (:215-231) against the scene's
+ *               mCurFrame.Twc: the answer is frame 0's SearchForNearest(k) alone, its count by KDTreeTwo's size rule
+ *               (kd_tree_two.h:119-124) -- a current frame of EXACTLY k points takes the fast path and returns nothing
+ *   merge path  otherwise: every present frame contributes its k nearest iff it holds MORE than k points (k' = min(k, size),
+ *               size <= k: no result); the candidates are ordered by squared distance, equal distances keep the earlier frame,
+ *               then the earlier neighbour within a frame; the first k are kept and the count is their number
+ *   Within a frame equal distances order by cloud index.  Slots beyond the count hold DBL_MAX, (0, 0, 0) and frame -1.  A query
+ *   with a NaN or infinite coordinate gets every slot empty (its count is unspecified, as in the step); a scene with no frame
+ *   yet gets count 0 everywhere.
+ * GetNearestDistance: sqrt of the minimum 1-NN squared distance over the frames whose obstacle cloud holds more than one point;
+ *   no fast path; sqrt(DBL_MAX) when no frame answers.                                                                          */
+int amk_kfmap_query_nearest(amk_kfmap *map, const struct amk_frame_camera *cam, const double *d_queries, int query_stride,
+                            int n_queries, int k, int query_edge, float *d_pts, double *d_sqdist, int *d_frame,
+                            int *d_counts, void *stream);
+int amk_kfmap_nearest_distance(amk_kfmap *map, const double *d_queries, int query_stride, int n_queries,
+                               double *d_dist, void *stream);
+/* Same with host buffers (stage through device memory, synchronise the device).  h_queries holds at least
+ * (S * n_queries - 1) * query_stride + 3 doubles.                                                                            */
+int amk_kfmap_query_nearest_host(amk_kfmap *map, const struct amk_frame_camera *cam, const double *h_queries, int query_stride,
+                                 int n_queries, int k, int query_edge, float *h_pts, double *h_sqdist, int *h_frame,
+                                 int *h_counts);
+int amk_kfmap_nearest_distance_host(amk_kfmap *map, const double *h_queries, int query_stride, int n_queries, double *h_dist);
+/* GetPtCloud (:490-515) for one scene (synchronises): the obstacle points of the scene's query frames in query-vector order,
+ * inside a frame in cloud order, packed xyz.  h_frame_sizes [amk_kfmap_frames()] (or NULL): the points per frame, -1 behind the
+ * scene's last frame; *n_points_out: their total.  capacity_points < total: nothing is written to h_xyz, the total and the
+ * sizes are still reported and the call returns AMK_ERR_INVALID_ARG; h_xyz == NULL with capacity 0 is the size probe (AMK_OK).  The
+ * reference's colours (white for the current frame, one random colour per keyframe tree) are the caller's to assign from the
+ * frame sizes.                                                                                                               */
+int amk_kfmap_points_host(amk_kfmap *map, int scene, float *h_xyz, long long capacity_points, int *h_frame_sizes,
+                          long long *n_points_out);
+/* The same two queries over a caller's list of frame handles (the frame model of amk_step_batch_frames): frames[f] are obstacle
+ * OR edge handles, as the caller chooses, frame 0 the current one; n_frames <= AMK_MAX_FRAMES (else AMK_ERR_UNSUPPORTED); every
+ * handle holds the same number of scenes S.  d_Twc [S][16] or NULL (every query counts as inside the current frame); d_Twc
+ * without cam is AMK_ERR_INVALID_ARG.  Scan-mode handles and handles in AMK_TIES_NANOFLANN / AMK_TIES_AUTO return
+ * AMK_ERR_UNSUPPORTED before anything is launched: the multi-frame query answers in the default tie order only.              */
+int amk_kd_query_frames(amk_kd *const *frames, int n_frames, const double *d_Twc, const struct amk_frame_camera *cam,
+                        const double *d_queries, int query_stride, int n_queries, int k, float *d_pts, double *d_sqdist,
+                        int *d_frame, int *d_counts, void *stream);
+int amk_kd_nearest_distance_frames(amk_kd *const *frames, int n_frames, const double *d_queries, int query_stride,
+                                   int n_queries, double *d_dist, void *stream);
+int amk_kd_query_frames_host(amk_kd *const *frames, int n_frames, const double *h_Twc, const struct amk_frame_camera *cam,
+                             const double *h_queries, int query_stride, int n_queries, int k, float *h_pts, double *h_sqdist,
+                             int *h_frame, int *h_counts);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Scenes sharded over the GPUs of a node (one process per GPU), RCCL over xGMI                 */
