@@ -23,6 +23,7 @@ import pytest
 from tests import _oracle
 from tests.test_depth_oracle import YAML, hostile_scene
 from tests.test_kd_oracle import _hostile_queries
+from tests._sweep_cases import _kept, _sweep_np   # (the sweep's contract in numpy: shared with the keyframe map's sweep tests)
 from avoid_mpc_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -62,10 +63,6 @@ def _search(torch, kd, qs, k):
     out = kd.search(torch.from_numpy(np.ascontiguousarray(qs, np.float64)).cuda(), k)
     torch.cuda.synchronize()
     return {n: v.cpu().numpy() for n, v in out.items()}
-
-
-def _kept(cloud):
-    return np.ascontiguousarray(cloud[~np.isnan(cloud[:, 0]), :3], np.float32)
 
 
 def _check_row(res, s, j, k, exp_idx, exp_d, kept, ctx):
@@ -322,27 +319,6 @@ def test_hostile_clouds_in_reference_tie_orders(tie, torch_cuda, oracle):
 
 
 # ---- d. keyframe sweep --------------------------------------------------------------------------------------------------
-def _sweep_np(kf, cur, th, th_count):
-    """FrameKDMap.cpp:462-485 on the contract: SearchForNearest(pt, 1) in the current frame yields a result iff that frame holds
-    more than one point (size rule); the result's squared distance is that of the nearest usable point, or DBL_MAX when the
-    point has none (a NaN / infinite keyframe point; a current frame of unusable points only) -- an outlier then iff the
-    current frame holds a usable point at all.  -> (outliers, rebuilt, keyframe afterwards)."""
-    kfk, curk = _kept(kf), _kept(cur)
-    out = np.zeros(len(kfk), bool)
-    if len(curk) > 1:
-        c = curk.astype(np.float64)
-        any_usable = bool(np.isfinite(c).all(axis=1).any())
-        for i0 in range(0, len(kfk), 256):
-            q = kfk[i0:i0 + 256].astype(np.float64)
-            with np.errstate(all="ignore"):
-                d = ((q[:, None, 0] - c[None, :, 0]) ** 2 + (q[:, None, 1] - c[None, :, 1]) ** 2) + (q[:, None, 2] - c[None, :, 2]) ** 2
-                dmin = np.where(d < DBL_MAX, d, np.inf).min(axis=1)
-                out[i0:i0 + 256] = np.where(np.isinf(dmin), any_usable, np.sqrt(dmin) > th)
-    n_out = int(out.sum())
-    rebuilt = int(n_out >= th_count)
-    return n_out, rebuilt, (kfk[out] if rebuilt else kfk)
-
-
 @pytest.mark.parametrize("tie_order", [0, 1])
 def test_keyframe_sweep_with_nonfinite_points(tie_order, torch_cuda, oracle):
     """Non-finite points in the keyframe, in the current frame, in both; a current frame without a usable point; points with a
