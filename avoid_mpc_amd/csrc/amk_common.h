@@ -71,12 +71,16 @@ struct TimedLaunch {  // RAII: records an event before and after the enclosed la
 }  // namespace amk
 
 struct amk_kd;
+// kd_index.hip, for kd_sweep.hip: the index-ordered planes made valid on `stream`; the reference-shaped trees of every scene
+int ensure_soa(amk_kd *kd, hipStream_t stream);
+int exact_build(amk_kd *kd, hipStream_t stream);
 namespace amk {
 // kd_index.hip: the frames of a pipeline gang built by one launch (see there)
 int kd_build_gang(amk_kd *obstacle, amk_kd *edge, int n_frames, int frame_scenes, const float *const *d_xyz,
                   const int *const *d_counts, const float *const *d_edge_xyz, const int *const *d_edge_counts, int point_stride,
                   hipStream_t stream, const int *const *d_keep_if_zero = nullptr);
-// kd_index.hip, for the keyframe map (kfmap.hip): builds and sweeps on a POOL handle (scene = physical slot * S + scene)
+// kd_index.hip / kd_sweep.hip, for the keyframe map (kfmap.hip): builds and sweeps on a POOL handle (scene = physical slot * S + scene)
+int pool_planes(amk_kd *kd);   // kd_sweep.hip: allocates a handle's index-ordered planes where it has none (every pool build writes them)
 int kd_build_mapped(amk_kd *obs_pool, amk_kd *edge_pool, int n_in, const float *d_xyz, const int *d_counts, const float *d_edge_xyz,
                     const int *d_edge_counts, int point_stride, const int *d_out_scene, hipStream_t stream);
 int kd_pool_reserve(amk_kd *pool, int n_rows);

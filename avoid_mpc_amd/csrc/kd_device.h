@@ -42,6 +42,67 @@ inline void scan_geometry(int n_queries, int &qpw, int &groups, int &wpb) {
     wpb = groups < 8 ? groups : 8;
 }
 
+// ---- what every search kernel shares: its launch shape and the rules of the result it stores ----
+// Block -> (scene, unit) map.  A unit is what one wavefront answers (a query; a group of QPW queries in the scan kernels); a
+// block holds `wpb` consecutive units of ONE scene, whose data its waves share in the CU's L1.  The dispatcher puts block b on
+// XCD b % 8, so the scenes are interleaved over the 8 XCDs: all blocks of a scene share one XCD's L2 copy of its index.
+// search_blocks is the grid that goes with it: whole rounds of 8 scenes; every kernel returns where s >= n_scenes || unit >= units.
+__host__ __device__ constexpr int blocks_per_scene(int units, int wpb) { return (units + wpb - 1) / wpb; }
+inline long long search_blocks(int n_scenes, int units, int wpb = 4) {
+    return (long long)((n_scenes + 7) / 8 * 8) * blocks_per_scene(units, wpb);
+}
+struct WaveSlot { int s, unit, w, lane; };
+__device__ __forceinline__ WaveSlot wave_slot(int units, int wpb = 4) {
+    const int bps = blocks_per_scene(units, wpb);
+    const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
+    WaveSlot m;
+    m.s = (j / bps) * 8 + xcd;
+    // wave-uniform by construction; telling the compiler so moves what derives from it (the scene pointers, the grid geometry,
+    // the query) into SGPRs and scalar loads -- 14 VGPRs less in step_knn_grid_kernel, which is what lets it fit in 64
+    m.w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    m.unit = (j % bps) * wpb + m.w;
+    m.lane = threadIdx.x & 63;
+    return m;
+}
+
+// Tie visibility on the cnt + 1 nearest of a query (lane i: the i-th best (distance, index), kNoIndex: empty): true, in every
+// lane, when two of them are at the same squared distance -- two kept neighbours, or the last kept and the best rejected one.
+// Only then can the index list (and, at the last slot, the neighbour SET) differ from nanoflann's, which keeps the first VISITED
+// of equal distances (KNNResultSet::addPoint, nanoflann_two.hpp:219-246) where this library keeps the lowest index.
+__device__ __forceinline__ bool wave_tie(double ld, int li, int lane, int cnt) {
+    const double ld_next = __shfl_down(ld, 1);
+    const int li_next = __shfl_down(li, 1);
+    const bool tie = lane < cnt && li != kNoIndex && li_next != kNoIndex && ld == ld_next;
+    return __ballot(tie) != 0ull;
+}
+
+// KDTreeTwo::SearchForNearest's count rule (kd_tree_two.h:119-124): of the min(k, size) neighbours nanoflann found, the
+// adaptor hands out `size` when the cloud holds fewer than k points, k when it holds more -- and NONE when it holds exactly k.
+__host__ __device__ constexpr int adaptor_count(int size, int k) { return size < k ? size : (size > k ? k : 0); }
+
+// One row of amk_kd_search's result (every output may be null): its count, and in lane < k slot `lane` -- the neighbour when
+// `found` and within the count, else index -1, DBL_MAX and zeros.  point(c): coordinate c of the
+// neighbour, a callable so that the tree and the scan read their planes only for a slot that holds one.
+// (No __restrict__ here or on the bodies that call it: through an inlined function it reaches the backend's store merging,
+// which a kernel's own parameters do not, and the default kernels' stores would no longer be the ones that were measured.)
+template <class Point>
+__device__ __forceinline__ void store_search_row(int *out_idx, double *out_d2, float *out_pts, int *out_cnt, size_t row, int k,
+                                                 int lane, int cnt, bool found, int li, double ld, Point point) {
+    if (lane == 0 && out_cnt) out_cnt[row] = cnt;
+    if (lane < k) {
+        const bool ok = lane < cnt && found;
+        const int idx = ok ? li : -1;
+        if (out_idx) out_idx[row * k + lane] = idx;
+        if (out_d2) out_d2[row * k + lane] = ok ? ld : DBL_MAX;
+        if (out_pts) {
+            float *o = out_pts + (row * k + lane) * 3;
+            o[0] = ok ? point(0) : 0.f;
+            o[1] = ok ? point(1) : 0.f;
+            o[2] = ok ? point(2) : 0.f;
+        }
+    }
+}
+
 // Conservative fp32 image of a squared-distance threshold: every point whose exact fp64 squared
 // distance is <= tau has an fp32-evaluated squared distance <= filter_threshold(tau, e).
 //   e = 2^-22 (|q|_inf + max|p|) bounds sqrt(3) x the per-coordinate error of fl32(fl32(q) - p)

@@ -39,6 +39,7 @@ constexpr int kGridPointsPerCell = AMK_GRID_PPC;  // target occupancy of a cell
 #define AMK_BUILD_THREADS 512
 #endif
 constexpr int kGridBuildThreads = AMK_BUILD_THREADS;
+constexpr int kCompactThreads = kGridBuildThreads;   // every one-block-per-scene pass over a cloud: the index build, the sweep's compaction
 #ifndef AMK_GRID_UNROLL
 #define AMK_GRID_UNROLL 16  // points in flight per thread of the two-pass build from SoA planes (keyframe sweep)
 #endif

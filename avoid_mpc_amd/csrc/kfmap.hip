@@ -411,7 +411,7 @@ int amk_kfmap_nearest_distance_host(amk_kfmap *m, const double *h_queries, int q
 }
 
 // FrameKDMap::GetPtCloud (:490-515) for one scene: the obstacle points of its query frames, in query-vector order, from the
-// pool's index-ordered planes (kd_index.hip: pool_planes -- written by every build, compacted by every sweep).  Synchronises.
+// pool's index-ordered planes (kd_sweep.hip: pool_planes -- written by every build, compacted by every sweep).  Synchronises.
 int amk_kfmap_points_host(amk_kfmap *m, int scene, float *h_xyz, long long capacity_points, int *h_frame_sizes, long long *n_points_out) {
     if (!m || scene < 0 || scene >= m->S || capacity_points < 0 || (!h_xyz && capacity_points > 0)) return AMK_ERR_INVALID_ARG;
     AMK_HIP(hipDeviceSynchronize());

@@ -41,12 +41,8 @@ __global__ __launch_bounds__(256) void map_query_kernel(QueryFrames qf, int n_sc
                                                         int *__restrict__ out_frame, int *__restrict__ out_cnt,
                                                         double *__restrict__ out_dist) {
     __shared__ GridWaveLds wl[4];
-    const int bps = (n_queries + 3) / 4;  // blocks per scene; scenes interleaved over the 8 XCDs like kd_grid_search_kernel
-    const int xcd = blockIdx.x & 7;
-    const int j = blockIdx.x >> 3;
-    const int s = (j / bps) * 8 + xcd;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)  /* wave-uniform: keeps what derives from it in SGPRs */, lane = threadIdx.x & 63;
-    const int q = (j % bps) * 4 + w;
+    const WaveSlot ws = wave_slot(n_queries);
+    const int s = ws.s, w = ws.w, lane = ws.lane, q = ws.unit;
     if (s >= n_scenes || q >= n_queries) return;
     const int k = DIST ? 1 : k_in;
     const size_t row = (size_t)s * n_queries + q;
@@ -80,7 +76,7 @@ __global__ __launch_bounds__(256) void map_query_kernel(QueryFrames qf, int n_sc
             int li, lpos;
             const GridScene gs = (MAP ? pool : qf.g[0]).scene(m0);
             grid_knn(gs, qx, qy, qz, k, ld, li, lpos, &wl[w]);
-            cnt = n0 > k ? k : 0;    // kd_tree_two.h:119-124: a cloud of exactly k points answers nothing
+            cnt = adaptor_count(n0, k);   // (n0 >= k here: k, or nothing from a cloud of exactly k points)
             if (lane < cnt && li != kNoIndex) {
                 const float4 rec = gs.pt[lpos];
                 rd = ld; rx = rec.x; ry = rec.y; rz = rec.z; rf = 0;
@@ -143,7 +139,7 @@ template <bool DIST>
 int launch_query(const QueryFrames &qf, int S, const double *d_queries, int query_stride, int n_queries, int k, const double *d_Twc,
                  const amk_frame_camera *cam, float *d_pts, double *d_sqdist, int *d_frame, int *d_counts, double *d_dist,
                  hipStream_t stream) {
-    const long long blocks = (long long)((S + 7) / 8 * 8) * ((n_queries + 3) / 4);
+    const long long blocks = search_blocks(S, n_queries);
     if (blocks > 0x7fffffffll) return AMK_ERR_UNSUPPORTED;
     amk_frame_camera c{};
     if (cam) c = *cam;

@@ -45,14 +45,9 @@ __global__ __launch_bounds__(512) void step_scan_kernel(const float *__restrict_
                                                         double *__restrict__ out_d2, const int *__restrict__ done) {
     const int groups = (n_queries + QPW - 1) / QPW;
     const int wpb = blockDim.x >> 6;
-    const int bps = (groups + wpb - 1) / wpb;
-    const int xcd = blockIdx.x & 7;
-    const int j = blockIdx.x >> 3;
-    const int s = (j / bps) * 8 + xcd;  // all blocks of a scene share one XCD's L2; its waves one CU's L1
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)  /* wave-uniform: keeps what derives from it in SGPRs */;
-    const int g = (j % bps) * wpb + w;
+    const WaveSlot m = wave_slot(groups, wpb);  // all blocks of a scene share one XCD's L2; its waves one CU's L1
+    const int s = m.s, w = m.w, g = m.unit, lane = m.lane;
     if (s >= n_scenes || g >= groups || done[s]) return;
-    const int lane = threadIdx.x & 63;
     const int size = sizes[s];
     const float *xs = X + (size_t)s * cap, *ys = Y + (size_t)s * cap, *zs = Z + (size_t)s * cap;
     extern __shared__ __attribute__((aligned(16))) unsigned char scan_smem[];
@@ -76,35 +71,50 @@ __global__ __launch_bounds__(512) void step_scan_kernel(const float *__restrict_
     }
 }
 
+// ---- AMK_TIES_AUTO (either handle): the same pass with tie detection in the queries that answer it, the reference-shaped tree
+// built lazily on the device for the scenes where something tied, and only the tied rows answered again by its traversal.
+// Every launch is unconditional (the host never learns whether anything tied): where nothing did, they return at once.
+struct StepAuto {
+    int obs, edge;               // the handle is in AMK_TIES_AUTO (and its flags are current)
+    int eager_obs, eager_edge;   // the handle is in AMK_TIES_NANOFLANN with a current tree: every row goes through it, as in step_knn_exact_kernel
+    ExactPtrs tobs, tedge;
+    int *need_obs, *need_edge;
+    const int *built_obs, *built_edge;
+    int *row_obs;                // [S][N] tie flag of obstacle query (s, q) of this pass
+    int *row_edge;               // [S]    tie flag of the edge query
+    int *requery_tied;           // [S]    the re-query of the snapped point tied in this pass
+};
+
 // Same outputs through the bucketed indices (kd_grid.h), both trees in one launch: wavefront q < N answers
 // the K-NN of reference point q in the obstacle index, wavefront q == N the 1-NN of reference point 0 in
 // the edge index (the Edge-KD-tree query of PlanWapionts, :270).
-// <= 48 VGPRs: a CU that holds its 8 solve waves (2 x 232 registers per SIMD, 142.6 of 160 KB of LDS since round 5) still
-// has 48 registers per SIMD and 17 KB of LDS free -- exactly one block of this kernel (one wave per SIMD), which then runs
-// in the issue slots the latency-bound solves leave empty instead of waiting for a CU to drain.
-__global__ __launch_bounds__(256) void step_knn_grid_kernel(GridPtrs gobs, GridPtrs gedge, int n_scenes,
-                                                            const double *__restrict__ ref_path, int N, int K,
-                                                            float *__restrict__ knn_pts, double *__restrict__ knn_d2,
-                                                            float *__restrict__ edge_pt, double *__restrict__ edge_d2,
-                                                            const int *__restrict__ done) {
+// AUTO (step_knn_grid_auto_kernel): one more candidate and the tie test for the handles in AMK_TIES_AUTO (raw results, so every one
+// of the k slots counts -- there is no adaptor count rule here).
+template <bool AUTO>
+__device__ __forceinline__ void step_knn_grid_row(const GridPtrs &gobs, const GridPtrs &gedge, int n_scenes,
+    const double *ref_path, int N, int K, float *knn_pts, double *knn_d2,
+    float *edge_pt, double *edge_d2, const int *done, const StepAuto &au) {
     __shared__ GridWaveLds wl[4];
     const int nq = N + 1;
-    const int bps = (nq + 3) / 4;
-    const int xcd = blockIdx.x & 7;
-    const int j = blockIdx.x >> 3;
-    const int s = (j / bps) * 8 + xcd;
-    // wave-uniform by construction; telling the compiler so moves the scene pointers, the grid geometry and the query into
-    // SGPRs (scalar loads) -- 14 VGPRs less, which is what lets the kernel fit in 64
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int q = (j % bps) * 4 + w;
+    const WaveSlot m = wave_slot(nq);
+    const int s = m.s, q = m.unit, lane = m.lane;
     if (s >= n_scenes || q >= nq || done[s]) return;
     const bool is_edge = q == N;
     const double *qp = ref_path + ((size_t)s * N + (is_edge ? 0 : q)) * SD;  // read in place from mRefPath
     const int k = is_edge ? 1 : K;
+    const bool detect = AUTO && (is_edge ? au.edge : au.obs);   // (wave-uniform)
     double ld;
     int li, lpos;
     const GridScene gs = is_edge ? gedge.scene(s) : gobs.scene(s);
-    grid_knn(gs, qp[0], qp[1], qp[2], k, ld, li, lpos, &wl[w]);
+    grid_knn(gs, qp[0], qp[1], qp[2], detect ? k + 1 : k, ld, li, lpos, &wl[m.w]);
+    if (detect) {
+        const bool any = wave_tie(ld, li, lane, k);
+        if (lane == 0) {
+            if (is_edge) au.row_edge[s] = any;
+            else au.row_obs[(size_t)s * N + q] = any;
+            if (any) (is_edge ? au.need_edge : au.need_obs)[s] = 1;   // (every wavefront that raises it stores the same value)
+        }
+    }
     if (lane < k) {
         const bool ok = li != kNoIndex;
         const float4 rec = gs.pt[lpos];  // the neighbour's coordinates (lpos = 0 for an empty slot: a valid address)
@@ -112,10 +122,43 @@ __global__ __launch_bounds__(256) void step_knn_grid_kernel(GridPtrs gobs, GridP
         else store_nbr(knn_pts, knn_d2, ((size_t)s * N + q) * K + lane, ok, ld, rec.x, rec.y, rec.z);
     }
 }
+// <= 48 VGPRs: a CU that holds its 8 solve waves (2 x 232 registers per SIMD, 142.6 of 160 KB of LDS since round 5) still
+// has 48 registers per SIMD and 17 KB of LDS free -- exactly one block of this kernel (one wave per SIMD), which then runs
+// in the issue slots the latency-bound solves leave empty instead of waiting for a CU to drain.
+__global__ __launch_bounds__(256) void step_knn_grid_kernel(GridPtrs gobs, GridPtrs gedge, int n_scenes,
+    const double *__restrict__ ref_path, int N, int K, float *__restrict__ knn_pts, double *__restrict__ knn_d2,
+    float *__restrict__ edge_pt, double *__restrict__ edge_d2, const int *__restrict__ done) {
+    step_knn_grid_row<false>(gobs, gedge, n_scenes, ref_path, N, K, knn_pts, knn_d2, edge_pt, edge_d2, done, StepAuto{});
+}
+// (a kernel of its own: the default one keeps its 48 registers)
+__global__ __launch_bounds__(256) void step_knn_grid_auto_kernel(GridPtrs gobs, GridPtrs gedge, int n_scenes,
+    const double *__restrict__ ref_path, int N, int K, float *__restrict__ knn_pts, double *__restrict__ knn_d2,
+    float *__restrict__ edge_pt, double *__restrict__ edge_d2, const int *__restrict__ done, StepAuto au) {
+    step_knn_grid_row<true>(gobs, gedge, n_scenes, ref_path, N, K, knn_pts, knn_d2, edge_pt, edge_d2, done, au);
+}
+
+// The StepAuto policy of step_knn_exact_row (step_common.h), for a pair of handles of which at least one is in AMK_TIES_AUTO: of
+// such a handle only the rows the kernel above flagged, and only where the scene's tree is built; a handle in AMK_TIES_NANOFLANN
+// every row, as with ExactPair.
+__device__ __forceinline__ bool exact_used(const StepAuto &au, int, bool edge) {
+    return edge ? (au.edge || au.eager_edge) : (au.obs || au.eager_obs);
+}
+__device__ __forceinline__ bool exact_row_wanted(const StepAuto &au, int, bool edge, int s, int q, int N) {
+    if (!(edge ? au.edge : au.obs)) return true;   // (AMK_TIES_NANOFLANN)
+    if (edge) return au.row_edge[s] && au.built_edge[s];
+    return au.row_obs[(size_t)s * N + q] && au.built_obs[s];
+}
+__device__ __forceinline__ ExactTree exact_scene(const StepAuto &au, int, bool edge, int s) {
+    return edge ? au.tedge.scene(s) : au.tobs.scene(s);
+}
+__global__ __launch_bounds__(256) void step_knn_exact_auto_kernel(StepAuto au, int n_scenes, const double *__restrict__ ref_path,
+    int N, int K, FrameBufs fb, const int *__restrict__ done) {
+    step_knn_exact_row(au, 0, n_scenes, ref_path, N, K, fb, done);
+}
 
 // PlanWapionts (:259-281) for reference point 0; called by the one wavefront that owns scene s.
 // AUTO (obstacle handle in AMK_TIES_AUTO mode, GRID only): the re-query of the snapped point asks for K + 1 neighbours and makes
-// the tie test of kd_tie_flags_kernel on them (raw results: every slot counts); a tie raises the scene's `need` word for the lazy
+// the tie test (wave_tie) on them (raw results: every slot counts); a tie raises the scene's `need` word for the lazy
 // tree build behind this kernel and `requery_tied`, which has step_requery_pack_auto_kernel redo the re-query in that tree.
 template <bool EXACT, bool GRID, bool AUTO = false>
 __device__ __forceinline__ void plan_scene(int s, GridPtrs gpt, ExactPtrs eobs,
@@ -159,12 +202,8 @@ __device__ __forceinline__ void plan_scene(int s, GridPtrs gpt, ExactPtrs eobs,
             double sld = DBL_MAX;
             if constexpr (GRID) {
                 grid_knn(gs, ex, ey, ez, AUTO ? K + 1 : K, gld, gli, glpos, &wl1_store);
-                if constexpr (AUTO) {
-                    const double ld_next = __shfl_down(gld, 1);
-                    const int li_next = __shfl_down(gli, 1);
-                    const bool tie = lane < K && gli != kNoIndex && li_next != kNoIndex && gld == ld_next;
-                    if (__ballot(tie) != 0ull && lane == 0) { need[s] = 1; requery_tied[s] = 1; }
-                }
+                if constexpr (AUTO)
+                    if (wave_tie(gld, gli, lane, K) && lane == 0) { need[s] = 1; requery_tied[s] = 1; }
             } else {
                 ScanLds<1> &ws1 = ws1_store;
                 q1[0] = ex; q1[1] = ey; q1[2] = ez;  // every lane stores the same values
@@ -240,96 +279,6 @@ __global__ __launch_bounds__(kWave) void step_plan_pack_kernel(
                knn_d2, ref_states, done, flags);
 }
 
-// ---- AMK_TIES_AUTO (either handle): the same pass with tie detection in the queries that answer it, the reference-shaped tree
-// built lazily on the device for the scenes where something tied, and only the tied rows answered again by its traversal.
-// Every launch is unconditional (the host never learns whether anything tied): where nothing did, they return at once.
-struct StepAuto {
-    int obs, edge;               // the handle is in AMK_TIES_AUTO (and its flags are current)
-    int eager_obs, eager_edge;   // the handle is in AMK_TIES_NANOFLANN with a current tree: every row goes through it, as in step_knn_exact_kernel
-    ExactPtrs tobs, tedge;
-    int *need_obs, *need_edge;
-    const int *built_obs, *built_edge;
-    int *row_obs;                // [S][N] tie flag of obstacle query (s, q) of this pass
-    int *row_edge;               // [S]    tie flag of the edge query
-    int *requery_tied;           // [S]    the re-query of the snapped point tied in this pass
-};
-
-// step_knn_grid_kernel with one more candidate and the tie test for the handles in AMK_TIES_AUTO (raw results, so every one of the
-// k slots counts -- there is no adaptor count rule here).  A kernel of its own: the default one keeps its 48 registers.
-__global__ __launch_bounds__(256) void step_knn_grid_auto_kernel(GridPtrs gobs, GridPtrs gedge, int n_scenes,
-                                                                 const double *__restrict__ ref_path, int N, int K,
-                                                                 float *__restrict__ knn_pts, double *__restrict__ knn_d2,
-                                                                 float *__restrict__ edge_pt, double *__restrict__ edge_d2,
-                                                                 const int *__restrict__ done, StepAuto au) {
-    __shared__ GridWaveLds wl[4];
-    const int nq = N + 1;
-    const int bps = (nq + 3) / 4;
-    const int xcd = blockIdx.x & 7;
-    const int j = blockIdx.x >> 3;
-    const int s = (j / bps) * 8 + xcd;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int q = (j % bps) * 4 + w;
-    if (s >= n_scenes || q >= nq || done[s]) return;
-    const bool is_edge = q == N;
-    const double *qp = ref_path + ((size_t)s * N + (is_edge ? 0 : q)) * SD;  // read in place from mRefPath
-    const int k = is_edge ? 1 : K;
-    const bool detect = is_edge ? au.edge : au.obs;   // (wave-uniform)
-    double ld;
-    int li, lpos;
-    const GridScene gs = is_edge ? gedge.scene(s) : gobs.scene(s);
-    grid_knn(gs, qp[0], qp[1], qp[2], detect ? k + 1 : k, ld, li, lpos, &wl[w]);
-    if (detect) {
-        const double ld_next = __shfl_down(ld, 1);
-        const int li_next = __shfl_down(li, 1);
-        const bool tie = lane < k && li != kNoIndex && li_next != kNoIndex && ld == ld_next;
-        const bool any = __ballot(tie) != 0ull;
-        if (lane == 0) {
-            if (is_edge) au.row_edge[s] = any;
-            else au.row_obs[(size_t)s * N + q] = any;
-            if (any) (is_edge ? au.need_edge : au.need_obs)[s] = 1;   // (every wavefront that raises it stores the same value)
-        }
-    }
-    if (lane < k) {
-        const bool ok = li != kNoIndex;
-        const float4 rec = gs.pt[lpos];  // the neighbour's coordinates (lpos = 0 for an empty slot: a valid address)
-        if (is_edge) store_nbr(edge_pt, edge_d2, s, ok, ld, rec.x, rec.y, rec.z);
-        else store_nbr(knn_pts, knn_d2, ((size_t)s * N + q) * K + lane, ok, ld, rec.x, rec.y, rec.z);
-    }
-}
-
-// step_knn_exact_kernel for a pair of handles of which at least one is in AMK_TIES_AUTO: of such a handle only the rows the
-// kernel above flagged, and only where the scene's tree is built; a handle in AMK_TIES_NANOFLANN every row, as there.
-__global__ __launch_bounds__(256) void step_knn_exact_auto_kernel(StepAuto au, int n_scenes, const double *__restrict__ ref_path,
-                                                                  int N, int K, FrameBufs fb, const int *__restrict__ done) {
-    __shared__ ExactWaveStack stacks[4];
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)  /* wave-uniform: keeps what derives from it in SGPRs */, lane = threadIdx.x & 63;
-    const int t = blockIdx.x * 4 + w;
-    const int nq = N + 1;
-    if (t >= n_scenes * nq) return;
-    const int s = t / nq, q = t - s * nq;
-    if (done[s]) return;
-    const bool is_edge = q == N;
-    if (is_edge ? au.edge : au.obs) {
-        const int flagged = is_edge ? au.row_edge[s] : au.row_obs[(size_t)s * N + q];
-        if (!flagged || !(is_edge ? au.built_edge : au.built_obs)[s]) return;
-    } else if (!(is_edge ? au.eager_edge : au.eager_obs)) {
-        return;
-    }
-    const double *qp = ref_path + ((size_t)s * N + (is_edge ? 0 : q)) * SD;
-    const ExactTree T = is_edge ? au.tedge.scene(s) : au.tobs.scene(s);
-    const int k = is_edge ? 1 : K;
-    double rd;
-    int ri;
-    const int got = exact_knn_wave(T, qp[0], qp[1], qp[2], k, rd, ri, &stacks[w]);
-    if (got < 0) return;
-    if (lane < k) {
-        const bool ok = lane < got;
-        const float px = ok ? T.x[ri] : 0.f, py = ok ? T.y[ri] : 0.f, pz = ok ? T.z[ri] : 0.f;
-        if (is_edge) store_nbr(fb.edge_pt, fb.edge_d2, s, ok, rd, px, py, pz);
-        else store_nbr(fb.knn_pts, fb.knn_d2, ((size_t)s * N + q) * K + lane, ok, rd, px, py, pz);
-    }
-}
-
 // Obstacle handle in AMK_TIES_AUTO: the two halves of step_plan_pack_kernel as two kernels, because the tree the snapped point's
 // re-query may need can only be built between them (the query point is computed by the first half).
 __global__ __launch_bounds__(kWave) void step_plan_auto_kernel(
@@ -401,8 +350,6 @@ extern "C" int amk_step_batch(amk_kd *obstacle, amk_kd *edge, amk_mpc *mpc, cons
     launch_step_begin(S, mpc->done.p, d_flags, d_u, stream); }
     int qpw, groups, wpb;
     scan_geometry(N, qpw, groups, wpb);
-    const int bps = (groups + wpb - 1) / wpb;
-    const int S8 = (S + 7) / 8 * 8;
     const int use_grid = (obstacle->mode == 0 && edge->mode == 0) ? 1 : 0;
     if (!use_grid) {  // the streaming-scan cross-check path reads the index-ordered planes
         int st = amk__kd_ensure_soa(obstacle, stream_);
@@ -445,7 +392,7 @@ extern "C" int amk_step_batch(amk_kd *obstacle, amk_kd *edge, amk_mpc *mpc, cons
         if (g_diag_skip & 1) {
         } else if (au_obs || au_edge) {
             TimedLaunch tl(KC_SCAN_OBS, stream);
-            hipLaunchKernelGGL(step_knn_grid_auto_kernel, dim3(S8 * ((N + 4) / 4)), dim3(256), 0, stream, gobs, gedge, S,
+            hipLaunchKernelGGL(step_knn_grid_auto_kernel, dim3((unsigned)search_blocks(S, N + 1)), dim3(256), 0, stream, gobs, gedge, S,
                                d_ref_path, N, K, mpc->knn_pts.p, mpc->knn_d2.p, mpc->edge_pt.p, mpc->edge_d2.p,
                                mpc->done.p, au);
             if (int st = kd_auto_build(au_obs ? obstacle : nullptr, au_edge ? edge : nullptr, stream); st != AMK_OK) return st;
@@ -453,7 +400,7 @@ extern "C" int amk_step_batch(amk_kd *obstacle, amk_kd *edge, amk_mpc *mpc, cons
                                N, K, out, mpc->done.p);
         } else if (use_grid) {
             TimedLaunch tl(KC_SCAN_OBS, stream);
-            hipLaunchKernelGGL(step_knn_grid_kernel, dim3(S8 * ((N + 4) / 4)), dim3(256), 0, stream, gobs, gedge, S,
+            hipLaunchKernelGGL(step_knn_grid_kernel, dim3((unsigned)search_blocks(S, N + 1)), dim3(256), 0, stream, gobs, gedge, S,
                                d_ref_path, N, K, mpc->knn_pts.p, mpc->knn_d2.p, mpc->edge_pt.p, mpc->edge_d2.p,
                                mpc->done.p);
             if (ex.use_obs || ex.use_edge)
@@ -461,11 +408,11 @@ extern "C" int amk_step_batch(amk_kd *obstacle, amk_kd *edge, amk_mpc *mpc, cons
                                    d_ref_path, N, K, out, mpc->done.p);
         } else {
         { TimedLaunch tl(KC_SCAN_OBS, stream);
-        hipLaunchKernelGGL(step_scan_kernel<5>, dim3(S8 * bps), dim3(wpb * kWave), scan_lds_bytes<5>(wpb), stream,
+        hipLaunchKernelGGL(step_scan_kernel<5>, dim3((unsigned)search_blocks(S, groups, wpb)), dim3(wpb * kWave), scan_lds_bytes<5>(wpb), stream,
                            obstacle->x.p, obstacle->y.p, obstacle->z.p, obstacle->cap, obstacle->size.p,
                            obstacle->pmax.p, S, d_ref_path, N, N, K, mpc->knn_pts.p, mpc->knn_d2.p, mpc->done.p); }
         { TimedLaunch tl(KC_SCAN_EDGE, stream);
-        hipLaunchKernelGGL(step_scan_kernel<1>, dim3(S8), dim3(kWave), scan_lds_bytes<1>(1), stream, edge->x.p,
+        hipLaunchKernelGGL(step_scan_kernel<1>, dim3((unsigned)search_blocks(S, 1, 1)), dim3(kWave), scan_lds_bytes<1>(1), stream, edge->x.p,
                            edge->y.p, edge->z.p, edge->cap, edge->size.p, edge->pmax.p, S, d_ref_path, N, 1, 1,
                            mpc->edge_pt.p, mpc->edge_d2.p, mpc->done.p); }
         }

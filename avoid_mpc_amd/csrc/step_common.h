@@ -60,15 +60,18 @@ __device__ __forceinline__ ExactTree exact_scene(const ExactPair &t, int, bool e
 __device__ __forceinline__ ExactTree exact_scene(const FrameExact *t, int f, bool edge, int s) {
     return edge ? t->edge[f].scene(s) : t->obs[f].scene(s);
 }
+// whether row (s, q) of a tree that is used goes through it: every row (step.hip's StepAuto: only the rows that tied)
+template <class Trees>
+__device__ __forceinline__ bool exact_row_wanted(const Trees &, int, bool, int, int, int) { return true; }
 
 // Handles in AMK_TIES_NANOFLANN mode: the raw results by nanoflann's own traversal of its own tree (kd_exact.h), one
 // WAVEFRONT per (frame, scene, query), overwriting what the bucketed search wrote wherever the tree is available.  With exact
 // ties (quantised edge clouds) this is what keeps the snapped edge point and the neighbour SET equal to the reference's.
+// One body for every source of trees (Trees: ExactPair, const FrameExact *, step.hip's StepAuto); f: the frame.
 template <class Trees>
-__global__ __launch_bounds__(256) void step_knn_exact_kernel(Trees trees, int n_scenes, const double *__restrict__ ref_path,
-                                                             int N, int K, FrameBufs fb, const int *__restrict__ done) {
+__device__ __forceinline__ void step_knn_exact_row(const Trees &trees, int f, int n_scenes, const double *ref_path,
+    int N, int K, const FrameBufs &fb, const int *done) {
     __shared__ ExactWaveStack stacks[4];
-    const int f = blockIdx.y;
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)  /* wave-uniform: keeps what derives from it in SGPRs */, lane = threadIdx.x & 63;
     const int t = blockIdx.x * 4 + w;
     const int nq = N + 1;
@@ -76,7 +79,7 @@ __global__ __launch_bounds__(256) void step_knn_exact_kernel(Trees trees, int n_
     const int s = t / nq, q = t - s * nq;
     if (done[s]) return;
     const bool is_edge = q == N;
-    if (!exact_used(trees, f, is_edge)) return;
+    if (!exact_used(trees, f, is_edge) || !exact_row_wanted(trees, f, is_edge, s, q, N)) return;
     const double *qp = ref_path + ((size_t)s * N + (is_edge ? 0 : q)) * SD;
     const ExactTree T = exact_scene(trees, f, is_edge, s);
     const int k = is_edge ? 1 : K;
@@ -91,6 +94,11 @@ __global__ __launch_bounds__(256) void step_knn_exact_kernel(Trees trees, int n_
         if (is_edge) store_nbr(fb.edge_pt, fb.edge_d2, o, ok, rd, px, py, pz);
         else store_nbr(fb.knn_pts, fb.knn_d2, (o * N + q) * K + lane, ok, rd, px, py, pz);
     }
+}
+template <class Trees>
+__global__ __launch_bounds__(256) void step_knn_exact_kernel(Trees trees, int n_scenes, const double *__restrict__ ref_path, int N,
+    int K, FrameBufs fb, const int *__restrict__ done) {
+    step_knn_exact_row(trees, blockIdx.y, n_scenes, ref_path, N, K, fb, done);
 }
 
 // AMK_TIES_NANOFLANN: the re-query of the snapped point (ProcessWaypoints queries it next, :210-215) by the reference's

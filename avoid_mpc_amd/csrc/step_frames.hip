@@ -59,12 +59,9 @@ __global__ __launch_bounds__(256) void step_knn_frames_kernel(FrameSet fs, int n
     // walking the ~6 frames of a flight's map in turn was the tail of every launch.  Frames 1 .. fc - 1 of the first chunk get a
     // wavefront each: "queries" N + 1 .. N + fc - 1 are reference point 0 in frame q - N.
     const int nq = N + 1, nv = MAP ? fc - 1 : 0;
-    const int bps = (nq + nv + 3) / 4;
-    const int xcd = blockIdx.x & 7;
-    const int j = blockIdx.x >> 3;
-    const int s = (j / bps) * 8 + xcd;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)  /* wave-uniform: keeps what derives from it in SGPRs */, lane = threadIdx.x & 63;
-    int q = (j % bps) * 4 + w;
+    const WaveSlot ws = wave_slot(nq + nv);
+    const int s = ws.s, w = ws.w, lane = ws.lane;
+    int q = ws.unit;
     if (s >= n_scenes || q >= nq + nv || done[s]) return;
     int f_only = -1;
     if (q >= nq) {
@@ -417,16 +414,15 @@ static int run_frames(const FrameSet &fs, amk_kd *const *obstacle, amk_kd *const
     else if (need_cpl <= 2) merge_kernel = step_merge_plan_pack_kernel<false, 2>;
     else if (need_cpl <= 4) merge_kernel = step_merge_plan_pack_kernel<false, 4>;
     launch_step_begin(S, mpc->done.p, d_flags, d_u, stream);
-    const int S8 = (S + 7) / 8 * 8;
     const int fc = 8;   // map mode: frames of the first chunk of search blocks (the chunks double: 8, 16, 32, ...)
     int n_chunks = 1;
     while (fc * ((1 << n_chunks) - 1) < F) ++n_chunks;
     for (int iter = 0; iter < prm->mpc_max_iter; ++iter) {
         if (fs.fmap)
-            hipLaunchKernelGGL(step_knn_frames_kernel<true>, dim3(S8 * ((N + 1 + (fc - 1) + 3) / 4), n_chunks), dim3(256), 0, stream, fs, S,
+            hipLaunchKernelGGL(step_knn_frames_kernel<true>, dim3((unsigned)search_blocks(S, N + 1 + (fc - 1)), n_chunks), dim3(256), 0, stream, fs, S,
                                d_ref_path, N, K, fb, mpc->done.p, fc, d_Twc, c);
         else
-            hipLaunchKernelGGL(step_knn_frames_kernel<false>, dim3(S8 * ((N + 4) / 4), F), dim3(256), 0, stream, fs, S, d_ref_path,
+            hipLaunchKernelGGL(step_knn_frames_kernel<false>, dim3((unsigned)search_blocks(S, N + 1), F), dim3(256), 0, stream, fs, S, d_ref_path,
                                N, K, fb, mpc->done.p, 1, d_Twc, c);
         if (any_exact)
             hipLaunchKernelGGL(step_knn_exact_kernel<const FrameExact *>, dim3((S * (N + 1) + 3) / 4, F), dim3(256), 0, stream,

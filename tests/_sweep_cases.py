@@ -1,5 +1,5 @@
 """Inputs that aim at the keyframe map's HASHED sweep (TEST INFRASTRUCTURE): kd_sweep_hash_build_kernel / kd_sweep_mark_hash_kernel
-(csrc/kd_index.hip) at cell faces, negative coordinates, hash-block boundaries, the threshold itself, every bucket count, the
+(csrc/kd_sweep.hip) at cell faces, negative coordinates, hash-block boundaries, the threshold itself, every bucket count, the
 large-coordinate fallback -- and the contract they are held to, in plain numpy.
 
   _sweep_np    the contract (include/avoid_mpc_amd.h at amk_kd_keyframe_sweep): fp64 squared distance ((dx^2 + dy^2) + dz^2), outlier
@@ -98,7 +98,7 @@ class SweepMap(kc.NumpyMap):
 
 # ------------------------------------------------------------------------------------------------------------------ the kernel's cells
 def cell_f32(p, th):
-    """sweep_cell (csrc/kd_index.hip) in numpy float32: floor(p * (float)(1 / cell)), clamped to +-5e8; cell = max(2.5 th, 1e-3)"""
+    """sweep_cell (csrc/kd_sweep.hip) in numpy float32: floor(p * (float)(1 / cell)), clamped to +-5e8; cell = max(2.5 th, 1e-3)"""
     inv_hf = f32(1.0 / max(2.5 * th, 1e-3))
     with np.errstate(all="ignore"):
         return np.clip(np.floor(np.asarray(p, f32) * inv_hf), f32(-5.0e8), f32(5.0e8)).astype(np.int64)
@@ -113,7 +113,7 @@ def cube_f32(q, th):
 
 
 def sweep_buckets(max_points):
-    """sweep_buckets (csrc/kd_index.hip): a power of two, about two per point, between 1024 and 16384"""
+    """sweep_buckets (csrc/kd_sweep.hip): a power of two, about two per point, between 1024 and 16384"""
     nb = 1024
     while nb < 16384 and nb < 2 * max_points:
         nb *= 2

@@ -1,4 +1,4 @@
-"""GPU: the keyframe map's sweep (amk_kfmap_update -> kd_sweep_mapped, csrc/kd_index.hip) on the scripts of tests/_sweep_cases.py, in
+"""GPU: the keyframe map's sweep (amk_kfmap_update -> kd_sweep_mapped, csrc/kd_sweep.hip) on the scripts of tests/_sweep_cases.py, in
 every sweep target and query order setting: the hashed grid with the keyframe in grid order where it has one (the default), the hashed
 grid in record order, the frames' own indices.  Finite frames only: the header leaves the map unspecified for the others.
 
