@@ -78,6 +78,33 @@ __device__ __forceinline__ real wave_reduce(real v) {
     const real r0 = readlane_r(v, 0), r1 = readlane_r(v, 16), r2 = readlane_r(v, 32), r3 = readlane_r(v, 48);
     return Op::f(Op::f(r0, r1), Op::f(r2, r3));
 }
+// Two / three independent wave reductions advanced level by level.  One ladder is six dependent steps (DPP move -> fp64 op, four
+// times, v_readlane, combine); written one after the other the compiler also issues them one after the other.  Each value keeps
+// its own order of operations: the results are those of wave_reduce<Op>.
+template <class OpA, class OpB>
+__device__ __forceinline__ void wave_reduce2(real &a, real &b) {
+    a = OpA::f(a, dpp_r<DPP_XOR1>(a)); b = OpB::f(b, dpp_r<DPP_XOR1>(b));
+    a = OpA::f(a, dpp_r<DPP_XOR2>(a)); b = OpB::f(b, dpp_r<DPP_XOR2>(b));
+    a = OpA::f(a, dpp_r<DPP_HALF_MIRROR>(a)); b = OpB::f(b, dpp_r<DPP_HALF_MIRROR>(b));
+    a = OpA::f(a, dpp_r<DPP_MIRROR>(a)); b = OpB::f(b, dpp_r<DPP_MIRROR>(b));
+    const real a0 = readlane_r(a, 0), a1 = readlane_r(a, 16), a2 = readlane_r(a, 32), a3 = readlane_r(a, 48);
+    const real b0 = readlane_r(b, 0), b1 = readlane_r(b, 16), b2 = readlane_r(b, 32), b3 = readlane_r(b, 48);
+    a = OpA::f(OpA::f(a0, a1), OpA::f(a2, a3));
+    b = OpB::f(OpB::f(b0, b1), OpB::f(b2, b3));
+}
+template <class OpA, class OpB, class OpC>
+__device__ __forceinline__ void wave_reduce3(real &a, real &b, real &c) {
+    a = OpA::f(a, dpp_r<DPP_XOR1>(a)); b = OpB::f(b, dpp_r<DPP_XOR1>(b)); c = OpC::f(c, dpp_r<DPP_XOR1>(c));
+    a = OpA::f(a, dpp_r<DPP_XOR2>(a)); b = OpB::f(b, dpp_r<DPP_XOR2>(b)); c = OpC::f(c, dpp_r<DPP_XOR2>(c));
+    a = OpA::f(a, dpp_r<DPP_HALF_MIRROR>(a)); b = OpB::f(b, dpp_r<DPP_HALF_MIRROR>(b)); c = OpC::f(c, dpp_r<DPP_HALF_MIRROR>(c));
+    a = OpA::f(a, dpp_r<DPP_MIRROR>(a)); b = OpB::f(b, dpp_r<DPP_MIRROR>(b)); c = OpC::f(c, dpp_r<DPP_MIRROR>(c));
+    const real a0 = readlane_r(a, 0), a1 = readlane_r(a, 16), a2 = readlane_r(a, 32), a3 = readlane_r(a, 48);
+    const real b0 = readlane_r(b, 0), b1 = readlane_r(b, 16), b2 = readlane_r(b, 32), b3 = readlane_r(b, 48);
+    const real c0 = readlane_r(c, 0), c1 = readlane_r(c, 16), c2 = readlane_r(c, 32), c3 = readlane_r(c, 48);
+    a = OpA::f(OpA::f(a0, a1), OpA::f(a2, a3));
+    b = OpB::f(OpB::f(b0, b1), OpB::f(b2, b3));
+    c = OpC::f(OpC::f(c0, c1), OpC::f(c2, c3));
+}
 __device__ __forceinline__ real wave_sum(real v) { return wave_reduce<OpSum>(v); }
 __device__ __forceinline__ real wave_min(real v) { return wave_reduce<OpMin>(v); }
 __device__ __forceinline__ real wave_max(real v) { return wave_reduce<OpMax>(v); }
@@ -404,8 +431,10 @@ __device__ __forceinline__ real evaluate(real *sm, const LdsMap &L, const SceneI
     }
     if (kTrace && tclk) tclk[2] += AMK_CLK() - tc3;
     if (DERIV && !EXACT) {
-        acc[0] = wave_max(cmax);
-        acc[1] = wave_max(cdev);
+        wave_reduce3<OpMax, OpMax, OpSum>(cmax, cdev, Jloc);
+        acc[0] = cmax;
+        acc[1] = cdev;
+        return Jloc;
     }
     return wave_sum(Jloc);
 }
@@ -578,7 +607,9 @@ __device__ __forceinline__ bool riccati_backward(real *sm, const LdsMap &L, cons
                                                  const int *plan_meta, int N, real delta, double *gains) {
     int lane = threadIdx.x; asm volatile("" : "+v"(lane));   // (opaque per phase: nothing derived from the lane is carried between the phases)
     // the lane's plan is (re)loaded per sweep -- L2-resident words -- instead of being held for the whole
-    // solve: it is dead weight (~90 VGPRs) during the objective evaluation, which sets the register peak
+    // solve: it is dead weight (~90 VGPRs) during the objective evaluation, which sets the register peak.  (Loaded once per
+    // iteration and kept for the inertia loop's retries it costs 17 registers, or address arithmetic in every stage that eats
+    // the gain: profiles/riccati_transport_ab.txt.)
     LanePlan lp;
     load_lane_plan(lp, plan_coef, plan_meta);
     real *P = sm + L.P, *pv = sm + L.p;
@@ -661,7 +692,7 @@ __device__ __forceinline__ bool riccati_backward(real *sm, const LdsMap &L, cons
 }
 
 // forward roll of the Newton step: dX_0 = 0, dU_k = K_k dX_k + d_k, dX_{k+1} = A dX_k + B dU_k.
-// Lane 16 a + j (j < 11) holds K_k[a][j] (j = 10: the feed-forward term; structural zeros are not loaded) -- one coalesced global load per stage,
+// Lane 16 a + j (j < 11) holds K_k[a][j] (j = 10: the feed-forward term; structural zeros are loaded and dropped) -- one coalesced global load per stage,
 // prefetched kFwdPrefetch stages ahead -- multiplies it with dX_k[j] from LDS, and a DPP row reduction leaves dU_k[a] in
 // every lane of row a.  State i is owned by a spare lane of the row of ITS control (p_a, v_a, a_a in row a; yaw in row 3:
 // B couples a state to that control only, cols_of_A_row / rows_of_B), so dX_{k+1}[i] needs no second exchange: a stage
@@ -689,11 +720,21 @@ __device__ __forceinline__ void riccati_forward(real *sm, const LdsMap &L, int N
         for (int t = 0; t < 3; ++t) ac[t] = t < nc ? (real)A[own * SD + cols[t]] : RL(0.0);
         bc = (real)B[own * UD + a];
     }
-    const int goff = j <= SD ? gain_offset(a, j) : -1;
+    int goff = j <= SD ? gain_offset(a, j) : -1;
+    // The ring of prefetched gains (kv) works only if each wait in the loop is for ONE load.  Three things keep it so:
+    // * the coefficients have landed before the first gain is asked for (the empty asm reads them and orders the gains' offset
+    //   behind itself): a coefficient still pending at the loop's entry puts its wait inside the loop, where it waits for all loads;
+    // * every lane loads every stage (idle lanes and the ring's last turns read a word they do not use, and the lane's zero is
+    //   selected where the gain is used): a load under a branch makes the number of loads in flight depend on the path;
+    // * a slot's next load is issued behind the last reader of its present value (below), so the value keeps its register.
+    // Before, the ring was register copies at the loop's back edge behind s_waitcnt vmcnt(0), and a second vmcnt(0) stood behind
+    // the first prefetch of every turn: two L2 round trips per five stages on the dependent chain.
+    asm volatile("" : "+v"(goff), "+v"(ac[0]), "+v"(ac[1]), "+v"(ac[2]), "+v"(bc));
     const bool gain_lane = goff >= 0;
+    const double *gp = gains + (gain_lane ? goff : 0);
     real kv[kFwdPrefetch];
 #pragma unroll
-    for (int u = 0; u < kFwdPrefetch; ++u) kv[u] = (u < N && gain_lane) ? (real)gains[u * GAIN_STAGE + goff] : RL(0.0);
+    for (int u = 0; u < kFwdPrefetch; ++u) kv[u] = (real)gp[(u < N ? u : N - 1) * GAIN_STAGE];
     if (lane < SD) sm[L.dX + lane] = RL(0.0);
     __syncthreads();
     const int xsrc = j < SD ? j : 0;
@@ -703,11 +744,19 @@ __device__ __forceinline__ void riccati_forward(real *sm, const LdsMap &L, int N
         for (int u = 0; u < kFwdPrefetch; ++u) {
             const int k = k0 + u;
             if (k >= N) break;
-            const real g = kv[u];
-            kv[u] = (k + kFwdPrefetch < N && gain_lane) ? (real)gains[(k + kFwdPrefetch) * GAIN_STAGE + goff] : RL(0.0);
+            const real g = gain_lane ? kv[u] : RL(0.0);
             const real *xk = sm + L.dX + k * SD;
             const real xj = xk[xsrc], x0 = xk[cols[0]], x1 = xk[cols[1]], x2 = xk[cols[2]];
-            const real du = row_reduce<OpSum>(g * (j < SD ? xj : RL(1.0)));  // lanes j > 10 hold g = 0
+            // row_reduce<OpSum>(g * (j < SD ? xj : 1)) with its first level written out (lanes j > 10 hold g = 0): that level is
+            // the last reader of g, and the empty asm orders the offset of the slot's next load behind it
+            real du = g * (j < SD ? xj : RL(1.0));
+            du = OpSum::f(du, dpp_r<DPP_XOR1>(du));
+            int nxt = (k + kFwdPrefetch < N ? k + kFwdPrefetch : N - 1) * GAIN_STAGE;
+            asm volatile("" : "+v"(du), "+v"(nxt));
+            kv[u] = (real)gp[nxt];
+            du = OpSum::f(du, dpp_r<DPP_XOR2>(du));
+            du = OpSum::f(du, dpp_r<DPP_HALF_MIRROR>(du));
+            du = OpSum::f(du, dpp_r<DPP_MIRROR>(du));
             const real ax = fma(ac[2], x2, ac[0] * x0) + ac[1] * x1;
             if (j == 0) sm[L.dU + k * UD + a] = du;
             if (own >= 0) sm[L.dX + (k + 1) * SD + own] = fma(bc, du, ax);
@@ -734,11 +783,13 @@ __device__ __forceinline__ real box_errors(const real *sm, const LdsMap &L, int 
         ecm = fmax(ecm, fmax(fabs(sl * zl - mu), fabs(su * zu - mu)));
         lg -= mu * real_log(sl * su);  // both slacks are positive and bounded by the box: no overflow
     }
-    zs = wave_sum(zs); ed = wave_max(ed); ec = fmax(wave_max(ec), acc[0]); ecm = fmax(wave_max(ecm), acc[1]);
+    wave_reduce3<OpSum, OpMax, OpSum>(zs, ed, lg);
+    wave_reduce2<OpMax, OpMax>(ec, ecm);
+    ec = fmax(ec, acc[0]); ecm = fmax(ecm, acc[1]);
     const real is_d = s_max * fast_rcp(fmax(s_max, zs / (RL(2.0) * nvar)));
     err[0] = fmax(ed, ecm) * is_d;
     err[1] = fmax(ed, ec) * is_d;
-    return wave_sum(lg);
+    return lg;
 }
 
 __device__ __forceinline__ real next_mu(real mu, real mu_min, real kappa_mu) {
@@ -917,14 +968,16 @@ __device__ __forceinline__ void solve_scene(real *sm, const LdsMap &L, int N, in
         __syncthreads();
         real delta = RL(0.0);
         int reg_now = 0;
-        bool ok = riccati_backward(sm, L, plan_coef, plan_meta, N, delta, gains);
-        while (!ok) {
+        bool ok;
+#pragma unroll 1
+        for (;;) {   // inertia loop: one body for the first attempt and the retries
+            ok = riccati_backward(sm, L, plan_coef, plan_meta, N, delta, gains);
+            if (ok) break;
             __syncthreads();
             if (delta == RL(0.0)) delta = (SC_DELTA_LAST == RL(0.0)) ? RL(1.0) : fmax(RL(1e-20), SC_DELTA_LAST / RL(3.0));
             else delta *= (SC_DELTA_LAST == RL(0.0)) ? RL(100.0) : RL(8.0);
             ++reg_now;
             if (delta > (AMK_REAL_F32 ? RL(1e30) : RL(1e40))) break;
-            ok = riccati_backward(sm, L, plan_coef, plan_meta, N, delta, gains);
         }
         if (!ok) { status = 2; break; }
         n_reg += reg_now;
@@ -951,7 +1004,8 @@ __device__ __forceinline__ void solve_scene(real *sm, const LdsMap &L, int N, in
             if (dzu < RL(0.0)) a_du = fmin(a_du, -tau * zu * fast_rcp(dzu));
             dphi += (sm[L.gU + e] - SC_MU * isl + SC_MU * isu) * du;
         }
-        a_pr = wave_min(a_pr); SC_A_DU = wave_min(a_du); SC_DPHI = wave_sum(dphi);   // (parked: see SC_MU)
+        wave_reduce3<OpMin, OpMin, OpSum>(a_pr, a_du, dphi);
+        SC_A_DU = a_du; SC_DPHI = dphi;   // (parked: see SC_MU)
         // ... and the multipliers of the collision terms (they do not enter the merit function)
         update_term_multipliers(sm, L, io, N, K, SC_MU, tau, o_kappa_sigma, ybuf);
         // backtracking Armijo line search on the barrier function
