@@ -36,6 +36,7 @@ SYMBOLS = [
     "amk_mpc_setup_weights", "amk_mpc_setup_tau", "amk_mpc_setup_gains", "amk_mpc_set_drag_coefficient", "amk_mpc_set_drone_radius",
     "amk_kfmap_pool_bytes", "amk_kfmap_create", "amk_kfmap_destroy", "amk_kfmap_reset", "amk_kfmap_scenes", "amk_kfmap_frames", "amk_kfmap_twc", "amk_kfmap_add_vertex",
     "amk_kfmap_update", "amk_kfmap_step", "amk_kfmap_state_host",
+    "amk_kfmap_set_tie_order", "amk_kfmap_tie_order_bytes", "amk_kfmap_exact_status_host",
     "amk_kfmap_query_nearest", "amk_kfmap_nearest_distance", "amk_kfmap_query_nearest_host", "amk_kfmap_nearest_distance_host",
     "amk_kfmap_points_host", "amk_kd_query_frames", "amk_kd_nearest_distance_frames", "amk_kd_query_frames_host",
     "amk_mpc_set_drone_accel_limits", "amk_mpc_set_solver_options", "amk_mpc_set_solve_budget", "amk_mpc_set_precision", "amk_mpc_solve",
@@ -210,6 +211,9 @@ def load():
         "amk_kfmap_update": (i, [vp, vp]),
         "amk_kfmap_step": (i, [vp, vp, vp, C.POINTER(StepParams), vp, vp, vp, vp, vp, vp, vp]),
         "amk_kfmap_state_host": (i, [vp, vp, vp, vp, vp]),
+        "amk_kfmap_set_tie_order": (i, [vp, i]),
+        "amk_kfmap_tie_order_bytes": (i, [i, i, i, i, C.POINTER(C.c_longlong)]),
+        "amk_kfmap_exact_status_host": (i, [vp, vp, vp]),
         "amk_kfmap_query_nearest": (i, [vp, C.POINTER(FrameCamera), vp, i, i, i, i, vp, vp, vp, vp, vp]),
         "amk_kfmap_nearest_distance": (i, [vp, vp, i, i, vp, vp]),
         "amk_kfmap_query_nearest_host": (i, [vp, C.POINTER(FrameCamera), vp, i, i, i, i, vp, vp, vp, vp]),

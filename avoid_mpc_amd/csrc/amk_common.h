@@ -92,6 +92,14 @@ int kd_sweep_mapped(amk_kd *pool, int n_rows, const int *d_kf_list, const int *d
 // kd_index.hip, AMK_TIES_AUTO: the lazy build of the reference-shaped trees of up to two handles (null: none) in two launches --
 // a workgroup returns at once unless its scene's `need` word is raised and its tree is not built yet (see amk_kd::au_state)
 int kd_auto_build(amk_kd *a, amk_kd *b, hipStream_t stream);
+// kd_index.hip, the keyframe map in AMK_TIES_NANOFLANN (amk_kfmap_set_tie_order): the reference-shaped trees of a pool's scenes.
+// _bytes: what _reserve allocates (host arithmetic); _build: two launches behind a mapped build (both pools, d_gate null) or a
+// sweep (obstacle pool, edge_pool null, d_gate = the sweep's rebuilt flags) -- row i builds pool scene d_rows[i] unless that is < 0
+// or its gate word is 0, decided on the device
+long long kd_pool_exact_bytes(long long scenes, int max_points, bool with_planes);
+int kd_pool_exact_reserve(amk_kd *pool);
+int kd_pool_exact_build(amk_kd *obs_pool, amk_kd *edge_pool, int n_rows, const int *d_rows, const int *d_gate, hipStream_t stream);
+int kd_pool_exact_status(amk_kd *pool, int *d_status, hipStream_t stream);   // amk_kd_exact_status's codes for every pool scene
 }  // namespace amk
 
 // ------------------------------------------------------------------------------------------------
@@ -116,6 +124,8 @@ struct amk_kd {
     // opt-in "nanoflann tie order" (amk_kd_set_tie_order, kd_exact.h): the reference's own tree, built beside the bucketed index
     int tie_order = 0;
     int ex_valid = 0;   // host flag: the exact tree was built from the cloud the bucketed index currently holds
+    int pool_exact = 0; // host flag, a keyframe map's pool only: the map is in AMK_TIES_NANOFLANN -- every pool scene that holds a frame holds
+                        // its tree (kd_pool_exact_build), and the mapped build writes this pool's index-ordered planes too
     int ex_max_nodes = 0;
     amk::DevBuf<unsigned> ex_vind, ex_left, ex_right, ex_sa, ex_sb;
     amk::DevBuf<float> ex_pc;   // [3][S][cap] the coordinates in vAcc_ order (leaves are contiguous runs)

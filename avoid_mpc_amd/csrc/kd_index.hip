@@ -218,6 +218,7 @@ int kd_build_mapped_gang(amk_kd *obs_pool, amk_kd *edge_pool, int n_frames, int 
         BuildArgs b = build_args(edge_pool, d_edge_xyz[f], point_stride, (long long)edge_pool->max_points * point_stride, d_edge_counts[f]);
         a.out_scene = b.out_scene = d_out_scene + (size_t)f * frame_scenes;
         a.soa_x = obs_pool->x.p; a.soa_y = obs_pool->y.p; a.soa_z = obs_pool->z.p;
+        if (edge_pool->pool_exact) { b.soa_x = edge_pool->x.p; b.soa_y = edge_pool->y.p; b.soa_z = edge_pool->z.p; }   // (the edge trees are built from them)
         args.t[2 * f] = a; args.t[2 * f + 1] = b;
     }
     {
@@ -432,16 +433,31 @@ __global__ __launch_bounds__(256) void kd_exact_search_auto_kernel(amk::ExactPtr
 }
 
 // builds the reference's tree of every scene from the index-ordered planes (made on demand from the bucket records)
+// All of the tree's arrays or none: ex_vind set means every one of them is (a failure part way through frees what it got, so a later
+// call starts over instead of finding ex_vind and taking the set for complete).
 static int exact_alloc(amk_kd *kd) {
     const size_t S = kd->n_scenes;
-    if (!kd->ex_vind.p) {
-        kd->ex_max_nodes = kd->cap / 2 + 64;  // ~0.29 nodes per point with 10-point leaves; more = pathological data
-        const size_t pc = S * (size_t)kd->cap, nc = S * (size_t)kd->ex_max_nodes;
-        AMK_HIP(kd->ex_vind.alloc(pc)); AMK_HIP(kd->ex_sa.alloc(pc)); AMK_HIP(kd->ex_sb.alloc(pc));
-        AMK_HIP(kd->ex_pc.alloc(3 * pc));
-        AMK_HIP(kd->ex_left.alloc(nc)); AMK_HIP(kd->ex_right.alloc(nc)); AMK_HIP(kd->ex_feat.alloc(nc));
-        AMK_HIP(kd->ex_child.alloc(nc)); AMK_HIP(kd->ex_low.alloc(nc)); AMK_HIP(kd->ex_high.alloc(nc));
-        AMK_HIP(kd->ex_nbbox.alloc(nc * 6)); AMK_HIP(kd->ex_root.alloc(S * 6)); AMK_HIP(kd->ex_nn.alloc(S));
+    if (kd->ex_vind.p) return AMK_OK;
+    kd->ex_max_nodes = kd->cap / 2 + 64;  // ~0.29 nodes per point with 10-point leaves; more = pathological data
+    const size_t pc = S * (size_t)kd->cap, nc = S * (size_t)kd->ex_max_nodes;
+    hipError_t e = kd->ex_vind.alloc(pc);
+    if (e == hipSuccess) e = kd->ex_sa.alloc(pc);
+    if (e == hipSuccess) e = kd->ex_sb.alloc(pc);
+    if (e == hipSuccess) e = kd->ex_pc.alloc(3 * pc);
+    if (e == hipSuccess) e = kd->ex_left.alloc(nc);
+    if (e == hipSuccess) e = kd->ex_right.alloc(nc);
+    if (e == hipSuccess) e = kd->ex_feat.alloc(nc);
+    if (e == hipSuccess) e = kd->ex_child.alloc(nc);
+    if (e == hipSuccess) e = kd->ex_low.alloc(nc);
+    if (e == hipSuccess) e = kd->ex_high.alloc(nc);
+    if (e == hipSuccess) e = kd->ex_nbbox.alloc(nc * 6);
+    if (e == hipSuccess) e = kd->ex_root.alloc(S * 6);
+    if (e == hipSuccess) e = kd->ex_nn.alloc(S);
+    if (e != hipSuccess) {
+        kd->ex_vind.release(); kd->ex_sa.release(); kd->ex_sb.release(); kd->ex_pc.release();
+        kd->ex_left.release(); kd->ex_right.release(); kd->ex_feat.release(); kd->ex_child.release(); kd->ex_low.release();
+        kd->ex_high.release(); kd->ex_nbbox.release(); kd->ex_root.release(); kd->ex_nn.release();
+        return amk::hip_fail(e);
     }
     return AMK_OK;
 }
@@ -555,6 +571,64 @@ int amk::kd_auto_build(amk_kd *a, amk_kd *b, hipStream_t stream) {
     AMK_HIP(hipGetLastError());
     return AMK_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// the keyframe map's pools in AMK_TIES_NANOFLANN (amk_kfmap_set_tie_order): a tree per POOL scene, built where a row names one
+// ------------------------------------------------------------------------------------------------
+// The gated build for the rows of a mapped build or of a sweep, for the obstacle pool and (blockIdx.y = 1) the edge pool: row i
+// names pool scene rows[i] (< 0: the row got no frame / swept nothing) and, behind a sweep, counts only when gate[i] is set (the
+// sweep rebuilt that keyframe: its planes now hold the outliers in cloud order, InitializeNew(newCloud), FrameKDMap.cpp:480-485).
+// Launched unconditionally behind every mapped build and every sweep of a map in the mode: the host never learns which rows built.
+struct PoolExactArgs {
+    amk::ExactPtrs ep[2];
+    amk::GridPtrs grid[2];
+    const int *sizes[2];
+    const int *rows, *gate;
+};
+__global__ __launch_bounds__(amk::kExactTopThreads) void kd_pool_exact_build_top_kernel(const PoolExactArgs a) {
+    const int m = a.rows[blockIdx.x], h = blockIdx.y;
+    if (m < 0 || (a.gate && !a.gate[blockIdx.x])) return;   // (block-uniform)
+    if (exact_refused(a.grid[h].scene(m), a.ep[h].scene(m))) return;
+    amk::exact_build_top(a.ep[h].scene(m), a.sizes[h][m]);
+}
+__global__ __launch_bounds__(amk::kExactThreads) void kd_pool_exact_build_rest_kernel(const PoolExactArgs a, int qcap) {
+    const int m = a.rows[blockIdx.x], h = blockIdx.y;
+    if (m < 0 || (a.gate && !a.gate[blockIdx.x])) return;   // (block-uniform)
+    amk::exact_build_rest(a.ep[h].scene(m), a.sizes[h][m], qcap);
+}
+namespace amk {
+// what kd_pool_exact_reserve allocates for a pool of `scenes` scenes of max_points points (host arithmetic: exact_alloc's arrays,
+// and the index-ordered planes where the pool has none yet -- the edge pool)
+long long kd_pool_exact_bytes(long long scenes, int max_points, bool with_planes) {
+    const long long cap = (long long)amk::round_up(max_points, 256) + 1024, mn = cap / 2 + 64;
+    return scenes * (4 * 3 * cap + 12 * cap + 4 * 4 * mn + 8 * 2 * mn + 8 * 6 * mn + 8 * 6 + 4 + (with_planes ? 12 * cap : 0));
+}
+// the trees' arrays of every pool scene (and the pool's planes), no scene has a tree yet
+int kd_pool_exact_reserve(amk_kd *pool) {
+    if (!pool) return AMK_ERR_INVALID_ARG;
+    int st = exact_alloc(pool);
+    if (st == AMK_OK) st = pool_planes(pool);
+    if (st != AMK_OK) return st;
+    AMK_HIP(hipMemset(pool->ex_nn.p, 0, sizeof(int) * (size_t)pool->n_scenes));
+    return AMK_OK;
+}
+int kd_pool_exact_build(amk_kd *obs_pool, amk_kd *edge_pool, int n_rows, const int *d_rows, const int *d_gate, hipStream_t stream) {
+    if (!obs_pool || !obs_pool->ex_vind.p || (edge_pool && !edge_pool->ex_vind.p) || n_rows < 1 || !d_rows) return AMK_ERR_INVALID_ARG;
+    PoolExactArgs a{};
+    amk_kd *pools[2] = {obs_pool, edge_pool};
+    for (int h = 0; h < (edge_pool ? 2 : 1); ++h) {
+        a.ep[h] = amk_exact_ptrs(pools[h]);
+        a.grid[h] = grid_ptrs(pools[h]);
+        a.sizes[h] = pools[h]->size.p;
+    }
+    a.rows = d_rows; a.gate = d_gate;
+    const dim3 grid(n_rows, edge_pool ? 2 : 1);
+    hipLaunchKernelGGL(kd_pool_exact_build_top_kernel, grid, dim3(amk::kExactTopThreads), 0, stream, a);
+    hipLaunchKernelGGL(kd_pool_exact_build_rest_kernel, grid, dim3(amk::kExactThreads), 0, stream, a, g_exact_queue_cap);
+    AMK_HIP(hipGetLastError());
+    return AMK_OK;
+}
+}  // namespace amk
 
 extern "C" int amk_kd_points_host(amk_kd *kd, float *h_xyz, int *h_sizes) {
     if (!kd || !h_xyz || !h_sizes) return AMK_ERR_INVALID_ARG;
@@ -799,6 +873,16 @@ int amk_kd_exact_status(amk_kd *kd, int *d_status, void *stream) {
     AMK_HIP(hipGetLastError());
     return AMK_OK;
 }
+
+}  // extern "C"
+int amk::kd_pool_exact_status(amk_kd *pool, int *d_status, hipStream_t stream) {
+    if (!pool || !d_status || !pool->ex_nn.p) return AMK_ERR_INVALID_ARG;
+    hipLaunchKernelGGL(kd_exact_status_kernel, dim3((pool->n_scenes + 63) / 64), dim3(64), 0, stream, pool->n_scenes, pool->ex_nn.p,
+                       pool->ex_feat.p, pool->ex_child.p, pool->ex_sa.p, pool->ex_max_nodes, pool->cap, d_status);
+    AMK_HIP(hipGetLastError());
+    return AMK_OK;
+}
+extern "C" {
 
 int amk_kd_exact_status_host(amk_kd *kd, int *h_status) {   // synchronises
     if (!kd || !h_status) return AMK_ERR_INVALID_ARG;

@@ -29,11 +29,12 @@
 namespace amk {
 int step_batch_map(amk_kd *obs_pool, amk_kd *edge_pool, int n_frames, const int *d_fmap, const double *d_Twc,
                    const amk_frame_camera *cam, amk_mpc *mpc, const amk_step_params *prm, const double *d_state_quad,
-                   const double *d_pos_x, double *d_ref_path, double *d_u, double *d_x0array, int *d_flags, hipStream_t stream);
+                   const double *d_pos_x, double *d_ref_path, double *d_u, double *d_x0array, int *d_flags, hipStream_t stream,
+                   bool exact);
 // map_query.hip: QueryNearest / GetNearestDistance over a pool, and the staging of their *_host variants
 int map_query_nearest(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_Twc, const amk_frame_camera *cam,
                       const double *d_queries, int query_stride, int n_queries, int k, float *d_pts, double *d_sqdist, int *d_frame,
-                      int *d_counts, hipStream_t stream);
+                      int *d_counts, hipStream_t stream, bool exact);
 int map_nearest_distance(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_queries, int query_stride,
                          int n_queries, double *d_dist, hipStream_t stream);
 int map_query_host(int S, const double *h_queries, int query_stride, int n_queries, int k, const double *h_Twc, float *h_pts,
@@ -55,6 +56,8 @@ struct amk_kfmap {
     amk::DevBuf<int> out_scene;  // [S]    scratch of add_vertex: pool scene the new frame is built into, -1: no new frame
     amk::DevBuf<int> kf_list, cur_list, outliers, rebuilt;   // [S] scratch of update (rows of the sweep)
     amk::DevBuf<int> fmap;       // [F][S] query vector: pool scene of frame f, -1 absent
+    int tie_order = AMK_TIES_LOWEST_INDEX;   // amk_kfmap_set_tie_order; AMK_TIES_NANOFLANN: the pools hold a tree per scene (kd_pool_exact_build)
+    bool had_frame = false;      // an AddVertex was enqueued (never cleared): the tie order can no longer change
 };
 
 namespace {
@@ -123,12 +126,15 @@ __global__ __launch_bounds__(256) void kf_alloc_gang_kernel(int S, int P, int n_
 }
 
 // KeyframeThreadWorker's body up to the sweep (:443-462), one wavefront per scene.
-__global__ __launch_bounds__(64) void kf_pop_kernel(int S, int P, GridPtrs pool, const int *__restrict__ pool_size,
-                                                    const int *__restrict__ cur_slot, int *__restrict__ kf_n,
-                                                    int *__restrict__ kf_slots, int *__restrict__ need,
-                                                    const double *__restrict__ Twc, const double *__restrict__ tinv,
-                                                    int max_frame_count, double depth_min, int *__restrict__ kf_list,
-                                                    int *__restrict__ cur_list) {
+// EXACT (the map in AMK_TIES_NANOFLANN): DroneBehindPts' ten neighbours by nanoflann's traversal of the keyframe's tree -- which
+// of several equidistant points is the tenth decides the pop; a pool scene without a tree keeps the bucketed index's ten.
+template <bool EXACT>
+__device__ __forceinline__ void kf_pop_scene(int S, int P, GridPtrs pool, const int *__restrict__ pool_size,
+                                             const int *__restrict__ cur_slot, int *__restrict__ kf_n,
+                                             int *__restrict__ kf_slots, int *__restrict__ need,
+                                             const double *__restrict__ Twc, const double *__restrict__ tinv,
+                                             int max_frame_count, double depth_min, int *__restrict__ kf_list,
+                                             int *__restrict__ cur_list, const ExactPtrs *ex) {
 #pragma clang fp contract(off)   // Twb = Twc * Tbc^-1 and ptb.x as the CPU restatement forms them (tests/_kfmap.py), sum in index order
     __shared__ GridWaveLds wl;
     const int s = blockIdx.x, lane = threadIdx.x;
@@ -162,17 +168,36 @@ __global__ __launch_bounds__(64) void kf_pop_kernel(int S, int P, GridPtrs pool,
             const int cnt = size < 10 ? size : 10;
             bool behind = true;
             if (size > cnt) {             // SearchForNearest(cnt) yields nothing when the cloud holds exactly cnt points (kd_tree_two.h:119-124)
-                const GridScene gs = pool.scene(m);
-                double ld;
-                int li, lpos;
-                grid_knn(gs, twb[0], twb[1], twb[2], cnt, ld, li, lpos, &wl);
-                bool bad = false;
-                if (lane < cnt && li != kNoIndex) {
-                    const float4 r = gs.pt[lpos];
-                    const double ptbx = (bx[0] * ((double)r.x - twb[0]) + bx[1] * ((double)r.y - twb[1])) + bx[2] * ((double)r.z - twb[2]);
-                    bad = ptbx <= depth_min;
+                bool have = false;
+                if constexpr (EXACT) {    // the ten by nanoflann's traversal of the keyframe's tree
+                    __shared__ ExactWaveStack xst;
+                    const ExactTree T = ex->scene(m);
+                    double rd;
+                    int ri;
+                    const int got = exact_knn_wave(T, twb[0], twb[1], twb[2], cnt, rd, ri, &xst);
+                    bool bad = false;
+                    if (lane < got) {
+                        const double ptbx = (bx[0] * ((double)T.x[ri] - twb[0]) + bx[1] * ((double)T.y[ri] - twb[1])) + bx[2] * ((double)T.z[ri] - twb[2]);
+                        bad = ptbx <= depth_min;
+                    }
+                    have = got >= 0;          // (wave-uniform; a pool scene without a tree: the bucketed index below)
+                    if (have) behind = __ballot(bad) == 0ull;
                 }
-                behind = __ballot(bad) == 0ull;
+                // (a constant for the front end in the default instantiation, which then emits the statements it always had: a
+                // run-time `if (!have)` that folds later cost kf_pop_kernel a VGPR)
+                if (EXACT ? !have : true) {
+                    const GridScene gs = pool.scene(m);
+                    double ld;
+                    int li, lpos;
+                    grid_knn(gs, twb[0], twb[1], twb[2], cnt, ld, li, lpos, &wl);
+                    bool bad = false;
+                    if (lane < cnt && li != kNoIndex) {
+                        const float4 r = gs.pt[lpos];
+                        const double ptbx = (bx[0] * ((double)r.x - twb[0]) + bx[1] * ((double)r.y - twb[1])) + bx[2] * ((double)r.z - twb[2]);
+                        bad = ptbx <= depth_min;
+                    }
+                    behind = __ballot(bad) == 0ull;
+                }
             }
             pop = !behind;
         }
@@ -192,6 +217,23 @@ __global__ __launch_bounds__(64) void kf_pop_kernel(int S, int P, GridPtrs pool,
     const int back = nk - 1 < 64 ? __shfl(d0, nk - 1) : __shfl(d1, nk - 1 - 64);
     if (back == cur) return;              // (the newest keyframe IS the current frame: a tree swept against itself has no outlier)
     if (lane == 0) { kf_list[s] = back * S + s; cur_list[s] = cur * S + s; }
+}
+__global__ __launch_bounds__(64) void kf_pop_kernel(int S, int P, GridPtrs pool, const int *__restrict__ pool_size,
+                                                    const int *__restrict__ cur_slot, int *__restrict__ kf_n,
+                                                    int *__restrict__ kf_slots, int *__restrict__ need,
+                                                    const double *__restrict__ Twc, const double *__restrict__ tinv,
+                                                    int max_frame_count, double depth_min, int *__restrict__ kf_list,
+                                                    int *__restrict__ cur_list) {
+    kf_pop_scene<false>(S, P, pool, pool_size, cur_slot, kf_n, kf_slots, need, Twc, tinv, max_frame_count, depth_min, kf_list, cur_list,
+                        nullptr);
+}
+__global__ __launch_bounds__(64) void kf_pop_exact_kernel(int S, int P, GridPtrs pool, ExactPtrs ex, const int *__restrict__ pool_size,
+                                                          const int *__restrict__ cur_slot, int *__restrict__ kf_n,
+                                                          int *__restrict__ kf_slots, int *__restrict__ need,
+                                                          const double *__restrict__ Twc, const double *__restrict__ tinv,
+                                                          int max_frame_count, double depth_min, int *__restrict__ kf_list,
+                                                          int *__restrict__ cur_list) {
+    kf_pop_scene<true>(S, P, pool, pool_size, cur_slot, kf_n, kf_slots, need, Twc, tinv, max_frame_count, depth_min, kf_list, cur_list, &ex);
 }
 
 // InsertKeyFrame for the scenes whose sweep rebuilt the newest keyframe (:486), then UpdateQueryVector (:64-74)
@@ -319,6 +361,69 @@ int amk_kfmap_scenes(const amk_kfmap *m) { return m ? m->S : -1; }
 int amk_kfmap_frames(const amk_kfmap *m) { return m ? m->F : -1; }
 const double *amk_kfmap_twc(const amk_kfmap *m) { return m ? m->Twc.p : nullptr; }
 
+// Device bytes amk_kfmap_set_tie_order(AMK_TIES_NANOFLANN) allocates: per pool scene of either pool the tree's arrays (vAcc_ and the
+// two lists of planeSplit, 4 B each, and the coordinates in vAcc_ order, 12 B, per point of capacity; 80 B per node of capacity
+// cap / 2 + 64; the root box and the node count), and for the edge pool the index-ordered planes its trees are built from (12 B).
+int amk_kfmap_tie_order_bytes(int n_scenes, int max_points, int max_edge_points, int max_frame_count, long long *bytes_out) {
+    if (!bytes_out || n_scenes <= 0 || max_points <= 0 || max_edge_points <= 0 || max_frame_count < 1) return AMK_ERR_INVALID_ARG;
+    const long long scenes = (long long)(max_frame_count + 2) * n_scenes;
+    *bytes_out = amk::kd_pool_exact_bytes(scenes, max_points, false) + amk::kd_pool_exact_bytes(scenes, max_edge_points, true);
+    return AMK_OK;
+}
+
+// The tie order of the map's searches (header).  Only before the first frame: every tree then belongs to the cloud its slot holds.
+int amk_kfmap_set_tie_order(amk_kfmap *m, int mode) {
+    if (!m) return AMK_ERR_INVALID_ARG;
+    if (mode != AMK_TIES_LOWEST_INDEX && mode != AMK_TIES_NANOFLANN) return AMK_ERR_UNSUPPORTED;   // (AMK_TIES_AUTO: not for the map)
+    if (m->had_frame) return AMK_ERR_INVALID_ARG;
+    if (mode == AMK_TIES_NANOFLANN && !m->obs->pool_exact) {   // all of the mode's memory, here and never on a later call
+        long long need = 0;
+        size_t free_b = 0, total_b = 0;
+        if (amk_kfmap_tie_order_bytes(m->S, m->obs->max_points, m->edge->max_points, m->prm.max_frame_count, &need) == AMK_OK &&
+            hipMemGetInfo(&free_b, &total_b) == hipSuccess && (unsigned long long)need > (unsigned long long)free_b) {
+            fprintf(stderr, "amk_kfmap_set_tie_order: the trees of %d scenes x (max_frame_count %d + 2) slots x (%d + %d) points need %.2f GiB, "
+                            "%.2f GiB are free on the device (amk_kfmap_tie_order_bytes)\n", m->S, m->prm.max_frame_count,
+                    m->obs->max_points, m->edge->max_points, need / 1073741824.0, free_b / 1073741824.0);
+            return AMK_ERR_UNSUPPORTED;
+        }
+        int st = amk::kd_pool_exact_reserve(m->obs);
+        if (st == AMK_OK) st = amk::kd_pool_exact_reserve(m->edge);
+        if (st != AMK_OK) return st;   // (the map stays in the default mode; a pool keeps its trees' arrays only as a complete set)
+    }
+    m->obs->pool_exact = m->edge->pool_exact = mode == AMK_TIES_NANOFLANN;
+    m->tie_order = mode;
+    return AMK_OK;
+}
+
+// amk_kd_exact_status's codes per query frame of every scene: h_obs / h_edge [S][F] (either may be NULL); AMK_EXACT_OFF for an
+// absent frame or a map in the default mode.  Synchronises the device.
+int amk_kfmap_exact_status_host(amk_kfmap *m, int *h_obs, int *h_edge) {
+    if (!m) return AMK_ERR_INVALID_ARG;
+    AMK_HIP(hipDeviceSynchronize());
+    const size_t S = m->S, F = m->F, PS = (size_t)m->P * S;
+    std::vector<int> fm(S * F), st(PS);
+    AMK_HIP(hipMemcpy(fm.data(), m->fmap.p, sizeof(int) * S * F, hipMemcpyDeviceToHost));
+    amk::DevBuf<int> d;
+    if (m->tie_order == AMK_TIES_NANOFLANN) AMK_HIP(d.alloc(PS));
+    amk_kd *pools[2] = {m->obs, m->edge};
+    int *outs[2] = {h_obs, h_edge};
+    for (int h = 0; h < 2; ++h) {
+        if (!outs[h]) continue;
+        if (m->tie_order == AMK_TIES_NANOFLANN) {
+            const int rc = amk::kd_pool_exact_status(pools[h], d.p, nullptr);
+            if (rc != AMK_OK) return rc;
+            AMK_HIP(hipDeviceSynchronize());
+            AMK_HIP(hipMemcpy(st.data(), d.p, sizeof(int) * PS, hipMemcpyDeviceToHost));
+        }
+        for (size_t s = 0; s < S; ++s)
+            for (size_t f = 0; f < F; ++f) {
+                const int p = fm[f * S + s];
+                outs[h][s * F + f] = (p < 0 || m->tie_order != AMK_TIES_NANOFLANN) ? AMK_EXACT_OFF : st[p];
+            }
+    }
+    return AMK_OK;
+}
+
 int amk_kfmap_add_vertex(amk_kfmap *m, int first_scene, int n_scenes, const float *d_xyz, const int *d_counts,
                          const float *d_edge_xyz, const int *d_edge_counts, int point_stride, const double *d_Twc, void *stream_) {
     if (!m || !d_xyz || !d_edge_xyz || !d_Twc || first_scene < 0 || n_scenes < 1 || first_scene + n_scenes > m->S ||
@@ -328,8 +433,11 @@ int amk_kfmap_add_vertex(amk_kfmap *m, int first_scene, int n_scenes, const floa
     hipLaunchKernelGGL(kf_alloc_kernel, dim3((n_scenes + 255) / 256), dim3(256), 0, stream, m->S, m->P, first_scene, n_scenes, d_counts,
                        d_Twc, m->cur_slot.p, m->kf_n.p, m->kf_slots.p, m->need.p, m->Twc.p, m->out_scene.p + first_scene, m->fmap.p);
     AMK_HIP(hipGetLastError());
-    return amk::kd_build_mapped(m->obs, m->edge, n_scenes, d_xyz, d_counts, d_edge_xyz, d_edge_counts, point_stride,
-                                m->out_scene.p + first_scene, stream);
+    m->had_frame = true;
+    const int st = amk::kd_build_mapped(m->obs, m->edge, n_scenes, d_xyz, d_counts, d_edge_xyz, d_edge_counts, point_stride,
+                                        m->out_scene.p + first_scene, stream);
+    if (st != AMK_OK || m->tie_order != AMK_TIES_NANOFLANN) return st;
+    return amk::kd_pool_exact_build(m->obs, m->edge, n_scenes, m->out_scene.p + first_scene, nullptr, stream);
 }
 
 }  // extern "C"
@@ -351,8 +459,11 @@ int kfmap_add_vertex_gang(amk_kfmap *m, int n_frames, int frame_scenes, const fl
     hipLaunchKernelGGL(kf_alloc_gang_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, m->S, m->P, n_frames, frame_scenes, in, m->cur_slot.p,
                        m->kf_n.p, m->kf_slots.p, m->need.p, m->Twc.p, m->out_scene.p, m->fmap.p);
     AMK_HIP(hipGetLastError());
-    return kd_build_mapped_gang(m->obs, m->edge, n_frames, frame_scenes, d_xyz, d_counts, d_edge_xyz, d_edge_counts, point_stride,
-                                m->out_scene.p, stream);
+    m->had_frame = true;
+    const int st = kd_build_mapped_gang(m->obs, m->edge, n_frames, frame_scenes, d_xyz, d_counts, d_edge_xyz, d_edge_counts, point_stride,
+                                        m->out_scene.p, stream);
+    if (st != AMK_OK || m->tie_order != AMK_TIES_NANOFLANN) return st;
+    return kd_pool_exact_build(m->obs, m->edge, n, m->out_scene.p, nullptr, stream);   // one launch pair for all G frames
 }
 }  // namespace amk
 extern "C" {
@@ -360,12 +471,20 @@ extern "C" {
 int amk_kfmap_update(amk_kfmap *m, void *stream_) {
     if (!m) return AMK_ERR_INVALID_ARG;
     hipStream_t stream = (hipStream_t)stream_;
-    hipLaunchKernelGGL(kf_pop_kernel, dim3(m->S), dim3(64), 0, stream, m->S, m->P, grid_ptrs(m->obs), m->obs->size.p, m->cur_slot.p, m->kf_n.p,
-                       m->kf_slots.p, m->need.p, m->Twc.p, m->tinv.p, m->prm.max_frame_count, m->prm.depth_min, m->kf_list.p,
-                       m->cur_list.p);
+    const bool exact = m->tie_order == AMK_TIES_NANOFLANN;
+    if (exact)
+        hipLaunchKernelGGL(kf_pop_exact_kernel, dim3(m->S), dim3(64), 0, stream, m->S, m->P, grid_ptrs(m->obs), amk_exact_ptrs(m->obs),
+                           m->obs->size.p, m->cur_slot.p, m->kf_n.p, m->kf_slots.p, m->need.p, m->Twc.p, m->tinv.p, m->prm.max_frame_count,
+                           m->prm.depth_min, m->kf_list.p, m->cur_list.p);
+    else
+        hipLaunchKernelGGL(kf_pop_kernel, dim3(m->S), dim3(64), 0, stream, m->S, m->P, grid_ptrs(m->obs), m->obs->size.p, m->cur_slot.p, m->kf_n.p,
+                           m->kf_slots.p, m->need.p, m->Twc.p, m->tinv.p, m->prm.max_frame_count, m->prm.depth_min, m->kf_list.p,
+                           m->cur_list.p);
     AMK_HIP(hipGetLastError());
-    const int st = amk::kd_sweep_mapped(m->obs, m->S, m->kf_list.p, m->cur_list.p, m->prm.keyframe_th_dist, m->prm.keyframe_th_count,
-                                        m->outliers.p, m->rebuilt.p, stream);
+    int st = amk::kd_sweep_mapped(m->obs, m->S, m->kf_list.p, m->cur_list.p, m->prm.keyframe_th_dist, m->prm.keyframe_th_count,
+                                  m->outliers.p, m->rebuilt.p, stream);
+    // a keyframe rebuilt from its outliers gets the tree of the new cloud (its edge tree stays: FrameKDMap.cpp:480-485)
+    if (st == AMK_OK && exact) st = amk::kd_pool_exact_build(m->obs, nullptr, m->S, m->kf_list.p, m->rebuilt.p, stream);
     if (st != AMK_OK) return st;
     hipLaunchKernelGGL(kf_insert_kernel, dim3((m->S + 255) / 256), dim3(256), 0, stream, m->S, m->P, m->F, m->cur_slot.p, m->kf_n.p,
                        m->kf_slots.p, m->rebuilt.p, m->fmap.p);
@@ -377,7 +496,7 @@ int amk_kfmap_step(amk_kfmap *m, const amk_frame_camera *cam, amk_mpc *mpc, cons
                    const double *d_pos_x, double *d_ref_path, double *d_u, double *d_x0array, int *d_flags, void *stream_) {
     if (!m || !mpc || mpc->S != m->S) return AMK_ERR_INVALID_ARG;
     return amk::step_batch_map(m->obs, m->edge, m->F, m->fmap.p, cam ? m->Twc.p : nullptr, cam, mpc, prm, d_state_quad, d_pos_x,
-                               d_ref_path, d_u, d_x0array, d_flags, (hipStream_t)stream_);
+                               d_ref_path, d_u, d_x0array, d_flags, (hipStream_t)stream_, m->tie_order == AMK_TIES_NANOFLANN);
 }
 
 // FrameKDMap::QueryNearest / GetNearestDistance over the map as it stands (map_query.hip); stream-ordered, no map state changes
@@ -385,7 +504,8 @@ int amk_kfmap_query_nearest(amk_kfmap *m, const amk_frame_camera *cam, const dou
                             int query_edge, float *d_pts, double *d_sqdist, int *d_frame, int *d_counts, void *stream) {
     if (!m) return AMK_ERR_INVALID_ARG;
     return amk::map_query_nearest(query_edge ? m->edge : m->obs, m->F, m->fmap.p, m->S, cam ? m->Twc.p : nullptr, cam, d_queries,
-                                  query_stride, n_queries, k, d_pts, d_sqdist, d_frame, d_counts, (hipStream_t)stream);
+                                  query_stride, n_queries, k, d_pts, d_sqdist, d_frame, d_counts, (hipStream_t)stream,
+                                  m->tie_order == AMK_TIES_NANOFLANN);
 }
 
 int amk_kfmap_nearest_distance(amk_kfmap *m, const double *d_queries, int query_stride, int n_queries, double *d_dist, void *stream) {

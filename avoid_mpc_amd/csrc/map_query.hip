@@ -32,14 +32,40 @@ struct QueryFrames {  // kernel argument: the frames of ONE kind of cloud (obsta
 
 __device__ __forceinline__ float wave_shr1_f32(float v) { return __int_as_float(wave_shr1_i32(__float_as_int(v))); }
 
+// One frame's sorted k-list for the fold (lane i < k: squared distance nd, DBL_MAX where there is none, and the point).
+// EXACT (a keyframe map in AMK_TIES_NANOFLANN): nanoflann's list from the pool scene's tree; a scene without a tree (given up,
+// too deep) keeps the bucketed index's, as a plain handle does.
+template <bool EXACT>
+__device__ __forceinline__ void frame_list(const GridScene &gs, const ExactPtrs &ex, int m, double qx, double qy, double qz, int k, int lane,
+                                           GridWaveLds *wl, double &nd, float4 &rec) {
+    if constexpr (EXACT) {
+        __shared__ ExactWaveStack xst[4];
+        const ExactTree T = ex.scene(m);
+        double xd;
+        int xi;
+        const int got = exact_knn_wave(T, qx, qy, qz, k, xd, xi, &xst[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)]);
+        if (got >= 0) {   // (wave-uniform)
+            const bool ok = lane < got;
+            nd = ok ? xd : DBL_MAX;
+            rec = ok ? make_float4(T.x[xi], T.y[xi], T.z[xi], 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+            return;
+        }
+    }
+    double ld;
+    int li, lpos;
+    grid_knn(gs, qx, qy, qz, k, ld, li, lpos, wl);
+    rec = gs.pt[lpos];   // (lpos = 0 for empty slots: a valid address)
+    nd = (lane < k && li != kNoIndex) ? ld : DBL_MAX;
+}
+
 // DIST: GetNearestDistance -- the same walk with k = 1 and no fast path; out_dist = sqrt of the best squared distance
-template <bool MAP, bool DIST>
-__global__ __launch_bounds__(256) void map_query_kernel(QueryFrames qf, int n_scenes, const double *__restrict__ queries,
-                                                        int query_stride, int n_queries, int k_in,
-                                                        const double *__restrict__ Twc, amk_frame_camera cam,
-                                                        float *__restrict__ out_pts, double *__restrict__ out_d2,
-                                                        int *__restrict__ out_frame, int *__restrict__ out_cnt,
-                                                        double *__restrict__ out_dist) {
+template <bool MAP, bool DIST, bool EXACT>
+__device__ __forceinline__ void map_query_row(const QueryFrames &qf, const ExactPtrs &ex, int n_scenes, const double *__restrict__ queries,
+                                              int query_stride, int n_queries, int k_in,
+                                              const double *__restrict__ Twc, const amk_frame_camera &cam,
+                                              float *__restrict__ out_pts, double *__restrict__ out_d2,
+                                              int *__restrict__ out_frame, int *__restrict__ out_cnt,
+                                              double *__restrict__ out_dist) {
     __shared__ GridWaveLds wl[4];
     const WaveSlot ws = wave_slot(n_queries);
     const int s = ws.s, w = ws.w, lane = ws.lane, q = ws.unit;
@@ -72,14 +98,21 @@ __global__ __launch_bounds__(256) void map_query_kernel(QueryFrames qf, int n_sc
         const int n0 = m0 < 0 ? 0 : (MAP ? pool_size : qf.size[0])[m0];
         fast = n0 >= k && (!Twc || pt_in_frame(Twc + (size_t)s * 16, cam, qx, qy, qz));
         if (fast) {
-            double ld;
-            int li, lpos;
             const GridScene gs = (MAP ? pool : qf.g[0]).scene(m0);
-            grid_knn(gs, qx, qy, qz, k, ld, li, lpos, &wl[w]);
             cnt = adaptor_count(n0, k);   // (n0 >= k here: k, or nothing from a cloud of exactly k points)
-            if (lane < cnt && li != kNoIndex) {
-                const float4 rec = gs.pt[lpos];
-                rd = ld; rx = rec.x; ry = rec.y; rz = rec.z; rf = 0;
+            if constexpr (EXACT) {
+                double nd;
+                float4 rec;
+                frame_list<true>(gs, ex, m0, qx, qy, qz, k, lane, &wl[w], nd, rec);
+                if (lane < cnt && nd < DBL_MAX) { rd = nd; rx = rec.x; ry = rec.y; rz = rec.z; rf = 0; }
+            } else {
+                double ld;
+                int li, lpos;
+                grid_knn(gs, qx, qy, qz, k, ld, li, lpos, &wl[w]);
+                if (lane < cnt && li != kNoIndex) {
+                    const float4 rec = gs.pt[lpos];
+                    rd = ld; rx = rec.x; ry = rec.y; rz = rec.z; rf = 0;
+                }
             }
         }
     }
@@ -89,12 +122,10 @@ __global__ __launch_bounds__(256) void map_query_kernel(QueryFrames qf, int n_sc
             if (m < 0) continue;     // (map mode: this scene's map has no frame f)
             const int n = (MAP ? pool_size : qf.size[f])[m];
             if (n <= k) continue;    // k' = min(k, size_f) results exist iff size_f > k'
-            double ld;
-            int li, lpos;
             const GridScene gs = (MAP ? pool : qf.g[f]).scene(m);
-            grid_knn(gs, qx, qy, qz, k, ld, li, lpos, &wl[w]);
-            const float4 rec = gs.pt[lpos];   // (lpos = 0 for empty slots: a valid address)
-            const double nd = (lane < k && li != kNoIndex) ? ld : DBL_MAX;
+            double nd;
+            float4 rec;
+            frame_list<EXACT>(gs, ex, m, qx, qy, qz, k, lane, &wl[w], nd, rec);
             for (int e = 0; e < k; ++e) {     // this frame's entries, best first
                 const double dc = readlane_f64(nd, e);
                 if (!(dc < DBL_MAX)) break;
@@ -134,15 +165,40 @@ __global__ __launch_bounds__(256) void map_query_kernel(QueryFrames qf, int n_sc
         }
     }
 }
+template <bool MAP, bool DIST>
+__global__ __launch_bounds__(256) void map_query_kernel(QueryFrames qf, int n_scenes, const double *__restrict__ queries,
+                                                        int query_stride, int n_queries, int k_in,
+                                                        const double *__restrict__ Twc, amk_frame_camera cam,
+                                                        float *__restrict__ out_pts, double *__restrict__ out_d2,
+                                                        int *__restrict__ out_frame, int *__restrict__ out_cnt,
+                                                        double *__restrict__ out_dist) {
+    map_query_row<MAP, DIST, false>(qf, ExactPtrs{}, n_scenes, queries, query_stride, n_queries, k_in, Twc, cam, out_pts, out_d2, out_frame,
+                                    out_cnt, out_dist);
+}
+// QueryNearest over a keyframe map in AMK_TIES_NANOFLANN: every contributing frame's list by nanoflann's traversal of its tree
+__global__ __launch_bounds__(256) void map_query_exact_kernel(QueryFrames qf, ExactPtrs ex, int n_scenes, const double *__restrict__ queries,
+                                                              int query_stride, int n_queries, int k_in,
+                                                              const double *__restrict__ Twc, amk_frame_camera cam,
+                                                              float *__restrict__ out_pts, double *__restrict__ out_d2,
+                                                              int *__restrict__ out_frame, int *__restrict__ out_cnt) {
+    map_query_row<true, false, true>(qf, ex, n_scenes, queries, query_stride, n_queries, k_in, Twc, cam, out_pts, out_d2, out_frame,
+                                     out_cnt, nullptr);
+}
 
 template <bool DIST>
 int launch_query(const QueryFrames &qf, int S, const double *d_queries, int query_stride, int n_queries, int k, const double *d_Twc,
                  const amk_frame_camera *cam, float *d_pts, double *d_sqdist, int *d_frame, int *d_counts, double *d_dist,
-                 hipStream_t stream) {
+                 hipStream_t stream, const ExactPtrs *ex = nullptr) {
     const long long blocks = search_blocks(S, n_queries);
     if (blocks > 0x7fffffffll) return AMK_ERR_UNSUPPORTED;
     amk_frame_camera c{};
     if (cam) c = *cam;
+    if (ex) {   // (a keyframe map in AMK_TIES_NANOFLANN; never GetNearestDistance: a distance does not depend on the order of ties)
+        hipLaunchKernelGGL(map_query_exact_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, qf, *ex, S, d_queries, query_stride, n_queries,
+                           k, d_Twc, c, d_pts, d_sqdist, d_frame, d_counts);
+        AMK_HIP(hipGetLastError());
+        return AMK_OK;
+    }
     auto kernel = qf.fmap ? map_query_kernel<true, DIST> : map_query_kernel<false, DIST>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, stream, qf, S, d_queries, query_stride, n_queries, k, d_Twc, c,
                        d_pts, d_sqdist, d_frame, d_counts, d_dist);
@@ -188,12 +244,17 @@ namespace amk {
 // The two queries over a keyframe map's pool (kfmap.hip): frame f of scene s = pool scene d_fmap[f * S + s] (< 0: absent).
 int map_query_nearest(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_Twc, const amk_frame_camera *cam,
                       const double *d_queries, int query_stride, int n_queries, int k, float *d_pts, double *d_sqdist, int *d_frame,
-                      int *d_counts, hipStream_t stream) {
+                      int *d_counts, hipStream_t stream, bool exact) {
     if (!pool || !d_fmap || n_frames < 1 || S < 1 || !query_args_ok(d_queries, query_stride, n_queries) || k < 1) return AMK_ERR_INVALID_ARG;
     if (d_Twc && !cam) return AMK_ERR_INVALID_ARG;
     if (k > AMK_MAX_K) return AMK_ERR_UNSUPPORTED;
+    ExactPtrs ex;
+    if (exact) {
+        if (!pool->ex_vind.p) return AMK_ERR_INVALID_ARG;   // (amk_kfmap_set_tie_order allocated the trees)
+        ex = amk_exact_ptrs(pool);
+    }
     return launch_query<false>(frames_of_pool(pool, n_frames, d_fmap, S), S, d_queries, query_stride, n_queries, k, d_Twc, cam, d_pts,
-                               d_sqdist, d_frame, d_counts, nullptr, stream);
+                               d_sqdist, d_frame, d_counts, nullptr, stream, exact ? &ex : nullptr);
 }
 
 int map_nearest_distance(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_queries, int query_stride,

@@ -50,6 +50,13 @@ struct FrameExact {
     ExactPtrs obs[AMK_MAX_FRAMES], edge[AMK_MAX_FRAMES];
     int use_obs[AMK_MAX_FRAMES], use_edge[AMK_MAX_FRAMES];
 };
+// ... or the two POOLS of a keyframe map in AMK_TIES_NANOFLANN (kfmap.hip), by value: frame f of scene s is pool scene
+// fmap[f * S + s] of either pool, absent when that is < 0 -- no device table, no host upload.
+struct MapTrees {
+    ExactPtrs obs_pool, edge_pool;
+    const int *fmap;
+    int S;
+};
 __device__ __forceinline__ bool exact_used(const ExactPair &t, int, bool edge) { return edge ? t.use_edge : t.use_obs; }
 __device__ __forceinline__ bool exact_used(const FrameExact *t, int f, bool edge) {
     return edge ? t->use_edge[f] : t->use_obs[f];
@@ -59,6 +66,10 @@ __device__ __forceinline__ ExactTree exact_scene(const ExactPair &t, int, bool e
 }
 __device__ __forceinline__ ExactTree exact_scene(const FrameExact *t, int f, bool edge, int s) {
     return edge ? t->edge[f].scene(s) : t->obs[f].scene(s);
+}
+__device__ __forceinline__ bool map_frame_present(const MapTrees &t, int f, int s) { return t.fmap[(size_t)f * t.S + s] >= 0; }
+__device__ __forceinline__ ExactTree exact_scene(const MapTrees &t, int f, bool edge, int s) {
+    return (edge ? t.edge_pool : t.obs_pool).scene(t.fmap[(size_t)f * t.S + s]);
 }
 // whether row (s, q) of a tree that is used goes through it: every row (step.hip's StepAuto: only the rows that tied)
 template <class Trees>

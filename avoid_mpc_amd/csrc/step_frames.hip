@@ -19,6 +19,8 @@
 //   mpc_solve_kernel              Solve + refill of the reference path (mpc_solve.hip)
 // Frames whose handles are in AMK_TIES_NANOFLANN mode are queried by nanoflann's own traversal of its own tree
 // (kd_exact.h): step_knn_exact_kernel (step_common.h) overwrites the raw results, the snap re-query follows suit.
+// A keyframe map in that mode (amk_kfmap_set_tie_order) holds a tree per pool scene: step_knn_exact_map_kernel and
+// step_merge_plan_pack_map_kernel do the same through MapTrees (step_common.h).
 #include "step_common.h"
 
 using namespace amk;
@@ -109,6 +111,60 @@ __global__ __launch_bounds__(256) void step_knn_frames_kernel(FrameSet fs, int n
     }
 }
 
+// A keyframe map in AMK_TIES_NANOFLANN: the raw rows once more, by nanoflann's traversal of the pool scenes' trees, over what
+// step_knn_frames_kernel<true> wrote (a pool scene without a tree keeps that).  One wavefront per (scene, query) walks the frames
+// the scene HOLDS and skips what that kernel skips: the frames behind the current one for a row that will take the fast path.
+// Reference point 0 is read in every frame: as there, frames 1 .. fc - 1 get a wavefront each ("queries" N + 1 .. N + fc - 1).
+__global__ __launch_bounds__(256) void step_knn_exact_map_kernel(MapTrees trees, const int *__restrict__ size_obs,
+                                                                 const int *__restrict__ size_edge, int n_frames, int n_scenes,
+                                                                 const double *__restrict__ ref_path, int N, int K, FrameBufs fb,
+                                                                 const int *__restrict__ done, int fc, const double *__restrict__ Twc,
+                                                                 amk_frame_camera cam) {
+    __shared__ ExactWaveStack stacks[4];
+    const int nq = N + 1, nv = fc - 1;
+    const WaveSlot ws = wave_slot(nq + nv);
+    const int s = ws.s, w = ws.w, lane = ws.lane;
+    int q = ws.unit;
+    if (s >= n_scenes || q >= nq + nv || done[s]) return;
+    int f_only = -1;
+    if (q >= nq) { f_only = q - N; q = 0; }
+    const bool is_edge = q == N;
+    const double *qp = ref_path + ((size_t)s * N + (is_edge ? 0 : q)) * SD;
+    const double qx = qp[0], qy = qp[1], qz = qp[2];
+    const int k = is_edge ? 1 : K;
+    bool cur_only = false;   // step_knn_frames_kernel's decision, from the same numbers
+    if (q != 0) {
+        const int m0 = trees.fmap[s];
+        const int n0 = m0 < 0 ? 0 : (is_edge ? size_edge : size_obs)[m0];
+        cur_only = n0 >= k && (!Twc || pt_in_frame(Twc + (size_t)s * 16, cam, qx, qy, qz));
+    }
+    int F = 0;               // frames this scene's map holds
+    for (int f0 = 0; f0 < n_frames; f0 += 64) {
+        const int f = f0 + lane;
+        const unsigned long long b = __ballot(f < n_frames && trees.fmap[(size_t)f * trees.S + s] >= 0);
+        if (b) F = f0 + 64 - __clzll((long long)b);
+    }
+    int f = 0, f_end = F;
+    if (f_only >= 0) { f = f_only; f_end = min(F, f_only + 1); }
+    for (; f < f_end; ++f) {
+        if (cur_only && f > 0) break;
+        if (f_only < 0 && q == 0 && f > 0 && f < fc) continue;   // (the wavefronts above)
+        if (!map_frame_present(trees, f, s)) continue;
+        const ExactTree T = exact_scene(trees, f, is_edge, s);
+        double rd;
+        int ri;
+        const int got = exact_knn_wave(T, qx, qy, qz, k, rd, ri, &stacks[w]);
+        if (got < 0) continue;
+        if (lane < k) {
+            const bool ok = lane < got;
+            const float px = ok ? T.x[ri] : 0.f, py = ok ? T.y[ri] : 0.f, pz = ok ? T.z[ri] : 0.f;
+            const size_t o = (size_t)f * n_scenes + s;
+            if (is_edge) store_nbr(fb.edge_pt, fb.edge_d2, o, ok, rd, px, py, pz);
+            else store_nbr(fb.knn_pts, fb.knn_d2, (o * N + q) * K + lane, ok, rd, px, py, pz);
+        }
+    }
+}
+
 __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -130,219 +186,27 @@ __global__ __launch_bounds__(4 * kWave) void step_merge_plan_pack_kernel(
     int max_iter, double speed, double T, double safety_distance, const double *__restrict__ state_quad,
     const double *__restrict__ pos_x, double *__restrict__ ref_path, float *__restrict__ knn_pts,
     double *__restrict__ knn_d2, double *__restrict__ ref_states, int *__restrict__ done, int *__restrict__ flags) {
-    // One workgroup per scene: nw = blockDim.x / 64 wavefronts (4; 1 when a frame is in AMK_TIES_NANOFLANN mode).  Wavefront 0
-    // decides PlanWapionts; the snapped point's re-queries (one search per frame) and the per-reference-point merges are dealt
-    // round-robin to the wavefronts, the rows that take QueryNearest's fast path are copied by all threads at once.
-    const int s = blockIdx.x, lane = threadIdx.x & 63, tid = threadIdx.x, nthr = blockDim.x;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;
-    if (done[s]) return;
-    // frames this scene's map holds: every loop below runs over them only (an absent frame contributes nothing to any query, and the
-    // candidate ids f K + j of the others do not move).  A map with room for 101 frames holds ~6 on a flight; each pass over
-    // absent frames is a chain of dependent loads (fmap, then the size) per frame.
-    int F = fs.n;
-    if (fs.fmap) {
-        int hi = 0;
-        for (int f0 = 0; f0 < fs.n; f0 += 64) {
-            const int f = f0 + lane;
-            const unsigned long long b = __ballot(f < fs.n && fs.fmap[(size_t)f * fs.S + s] >= 0);
-            if (b) hi = f0 + 64 - __clzll((long long)b);
-        }
-        F = hi;
-    }
-    __shared__ GridWaveLds wl[4];
-    __shared__ int cntq[AMK_MAX_HORIZON];
-    __shared__ int sh_safety, sh_snap;
-    __shared__ double sh_e[3];
-    double *rp = ref_path + (size_t)s * N * SD;
-    const double *Ts = Twc ? Twc + (size_t)s * 16 : nullptr;
-    auto in_frame = [&](double x, double y, double z) { return Ts ? pt_in_frame(Ts, cam, x, y, z) : true; };
-    const int n_obs0 = fs.n_obs(0, s);
-    // ---- PlanWapionts (:259-281) for reference point 0
-    if (w == 0) {
-        const double p0x = rp[0], p0y = rp[1], p0z = rp[2];
-        // GetNearestDistance: 1-NN per frame exists iff the frame holds more than one point (lane = frame)
-        unsigned long long d2n_key = ~0ull;
-        for (int f0 = 0; f0 < F; f0 += 64) {
-            const int f = f0 + lane;
-            if (f < F && fs.n_obs(f, s) > 1) {
-                const double d = fb.knn_d2[(((size_t)f * S + s) * N) * K];
-                // fmin semantics: a NaN distance is ignored; d >= 0, so the bit pattern orders like the value
-                if (d == d) { const unsigned long long k64 = (unsigned long long)__double_as_longlong(d); d2n_key = k64 < d2n_key ? k64 : d2n_key; }
-            }
-        }
-        d2n_key = wave_min_u64(d2n_key);
-        const double d2n = d2n_key == ~0ull ? DBL_MAX : __longlong_as_double((long long)d2n_key);
-        int is_safety = 1, snap = 0;
-        if (!(sqrt(d2n) > safety_distance)) {
-            // QueryNearest(p1, 1, ..., queryEdge = true): fast path iff the current edge cloud holds >= 1 point and p1 is in frame
-            int bf = -1;
-            if (fs.n_edge(0, s) >= 1 && in_frame(p0x, p0y, p0z)) {
-                if (fs.n_edge(0, s) > 1 && fb.edge_d2[s] < DBL_MAX) bf = 0;
-            } else {
-                // k' = min(1, size_f): a result iff size_f > 1; ties keep the earlier frame (lane = frame; strict < in frame order)
-                unsigned long long bk = ~0ull;
-                int mf = 0x7fffffff;
-                for (int f0 = 0; f0 < F; f0 += 64) {
-                    const int f = f0 + lane;
-                    if (f < F && fs.n_edge(f, s) > 1) {
-                        const double d = fb.edge_d2[(size_t)f * S + s];
-                        if (d < DBL_MAX) {
-                            const unsigned long long k64 = (unsigned long long)__double_as_longlong(d);
-                            if (k64 < bk) { bk = k64; mf = f; }
-                        }
-                    }
-                }
-                const unsigned long long wb = wave_min_u64(bk);
-                if (wb != ~0ull) {
-                    int win = bk == wb ? mf : 0x7fffffff;
-#pragma unroll
-                    for (int off = 32; off > 0; off >>= 1) win = min(win, __shfl_xor(win, off));
-                    bf = win;
-                }
-            }
-            if (bf < 0) {
-                is_safety = 0;
-            } else {
-                snap = 1;
-                const float *ep = fb.edge_pt + 3 * ((size_t)bf * S + s);
-                if (lane == 0) { sh_e[0] = (double)ep[0]; sh_e[1] = (double)ep[1]; sh_e[2] = (double)ep[2]; }
-            }
-        }
-        if (lane == 0) { sh_safety = is_safety; sh_snap = snap; flags[4 * s + 0] = is_safety; }
-    }
-    __syncthreads();
-    const int is_safety = sh_safety;
-    if (sh_snap) {
-        const double ex = sh_e[0], ey = sh_e[1], ez = sh_e[2];
-        for (int f = w; f < F; f += nw) {  // the snapped point is what ProcessWaypoints queries next (:210-215)
-            double gld;
-            int gli, glpos;
-            const int mf = fs.scene_of(f, s);
-            if (mf >= 0) {   // (wave-uniform)
-                const GridScene gs = fs.obs_scene(f, mf);
-                grid_knn(gs, ex, ey, ez, K, gld, gli, glpos, &wl[w]);
-                if (lane < K) {
-                    const float4 rec = gs.pt[glpos];
-                    store_nbr(fb.knn_pts, fb.knn_d2, ((size_t)f * S + s) * N * K + lane, gli != kNoIndex, gld, rec.x, rec.y,
-                              rec.z);
-                }
-            }
-            if constexpr (EXACT) {   // (nw == 1: the barriers below are this wavefront's own)
-                __syncthreads();
-                if (mf >= 0 && fe->use_obs[f]) {  // AMK_TIES_NANOFLANN frame
-                    exact_requery(fe->obs[f].scene(s), ex, ey, ez, K, fb.knn_pts, fb.knn_d2, ((size_t)f * S + s) * N);
-                    __syncthreads();
-                }
-            }
-        }
-        if (tid == 0) { rp[0] = ex; rp[1] = ey; rp[2] = ez; }
-    }
-    __threadfence_block();
-    __syncthreads();
-    // ---- ProcessWaypoints' queries (:204-215): fast path or merge over the frames, per reference point
-    // QueryNearestWithCurFrame (:254-275, 339-345) for the reference points the current image sees (lane = reference point)
-    bool inf = false;
-    if (lane < N) inf = n_obs0 >= K && in_frame(rp[lane * SD], rp[lane * SD + 1], rp[lane * SD + 2]);
-    const unsigned long long fast = __ballot(inf);
-    {
-        const int cnt_fast = n_obs0 > K ? K : 0;      // kd_tree_two.h:119-124
-        const size_t base = (size_t)s * N * K;        // frame 0's rows of this scene = the output rows' layout
-        for (int e = tid; e < N * K; e += nthr) {
-            const int i = e / K;
-            if ((fast >> i) & 1ull) {
-                knn_d2[base + e] = fb.knn_d2[base + e];
-                for (int c = 0; c < 3; ++c) knn_pts[(base + e) * 3 + c] = fb.knn_pts[(base + e) * 3 + c];
-            }
-        }
-        if (w == 0 && inf) cntq[lane] = cnt_fast;
-    }
-    for (int i = w; i < N; i += nw) {
-        if ((fast >> i) & 1ull) continue;
-        const size_t orow = ((size_t)s * N + i) * K;
-        // QueryNearestThreadWorker over mVecQueryVector (:276-321) + sort (:371): candidate c = f * K + j
-        const int ncand = F * K;
-        int cnt = 0;
-        if constexpr (CPL > 0) {
-        unsigned long long key[CPL];
-#pragma unroll
-        for (int r = 0; r < CPL; ++r) {
-            const int c = lane + 64 * r;
-            key[r] = ~0ull;
-            if (c < ncand) {
-                const int f = c / K, jj = c - f * K;
-                if (fs.n_obs(f, s) > K) {  // k' = min(K, size_f) results exist iff size_f > k'
-                    const double d = fb.knn_d2[(((size_t)f * S + s) * N + i) * K + jj];
-                    if (d < DBL_MAX) key[r] = (unsigned long long)__double_as_longlong(d);  // d >= 0: order-preserving
-                }
-            }
-        }
-        for (int m = 0; m < K; ++m) {  // K rounds of "smallest remaining (distance, candidate id)"
-            unsigned long long loc = ~0ull;
-#pragma unroll
-            for (int r = 0; r < CPL; ++r) loc = key[r] < loc ? key[r] : loc;
-            const unsigned long long best = wave_min_u64(loc);
-            if (best == ~0ull) break;
-            int myc = 0x7fffffff;  // lowest candidate id holding `best`
-#pragma unroll
-            for (int r = CPL - 1; r >= 0; --r)
-                if (key[r] == best) myc = lane + 64 * r;
-            int win = myc;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) win = min(win, __shfl_xor(win, off));
-            if (myc == win) {
-                const int f = win / K, jj = win - f * K;
-                const size_t irow = (((size_t)f * S + s) * N + i) * K + jj;
-                knn_d2[orow + m] = __longlong_as_double((long long)best);
-                for (int c = 0; c < 3; ++c) knn_pts[(orow + m) * 3 + c] = fb.knn_pts[irow * 3 + c];
-#pragma unroll
-                for (int r = 0; r < CPL; ++r)
-                    if (lane + 64 * r == win) key[r] = ~0ull;
-            }
-            ++cnt;
-        }
-        } else {
-        // wide map: the same K rounds, the candidates re-read from the raw rows every round (L2-resident: F K doubles per
-        // reference point), a lane's taken candidates remembered as bits (candidate lane + 64 r = bit r; F K <= 64 x 128)
-        unsigned long long taken0 = 0ull, taken1 = 0ull;
-        for (int m = 0; m < K; ++m) {
-            unsigned long long loc = ~0ull;
-            int myc = 0x7fffffff;
-            for (int r = 0; lane + 64 * r < ncand; ++r) {
-                if ((r < 64 ? taken0 >> r : taken1 >> (r - 64)) & 1ull) continue;
-                const int c = lane + 64 * r;
-                const int f = c / K, jj = c - f * K;
-                if (fs.n_obs(f, s) > K) {
-                    const double d = fb.knn_d2[(((size_t)f * S + s) * N + i) * K + jj];
-                    if (d < DBL_MAX) {
-                        const unsigned long long k64 = (unsigned long long)__double_as_longlong(d);
-                        if (k64 < loc) { loc = k64; myc = c; }   // (ascending r: the lowest candidate id among equal keys of this lane)
-                    }
-                }
-            }
-            const unsigned long long best = wave_min_u64(loc);
-            if (best == ~0ull) break;
-            int win = loc == best ? myc : 0x7fffffff;
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) win = min(win, __shfl_xor(win, off));
-            if (loc == best && myc == win) {
-                const int f = win / K, jj = win - f * K;
-                const size_t irow = (((size_t)f * S + s) * N + i) * K + jj;
-                knn_d2[orow + m] = __longlong_as_double((long long)best);
-                for (int c = 0; c < 3; ++c) knn_pts[(orow + m) * 3 + c] = fb.knn_pts[irow * 3 + c];
-                const int r = win >> 6;
-                if (r < 64) taken0 |= 1ull << r; else taken1 |= 1ull << (r - 64);
-            }
-            ++cnt;
-        }
-        }
-        if (lane == 0) cntq[i] = cnt;
-    }
-    __threadfence_block();
-    __syncthreads();
-    pack_ref_states(tid, nthr, s, N, K, nref, iter, max_iter, speed, T, safety_distance, is_safety,
-                    [&](int i) { return cntq[i]; }, state_quad, pos_x, rp, knn_pts, knn_d2, ref_states, done);
+    constexpr bool kMapTrees = false;
+    const MapTrees *trees = nullptr;
+#define AMK_STEP_MERGE_PLAN_PACK_BODY   // (the body refuses to be included anywhere else)
+#include "step_merge_plan_pack_body.h"
+#undef AMK_STEP_MERGE_PLAN_PACK_BODY
 }
-
+// the same over a keyframe map in AMK_TIES_NANOFLANN: the snap's re-query through the pool scenes' trees, four wavefronts
+// (CPL 4, or 0: the wide merge)
+template <int CPL>
+__global__ __launch_bounds__(4 * kWave) void step_merge_plan_pack_map_kernel(
+    FrameSet fs, MapTrees map_trees, FrameBufs fb, int S, const double *__restrict__ Twc, amk_frame_camera cam, int N, int K, int nref, int iter,
+    int max_iter, double speed, double T, double safety_distance, const double *__restrict__ state_quad,
+    const double *__restrict__ pos_x, double *__restrict__ ref_path, float *__restrict__ knn_pts,
+    double *__restrict__ knn_d2, double *__restrict__ ref_states, int *__restrict__ done, int *__restrict__ flags) {
+    constexpr bool EXACT = true, kMapTrees = true;
+    const MapTrees *trees = &map_trees;
+    const FrameExact *fe = nullptr;
+#define AMK_STEP_MERGE_PLAN_PACK_BODY   // (the body refuses to be included anywhere else)
+#include "step_merge_plan_pack_body.h"
+#undef AMK_STEP_MERGE_PLAN_PACK_BODY
+}
 }  // namespace
 
 // tests only (tests/test_kfmap_gpu.py): take the wide-map merge (candidates re-read every round) whatever the map's size
@@ -352,7 +216,8 @@ extern "C" void amk__frames_force_wide(int on) { g_force_wide = on; }
 // the rounds of the step over a frame set (plain handles or the keyframe map's pool), shared by the two entry points below
 static int run_frames(const FrameSet &fs, amk_kd *const *obstacle, amk_kd *const *edge, const double *d_Twc,
                       const amk_frame_camera *cam, amk_mpc *mpc, const amk_step_params *prm, const double *d_state_quad,
-                      const double *d_pos_x, double *d_ref_path, double *d_u, double *d_x0array, int *d_flags, hipStream_t stream) {
+                      const double *d_pos_x, double *d_ref_path, double *d_u, double *d_x0array, int *d_flags, hipStream_t stream,
+                      const MapTrees *map_trees = nullptr) {
     const int N = mpc->N, K = mpc->K, F = fs.n;
     if (int st = ensure_step_workspace(mpc); st != AMK_OK) return st;
     const int Sall = mpc->S;
@@ -407,6 +272,8 @@ static int run_frames(const FrameSet &fs, amk_kd *const *obstacle, amk_kd *const
     // a keyframe map beyond 4 candidates per lane takes the wide merge: 61 VGPRs (it runs beside the solves' waves; the 16-wide
     // instantiation cannot), and with the loops bounded by the frames a scene actually holds its re-reads are few
     const bool wide = F * K > 64 * kMaxCandPerLane || (fs.fmap && need_cpl > 4) || (g_force_wide && !any_exact);
+    // a keyframe map in AMK_TIES_NANOFLANN: every (max_frame_count, K) of the default map step, by the wide merge or four candidates per lane
+    auto map_merge_kernel = wide ? step_merge_plan_pack_map_kernel<kMaxCandPerLaneMap> : step_merge_plan_pack_map_kernel<4>;
     auto merge_kernel = step_merge_plan_pack_kernel<false, kMaxCandPerLane>;
     if (wide) merge_kernel = step_merge_plan_pack_kernel<false, kMaxCandPerLaneMap>;
     else if (any_exact) merge_kernel = step_merge_plan_pack_kernel<true>;
@@ -427,6 +294,13 @@ static int run_frames(const FrameSet &fs, amk_kd *const *obstacle, amk_kd *const
         if (any_exact)
             hipLaunchKernelGGL(step_knn_exact_kernel<const FrameExact *>, dim3((S * (N + 1) + 3) / 4, F), dim3(256), 0, stream,
                                fe_dev, S, d_ref_path, N, K, fb, mpc->done.p);
+        if (map_trees) {
+            hipLaunchKernelGGL(step_knn_exact_map_kernel, dim3((unsigned)search_blocks(S, N + 1 + (fc - 1))), dim3(256), 0, stream, *map_trees,
+                               fs.size_obs[0], fs.size_edge[0], F, S, d_ref_path, N, K, fb, mpc->done.p, fc, d_Twc, c);
+            hipLaunchKernelGGL(map_merge_kernel, dim3(S), dim3(4 * kWave), 0, stream, fs, *map_trees, fb, S, d_Twc, c, N, K, mpc->nref,
+                               iter, prm->mpc_max_iter, prm->speed, mpc->T, prm->safety_distance, d_state_quad, d_pos_x,
+                               d_ref_path, mpc->knn_pts.p, mpc->knn_d2.p, mpc->ref_states.p, mpc->done.p, d_flags);
+        } else
         hipLaunchKernelGGL(merge_kernel, dim3(S), dim3(any_exact ? kWave : 4 * kWave), 0, stream, fs, fe_dev, fb, S, d_Twc, c, N, K, mpc->nref,
                            iter, prm->mpc_max_iter, prm->speed, mpc->T, prm->safety_distance, d_state_quad, d_pos_x,
                            d_ref_path, mpc->knn_pts.p, mpc->knn_d2.p, mpc->ref_states.p, mpc->done.p, d_flags);
@@ -470,7 +344,8 @@ namespace amk {
 // scene d_fmap[f * S + s] (< 0: absent); n_frames = 1 + max_frame_count of the map, <= AMK_MAX_MAP_FRAMES.
 int step_batch_map(amk_kd *obs_pool, amk_kd *edge_pool, int n_frames, const int *d_fmap, const double *d_Twc,
                    const amk_frame_camera *cam, amk_mpc *mpc, const amk_step_params *prm, const double *d_state_quad,
-                   const double *d_pos_x, double *d_ref_path, double *d_u, double *d_x0array, int *d_flags, hipStream_t stream) {
+                   const double *d_pos_x, double *d_ref_path, double *d_u, double *d_x0array, int *d_flags, hipStream_t stream,
+                   bool exact) {
     if (!obs_pool || !edge_pool || !d_fmap || !mpc || !prm || !d_state_quad || !d_pos_x || !d_ref_path || !d_u || !d_flags || n_frames < 1)
         return AMK_ERR_INVALID_ARG;
     if (d_Twc && !cam) return AMK_ERR_INVALID_ARG;
@@ -484,6 +359,15 @@ int step_batch_map(amk_kd *obs_pool, amk_kd *edge_pool, int n_frames, const int 
     fs.edge[0] = grid_ptrs(edge_pool);
     fs.size_obs[0] = obs_pool->size.p;
     fs.size_edge[0] = edge_pool->size.p;
-    return run_frames(fs, nullptr, nullptr, d_Twc, cam, mpc, prm, d_state_quad, d_pos_x, d_ref_path, d_u, d_x0array, d_flags, stream);
+    MapTrees trees{};
+    if (exact) {   // the map is in AMK_TIES_NANOFLANN: amk_kfmap_set_tie_order allocated the trees, every build behind it filled them
+        if (!obs_pool->ex_vind.p || !edge_pool->ex_vind.p) return AMK_ERR_INVALID_ARG;
+        trees.obs_pool = amk_exact_ptrs(obs_pool);
+        trees.edge_pool = amk_exact_ptrs(edge_pool);
+        trees.fmap = d_fmap;
+        trees.S = mpc->S;
+    }
+    return run_frames(fs, nullptr, nullptr, d_Twc, cam, mpc, prm, d_state_quad, d_pos_x, d_ref_path, d_u, d_x0array, d_flags, stream,
+                      exact ? &trees : nullptr);
 }
 }  // namespace amk

@@ -396,6 +396,18 @@ class KfMap:
                                                  out.ctypes.data_as(C.c_void_p), sz.ctypes.data_as(C.c_void_p)), "amk_kfmap_state_host")
         return dict(n_keyframes=nk, n_query_frames=nq, last_outliers=out, frame_sizes=sz)
 
+    def set_tie_order(self, mode):
+        """amk_kfmap_set_tie_order: capi.AMK_TIES_LOWEST_INDEX (default) or capi.AMK_TIES_NANOFLANN, before the map's first frame."""
+        capi.check(self.lib.amk_kfmap_set_tie_order(self.h, int(mode)), "amk_kfmap_set_tie_order")
+
+    def exact_status(self):
+        """amk_kfmap_exact_status_host -> dict(obs [S, F], edge [S, F]) int32: amk_kd_exact_status's codes per query frame,
+        capi.AMK_EXACT_OFF for an absent frame or a map in the default mode (synchronises)"""
+        obs = np.zeros((self.S, self.F), np.int32); edge = np.zeros((self.S, self.F), np.int32)
+        capi.check(self.lib.amk_kfmap_exact_status_host(self.h, obs.ctypes.data_as(C.c_void_p), edge.ctypes.data_as(C.c_void_p)),
+                   "amk_kfmap_exact_status_host")
+        return dict(obs=obs, edge=edge)
+
     def reset(self, first_scene, n_scenes, stream=None):
         capi.check(self.lib.amk_kfmap_reset(self.h, int(first_scene), int(n_scenes), capi.stream_ptr(stream)), "amk_kfmap_reset")
 

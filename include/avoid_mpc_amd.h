@@ -147,7 +147,9 @@ int amk_kd_tie_flags(amk_kd *kd, const double *d_queries, int query_stride, int 
  * multi-frame paths do NOT support it: amk_step_batch_frames with a handle in this mode, amk_kd_keyframe_sweep with either
  * handle in it (the sweep compacts a cloud in place: a lazily built tree would go stale) and a pipeline slot with a keyframe
  * map or keyframe handles whose amk_pipeline_kd handles are in it return AMK_ERR_UNSUPPORTED before launching anything;
- * the keyframe map's own pool handles stay in the default mode.  A handle in scan mode ignores the mode.                  */
+ * the keyframe map has a mode of its own, amk_kfmap_set_tie_order (AMK_TIES_LOWEST_INDEX or AMK_TIES_NANOFLANN for all of its
+ * frames; no AMK_TIES_AUTO: lazily built trees under a sweep that compacts clouds in place would need per-pool-scene tie flags
+ * and staleness rules of their own).  A handle in scan mode ignores the mode.                                              */
 #define AMK_TIES_LOWEST_INDEX 0
 #define AMK_TIES_NANOFLANN 1
 #define AMK_TIES_AUTO 2
@@ -600,6 +602,33 @@ int amk_kfmap_step(amk_kfmap *map, const struct amk_frame_camera *cam, amk_mpc *
 /* Introspection (synchronises): per scene mKeyFrameMap.size(), mVecQueryVector.size(), the outliers of the last sweep and --
  * h_frame_sizes [S][amk_kfmap_frames()] or NULL -- the obstacle-cloud size of every query frame (-1 behind the scene's last). */
 int amk_kfmap_state_host(amk_kfmap *map, int *h_n_keyframes, int *h_n_query_frames, int *h_last_outliers, int *h_frame_sizes);
+/* Tie order of the map (see amk_kd_set_tie_order).  AMK_TIES_LOWEST_INDEX is the default.  AMK_TIES_NANOFLANN: every frame of
+ * every scene -- obstacle and edge cloud, the current frame, the keyframes, keyframes rebuilt from their outliers -- also holds
+ * the reference's own tree, built on the device behind the AddVertex or the sweep that gave the slot its cloud (the host never
+ * learns which), and every search whose result SET can depend on the order of equal distances answers by nanoflann's traversal:
+ *   - the step's N x K-NN and edge 1-NN per frame and the snap's re-query (amk_kfmap_step),
+ *   - DroneBehindPts' SearchForNearest(min(size, 10)) (amk_kfmap_update: which ten decides the pop),
+ *   - amk_kfmap_query_nearest.
+ * Only the per-frame list changes; the rules above it (fast path / merge path, k' = min(k, size), the merge order by distance,
+ * then frame, then position in the frame's list, padding, counts) do not.  GetNearestDistance (the step's and
+ * amk_kfmap_nearest_distance) and the sweep's n x 1-NN read distances only and are unchanged.  A pool scene without a tree
+ * (amk_kfmap_exact_status_host: GAVE_UP, TOO_DEEP; a cloud that kept a non-finite point) keeps the bucketed index's answer for
+ * its searches, as a plain handle does; other frames and scenes are unaffected.
+ * The call is allowed only on a map that has never been given a frame (amk_kfmap_add_vertex, or a pipeline submit; amk_kfmap_reset
+ * does not re-open it): afterwards AMK_ERR_INVALID_ARG -- every tree always belongs to the cloud its slot holds.  Any mode but
+ * the two (AMK_TIES_AUTO included): AMK_ERR_UNSUPPORTED.  A pipeline has no config field for it: set it on
+ * amk_pipeline_kfmap(p, slot) of every slot before the first submit.
+ * Memory: the call allocates all of the mode's device memory (never a later call), amk_kfmap_tie_order_bytes (host arithmetic):
+ *   (max_frame_count + 2) x n_scenes x [ 24 cap(max_points) + 36 cap(max_edge_points) + 80 (nodes(max_points) + nodes(max_edge_points)) + 104 ]
+ * with nodes(p) = cap(p) / 2 + 64 -- 64 B per obstacle point per slot, about 2.5 x amk_kfmap_pool_bytes: the reference's
+ * max_frame_count = 100 at its 3072-point frames (512 edge points) is 38 MB per robot.  It compares the figure with the free memory first and
+ * returns AMK_ERR_UNSUPPORTED (both numbers on stderr) when it does not fit; the map then stays in the default mode.        */
+int amk_kfmap_set_tie_order(amk_kfmap *map, int mode);
+int amk_kfmap_tie_order_bytes(int n_scenes, int max_points, int max_edge_points, int max_frame_count, long long *bytes_out);
+/* amk_kd_exact_status's codes per query frame of every scene (synchronises): h_obs / h_edge [S][amk_kfmap_frames()], either may
+ * be NULL.  AMK_EXACT_OFF: an absent frame, or the map is in the default mode.  A caller that needs the reference's lists checks
+ * for AMK_EXACT_IN_USE on every present frame.                                                                            */
+int amk_kfmap_exact_status_host(amk_kfmap *map, int *h_obs, int *h_edge);
 
 /* The map's own queries: FrameKDMap::QueryNearest, GetNearestDistance and GetPtCloud (FrameKDMap.h:60-67) for any points,
  * outside a control step.  They answer from the map as it stands, change no map state, need no amk_mpc and allocate nothing
@@ -621,7 +650,7 @@ int amk_kfmap_state_host(amk_kfmap *map, int *h_n_keyframes, int *h_n_query_fram
  *   merge path  otherwise: every present frame contributes its k nearest iff it holds MORE than k points (k' = min(k, size),
  *               size <= k: no result); the candidates are ordered by squared distance, equal distances keep the earlier frame,
  *               then the earlier neighbour within a frame; the first k are kept and the count is their number
- *   Within a frame equal distances order by cloud index.  Slots beyond the count hold DBL_MAX, (0, 0, 0) and frame -1.  A query
+ *   Within a frame equal distances order by cloud index (amk_kfmap_set_tie_order(AMK_TIES_NANOFLANN): in nanoflann's order).  Slots beyond the count hold DBL_MAX, (0, 0, 0) and frame -1.  A query
  *   with a NaN or infinite coordinate gets every slot empty (its count is unspecified, as in the step); a scene with no frame
  *   yet gets count 0 everywhere.
  * GetNearestDistance: sqrt of the minimum 1-NN squared distance over the frames whose obstacle cloud holds more than one point;
