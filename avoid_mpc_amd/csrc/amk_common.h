@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <functional>
 #include <vector>
 
 #include "../../include/avoid_mpc_amd.h"
@@ -71,8 +72,10 @@ struct TimedLaunch {  // RAII: records an event before and after the enclosed la
 }  // namespace amk
 
 struct amk_kd;
+struct amk_mpc;
 // kd_index.hip, for kd_sweep.hip: the index-ordered planes made valid on `stream`; the reference-shaped trees of every scene
 int ensure_soa(amk_kd *kd, hipStream_t stream);
+extern "C" int amk__kd_ensure_soa(amk_kd *kd, void *stream);   // ensure_soa for step.hip (internal: not in include/avoid_mpc_amd.h)
 int exact_build(amk_kd *kd, hipStream_t stream);
 namespace amk {
 // kd_index.hip: the frames of a pipeline gang built by one launch (see there)
@@ -100,6 +103,25 @@ long long kd_pool_exact_bytes(long long scenes, int max_points, bool with_planes
 int kd_pool_exact_reserve(amk_kd *pool);
 int kd_pool_exact_build(amk_kd *obs_pool, amk_kd *edge_pool, int n_rows, const int *d_rows, const int *d_gate, hipStream_t stream);
 int kd_pool_exact_status(amk_kd *pool, int *d_status, hipStream_t stream);   // amk_kd_exact_status's codes for every pool scene
+// step_frames.hip, for kfmap.hip: the control step over a keyframe map -- every frame of every scene in the two pool handles, frame f
+// of scene s = pool scene d_fmap[f * S + s] (< 0: absent); n_frames = 1 + max_frame_count of the map, <= AMK_MAX_MAP_FRAMES
+int step_batch_map(amk_kd *obs_pool, amk_kd *edge_pool, int n_frames, const int *d_fmap, const double *d_Twc,
+                   const amk_frame_camera *cam, amk_mpc *mpc, const amk_step_params *prm, const double *d_state_quad,
+                   const double *d_pos_x, double *d_ref_path, double *d_u, double *d_x0array, int *d_flags, hipStream_t stream,
+                   bool exact);
+// map_query.hip, for kfmap.hip: QueryNearest / GetNearestDistance over a pool, and the staging of their *_host variants
+int map_query_nearest(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_Twc, const amk_frame_camera *cam,
+                      const double *d_queries, int query_stride, int n_queries, int k, float *d_pts, double *d_sqdist, int *d_frame,
+                      int *d_counts, hipStream_t stream, bool exact);
+int map_nearest_distance(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_queries, int query_stride,
+                         int n_queries, double *d_dist, hipStream_t stream);
+int map_query_host(int S, const double *h_queries, int query_stride, int n_queries, int k, const double *h_Twc, float *h_pts,
+                   double *h_sqdist, int *h_frame, int *h_counts, double *h_dist,
+                   const std::function<int(const double *, const double *, float *, double *, int *, int *, double *)> &launch);
+// kfmap.hip, for pipeline.hip: AddVertex for the frames of a gang (see there)
+int kfmap_add_vertex_gang(amk_kfmap *m, int n_frames, int frame_scenes, const float *const *d_xyz, const int *const *d_counts,
+                          const float *const *d_edge_xyz, const int *const *d_edge_counts, int point_stride, const double *const *d_Twc,
+                          hipStream_t stream);
 }  // namespace amk
 
 // ------------------------------------------------------------------------------------------------

@@ -23,24 +23,7 @@
 #include "mpc_handle.h"
 
 #include <cstdio>
-#include <functional>
 #include <vector>
-
-namespace amk {
-int step_batch_map(amk_kd *obs_pool, amk_kd *edge_pool, int n_frames, const int *d_fmap, const double *d_Twc,
-                   const amk_frame_camera *cam, amk_mpc *mpc, const amk_step_params *prm, const double *d_state_quad,
-                   const double *d_pos_x, double *d_ref_path, double *d_u, double *d_x0array, int *d_flags, hipStream_t stream,
-                   bool exact);
-// map_query.hip: QueryNearest / GetNearestDistance over a pool, and the staging of their *_host variants
-int map_query_nearest(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_Twc, const amk_frame_camera *cam,
-                      const double *d_queries, int query_stride, int n_queries, int k, float *d_pts, double *d_sqdist, int *d_frame,
-                      int *d_counts, hipStream_t stream, bool exact);
-int map_nearest_distance(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_queries, int query_stride,
-                         int n_queries, double *d_dist, hipStream_t stream);
-int map_query_host(int S, const double *h_queries, int query_stride, int n_queries, int k, const double *h_Twc, float *h_pts,
-                   double *h_sqdist, int *h_frame, int *h_counts, double *h_dist,
-                   const std::function<int(const double *, const double *, float *, double *, int *, int *, double *)> &launch);
-}
 
 struct amk_kfmap {
     int S = 0, P = 0, F = 0;   // scenes, physical slots per scene, frames of the query vector (1 + max_frame_count)

@@ -14,8 +14,6 @@
 // running list is full of near points a frame that holds nothing nearer costs ONE rank (a ballot and a population count).
 #include "step_common.h"
 
-#include <functional>
-
 using namespace amk;
 
 namespace {
@@ -23,11 +21,7 @@ namespace {
 struct QueryFrames {  // kernel argument: the frames of ONE kind of cloud (obstacle or edge)
     GridPtrs g[AMK_MAX_FRAMES];
     const int *size[AMK_MAX_FRAMES];
-    int n;
-    // Map mode (kfmap.hip): every frame of every scene lives in ONE pool handle (g[0] / size[0]); frame f of scene s is pool
-    // scene fmap[f * S + s], or absent (< 0).  n may then exceed AMK_MAX_FRAMES.
-    const int *fmap;
-    int S;
+    FrameMap map;  // a keyframe map: the pool is g[0] / size[0]
 };
 
 __device__ __forceinline__ float wave_shr1_f32(float v) { return __int_as_float(wave_shr1_i32(__float_as_int(v))); }
@@ -74,18 +68,8 @@ __device__ __forceinline__ void map_query_row(const QueryFrames &qf, const Exact
     const size_t row = (size_t)s * n_queries + q;
     const double *qp = queries + row * query_stride;
     const double qx = qp[0], qy = qp[1], qz = qp[2];
-    // frames this scene's map holds: the walk ends at its last present frame (step_merge_plan_pack_kernel's ballot)
-    int F = qf.n;
-    if (MAP) {
-        int hi = 0;
-        for (int f0 = 0; f0 < qf.n; f0 += 64) {
-            const int f = f0 + lane;
-            const unsigned long long b = __ballot(f < qf.n && qf.fmap[(size_t)f * qf.S + s] >= 0);
-            if (b) hi = f0 + 64 - __clzll((long long)b);
-        }
-        F = hi;
-    }
-    auto scene_of = [&](int f) { return MAP ? qf.fmap[(size_t)f * qf.S + s] : s; };
+    const int F = MAP ? qf.map.held(s, lane) : qf.map.n;   // the walk ends at the last frame this scene's map holds
+    auto scene_of = [&](int f) { return MAP ? qf.map.pool_scene(f, s) : s; };
     const GridPtrs pool = qf.g[0];   // (map mode: one set of pool pointers stays live over the loop)
     const int *pool_size = qf.size[0];
 
@@ -199,7 +183,7 @@ int launch_query(const QueryFrames &qf, int S, const double *d_queries, int quer
         AMK_HIP(hipGetLastError());
         return AMK_OK;
     }
-    auto kernel = qf.fmap ? map_query_kernel<true, DIST> : map_query_kernel<false, DIST>;
+    auto kernel = qf.map.fmap ? map_query_kernel<true, DIST> : map_query_kernel<false, DIST>;
     hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, stream, qf, S, d_queries, query_stride, n_queries, k, d_Twc, c,
                        d_pts, d_sqdist, d_frame, d_counts, d_dist);
     AMK_HIP(hipGetLastError());
@@ -217,9 +201,8 @@ int frames_of_handles(amk_kd *const *frames, int n_frames, QueryFrames &qf, int 
     for (int f = 0; f < n_frames; ++f)
         if (!frames[f] || frames[f]->n_scenes != frames[0]->n_scenes) return AMK_ERR_INVALID_ARG;
     qf = QueryFrames{};
-    qf.n = n_frames;
-    qf.fmap = nullptr;
-    qf.S = S = frames[0]->n_scenes;
+    S = frames[0]->n_scenes;
+    qf.map = FrameMap{n_frames, nullptr, S};
     for (int f = 0; f < n_frames; ++f) {
         if (frames[f]->mode != 0 || frames[f]->tie_order != AMK_TIES_LOWEST_INDEX) return AMK_ERR_UNSUPPORTED;
         qf.g[f] = grid_ptrs(frames[f]);
@@ -230,9 +213,7 @@ int frames_of_handles(amk_kd *const *frames, int n_frames, QueryFrames &qf, int 
 
 QueryFrames frames_of_pool(amk_kd *pool, int n_frames, const int *d_fmap, int S) {
     QueryFrames qf{};
-    qf.n = n_frames;
-    qf.fmap = d_fmap;
-    qf.S = S;
+    qf.map = FrameMap{n_frames, d_fmap, S};
     qf.g[0] = grid_ptrs(pool);
     qf.size[0] = pool->size.p;
     return qf;

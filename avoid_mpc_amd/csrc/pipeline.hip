@@ -22,12 +22,6 @@
 #include <cstring>
 #include <vector>
 
-namespace amk {
-int kfmap_add_vertex_gang(amk_kfmap *m, int n_frames, int frame_scenes, const float *const *d_xyz, const int *const *d_counts,
-                          const float *const *d_edge_xyz, const int *const *d_edge_counts, int point_stride, const double *const *d_Twc,
-                          hipStream_t stream);   // kfmap.hip
-}
-
 struct amk_pipeline {
     amk_pipeline_config cfg;
     struct Staged {  // a frame of the open gang

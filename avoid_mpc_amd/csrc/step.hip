@@ -17,8 +17,6 @@
 
 using namespace amk;
 
-extern "C" int amk__kd_ensure_soa(amk_kd *kd, void *stream);  // kd_index.hip
-
 namespace {
 
 __global__ void step_begin_kernel(int S, int *__restrict__ done, int *__restrict__ flags, double *__restrict__ u) {

@@ -39,6 +39,29 @@ __device__ __forceinline__ bool pt_in_frame(const double *__restrict__ T, const 
     return true;
 }
 
+// The frames of a multi-frame map, for every kernel that walks them (step_frames.hip, map_query.hip).  A list of handles (fmap
+// null): frame f of scene s is scene s of handle f, and every frame exists.  A keyframe map (kfmap.hip): every frame of every scene
+// lives in ONE pool handle, frame f of scene s is pool scene fmap[f * S + s], or absent (< 0: this scene's map is shorter) -- an
+// absent frame behaves like an empty cloud, which contributes nothing to any query (FrameKDMap.cpp:298,385-387).  n may then
+// exceed AMK_MAX_FRAMES.
+struct FrameMap {
+    int n;
+    const int *fmap;
+    int S;
+    __device__ __forceinline__ int pool_scene(int f, int s) const { return fmap[(size_t)f * S + s]; }   // (a keyframe map)
+    __device__ __forceinline__ int scene_of(int f, int s) const { return fmap ? pool_scene(f, s) : s; }
+    // A keyframe map: one past the last frame scene s holds (frames before it may be absent), asked by a whole wavefront.
+    __device__ __forceinline__ int held(int s, int lane) const {
+        int hi = 0;
+        for (int f0 = 0; f0 < n; f0 += 64) {
+            const int f = f0 + lane;
+            const unsigned long long b = __ballot(f < n && pool_scene(f, s) >= 0);
+            if (b) hi = f0 + 64 - __clzll((long long)b);
+        }
+        return hi;
+    }
+};
+
 // Where the AMK_TIES_NANOFLANN trees come from: one frame's two trees by value (the single-frame path: no table to upload,
 // its steps stay graph-capturable), or the device table of a frame list (too large for the kernel-argument segment next to
 // FrameSet; frame = blockIdx.y).
@@ -50,12 +73,10 @@ struct FrameExact {
     ExactPtrs obs[AMK_MAX_FRAMES], edge[AMK_MAX_FRAMES];
     int use_obs[AMK_MAX_FRAMES], use_edge[AMK_MAX_FRAMES];
 };
-// ... or the two POOLS of a keyframe map in AMK_TIES_NANOFLANN (kfmap.hip), by value: frame f of scene s is pool scene
-// fmap[f * S + s] of either pool, absent when that is < 0 -- no device table, no host upload.
+// ... or the two POOLS of a keyframe map in AMK_TIES_NANOFLANN (kfmap.hip), by value: no device table, no host upload.  Which pool
+// scene is frame f of scene s says the FrameMap that travels with them.
 struct MapTrees {
     ExactPtrs obs_pool, edge_pool;
-    const int *fmap;
-    int S;
 };
 __device__ __forceinline__ bool exact_used(const ExactPair &t, int, bool edge) { return edge ? t.use_edge : t.use_obs; }
 __device__ __forceinline__ bool exact_used(const FrameExact *t, int f, bool edge) {
@@ -66,10 +87,6 @@ __device__ __forceinline__ ExactTree exact_scene(const ExactPair &t, int, bool e
 }
 __device__ __forceinline__ ExactTree exact_scene(const FrameExact *t, int f, bool edge, int s) {
     return edge ? t->edge[f].scene(s) : t->obs[f].scene(s);
-}
-__device__ __forceinline__ bool map_frame_present(const MapTrees &t, int f, int s) { return t.fmap[(size_t)f * t.S + s] >= 0; }
-__device__ __forceinline__ ExactTree exact_scene(const MapTrees &t, int f, bool edge, int s) {
-    return (edge ? t.edge_pool : t.obs_pool).scene(t.fmap[(size_t)f * t.S + s]);
 }
 // whether row (s, q) of a tree that is used goes through it: every row (step.hip's StepAuto: only the rows that tied)
 template <class Trees>
