@@ -73,11 +73,69 @@ struct TimedLaunch {  // RAII: records an event before and after the enclosed la
 
 struct amk_kd;
 struct amk_mpc;
-// kd_index.hip, for kd_sweep.hip: the index-ordered planes made valid on `stream`; the reference-shaped trees of every scene
+// kd_index.hip, for kd_sweep.hip and kd_exact.hip: the index-ordered planes made valid on `stream`
 int ensure_soa(amk_kd *kd, hipStream_t stream);
 extern "C" int amk__kd_ensure_soa(amk_kd *kd, void *stream);   // ensure_soa for step.hip (internal: not in include/avoid_mpc_amd.h)
+
+// ---- kd_exact.hip: the reference-shaped tree (AMK_TIES_NANOFLANN, AMK_TIES_AUTO, the keyframe map's tie order) -- everything the
+// other translation units call.  The tree's C ABI (amk_kd_set_tie_order, amk_kd_exact_status*, amk__kd_exact_*,
+// amk__exact_set_queue_cap) lives there too.
+// the trees of every scene of a handle in AMK_TIES_NANOFLANN, from its index-ordered planes (made on demand): two launches
 int exact_build(amk_kd *kd, hipStream_t stream);
+// what every index build of a handle ends with: AUTO's per-scene words cleared for the new cloud, exact_build in AMK_TIES_NANOFLANN
+int exact_after_index_build(amk_kd *kd, hipStream_t stream);
+// nanoflann's own traversal over the results of the bucketed search launched before it on `stream`: every row of every scene whose
+// tree is available, or (kd->auto_on()) the rows the search flagged in the scenes whose tree is built.  One launch.
+int exact_search(amk_kd *kd, const double *d_queries, int n_queries, int k, int *d_indices, double *d_sqdist, float *d_pts,
+                 int *d_counts, hipStream_t stream);
 namespace amk {
+// AMK_TIES_AUTO: the lazy build of the trees of up to two handles (null: none) in two launches -- a workgroup returns at once
+// unless its scene's `need` word is raised and its tree is not built yet (see amk_kd::au_state)
+int kd_auto_build(amk_kd *a, amk_kd *b, hipStream_t stream);
+// The keyframe map in AMK_TIES_NANOFLANN (amk_kfmap_set_tie_order): the trees of a pool's scenes.
+// _bytes: what _reserve allocates (host arithmetic); _build: two launches behind a mapped build (both pools, d_gate null) or a
+// sweep (obstacle pool, edge_pool null, d_gate = the sweep's rebuilt flags) -- row i builds pool scene d_rows[i] unless that is < 0
+// or its gate word is 0, decided on the device
+long long kd_pool_exact_bytes(long long scenes, int max_points, bool with_planes);
+int kd_pool_exact_reserve(amk_kd *pool);
+int kd_pool_exact_build(amk_kd *obs_pool, amk_kd *edge_pool, int n_rows, const int *d_rows, const int *d_gate, hipStream_t stream);
+int kd_pool_exact_status(amk_kd *pool, int *d_status, hipStream_t stream);   // amk_kd_exact_status's codes for every pool scene
+
+struct ExactPtrs;   // kd_exact.h
+// The tree's device arrays for the scenes of one handle: all of them or none.  ONE description (kArrays) gives every array's element
+// size and extent; alloc and bytes both read it.
+struct ExactStore {
+    enum Id { VIND, SA, SB, PC, LEFT, RIGHT, FEAT, CHILD, LOW, HIGH, NBBOX, ROOT, NN, kCount };
+    enum Extent { kPerPoint, kPerNode, kPerScene };   // x (scenes * cap), x (scenes * max_nodes), x scenes
+    struct Array { int bytes; Extent per; };
+    static constexpr Array kArrays[kCount] = {
+        {4, kPerPoint}, {4, kPerPoint}, {4, kPerPoint},   // VIND vAcc_ | SA, SB planeSplit's lists of misplaced positions
+        {12, kPerPoint},                                  // PC [3][S][cap] the coordinates in vAcc_ order (leaves are contiguous runs)
+        {4, kPerNode}, {4, kPerNode}, {4, kPerNode}, {4, kPerNode},   // LEFT, RIGHT node range in vAcc_ | FEAT divfeat | CHILD child1
+        {8, kPerNode}, {8, kPerNode}, {48, kPerNode},     // LOW divlow | HIGH divhigh | NBBOX the box divideTree hands down
+        {48, kPerScene}, {4, kPerScene},                  // ROOT root_bbox_ | NN number of nodes, -1: the tree is not available
+    };
+    static long long nodes_for(long long cap) { return cap / 2 + 64; }   // ~0.29 nodes per point with 10-point leaves; more = pathological data
+    static long long array_bytes(Id i, long long scenes, long long cap) {
+        const Extent e = kArrays[i].per;
+        return kArrays[i].bytes * scenes * (e == kPerPoint ? cap : e == kPerNode ? nodes_for(cap) : 1);
+    }
+    static long long bytes(long long scenes, long long cap) {
+        long long b = 0;
+        for (int i = 0; i < kCount; ++i) b += array_bytes((Id)i, scenes, cap);
+        return b;
+    }
+    DevBuf<unsigned char> buf[kCount];
+    int max_nodes = 0;
+    int alloc(int scenes, int cap);   // AMK_OK when they exist already; a failure part way through frees what it got
+    void release() { for (auto &b : buf) b.release(); }
+    bool allocated() const { return buf[VIND].p != nullptr; }
+    template <typename T> T *at(Id i) const { return reinterpret_cast<T *>(buf[i].p); }
+    int *n_nodes() const { return at<int>(NN); }
+    // the batch pointers over the handle's index-ordered planes x / y / z (kd_exact.h)
+    ExactPtrs ptrs(const float *x, const float *y, const float *z, int cap, int scenes) const;
+};
+
 // kd_index.hip: the frames of a pipeline gang built by one launch (see there)
 int kd_build_gang(amk_kd *obstacle, amk_kd *edge, int n_frames, int frame_scenes, const float *const *d_xyz,
                   const int *const *d_counts, const float *const *d_edge_xyz, const int *const *d_edge_counts, int point_stride,
@@ -92,17 +150,6 @@ int kd_build_mapped_gang(amk_kd *obs_pool, amk_kd *edge_pool, int n_frames, int 
                          const int *d_out_scene, hipStream_t stream);
 int kd_sweep_mapped(amk_kd *pool, int n_rows, const int *d_kf_list, const int *d_cur_list, double th_dist, int th_count,
                     int *d_outliers, int *d_rebuilt, hipStream_t stream);
-// kd_index.hip, AMK_TIES_AUTO: the lazy build of the reference-shaped trees of up to two handles (null: none) in two launches --
-// a workgroup returns at once unless its scene's `need` word is raised and its tree is not built yet (see amk_kd::au_state)
-int kd_auto_build(amk_kd *a, amk_kd *b, hipStream_t stream);
-// kd_index.hip, the keyframe map in AMK_TIES_NANOFLANN (amk_kfmap_set_tie_order): the reference-shaped trees of a pool's scenes.
-// _bytes: what _reserve allocates (host arithmetic); _build: two launches behind a mapped build (both pools, d_gate null) or a
-// sweep (obstacle pool, edge_pool null, d_gate = the sweep's rebuilt flags) -- row i builds pool scene d_rows[i] unless that is < 0
-// or its gate word is 0, decided on the device
-long long kd_pool_exact_bytes(long long scenes, int max_points, bool with_planes);
-int kd_pool_exact_reserve(amk_kd *pool);
-int kd_pool_exact_build(amk_kd *obs_pool, amk_kd *edge_pool, int n_rows, const int *d_rows, const int *d_gate, hipStream_t stream);
-int kd_pool_exact_status(amk_kd *pool, int *d_status, hipStream_t stream);   // amk_kd_exact_status's codes for every pool scene
 // step_frames.hip, for kfmap.hip: the control step over a keyframe map -- every frame of every scene in the two pool handles, frame f
 // of scene s = pool scene d_fmap[f * S + s] (< 0: absent); n_frames = 1 + max_frame_count of the map, <= AMK_MAX_MAP_FRAMES
 int step_batch_map(amk_kd *obs_pool, amk_kd *edge_pool, int n_frames, const int *d_fmap, const double *d_Twc,
@@ -125,7 +172,7 @@ int kfmap_add_vertex_gang(amk_kfmap *m, int n_frames, int frame_scenes, const fl
 }  // namespace amk
 
 // ------------------------------------------------------------------------------------------------
-// handle layouts (shared between kd_index.hip, mpc_solve.hip and step.hip)
+// handle layouts (shared between kd_index.hip, kd_exact.hip, mpc_solve.hip and step.hip)
 // ------------------------------------------------------------------------------------------------
 struct amk_kd {
     int n_scenes = 0;
@@ -148,11 +195,7 @@ struct amk_kd {
     int ex_valid = 0;   // host flag: the exact tree was built from the cloud the bucketed index currently holds
     int pool_exact = 0; // host flag, a keyframe map's pool only: the map is in AMK_TIES_NANOFLANN -- every pool scene that holds a frame holds
                         // its tree (kd_pool_exact_build), and the mapped build writes this pool's index-ordered planes too
-    int ex_max_nodes = 0;
-    amk::DevBuf<unsigned> ex_vind, ex_left, ex_right, ex_sa, ex_sb;
-    amk::DevBuf<float> ex_pc;   // [3][S][cap] the coordinates in vAcc_ order (leaves are contiguous runs)
-    amk::DevBuf<int> ex_feat, ex_child, ex_nn;
-    amk::DevBuf<double> ex_low, ex_high, ex_nbbox, ex_root;
+    amk::ExactStore exact;   // the tree's arrays (kd_exact.hip allocates them: the two modes and the keyframe map's pools)
     // AMK_TIES_AUTO: the same tree, built on the device for the scenes where a query tied, by the searches that saw the tie.
     // Every index build clears au_state on its stream, so a tree never answers for a cloud it was not built from.
     int au_active = 0;            // host flag: the last index build ran in AMK_TIES_AUTO and cleared au_state for the cloud held

@@ -401,15 +401,6 @@ __device__ __forceinline__ void grid_build_tiles_scene(int s, const float *__res
     }
 }
 
-static __global__ __launch_bounds__(kGridBuildThreads) void kd_grid_build_kernel(
-    const float *__restrict__ X, const float *__restrict__ Y, const float *__restrict__ Z, int cap,
-    const int *__restrict__ sizes, const float *__restrict__ bbox, float4 *__restrict__ GP,
-    int *__restrict__ cell_start, int ntiles, double *__restrict__ gparams) {
-    const int s = blockIdx.x;
-    grid_build_scene(s, X + (size_t)s * cap, Y + (size_t)s * cap, Z + (size_t)s * cap, cap, sizes[s], bbox, GP, cell_start, ntiles,
-                     gparams);
-}
-
 // ------------------------------------------------------------------------------------------------
 // search: one wavefront per query
 // ------------------------------------------------------------------------------------------------

@@ -12,7 +12,8 @@
 // 16-byte record (x, y, z, cloud index) per point into a bucketed grid (kd_grid.h).  search = one wavefront per
 // (scene, query) walking Chebyshev rings of grid cells with nanoflann's branch-and-bound stop rule.  The streaming scan
 // of index-ordered SoA planes (kd_device.h; the first correct path) is kept as a cross-check (amk__kd_set_mode) and
-// makes its planes on demand.
+// makes its planes on demand.  The opt-in reference-shaped tree beside the index (tie orders AMK_TIES_NANOFLANN / AMK_TIES_AUTO) is
+// kd_exact.hip, the keyframe sweep kd_sweep.hip; what this file calls of the tree is the block "kd_exact.hip" of amk_common.h.
 #include "kd_exact.h"
 
 #include <cstring>
@@ -363,273 +364,6 @@ __global__ __launch_bounds__(256) void kd_tie_flags_kernel(amk::GridPtrs gpt, co
     if (m.lane == 0) out_flags[row] = any;
 }
 
-// ------------------------------------------------------------------------------------------------
-// opt-in nanoflann tie order (kd_exact.h): the reference's own tree beside the bucketed index
-// ------------------------------------------------------------------------------------------------
-// The guard of both builds: nanoflann's divideTree compares coordinates against split planes and is undefined on a NaN or an
-// infinity (the reference's own header ends with a segmentation fault on most clouds that keep such a point; some build and
-// then prune wrongly).  A scene whose bucketed index holds anything in its trash bucket does not start the build: its tree is
-// marked unavailable (amk_kd_exact_status: AMK_EXACT_GAVE_UP), the bucketed index answers.  Decided on the device, from
-// the index the build kernel has just written on the same stream.  Block-uniform.
-__device__ __forceinline__ bool exact_refused(const amk::GridScene &gs, const amk::ExactTree &T) {
-    if (amk::grid_trash_count(gs) == 0) return false;
-    if (threadIdx.x == 0) *T.n_nodes = -1;   // (exact_build_rest then finds nothing to do and leaves it at -1)
-    return true;
-}
-__global__ __launch_bounds__(amk::kExactTopThreads) void kd_exact_build_top_kernel(amk::ExactPtrs ep, amk::GridPtrs gpt,
-                                                                                   const int *__restrict__ sizes) {
-    const int s = blockIdx.x;
-    if (exact_refused(gpt.scene(s), ep.scene(s))) return;
-    amk::exact_build_top(ep.scene(s), sizes[s]);
-}
-__global__ __launch_bounds__(amk::kExactThreads) void kd_exact_build_kernel(amk::ExactPtrs ep, const int *__restrict__ sizes, int qcap) {
-    const int s = blockIdx.x;
-    amk::exact_build_rest(ep.scene(s), sizes[s], qcap);
-}
-// tests only (tests/test_kd_gpu.py): a smaller ring of open nodes, so that the give-up path of exact_build_rest is reachable
-// with a cloud that fits a test (0 = the compiled capacity)
-static int g_exact_queue_cap = amk::kExactQueue;
-extern "C" int amk__exact_set_queue_cap(int cap) {
-    if (cap == 0) cap = amk::kExactQueue;
-    if (cap < 2 || cap > amk::kExactQueue || (cap & (cap - 1))) return AMK_ERR_INVALID_ARG;
-    g_exact_queue_cap = cap;
-    return AMK_OK;
-}
-
-// one WAVEFRONT per (scene, query): nanoflann's own traversal (kd_exact.h: exact_knn_wave).  Overwrites the outputs of the
-// bucketed search (launched before it on the same stream) wherever the tree is available; a scene whose tree is not (node
-// capacity or traversal depth exceeded on pathological data) keeps the bucketed index's answer.
-// AUTO (kd_exact_search_auto_kernel): only the rows the search flagged, in the scenes whose tree is built.
-template <bool AUTO>
-__device__ __forceinline__ void exact_search_row(const amk::ExactPtrs &ep, const int *sizes, int n_scenes, const double *queries,
-    int n_queries, int k, int *out_idx, double *out_d2, float *out_pts, int *out_cnt, const int *rowflag, const int *built) {
-    __shared__ amk::ExactWaveStack stacks[4];
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6)  /* wave-uniform: keeps what derives from it in SGPRs */, lane = threadIdx.x & 63;
-    const size_t row = (size_t)blockIdx.x * 4 + w;
-    if (row >= (size_t)n_scenes * n_queries) return;
-    const int s = (int)(row / n_queries);
-    if constexpr (AUTO)
-        if (!rowflag[row] || !built[s]) return;   // (wave-uniform)
-    const amk::ExactTree T = ep.scene(s);
-    const double *qp = queries + row * 3;
-    const int size = sizes[s];
-    double rd;
-    int ri;
-    const int got = amk::exact_knn_wave(T, qp[0], qp[1], qp[2], k, rd, ri, &stacks[w]);
-    if (got < 0) return;
-    const int cnt = amk::adaptor_count(size, k);
-    amk::store_search_row(out_idx, out_d2, out_pts, out_cnt, row, k, lane, cnt, lane < got, ri, rd,
-                          [&](int c) { return (c == 0 ? T.x : c == 1 ? T.y : T.z)[ri]; });
-}
-__global__ __launch_bounds__(256) void kd_exact_search_kernel(amk::ExactPtrs ep, const int *__restrict__ sizes, int n_scenes,
-    const double *__restrict__ queries, int n_queries, int k, int *__restrict__ out_idx, double *__restrict__ out_d2,
-    float *__restrict__ out_pts, int *__restrict__ out_cnt) {
-    exact_search_row<false>(ep, sizes, n_scenes, queries, n_queries, k, out_idx, out_d2, out_pts, out_cnt, nullptr, nullptr);
-}
-__global__ __launch_bounds__(256) void kd_exact_search_auto_kernel(amk::ExactPtrs ep, const int *__restrict__ sizes, int n_scenes,
-    const double *__restrict__ queries, int n_queries, int k, int *__restrict__ out_idx, double *__restrict__ out_d2,
-    float *__restrict__ out_pts, int *__restrict__ out_cnt, const int *__restrict__ rowflag, const int *__restrict__ built) {
-    exact_search_row<true>(ep, sizes, n_scenes, queries, n_queries, k, out_idx, out_d2, out_pts, out_cnt, rowflag, built);
-}
-
-// builds the reference's tree of every scene from the index-ordered planes (made on demand from the bucket records)
-// All of the tree's arrays or none: ex_vind set means every one of them is (a failure part way through frees what it got, so a later
-// call starts over instead of finding ex_vind and taking the set for complete).
-static int exact_alloc(amk_kd *kd) {
-    const size_t S = kd->n_scenes;
-    if (kd->ex_vind.p) return AMK_OK;
-    kd->ex_max_nodes = kd->cap / 2 + 64;  // ~0.29 nodes per point with 10-point leaves; more = pathological data
-    const size_t pc = S * (size_t)kd->cap, nc = S * (size_t)kd->ex_max_nodes;
-    hipError_t e = kd->ex_vind.alloc(pc);
-    if (e == hipSuccess) e = kd->ex_sa.alloc(pc);
-    if (e == hipSuccess) e = kd->ex_sb.alloc(pc);
-    if (e == hipSuccess) e = kd->ex_pc.alloc(3 * pc);
-    if (e == hipSuccess) e = kd->ex_left.alloc(nc);
-    if (e == hipSuccess) e = kd->ex_right.alloc(nc);
-    if (e == hipSuccess) e = kd->ex_feat.alloc(nc);
-    if (e == hipSuccess) e = kd->ex_child.alloc(nc);
-    if (e == hipSuccess) e = kd->ex_low.alloc(nc);
-    if (e == hipSuccess) e = kd->ex_high.alloc(nc);
-    if (e == hipSuccess) e = kd->ex_nbbox.alloc(nc * 6);
-    if (e == hipSuccess) e = kd->ex_root.alloc(S * 6);
-    if (e == hipSuccess) e = kd->ex_nn.alloc(S);
-    if (e != hipSuccess) {
-        kd->ex_vind.release(); kd->ex_sa.release(); kd->ex_sb.release(); kd->ex_pc.release();
-        kd->ex_left.release(); kd->ex_right.release(); kd->ex_feat.release(); kd->ex_child.release(); kd->ex_low.release();
-        kd->ex_high.release(); kd->ex_nbbox.release(); kd->ex_root.release(); kd->ex_nn.release();
-        return amk::hip_fail(e);
-    }
-    return AMK_OK;
-}
-int exact_build(amk_kd *kd, hipStream_t stream) {
-    int st = exact_alloc(kd);
-    if (st == AMK_OK) st = ensure_soa(kd, stream);
-    if (st != AMK_OK) return st;
-    hipLaunchKernelGGL(kd_exact_build_top_kernel, dim3(kd->n_scenes), dim3(amk::kExactTopThreads), 0, stream, amk_exact_ptrs(kd),
-                       grid_ptrs(kd), kd->size.p);
-    hipLaunchKernelGGL(kd_exact_build_kernel, dim3(kd->n_scenes), dim3(amk::kExactThreads), 0, stream, amk_exact_ptrs(kd),
-                       kd->size.p, g_exact_queue_cap);
-    AMK_HIP(hipGetLastError());
-    kd->ex_valid = 1;
-    return AMK_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// opt-in AMK_TIES_AUTO: the same tree, but only for the scenes where a query tied, and only the tied queries go through it
-// ------------------------------------------------------------------------------------------------
-// The lazy build, for up to two handles per launch (blockIdx.y; the control step passes its obstacle and edge handle).  A
-// workgroup returns at once unless a query of its scene tied (need) and the scene's tree does not belong to the current cloud
-// yet (built); launched unconditionally behind every search, so the host never learns whether anything tied.
-struct AutoBuildArgs {
-    amk::ExactPtrs ep[2];
-    amk::GridPtrs grid[2];
-    const float4 *gp[2];
-    float *x[2], *y[2], *z[2];
-    const int *sizes[2], *need[2];
-    int *built[2];
-};
-// the scene's index-ordered planes from its bucket records (kd_records_to_soa_kernel for one scene: the index build does not
-// write them in this mode, which would be 12 bytes per point stored for nothing on the untied path), then exact_build_top.
-// The scatter is what a tied scene pays over AMK_TIES_NANOFLANN, whose index build writes the planes coalesced: +0.29 ms per
-// 256 x 50 k-point build.  (Measured and not kept: the scatter as a kernel of its own -- 12 blocks per scene in dispatch order
-// 0.15 ms SLOWER, 16 or 64 blocks per scene pinned to the XCD s % 8 0.09 ms faster, which leaves 0.2 ms and costs every lazy
-// build one more launch that returns at once on the untied path: profiles/tie_auto_cost.txt.)
-__global__ __launch_bounds__(amk::kExactTopThreads) void kd_auto_build_top_kernel(const AutoBuildArgs a) {
-    const int s = blockIdx.x, h = blockIdx.y;
-    if (!a.need[h][s] || a.built[h][s]) return;   // (block-uniform)
-    if (exact_refused(a.grid[h].scene(s), a.ep[h].scene(s))) return;   // (kd_auto_build_rest_kernel marks the scene built: GAVE_UP)
-    const int cap = a.ep[h].cap, n = a.sizes[h][s];
-    const size_t base = (size_t)s * cap;
-    const float4 *gp = a.gp[h] + base;
-    float *xs = a.x[h] + base, *ys = a.y[h] + base, *zs = a.z[h] + base;
-    const float qnan = __builtin_nanf("");
-    for (int i = threadIdx.x; i < cap; i += amk::kExactTopThreads) {
-        if (i < n) {
-            const float4 r = gp[i];
-            const int idx = __float_as_int(r.w);   // < n: the padding stores below touch other elements
-            xs[idx] = r.x; ys[idx] = r.y; zs[idx] = r.z;
-        } else {
-            xs[i] = qnan; ys[i] = qnan; zs[i] = qnan;
-        }
-    }
-    __threadfence_block();
-    __syncthreads();   // the planes are read back by the tree build
-    amk::exact_build_top(a.ep[h].scene(s), n);
-}
-// exact_build_rest; the tree now belongs to the cloud held (also a tree that was given up: n_nodes = -1 says so)
-__global__ __launch_bounds__(amk::kExactThreads) void kd_auto_build_rest_kernel(const AutoBuildArgs a, int qcap) {
-    const int s = blockIdx.x, h = blockIdx.y;
-    if (!a.need[h][s] || a.built[h][s]) return;   // (block-uniform)
-    amk::exact_build_rest(a.ep[h].scene(s), a.sizes[h][s], qcap);
-    if (threadIdx.x == 0) a.built[h][s] = 1;
-}
-
-// The mode's device memory: everything AMK_TIES_NANOFLANN holds plus the three words per scene and the row flags.  Called by
-// amk_kd_set_tie_order(AUTO) -- never by a search or a step.
-static int auto_alloc(amk_kd *kd) {
-    const size_t S = kd->n_scenes;
-    int st = exact_alloc(kd);
-    if (st == AMK_OK) st = amk::pool_planes(kd);
-    if (st != AMK_OK) return st;
-    if (!kd->au_rowflag.p) {
-        AMK_HIP(kd->au_rowflag.alloc(S * AMK_MAX_QUERIES));
-        AMK_HIP(hipMemset(kd->au_rowflag.p, 0, sizeof(int) * S * AMK_MAX_QUERIES));
-    }
-    if (!kd->au_state.p) {
-        AMK_HIP(kd->au_state.alloc(3 * S));
-        AMK_HIP(hipMemset(kd->au_state.p, 0, sizeof(int) * 3 * S));
-    }
-    return AMK_OK;
-}
-// Called by EVERY index build of a handle, behind its launch: whatever trees the handle holds describe the previous cloud.
-static int auto_reset(amk_kd *kd, hipStream_t stream) {
-    kd->au_active = 0;
-    if (kd->tie_order != AMK_TIES_AUTO) return AMK_OK;
-    if (!kd->au_state.p) return AMK_ERR_INVALID_ARG;   // (amk_kd_set_tie_order allocated it)
-    AMK_HIP(hipMemsetAsync(kd->au_state.p, 0, sizeof(int) * 3 * (size_t)kd->n_scenes, stream));
-    kd->au_active = 1;
-    return AMK_OK;
-}
-static void auto_build_entry(AutoBuildArgs &a, int h, amk_kd *kd) {
-    a.ep[h] = amk_exact_ptrs(kd);
-    a.grid[h] = grid_ptrs(kd);
-    a.gp[h] = kd->gpt.p;
-    a.x[h] = kd->x.p; a.y[h] = kd->y.p; a.z[h] = kd->z.p;
-    a.sizes[h] = kd->size.p; a.need[h] = kd->au_need();
-    a.built[h] = kd->au_built();
-}
-int amk::kd_auto_build(amk_kd *a, amk_kd *b, hipStream_t stream) {
-    if (!a) { a = b; b = nullptr; }
-    if (!a) return AMK_OK;
-    if (b && b->n_scenes != a->n_scenes) return AMK_ERR_INVALID_ARG;
-    AutoBuildArgs args{};
-    auto_build_entry(args, 0, a);
-    if (b) auto_build_entry(args, 1, b);
-    const dim3 grid(a->n_scenes, b ? 2 : 1);
-    hipLaunchKernelGGL(kd_auto_build_top_kernel, grid, dim3(amk::kExactTopThreads), 0, stream, args);
-    hipLaunchKernelGGL(kd_auto_build_rest_kernel, grid, dim3(amk::kExactThreads), 0, stream, args, g_exact_queue_cap);
-    AMK_HIP(hipGetLastError());
-    return AMK_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// the keyframe map's pools in AMK_TIES_NANOFLANN (amk_kfmap_set_tie_order): a tree per POOL scene, built where a row names one
-// ------------------------------------------------------------------------------------------------
-// The gated build for the rows of a mapped build or of a sweep, for the obstacle pool and (blockIdx.y = 1) the edge pool: row i
-// names pool scene rows[i] (< 0: the row got no frame / swept nothing) and, behind a sweep, counts only when gate[i] is set (the
-// sweep rebuilt that keyframe: its planes now hold the outliers in cloud order, InitializeNew(newCloud), FrameKDMap.cpp:480-485).
-// Launched unconditionally behind every mapped build and every sweep of a map in the mode: the host never learns which rows built.
-struct PoolExactArgs {
-    amk::ExactPtrs ep[2];
-    amk::GridPtrs grid[2];
-    const int *sizes[2];
-    const int *rows, *gate;
-};
-__global__ __launch_bounds__(amk::kExactTopThreads) void kd_pool_exact_build_top_kernel(const PoolExactArgs a) {
-    const int m = a.rows[blockIdx.x], h = blockIdx.y;
-    if (m < 0 || (a.gate && !a.gate[blockIdx.x])) return;   // (block-uniform)
-    if (exact_refused(a.grid[h].scene(m), a.ep[h].scene(m))) return;
-    amk::exact_build_top(a.ep[h].scene(m), a.sizes[h][m]);
-}
-__global__ __launch_bounds__(amk::kExactThreads) void kd_pool_exact_build_rest_kernel(const PoolExactArgs a, int qcap) {
-    const int m = a.rows[blockIdx.x], h = blockIdx.y;
-    if (m < 0 || (a.gate && !a.gate[blockIdx.x])) return;   // (block-uniform)
-    amk::exact_build_rest(a.ep[h].scene(m), a.sizes[h][m], qcap);
-}
-namespace amk {
-// what kd_pool_exact_reserve allocates for a pool of `scenes` scenes of max_points points (host arithmetic: exact_alloc's arrays,
-// and the index-ordered planes where the pool has none yet -- the edge pool)
-long long kd_pool_exact_bytes(long long scenes, int max_points, bool with_planes) {
-    const long long cap = (long long)amk::round_up(max_points, 256) + 1024, mn = cap / 2 + 64;
-    return scenes * (4 * 3 * cap + 12 * cap + 4 * 4 * mn + 8 * 2 * mn + 8 * 6 * mn + 8 * 6 + 4 + (with_planes ? 12 * cap : 0));
-}
-// the trees' arrays of every pool scene (and the pool's planes), no scene has a tree yet
-int kd_pool_exact_reserve(amk_kd *pool) {
-    if (!pool) return AMK_ERR_INVALID_ARG;
-    int st = exact_alloc(pool);
-    if (st == AMK_OK) st = pool_planes(pool);
-    if (st != AMK_OK) return st;
-    AMK_HIP(hipMemset(pool->ex_nn.p, 0, sizeof(int) * (size_t)pool->n_scenes));
-    return AMK_OK;
-}
-int kd_pool_exact_build(amk_kd *obs_pool, amk_kd *edge_pool, int n_rows, const int *d_rows, const int *d_gate, hipStream_t stream) {
-    if (!obs_pool || !obs_pool->ex_vind.p || (edge_pool && !edge_pool->ex_vind.p) || n_rows < 1 || !d_rows) return AMK_ERR_INVALID_ARG;
-    PoolExactArgs a{};
-    amk_kd *pools[2] = {obs_pool, edge_pool};
-    for (int h = 0; h < (edge_pool ? 2 : 1); ++h) {
-        a.ep[h] = amk_exact_ptrs(pools[h]);
-        a.grid[h] = grid_ptrs(pools[h]);
-        a.sizes[h] = pools[h]->size.p;
-    }
-    a.rows = d_rows; a.gate = d_gate;
-    const dim3 grid(n_rows, edge_pool ? 2 : 1);
-    hipLaunchKernelGGL(kd_pool_exact_build_top_kernel, grid, dim3(amk::kExactTopThreads), 0, stream, a);
-    hipLaunchKernelGGL(kd_pool_exact_build_rest_kernel, grid, dim3(amk::kExactThreads), 0, stream, a, g_exact_queue_cap);
-    AMK_HIP(hipGetLastError());
-    return AMK_OK;
-}
-}  // namespace amk
-
 extern "C" int amk_kd_points_host(amk_kd *kd, float *h_xyz, int *h_sizes) {
     if (!kd || !h_xyz || !h_sizes) return AMK_ERR_INVALID_ARG;
     AMK_HIP(hipDeviceSynchronize());
@@ -737,9 +471,7 @@ int amk_kd_build(amk_kd *kd, const float *d_xyz, int point_stride, long long sce
         kd->async_pending = 1;
     }
     AMK_HIP(hipGetLastError());
-    if (const int st = auto_reset(kd, (hipStream_t)stream); st != AMK_OK) return st;
-    if (kd->tie_order == AMK_TIES_NANOFLANN) return exact_build(kd, (hipStream_t)stream);
-    return AMK_OK;
+    return exact_after_index_build(kd, (hipStream_t)stream);
 }
 
 int amk_kd_build_pair(amk_kd *obstacle, const float *d_xyz, const int *d_counts, amk_kd *edge, const float *d_edge_xyz,
@@ -784,128 +516,12 @@ int kd_build_gang(amk_kd *obstacle, amk_kd *edge, int n_frames, int frame_scenes
         }
     }
     AMK_HIP(hipGetLastError());
-    for (amk_kd *kd : {obstacle, edge}) {
-        if (const int st = auto_reset(kd, stream); st != AMK_OK) return st;
-        if (kd->tie_order == AMK_TIES_NANOFLANN) {
-            const int st = exact_build(kd, stream);
-            if (st != AMK_OK) return st;
-        }
-    }
+    for (amk_kd *kd : {obstacle, edge})
+        if (const int st = exact_after_index_build(kd, stream); st != AMK_OK) return st;
     return AMK_OK;
 }
 }  // namespace amk
 extern "C" {
-
-// internal (tests): number of nodes of every scene's reference-shaped tree (-1: not available), after synchronising
-// A handle in AMK_TIES_AUTO: 0 for a scene whose tree has not been built for the current cloud (no tree, no nodes).
-int amk__kd_exact_nodes(amk_kd *kd, int *h_nodes) {
-    if (!kd || !h_nodes || !kd->ex_nn.p) return AMK_ERR_INVALID_ARG;
-    AMK_HIP(hipDeviceSynchronize());
-    AMK_HIP(hipMemcpy(h_nodes, kd->ex_nn.p, sizeof(int) * kd->n_scenes, hipMemcpyDeviceToHost));
-    if (kd->tie_order == AMK_TIES_AUTO) {
-        std::vector<int> built((size_t)kd->n_scenes, 0);
-        if (kd->au_active) AMK_HIP(hipMemcpy(built.data(), kd->au_built(), sizeof(int) * kd->n_scenes, hipMemcpyDeviceToHost));
-        for (int s = 0; s < kd->n_scenes; ++s)
-            if (!built[s]) h_nodes[s] = 0;
-    }
-    return AMK_OK;
-}
-
-#ifdef AMK_EXACT_TRACE
-// diagnostics build only (tools/experiments/exact_phase_clocks.py): the first n words of the scene-0 list buffer, where the
-// lower-level build kernel leaves its per-wavefront phase clocks
-int amk__kd_exact_trace(amk_kd *kd, unsigned *h, int n) {
-    if (!kd || !h || !kd->ex_sa.p) return AMK_ERR_INVALID_ARG;
-    AMK_HIP(hipDeviceSynchronize());
-    AMK_HIP(hipMemcpy(h, kd->ex_sa.p, sizeof(unsigned) * n, hipMemcpyDeviceToHost));
-    return AMK_OK;
-}
-#endif
-
-// depth of every scene's reference-shaped tree: children are created after their parent (ids grow downwards), so one pass in
-// id order carries the depths; one lane per scene, the build's list scratch (sa) holds depth[node] -- a diagnostic call.
-// built (a handle in AMK_TIES_AUTO) or null: a scene without a tree for the current cloud has not needed one.
-static __device__ __forceinline__ void exact_status_scene(int S, const int *__restrict__ built, const int *__restrict__ n_nodes,
-    const int *__restrict__ feat, const int *__restrict__ child, unsigned *__restrict__ scratch, int max_nodes, int cap,
-    int *__restrict__ status) {
-    const int s = blockIdx.x * 64 + threadIdx.x;
-    if (s >= S) return;
-    if (built && !built[s]) { status[s] = AMK_EXACT_NOT_NEEDED; return; }
-    const int nn = n_nodes[s];
-    if (nn < 0) { status[s] = AMK_EXACT_GAVE_UP; return; }
-    const int *f = feat + (size_t)s * max_nodes, *c = child + (size_t)s * max_nodes;
-    unsigned *d = scratch + (size_t)s * cap;
-    unsigned deepest = 0;
-    if (nn > 0) d[0] = 0;
-    for (int id = 0; id < nn; ++id) {
-        const unsigned dep = d[id];
-        if (f[id] >= 0) { d[c[id]] = dep + 1; d[c[id] + 1] = dep + 1; }   // an internal node: the traversal pushes one frame here
-        else deepest = dep > deepest ? dep : deepest;                      // a leaf at depth dep is reached with dep frames on the stack
-    }
-    status[s] = deepest > (unsigned)amk::kExactMaxDepth ? AMK_EXACT_TOO_DEEP : AMK_EXACT_IN_USE;
-}
-static __global__ __launch_bounds__(64) void kd_exact_status_kernel(int S, const int *__restrict__ n_nodes,
-    const int *__restrict__ feat, const int *__restrict__ child, unsigned *__restrict__ scratch, int max_nodes, int cap,
-    int *__restrict__ status) {
-    exact_status_scene(S, nullptr, n_nodes, feat, child, scratch, max_nodes, cap, status);
-}
-static __global__ __launch_bounds__(64) void kd_auto_status_kernel(int S, const int *__restrict__ built,
-    const int *__restrict__ n_nodes, const int *__restrict__ feat, const int *__restrict__ child, unsigned *__restrict__ scratch,
-    int max_nodes, int cap, int *__restrict__ status) {
-    exact_status_scene(S, built, n_nodes, feat, child, scratch, max_nodes, cap, status);
-}
-
-// Which index answers a handle's searches, per scene (header).  Stream-ordered.
-int amk_kd_exact_status(amk_kd *kd, int *d_status, void *stream) {
-    if (!kd || !d_status) return AMK_ERR_INVALID_ARG;
-    if (kd->tie_order == AMK_TIES_AUTO && kd->au_active) {
-        hipLaunchKernelGGL(kd_auto_status_kernel, dim3((kd->n_scenes + 63) / 64), dim3(64), 0, (hipStream_t)stream, kd->n_scenes,
-                           kd->au_built(), kd->ex_nn.p, kd->ex_feat.p, kd->ex_child.p, kd->ex_sa.p, kd->ex_max_nodes, kd->cap, d_status);
-        AMK_HIP(hipGetLastError());
-        return AMK_OK;
-    }
-    if (kd->tie_order != AMK_TIES_NANOFLANN || !kd->ex_valid || !kd->ex_nn.p) {   // the bucketed index answers everything: not a fallback
-        AMK_HIP(hipMemsetAsync(d_status, 0xff, sizeof(int) * kd->n_scenes, (hipStream_t)stream));   // AMK_EXACT_OFF == -1
-        return AMK_OK;
-    }
-    hipLaunchKernelGGL(kd_exact_status_kernel, dim3((kd->n_scenes + 63) / 64), dim3(64), 0, (hipStream_t)stream, kd->n_scenes,
-                       kd->ex_nn.p, kd->ex_feat.p, kd->ex_child.p, kd->ex_sa.p, kd->ex_max_nodes, kd->cap, d_status);
-    AMK_HIP(hipGetLastError());
-    return AMK_OK;
-}
-
-}  // extern "C"
-int amk::kd_pool_exact_status(amk_kd *pool, int *d_status, hipStream_t stream) {
-    if (!pool || !d_status || !pool->ex_nn.p) return AMK_ERR_INVALID_ARG;
-    hipLaunchKernelGGL(kd_exact_status_kernel, dim3((pool->n_scenes + 63) / 64), dim3(64), 0, stream, pool->n_scenes, pool->ex_nn.p,
-                       pool->ex_feat.p, pool->ex_child.p, pool->ex_sa.p, pool->ex_max_nodes, pool->cap, d_status);
-    AMK_HIP(hipGetLastError());
-    return AMK_OK;
-}
-extern "C" {
-
-int amk_kd_exact_status_host(amk_kd *kd, int *h_status) {   // synchronises
-    if (!kd || !h_status) return AMK_ERR_INVALID_ARG;
-    amk::DevBuf<int> d;
-    AMK_HIP(d.alloc(kd->n_scenes));
-    const int st = amk_kd_exact_status(kd, d.p, nullptr);
-    if (st != AMK_OK) return st;
-    AMK_HIP(hipDeviceSynchronize());
-    AMK_HIP(hipMemcpy(h_status, d.p, sizeof(int) * kd->n_scenes, hipMemcpyDeviceToHost));
-    return AMK_OK;
-}
-
-int amk_kd_set_tie_order(amk_kd *kd, int mode) {
-    if (!kd) return AMK_ERR_INVALID_ARG;
-    if (mode != AMK_TIES_LOWEST_INDEX && mode != AMK_TIES_NANOFLANN && mode != AMK_TIES_AUTO) return AMK_ERR_UNSUPPORTED;
-    if (mode == AMK_TIES_AUTO) {   // the mode's memory, here and not on the search path (a failure leaves the handle as it was)
-        const int st = auto_alloc(kd);
-        if (st != AMK_OK) return st;
-    }
-    kd->tie_order = mode;
-    return AMK_OK;
-}
-
 int amk_kd_sizes(amk_kd *kd, int *h_sizes, void *stream) {
     if (!kd || !h_sizes) return AMK_ERR_INVALID_ARG;
     AMK_HIP(hipMemcpyAsync(h_sizes, kd->size.p, sizeof(int) * kd->n_scenes, hipMemcpyDeviceToHost, (hipStream_t)stream));
@@ -924,24 +540,14 @@ int amk_kd_search(amk_kd *kd, const double *d_queries, int n_queries, int k, int
                            kd->n_scenes, d_queries, n_queries, k, d_indices, d_sqdist, d_pts, d_counts, kd->au_rowflag.p, kd->au_need());
         AMK_HIP(hipGetLastError());
         if (const int st = amk::kd_auto_build(kd, nullptr, (hipStream_t)stream); st != AMK_OK) return st;
-        const size_t rows = (size_t)kd->n_scenes * n_queries;
-        hipLaunchKernelGGL(kd_exact_search_auto_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                           amk_exact_ptrs(kd), kd->size.p, kd->n_scenes, d_queries, n_queries, k, d_indices, d_sqdist, d_pts, d_counts,
-                           kd->au_rowflag.p, kd->au_built());
-        AMK_HIP(hipGetLastError());
-        return AMK_OK;
+        return exact_search(kd, d_queries, n_queries, k, d_indices, d_sqdist, d_pts, d_counts, (hipStream_t)stream);
     }
     if (kd->mode == 0) {
         hipLaunchKernelGGL(kd_grid_search_kernel, dim3((unsigned)amk::search_blocks(kd->n_scenes, n_queries)), dim3(256), 0, (hipStream_t)stream, grid_ptrs(kd), kd->size.p,
                            kd->n_scenes, d_queries, n_queries, k, d_indices, d_sqdist, d_pts, d_counts);
         AMK_HIP(hipGetLastError());
-        if (kd->tie_order == AMK_TIES_NANOFLANN && kd->ex_valid) {  // nanoflann's own traversal where its tree is available (and current)
-            const size_t rows = (size_t)kd->n_scenes * n_queries;
-            hipLaunchKernelGGL(kd_exact_search_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
-                               amk_exact_ptrs(kd), kd->size.p, kd->n_scenes, d_queries, n_queries, k, d_indices, d_sqdist, d_pts,
-                               d_counts);
-            AMK_HIP(hipGetLastError());
-        }
+        if (kd->tie_order == AMK_TIES_NANOFLANN && kd->ex_valid)   // nanoflann's own traversal where its tree is available (and current)
+            return exact_search(kd, d_queries, n_queries, k, d_indices, d_sqdist, d_pts, d_counts, (hipStream_t)stream);
         return AMK_OK;
     }
     {   // the streaming scan reads the index-ordered planes

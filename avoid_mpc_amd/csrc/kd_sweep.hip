@@ -172,6 +172,25 @@ __global__ __launch_bounds__(kCompactThreads) void kd_sweep_compact_kernel(
     }
 }
 
+// the bucketed index of a compacted keyframe from its planes: every scene of a handle, or (the pool) the scenes the sweep rebuilt
+__global__ __launch_bounds__(amk::kGridBuildThreads) void kd_grid_build_kernel(
+    const float *__restrict__ X, const float *__restrict__ Y, const float *__restrict__ Z, int cap,
+    const int *__restrict__ sizes, const float *__restrict__ bbox, float4 *__restrict__ GP,
+    int *__restrict__ cell_start, int ntiles, double *__restrict__ gparams) {
+    const int s = blockIdx.x;
+    amk::grid_build_scene(s, X + (size_t)s * cap, Y + (size_t)s * cap, Z + (size_t)s * cap, cap, sizes[s], bbox, GP, cell_start, ntiles,
+                          gparams);
+}
+__global__ __launch_bounds__(amk::kGridBuildThreads) void kd_grid_build_list_kernel(
+    const float *__restrict__ X, const float *__restrict__ Y, const float *__restrict__ Z, int cap,
+    const int *__restrict__ sizes, const float *__restrict__ bbox, float4 *__restrict__ GP, int *__restrict__ cell_start,
+    int ntiles, double *__restrict__ gparams, const int *__restrict__ list, const int *__restrict__ rebuilt) {
+    const int s = list[blockIdx.x];
+    if (s < 0 || !rebuilt[blockIdx.x]) return;   // (block-uniform)
+    amk::grid_build_scene(s, X + (size_t)s * cap, Y + (size_t)s * cap, Z + (size_t)s * cap, cap, sizes[s], bbox, GP, cell_start,
+                          ntiles, gparams);
+}
+
 extern "C" int amk_kd_keyframe_sweep(amk_kd *keyframe, amk_kd *current, double th_dist, int th_count, int *d_outliers,
                                      int *d_rebuilt, void *stream_) {
     if (!keyframe || !current || keyframe == current || keyframe->n_scenes != current->n_scenes) return AMK_ERR_INVALID_ARG;
@@ -196,7 +215,7 @@ extern "C" int amk_kd_keyframe_sweep(amk_kd *keyframe, amk_kd *current, double t
                        keyframe->z.p, keyframe->cap, keyframe->size.p, keyframe->pmax.p, keyframe->bbox.p, keyframe->flags.p,
                        th_count, keyframe->sweep_cnt.p, d_outliers, d_rebuilt);
     // the bucketed index of every scene is rebuilt (a no-op in effect for the untouched ones)
-    hipLaunchKernelGGL(amk::kd_grid_build_kernel, dim3(S), dim3(amk::kGridBuildThreads), 0, stream, keyframe->x.p,
+    hipLaunchKernelGGL(kd_grid_build_kernel, dim3(S), dim3(amk::kGridBuildThreads), 0, stream, keyframe->x.p,
                        keyframe->y.p, keyframe->z.p, keyframe->cap, keyframe->size.p, keyframe->bbox.p, keyframe->gpt.p,
                        keyframe->cell_start.p, keyframe->ntiles, keyframe->gparams.p);
     keyframe->async_pending = 1;
@@ -209,16 +228,6 @@ extern "C" int amk_kd_keyframe_sweep(amk_kd *keyframe, amk_kd *current, double t
 // ------------------------------------------------------------------------------------------------
 // the keyframe map's pool (kfmap.hip): one handle holds P physical frames x S scenes, scene index = slot * S + s
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(amk::kGridBuildThreads) void kd_grid_build_list_kernel(
-    const float *__restrict__ X, const float *__restrict__ Y, const float *__restrict__ Z, int cap,
-    const int *__restrict__ sizes, const float *__restrict__ bbox, float4 *__restrict__ GP, int *__restrict__ cell_start,
-    int ntiles, double *__restrict__ gparams, const int *__restrict__ list, const int *__restrict__ rebuilt) {
-    const int s = list[blockIdx.x];
-    if (s < 0 || !rebuilt[blockIdx.x]) return;   // (block-uniform)
-    amk::grid_build_scene(s, X + (size_t)s * cap, Y + (size_t)s * cap, Z + (size_t)s * cap, cap, sizes[s], bbox, GP, cell_start,
-                          ntiles, gparams);
-}
-
 // ------------------------------------------------------------------------------------------------
 // The pool's sweep target as a FINE HASHED GRID.  The frames' own indices have cells of ~1 m at 50 k points (<= 1024 cells: what the
 // K-NN searches want), the sweep asks "any point within th = 0.1 m?": a query read 70 (inlier) to 1200 (outlier) candidates of the

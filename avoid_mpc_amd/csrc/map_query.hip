@@ -231,7 +231,7 @@ int map_query_nearest(amk_kd *pool, int n_frames, const int *d_fmap, int S, cons
     if (k > AMK_MAX_K) return AMK_ERR_UNSUPPORTED;
     ExactPtrs ex;
     if (exact) {
-        if (!pool->ex_vind.p) return AMK_ERR_INVALID_ARG;   // (amk_kfmap_set_tie_order allocated the trees)
+        if (!pool->exact.allocated()) return AMK_ERR_INVALID_ARG;   // (amk_kfmap_set_tie_order allocated the trees)
         ex = amk_exact_ptrs(pool);
     }
     return launch_query<false>(frames_of_pool(pool, n_frames, d_fmap, S), S, d_queries, query_stride, n_queries, k, d_Twc, cam, d_pts,

@@ -551,7 +551,7 @@ int step_batch_map(amk_kd *obs_pool, amk_kd *edge_pool, int n_frames, const int 
     fs.size_edge[0] = edge_pool->size.p;
     MapTrees trees{};
     if (exact) {   // the map is in AMK_TIES_NANOFLANN: amk_kfmap_set_tie_order allocated the trees, every build behind it filled them
-        if (!obs_pool->ex_vind.p || !edge_pool->ex_vind.p) return AMK_ERR_INVALID_ARG;
+        if (!obs_pool->exact.allocated() || !edge_pool->exact.allocated()) return AMK_ERR_INVALID_ARG;
         trees.obs_pool = amk_exact_ptrs(obs_pool);
         trees.edge_pool = amk_exact_ptrs(edge_pool);
     }

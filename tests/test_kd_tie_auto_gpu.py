@@ -294,3 +294,62 @@ def test_auto_refusals(torch_cuda):
     assert kd.search(q, K)["indices"].shape == (2, 4, K)
     torch.cuda.synchronize()
     kd.close(); other.close()
+
+
+GATE_SIZES = (0, 11, 4097, 4200)   # empty / just above the 10-point leaf / just above kExactBigNode (4096): the build's path changes
+
+
+def _gate_batch():
+    """Four scenes of GATE_SIZES points: distinct points of a 0.25 m lattice (coordinates exact in float32, so equal distances are
+    exact ties), drawn from the smallest cube that holds them; 16 queries per scene at its own points (the empty scene: at the
+    origin's corner of the lattice)."""
+    rng = np.random.default_rng(34)
+    cap, Q = max(GATE_SIZES), 16
+    cl, qs = np.zeros((len(GATE_SIZES), cap, 3), np.float32), np.zeros((len(GATE_SIZES), Q, 3), np.float64)
+    for s, n in enumerate(GATE_SIZES):
+        if n == 0:
+            continue
+        L = int(np.ceil(n ** (1 / 3)))
+        L += L ** 3 < n
+        ijk = np.stack(np.unravel_index(rng.permutation(L ** 3)[:n], (L, L, L)), axis=1)
+        cl[s, :n] = ijk * 0.25
+        qs[s] = cl[s, rng.integers(0, n, Q)]
+    return cl, np.array(GATE_SIZES, np.int32), qs
+
+
+def test_one_build_pair_template_serves_both_modes(torch_cuda):
+    """The build kernels are one pair template whose gate decides which workgroups build (csrc/kd_exact.hip): every scene for a
+    handle in AMK_TIES_NANOFLANN, the scenes with a tied query for one in AMK_TIES_AUTO.  GATE_SIZES in one batch, every non-empty
+    scene on a lattice: before a search no AUTO scene holds a tree; after it every scene with a flagged query (amk_kd_tie_flags --
+    asserted to be all the non-empty ones) holds the NANOFLANN handle's node count and returns its k = 5 index lists, a scene
+    without one (the empty scene) still reports no tree; a second search finds the trees built and answers the same."""
+    torch = torch_cuda
+    from avoid_mpc_amd import capi
+    from avoid_mpc_amd.host import KdBatch, kd_tie_flags
+    cl, counts, qs = _gate_batch()
+    k = 5
+    d_cl, d_counts, d_qs = torch.from_numpy(cl).cuda(), torch.from_numpy(counts).cuda(), torch.from_numpy(qs).cuda()
+    kds = {}
+    for mode in (capi.AMK_TIES_NANOFLANN, capi.AMK_TIES_AUTO):
+        kds[mode] = KdBatch(*cl.shape[:2])
+        kds[mode].set_tie_order(mode)
+        kds[mode].build(d_cl, d_counts)
+    kd1, kd2 = kds[capi.AMK_TIES_NANOFLANN], kds[capi.AMK_TIES_AUTO]
+    assert (_nodes(kd2) == NO_TREE).all()
+    tied = kd_tie_flags(kd2, d_qs, k).cpu().numpy().any(axis=1)
+    assert tied.tolist() == [n > 0 for n in GATE_SIZES], tied
+    r1, r2 = _search(torch, kd1, qs, k), _search(torch, kd2, qs, k)
+    nn1, nn2 = _nodes(kd1), _nodes(kd2)
+    print("nodes NANOFLANN", nn1.tolist(), "AUTO", nn2.tolist())
+    assert nn1[0] == 0 and (nn1[1:] > 1).all(), nn1
+    for s in range(len(GATE_SIZES)):
+        if tied[s]:
+            assert nn2[s] == nn1[s], (s, nn2, nn1)
+            assert np.array_equal(r2["indices"][s], r1["indices"][s]), s
+        else:
+            assert nn2[s] == NO_TREE, (s, nn2)
+    assert np.array_equal(r2["counts"], r1["counts"])
+    again = _search(torch, kd2, qs, k)
+    _same(again, r2, "second search")
+    assert np.array_equal(_nodes(kd2), nn2)
+    kd1.close(); kd2.close()

@@ -12,7 +12,7 @@ NEW = ("amk_kfmap_set_tie_order", "amk_kfmap_tie_order_bytes", "amk_kfmap_exact_
 
 
 def tie_order_bytes(S, max_points, max_edge_points, max_frame_count):
-    """exact_alloc's arrays (csrc/kd_index.hip) for both pools of (max_frame_count + 2) * S scenes, and the edge pool's planes"""
+    """the tree's arrays (amk::ExactStore, csrc/kd_exact.hip) for both pools of (max_frame_count + 2) * S scenes, and the edge pool's planes"""
     scenes = (max_frame_count + 2) * S
 
     def tree(mp):
