@@ -51,6 +51,13 @@ struct amk_mpc {
 };
 
 namespace amk {
+// amk_mpc::run_scenes for the length of a scope (amk_pipeline's control step): whichever way the scope is left, it is 0 again
+struct RunScenes {
+    amk_mpc *m;
+    RunScenes(amk_mpc *mpc, int n) : m(mpc) { m->run_scenes = n; }
+    ~RunScenes() { m->run_scenes = 0; }
+    RunScenes(const RunScenes &) = delete;
+};
 // Launches the solve for every scene of `m` (skipping scenes with d_done[s] != 0 when given).
 // d_ref_path / d_step_flags: control-step mode (refill mRefPath, count solves / iterations).
 // budget / max_passes (control step only, amk_step_batch): see mpc_device.h SolveSched; both 0 = the plain solve.

@@ -25,25 +25,11 @@
 struct amk_pipeline {
     amk_pipeline_config cfg;
     struct Staged {  // a frame of the open gang
-        const float *cloud, *edge;
-        const int *cloud_counts, *edge_counts;
-        const double *state_quad, *pos_x;   // read directly when gang == 1, gathered at launch otherwise
-        const double *ref_path_init;
-        double *u_out;
-        int keep_warm_start;
-        hipEvent_t input_ready;             // the caller's event (or null): the slot's stream waits for it before reading the inputs
-        const double *odom;                 // TASK mode (amk_pipeline_frame.d_odom): prologue / epilogue on the device
-        double odom_age;
-        double *cmd_out;
-        const void *depth;                  // raw depth image (amk_pipeline_frame.d_depth): ProcessDepth / BuildEdgeCloud on the device
-        int depth_type, depth_rows, depth_cols;
-        const double *Twb;
-        // multi-frame map (gang 1 only): the caller's keyframe handles behind the slot's own indices of this frame
-        std::vector<amk_kd *> kf_obstacle, kf_edge;
-        const double *Twc_cur;
-        bool has_camera;
-        amk_frame_camera camera;
-        const double *global_goal;          // TASK mode, task global_goal: mStateGlobalGoal per scene (or null: {0, 0, height})
+        amk_pipeline_frame frame;           // the caller's record: its DEVICE pointers are read at the launch; its host pointers are copied:
+        std::vector<amk_kd *> kf_obstacle, kf_edge;   // frame.kf_*: the caller's keyframe handles behind the slot's own indices (gang 1 only)
+        bool has_camera = false;
+        amk_frame_camera camera{};          // *frame.camera
+        hipEvent_t input_ready = nullptr;   // frame.input_ready: the slot's stream waits for it before reading the inputs
     };
     struct Slot {
         hipStream_t stream = nullptr;
@@ -218,10 +204,30 @@ __global__ __launch_bounds__(256) void pipeline_task_prologue_kernel(const Prolo
     }
 }
 
+using Slot = amk_pipeline::Slot;
+bool env_flag(const char *name) { const char *e = std::getenv(name); return e && e[0] == '1'; }
+// Host microseconds for the diagnostics of AMK_PIPELINE_TRACE=1.  With the trace off no clock is read.
+struct Stopwatch {
+    static bool on() { static const bool trace = env_flag("AMK_PIPELINE_TRACE"); return trace; }
+    static double now() { return on() ? std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count() : 0.0; }
+    double t0 = now(), us[3] = {};   // us: the laps taken so far, by number (launch_gang's trace line prints three)
+    double lap(int i = 0) { const double t = now(); us[i] = t - t0; t0 = t; return us[i]; }   // since the start or the last lap
+};
+// DevBuf::alloc for a list of (buffer, count) pairs, in order; the first error ends it
+inline hipError_t alloc_all() { return hipSuccess; }
+template <typename T, typename... Rest>
+hipError_t alloc_all(amk::DevBuf<T> &buf, size_t count, Rest &&...rest) {
+    const hipError_t e = buf.alloc(count);
+    return e != hipSuccess ? e : alloc_all(rest...);
+}
+Slot *slot_at(amk_pipeline *p, int slot) { return (p && slot >= 0 && slot < (int)p->slots.size()) ? &p->slots[slot] : nullptr; }
+Slot *slot_of(amk_pipeline *p, int ticket) {   // ticket = position in the gang * n_slots + slot
+    return (p && ticket >= 0 && ticket < (int)p->slots.size() * p->gang) ? &p->slots[ticket % (int)p->slots.size()] : nullptr;
+}
 // Waits for a slot's launch.  hipEventSynchronize parks the thread on an HSA signal; with AMK_PIPELINE_SPIN=1 the thread polls
 // hipEventQuery instead (diagnostics: tools/experiments/rccl_presence.py).
 int wait_event(hipEvent_t ev) {
-    static const bool spin = [] { const char *e = std::getenv("AMK_PIPELINE_SPIN"); return e && e[0] == '1'; }();
+    static const bool spin = env_flag("AMK_PIPELINE_SPIN");
     if (!spin) {
         AMK_HIP(hipEventSynchronize(ev));
         return AMK_OK;
@@ -232,168 +238,170 @@ int wait_event(hipEvent_t ev) {
         if (e != hipErrorNotReady) return amk::hip_fail(e);
     }
 }
-
-// Launches the slot's open gang: both index builds of every staged frame in one launch, one control step over all of them.
-// A gang that is not full (wait / drain before the G-th submit) runs on the leading scenes of the slot's handles only.
-int launch_gang(amk_pipeline *p, amk_pipeline::Slot &s) {
-    if (s.open.empty()) return AMK_OK;
-    const amk_pipeline_config &c = p->cfg;
-    const int G = p->gang, S = c.n_scenes, N = amk_mpc_horizon(s.mpc), mi = c.step.mpc_max_iter;
-    const int filled = (int)s.open.size();
-    if (filled > G || filled > AMK_PIPELINE_MAX_GANG) return AMK_ERR_INVALID_ARG;   // (submit() never stages more than a gang)
-    // AMK_TIES_AUTO on the slot's handles (amk_pipeline_kd) is for the single-frame step only (header): refused before anything is launched
-    if ((s.map || !s.open[0].kf_obstacle.empty()) && ((s.obstacle && s.obstacle->tie_order == AMK_TIES_AUTO) || (s.edge && s.edge->tie_order == AMK_TIES_AUTO)))
-        return AMK_ERR_UNSUPPORTED;
-    hipStream_t st = s.stream;
-    for (const auto &f : s.open)   // inputs produced on the caller's streams: ordered on the device, not by the host
-        if (f.input_ready) AMK_HIP(hipStreamWaitEvent(st, f.input_ready, 0));
-    // a robot that starts over (a TASK frame with d_ref_path_init: InitCircleState's role) also starts with a new FrameKDMap:
-    // no keyframes, mCurFrame.Twc = identity -- before the depth stage, whose edge cloud goes through that (stale) pose (:209)
-    for (int g = 0; g < (int)s.open.size(); ++g) {
-        const amk_pipeline::Staged &f = s.open[g];
-        if (!(f.odom && f.ref_path_init)) continue;
-        if (s.map) {
-            const int rr = amk_kfmap_reset(s.map, g * S, S, st);
-            if (rr != AMK_OK) return rr;
-        }
-        if (s.map && s.Twc.p) {   // (without a map the slot's Twc keeps its round-4 behaviour: it persists)
-            hipLaunchKernelGGL(pipeline_twc_init_kernel, dim3((S * 16 + 255) / 256), dim3(256), 0, st, s.Twc.p + (size_t)g * S * 16, S);
-            AMK_HIP(hipGetLastError());
-        }
-    }
+// One launch of a slot's open gang: what its stages share.  Position g occupies scenes [g S, (g + 1) S) of the slot's handles.
+struct Launch {
+    amk_pipeline *p;
+    const amk_pipeline_config &c;   // p->cfg
+    Slot &s;
+    int G, S, N, mi, filled;   // filled < G: wait / drain before the G-th submit; the launch runs on the leading scenes only
+    hipStream_t st;
+    // per position, written once by the stage that decides them (depth_stage): the clouds and counts the indices are built from,
+    // the counts whose zeros keep a scene's previous frame (a depth frame's; else null), mCurFrame.Twc for the slot's map
     const float *cl[AMK_PIPELINE_MAX_GANG], *ed[AMK_PIPELINE_MAX_GANG];
-    const int *cc[AMK_PIPELINE_MAX_GANG], *ec[AMK_PIPELINE_MAX_GANG];
+    const int *cc[AMK_PIPELINE_MAX_GANG], *ec[AMK_PIPELINE_MAX_GANG], *keep[AMK_PIPELINE_MAX_GANG];
+    const double *twc[AMK_PIPELINE_MAX_GANG];
+    bool any_task, any_depth, own_inputs;   // own_inputs: the step reads the slot's contiguous copies (gang 1 without TASK mode: the caller's)
+    const amk_pipeline_frame &frame(int g) const { return s.open[g].frame; }
+    int wait_for_inputs(), restart_robots(), gather_inputs(), depth_stage();   // the stages, in launch_gang's order
+    int build_indices(Stopwatch &watch), control_step(), finish();
+    int ensure_depth_buffers(), depth_camera(amk_frame_camera *cam);   // (parts of depth_stage and control_step)
+};
+int Launch::wait_for_inputs() {   // inputs produced on the caller's streams: ordered on the device, not by the host
+    for (const auto &o : s.open)
+        if (o.input_ready) AMK_HIP(hipStreamWaitEvent(st, o.input_ready, 0));
+    return AMK_OK;
+}
+// A robot that starts over (a TASK frame with d_ref_path_init: InitCircleState's role) also starts with a new FrameKDMap:
+// no keyframes, mCurFrame.Twc = identity -- before the depth stage, whose edge cloud goes through that (stale) pose (:209).
+// (Without a map the slot's Twc keeps its round-4 behaviour: it persists.)
+int Launch::restart_robots() {
+    if (!s.map) return AMK_OK;
+    for (int g = 0; g < filled; ++g) {
+        if (!(frame(g).d_odom && frame(g).d_ref_path_init)) continue;
+        if (const int rr = amk_kfmap_reset(s.map, g * S, S, st); rr != AMK_OK) return rr;
+        if (!s.Twc.p) continue;
+        hipLaunchKernelGGL(pipeline_twc_init_kernel, dim3((S * 16 + 255) / 256), dim3(256), 0, st, s.Twc.p + (size_t)g * S * 16, S);
+        AMK_HIP(hipGetLastError());
+    }
+    return AMK_OK;
+}
+// The small inputs into the slot's buffers (pipeline_gather_kernel), then the TASK frames' prologue
+int Launch::gather_inputs() {
     GatherArgs ga{};
     PrologueArgs pa{};
-    bool any_task = false;
     for (int g = 0; g < filled; ++g) {
-        const amk_pipeline::Staged &f = s.open[g];
-        cl[g] = f.cloud; ed[g] = f.edge; cc[g] = f.cloud_counts; ec[g] = f.edge_counts;
-        const bool task = f.odom != nullptr;
+        const amk_pipeline_frame &f = frame(g);
+        const bool task = f.d_odom != nullptr;
         any_task = any_task || task;
-        ga.sq[g] = task ? nullptr : f.state_quad; ga.px[g] = task ? nullptr : f.pos_x; ga.ref[g] = task ? nullptr : f.ref_path_init;
-        pa.odom[g] = f.odom; pa.ref_init[g] = f.ref_path_init; pa.age[g] = f.odom_age; pa.goal[g] = f.global_goal;
+        ga.sq[g] = task ? nullptr : f.d_state_quad; ga.px[g] = task ? nullptr : f.d_pos_x; ga.ref[g] = task ? nullptr : f.d_ref_path_init;
+        pa.odom[g] = f.d_odom; pa.ref_init[g] = f.d_ref_path_init; pa.age[g] = f.odom_age; pa.goal[g] = f.d_global_goal;
         // fresh frame: mRefPath after GetInitPath, zero warm start unless the caller carries it over (HighLvlMpc.cpp:26-27,35,129)
         ga.keep_warm_start[g] = f.keep_warm_start;
     }
-    const bool own_inputs = G > 1 || any_task;   // the step reads the slot's contiguous copies (gang 1 without TASK mode: the caller's)
+    own_inputs = G > 1 || any_task;
     ga.sq_dst = own_inputs ? s.state_quad.p : nullptr; ga.px_dst = own_inputs ? s.pos_x.p : nullptr;
     ga.ref_dst = s.ref_path.p; ga.w0 = s.mpc->w0.p;
     ga.n_sq = S * mi * 10; ga.n_px = S; ga.n_ref = S * N * 10; ga.n_w0 = S * s.mpc->nx;
-    {
-        const int longest = ga.n_w0 > ga.n_ref ? ga.n_w0 : ga.n_ref;
-        int bx = (longest + 1023) / 1024;
-        bx = bx < 1 ? 1 : (bx > 64 ? 64 : bx);
-        hipLaunchKernelGGL(pipeline_gather_kernel, dim3(bx, filled), dim3(256), 0, st, ga);
-        AMK_HIP(hipGetLastError());
+    const int longest = ga.n_w0 > ga.n_ref ? ga.n_w0 : ga.n_ref;
+    int bx = (longest + 1023) / 1024;
+    bx = bx < 1 ? 1 : (bx > 64 ? 64 : bx);
+    hipLaunchKernelGGL(pipeline_gather_kernel, dim3(bx, filled), dim3(256), 0, st, ga);
+    AMK_HIP(hipGetLastError());
+    if (!any_task) return AMK_OK;
+    const amk_task_params &t = c.task;
+    pa.sq_dst = s.state_quad.p; pa.px_dst = s.pos_x.p; pa.ref_dst = s.ref_path.p;
+    pa.S = S; pa.N = N; pa.mi = mi;
+    pa.decay = t.decay; pa.iter_time = t.iter_time > 0 ? t.iter_time : t.decay; pa.farest = t.farest_point; pa.height = t.height;
+    pa.speed = c.step.speed; pa.T = c.T; pa.dt = c.dt; pa.use_odom_est = t.use_odom_est; pa.task = t.task;
+    hipLaunchKernelGGL(pipeline_task_prologue_kernel, dim3((S + 3) / 4, filled), dim3(256), 0, st, pa);
+    AMK_HIP(hipGetLastError());
+    return AMK_OK;
+}
+// The slot's own clouds, counts and Twc, allocated by its first depth frame -- or again after an attempt that ran out of memory
+// half-way: all five buffers or none.  Every scene's Twc starts from the identity.
+int Launch::ensure_depth_buffers() {
+    if (s.dcloud.p && s.dedge.p && s.dcount.p && s.decount.p && s.Twc.p) return AMK_OK;
+    const size_t GS = (size_t)G * S;
+    const hipError_t e = alloc_all(s.dcloud, GS * c.max_points * 3, s.dedge, GS * c.max_edge_points * 3, s.dcount, GS, s.decount, GS, s.Twc, GS * 16);
+    if (e != hipSuccess) {
+        s.dcloud.release(); s.dedge.release(); s.dcount.release(); s.decount.release(); s.Twc.release();
+        return amk::hip_fail(e);
     }
-    if (any_task) {
-        const amk_task_params &t = c.task;
-        pa.sq_dst = s.state_quad.p; pa.px_dst = s.pos_x.p; pa.ref_dst = s.ref_path.p;
-        pa.S = S; pa.N = N; pa.mi = mi;
-        pa.decay = t.decay; pa.iter_time = t.iter_time > 0 ? t.iter_time : t.decay; pa.farest = t.farest_point; pa.height = t.height;
-        pa.speed = c.step.speed; pa.T = c.T; pa.dt = c.dt; pa.use_odom_est = t.use_odom_est; pa.task = t.task;
-        hipLaunchKernelGGL(pipeline_task_prologue_kernel, dim3((S + 3) / 4, filled), dim3(256), 0, st, pa);
-        AMK_HIP(hipGetLastError());
-    }
-    int rc;
-    if (p->inject_failure == 1) { p->inject_failure = 0; return AMK_ERR_HIP; }
-    // frames that start at the depth image: ProcessDepth + BuildEdgeCloud (FrameKDMap.cpp:90-130,176-214) into the slot's clouds
-    const int *keep[AMK_PIPELINE_MAX_GANG];
-    bool any_depth = false;
+    hipLaunchKernelGGL(pipeline_twc_init_kernel, dim3((unsigned)((GS * 16 + 255) / 256)), dim3(256), 0, st, s.Twc.p, (int)GS);
+    AMK_HIP(hipGetLastError());
+    return AMK_OK;
+}
+// Where every position's index is built from: the caller's clouds, or -- a frame that starts at the depth image -- ProcessDepth +
+// BuildEdgeCloud (FrameKDMap.cpp:90-130,176-214) into the slot's own, and the new mCurFrame.Twc behind them
+int Launch::depth_stage() {
     for (int g = 0; g < filled; ++g) {
-        const amk_pipeline::Staged &f = s.open[g];
-        keep[g] = nullptr;
-        if (!f.depth) continue;
-        if (s.point_stride != 3) return AMK_ERR_INVALID_ARG;   // the slot's own clouds are packed xyz
-        if (!s.dcloud.p || !s.dedge.p || !s.dcount.p || !s.decount.p || !s.Twc.p) {   // first depth frame of this slot (or an
-            // earlier attempt ran out of memory half-way: ADVICE r4 -- all five buffers or none)
-            const size_t GS = (size_t)G * S;
-            hipError_t e;
-            if ((e = s.dcloud.alloc(GS * c.max_points * 3)) != hipSuccess || (e = s.dedge.alloc(GS * c.max_edge_points * 3)) != hipSuccess ||
-                (e = s.dcount.alloc(GS)) != hipSuccess || (e = s.decount.alloc(GS)) != hipSuccess || (e = s.Twc.alloc(GS * 16)) != hipSuccess) {
-                s.dcloud.release(); s.dedge.release(); s.dcount.release(); s.decount.release(); s.Twc.release();
-                return amk::hip_fail(e);
-            }
-            hipLaunchKernelGGL(pipeline_twc_init_kernel, dim3((unsigned)((GS * 16 + 255) / 256)), dim3(256), 0, st, s.Twc.p, (int)GS);
-            AMK_HIP(hipGetLastError());
+        const amk_pipeline_frame &f = frame(g);
+        if (!f.d_depth) {
+            cl[g] = f.d_cloud; ed[g] = f.d_edge; cc[g] = f.d_cloud_counts; ec[g] = f.d_edge_counts; keep[g] = nullptr; twc[g] = f.d_Twc_cur;
+            continue;
         }
+        if (s.point_stride != 3) return AMK_ERR_INVALID_ARG;   // the slot's own clouds are packed xyz
+        if (const int rc = ensure_depth_buffers(); rc != AMK_OK) return rc;
         any_depth = true;
         const size_t o = (size_t)g * S;
         float *dc = s.dcloud.p + o * c.max_points * 3, *de = s.dedge.p + o * c.max_edge_points * 3;
         const long long img = (long long)f.depth_rows * f.depth_cols;
-        rc = amk_depth_to_cloud(f.depth, f.depth_type, f.depth_rows, f.depth_cols, img, S, &c.depth, f.Twb, dc, 3,
-                                (long long)c.max_points * 3, s.dcount.p + o, st);
+        int rc = amk_depth_to_cloud(f.d_depth, f.depth_type, f.depth_rows, f.depth_cols, img, S, &c.depth, f.d_Twb, dc, 3,
+                                    (long long)c.max_points * 3, s.dcount.p + o, st);
         if (rc != AMK_OK) return rc;
-        rc = amk_depth_to_edge_cloud(f.depth, f.depth_type, f.depth_rows, f.depth_cols, img, S, &c.depth, s.Twc.p + o * 16, de, 3,
+        rc = amk_depth_to_edge_cloud(f.d_depth, f.depth_type, f.depth_rows, f.depth_cols, img, S, &c.depth, s.Twc.p + o * 16, de, 3,
                                      (long long)c.max_edge_points * 3, s.decount.p + o, st);
         if (rc != AMK_OK) return rc;
-        hipLaunchKernelGGL(pipeline_twc_update_kernel, dim3((S * 16 + 255) / 256), dim3(256), 0, st, f.Twb, s.dcount.p + o, s.Twc.p + o * 16, S, c.depth);
+        hipLaunchKernelGGL(pipeline_twc_update_kernel, dim3((S * 16 + 255) / 256), dim3(256), 0, st, f.d_Twb, s.dcount.p + o, s.Twc.p + o * 16, S, c.depth);
         AMK_HIP(hipGetLastError());
-        cl[g] = dc; ed[g] = de; cc[g] = s.dcount.p + o; ec[g] = s.decount.p + o;
-        keep[g] = s.dcount.p + o;
+        cl[g] = dc; ed[g] = de; cc[g] = keep[g] = s.dcount.p + o; ec[g] = s.decount.p + o; twc[g] = s.Twc.p + o * 16;
     }
-    // FrameKDMap::AddVertex: obstacle index and edge index of every frame (FrameKDMap.cpp:44-47)
-    static const bool trace_host = [] { const char *e = std::getenv("AMK_PIPELINE_TRACE"); return e && e[0] == '1'; }();
-    auto now_us = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_h0 = trace_host ? now_us() : 0.0;
-    double t_h1 = 0.0, t_h2 = 0.0;
-    if (s.map) {   // ... into the slot's keyframe map: the scenes' own physical slots, mCurFrame.Twc, then KeyframeThreadWorker's body
-        const double *twcs[AMK_PIPELINE_MAX_GANG] = {};
-        for (int g = 0; g < filled; ++g) {
-            const amk_pipeline::Staged &f = s.open[g];
-            twcs[g] = f.depth ? s.Twc.p + (size_t)g * S * 16 : f.Twc_cur;
-            if (!twcs[g]) return AMK_ERR_INVALID_ARG;   // (submit() checked)
-        }
-        // AddVertex of every position of the gang: one bookkeeping launch + one build launch (both trees of all frames)
-        rc = amk::kfmap_add_vertex_gang(s.map, filled, S, cl, cc, ed, ec, s.point_stride, twcs, st);
-        if (rc != AMK_OK) return rc;
-        if (trace_host) t_h1 = now_us();
-        rc = amk_kfmap_update(s.map, st);
-        if (trace_host) t_h2 = now_us();
-    } else if (G == 1 && !any_depth) rc = amk_kd_build_pair(s.obstacle, cl[0], cc[0], s.edge, ed[0], ec[0], s.point_stride, st);
-    else rc = amk::kd_build_gang(s.obstacle, s.edge, filled, S, cl, cc, ed, ec, s.point_stride, st, any_depth ? keep : nullptr);
-    if (rc != AMK_OK) return rc;
-    if (p->inject_failure == 2) { p->inject_failure = 0; return AMK_ERR_HIP; }
-    double *u = (G == 1 && s.open[0].u_out && !any_task) ? s.open[0].u_out : s.u.p;
-    const double *sq = own_inputs ? s.state_quad.p : s.open[0].state_quad, *px = own_inputs ? s.pos_x.p : s.open[0].pos_x;
-    s.mpc->run_scenes = filled * S;
-    if (s.map) {   // the step over the slot's own map: mVecQueryVector = [current, keyframes but the newest] of every scene
-        const amk_pipeline::Staged &f = s.open[0];
-        amk_frame_camera cam{};
-        bool has_cam = f.has_camera;
-        if (has_cam) cam = f.camera;
-        if (f.depth) {   // the FrameKDMap constructor's down-scaled intrinsics and ProcessDepth's image size (:21-24,106-107)
-            int w = 0, h = 0;
-            rc = amk_depth_out_size(f.depth_rows, f.depth_cols, c.depth.resize_scale, &w, &h);
-            if (rc != AMK_OK) return rc;
-            cam.fx = c.depth.fx / c.depth.resize_scale; cam.fy = c.depth.fy / c.depth.resize_scale;
-            cam.cx = c.depth.cx / c.depth.resize_scale; cam.cy = c.depth.cy / c.depth.resize_scale;
-            cam.depth_max = c.depth.depth_max; cam.width = w; cam.height = h;
-            has_cam = true;
-        }
-        rc = amk_kfmap_step(s.map, has_cam ? &cam : nullptr, s.mpc, &c.step, sq, px, s.ref_path.p, u, s.x0array.p, s.flags.p, st);
-    } else if (!s.open[0].kf_obstacle.empty()) {   // mVecQueryVector = [this frame, keyframes ...] (gang 1: submit() checked)
-        const amk_pipeline::Staged &f = s.open[0];
-        std::vector<amk_kd *> ob{s.obstacle}, ed2{s.edge};
-        ob.insert(ob.end(), f.kf_obstacle.begin(), f.kf_obstacle.end());
-        ed2.insert(ed2.end(), f.kf_edge.begin(), f.kf_edge.end());
-        const double *twc = f.Twc_cur ? f.Twc_cur : (f.depth ? s.Twc.p : nullptr);
-        rc = amk_step_batch_frames(ob.data(), ed2.data(), (int)ob.size(), twc, f.has_camera ? &f.camera : nullptr, s.mpc, &c.step, sq, px,
-                                   s.ref_path.p, u, s.x0array.p, s.flags.p, st);
-    } else {
-        rc = amk_step_batch(s.obstacle, s.edge, s.mpc, &c.step, sq, px, s.ref_path.p, u, s.x0array.p, s.flags.p, st);
+    return AMK_OK;
+}
+// FrameKDMap::AddVertex: obstacle index and edge index of every frame (FrameKDMap.cpp:44-47)
+int Launch::build_indices(Stopwatch &watch) {
+    if (!s.map) {
+        if (G == 1 && !any_depth) return amk_kd_build_pair(s.obstacle, cl[0], cc[0], s.edge, ed[0], ec[0], s.point_stride, st);
+        return amk::kd_build_gang(s.obstacle, s.edge, filled, S, cl, cc, ed, ec, s.point_stride, st, any_depth ? keep : nullptr);
     }
-    s.mpc->run_scenes = 0;
-    if (trace_host)   // diagnostics (AMK_PIPELINE_TRACE=1): host microseconds spent enqueueing the stages of this launch
-        fprintf(stderr, "amk_pipeline launch: add_vertex %.0f us, map update %.0f us, step %.0f us (host enqueue time)\n", t_h1 - t_h0,
-                t_h2 - t_h1, now_us() - (s.map ? t_h2 : t_h0));
+    // ... into the slot's keyframe map: the scenes' own physical slots, mCurFrame.Twc, then KeyframeThreadWorker's body
+    for (int g = 0; g < filled; ++g)
+        if (!twc[g]) return AMK_ERR_INVALID_ARG;   // (submit() checked)
+    // AddVertex of every position of the gang: one bookkeeping launch + one build launch (both trees of all frames)
+    int rc = amk::kfmap_add_vertex_gang(s.map, filled, S, cl, cc, ed, ec, s.point_stride, twc, st);
     if (rc != AMK_OK) return rc;
-    if (G > 1 || any_task) {
+    watch.lap(0);
+    rc = amk_kfmap_update(s.map, st);
+    watch.lap(1);
+    return rc;
+}
+// The camera model of the step over the slot's map (ONE per launch, position 0's: submit() makes a gang agree on it): a cloud
+// frame brings it; a depth frame's is the FrameKDMap constructor's down-scaled intrinsics and ProcessDepth's image size (:21-24,106-107)
+int Launch::depth_camera(amk_frame_camera *cam) {
+    const amk_pipeline_frame &f = frame(0);
+    const amk_depth_params &d = c.depth;
+    cam->fx = d.fx / d.resize_scale; cam->fy = d.fy / d.resize_scale; cam->cx = d.cx / d.resize_scale; cam->cy = d.cy / d.resize_scale;
+    cam->depth_max = d.depth_max;
+    return amk_depth_out_size(f.depth_rows, f.depth_cols, d.resize_scale, &cam->width, &cam->height);
+}
+// One control step over all frames: over the slot's map, over [this frame, the caller's keyframes ...], or over this frame alone
+int Launch::control_step() {
+    const amk_pipeline::Staged &o = s.open[0];
+    double *u = (G == 1 && o.frame.d_u_out && !any_task) ? o.frame.d_u_out : s.u.p;
+    const double *sq = own_inputs ? s.state_quad.p : o.frame.d_state_quad, *px = own_inputs ? s.pos_x.p : o.frame.d_pos_x;
+    const amk::RunScenes leading(s.mpc, filled * S);   // (a gang that is not full; reset on every way out)
+    if (s.map) {   // mVecQueryVector = [current, keyframes but the newest] of every scene
+        amk_frame_camera cam = o.camera;
+        if (const int rc = o.frame.d_depth ? depth_camera(&cam) : AMK_OK; rc != AMK_OK) return rc;
+        return amk_kfmap_step(s.map, (o.has_camera || o.frame.d_depth) ? &cam : nullptr, s.mpc, &c.step, sq, px, s.ref_path.p, u, s.x0array.p, s.flags.p, st);
+    }
+    if (o.kf_obstacle.empty()) return amk_step_batch(s.obstacle, s.edge, s.mpc, &c.step, sq, px, s.ref_path.p, u, s.x0array.p, s.flags.p, st);
+    // mVecQueryVector = [this frame, keyframes ...] (gang 1: submit() checked)
+    std::vector<amk_kd *> kd_ob{s.obstacle}, kd_ed{s.edge};
+    kd_ob.insert(kd_ob.end(), o.kf_obstacle.begin(), o.kf_obstacle.end());
+    kd_ed.insert(kd_ed.end(), o.kf_edge.begin(), o.kf_edge.end());
+    const double *twc_cur = o.frame.d_Twc_cur ? o.frame.d_Twc_cur : (o.frame.d_depth ? s.Twc.p : nullptr);
+    return amk_step_batch_frames(kd_ob.data(), kd_ed.data(), (int)kd_ob.size(), twc_cur, o.has_camera ? &o.camera : nullptr, s.mpc, &c.step, sq, px,
+                                 s.ref_path.p, u, s.x0array.p, s.flags.p, st);
+}
+// The controls to where the callers want them (pipeline_scatter_kernel), the completion event, the slot's books
+int Launch::finish() {
+    if (own_inputs) {
         ScatterArgs sa{};
         bool any = false;
         for (int g = 0; g < filled; ++g) {
-            sa.dst[g] = s.open[g].u_out; sa.cmd[g] = s.open[g].odom ? s.open[g].cmd_out : nullptr; sa.odom[g] = s.open[g].odom;
+            const amk_pipeline_frame &f = frame(g);
+            sa.dst[g] = f.d_u_out; sa.cmd[g] = f.d_odom ? f.d_cmd_out : nullptr; sa.odom[g] = f.d_odom;
             any = any || sa.dst[g] || sa.cmd[g];
         }
         sa.u = s.u.p; sa.flags = s.flags.p; sa.n_u = S * 4; sa.S = S;
@@ -406,23 +414,43 @@ int launch_gang(amk_pipeline *p, amk_pipeline::Slot &s) {
     AMK_HIP(hipEventRecord(s.done[s.count % p->depth], st));
     ++s.count;
     for (int g = 0; g < filled; ++g)
-        if (s.open[g].odom && s.open[g].ref_path_init) s.ref_inited[g] = true;
+        if (frame(g).d_odom && frame(g).d_ref_path_init) s.ref_inited[g] = true;
     s.open.clear();
     return AMK_OK;
 }
-
-// launch_gang with the slot left consistent whatever happens: on a failure half-way (a build or a step that could not be
-// launched) the staged frames are DROPPED -- a later submit() starts a new gang instead of re-launching a half-consumed one,
-// and wait() / drain() have an event to wait for (what did get enqueued stays ordered on the slot's stream) and report the
-// failure.  The round robin moves on either way.
-int launch_slot(amk_pipeline *p, amk_pipeline::Slot &s) {
+// Launches the slot's open gang (not empty): both index builds of every staged frame in one launch, one control step over all of
+// them.  A stage that fails ends the launch; what the stages before it enqueued stays enqueued (launch_slot).
+int launch_gang(amk_pipeline *p, Slot &s) {
+    const int filled = (int)s.open.size();
+    if (filled > p->gang || filled > AMK_PIPELINE_MAX_GANG) return AMK_ERR_INVALID_ARG;   // (submit() never stages more than a gang)
+    // AMK_TIES_AUTO on the slot's handles (amk_pipeline_kd) is for the single-frame step only (header): refused before anything is launched
+    if ((s.map || !s.open[0].kf_obstacle.empty()) && ((s.obstacle && s.obstacle->tie_order == AMK_TIES_AUTO) || (s.edge && s.edge->tie_order == AMK_TIES_AUTO)))
+        return AMK_ERR_UNSUPPORTED;
+    Launch L{p, p->cfg, s, p->gang, p->cfg.n_scenes, amk_mpc_horizon(s.mpc), p->cfg.step.mpc_max_iter, filled, s.stream};
+    int rc;
+    if ((rc = L.wait_for_inputs()) != AMK_OK) return rc;
+    if ((rc = L.restart_robots()) != AMK_OK) return rc;
+    if ((rc = L.gather_inputs()) != AMK_OK) return rc;
+    if (p->inject_failure == 1) { p->inject_failure = 0; return AMK_ERR_HIP; }
+    if ((rc = L.depth_stage()) != AMK_OK) return rc;
+    Stopwatch watch;   // AMK_PIPELINE_TRACE=1: host microseconds spent enqueueing the build and the step
+    if ((rc = L.build_indices(watch)) != AMK_OK) return rc;
+    if (p->inject_failure == 2) { p->inject_failure = 0; return AMK_ERR_HIP; }
+    rc = L.control_step();
+    if (Stopwatch::on())
+        fprintf(stderr, "amk_pipeline launch: add_vertex %.0f us, map update %.0f us, step %.0f us (host enqueue time)\n", watch.us[0],
+                watch.us[1], watch.lap(2));
+    return rc != AMK_OK ? rc : L.finish();
+}
+// launch_gang, if a gang is open, with the slot left consistent whatever happens: on a failure half-way (a build or a step that
+// could not be launched) the staged frames are DROPPED -- a later submit() starts a new gang instead of re-launching a
+// half-consumed one, and wait() / drain() have an event to wait for (what did get enqueued stays ordered on the slot's stream)
+// and report the failure.  The round robin moves on either way.
+int launch_slot(amk_pipeline *p, Slot &s) {
     if (s.open.empty()) return AMK_OK;
-    static const bool trace_host = [] { const char *e = std::getenv("AMK_PIPELINE_TRACE"); return e && e[0] == '1'; }();
-    const auto t0 = std::chrono::steady_clock::now();
+    Stopwatch watch;
     const int st = launch_gang(p, s);
-    if (trace_host)
-        fprintf(stderr, "amk_pipeline launch_gang total: %.0f us (host)\n",
-                std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count());
+    if (Stopwatch::on()) fprintf(stderr, "amk_pipeline launch_gang total: %.0f us (host)\n", watch.lap());
     if (st != AMK_OK) {
         // What had been enqueued before the failure stays enqueued: a TASK frame's GetInitPath may already have shifted the slot's
         // mRefPath, its warm start may have been reset, a depth frame's Twc may have moved on.  The slot's persistent
@@ -430,7 +458,6 @@ int launch_slot(amk_pipeline *p, amk_pipeline::Slot &s) {
         // (submit() rejects it otherwise) -- re-submitting the failed period as it was would shift the path twice.
         for (bool &b : s.ref_inited) b = false;
         s.open.clear();
-        s.mpc->run_scenes = 0;
         (void)hipEventRecord(s.done[s.count % p->depth], s.stream);
         ++s.count;
     }
@@ -438,10 +465,60 @@ int launch_slot(amk_pipeline *p, amk_pipeline::Slot &s) {
     if (&s == &p->slots[p->next]) p->next = (p->next + 1) % (int)p->slots.size();
     return st;
 }
+// A slot's stream, events, handles and buffers; what a failure leaves behind is amk_pipeline_destroy's
+int create_slot(const amk_pipeline *p, Slot &s) {
+    const amk_pipeline_config &cfg = p->cfg;
+    const int GS = p->gang * cfg.n_scenes;
+    AMK_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+    s.done.assign(p->depth, nullptr);
+    for (auto &ev : s.done) AMK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    int st;
+    if ((st = amk_kd_create(GS, cfg.max_points, &s.obstacle)) != AMK_OK) return st;
+    if ((st = amk_kd_create(GS, cfg.max_edge_points, &s.edge)) != AMK_OK) return st;
+    if ((st = amk_mpc_create(cfg.T, cfg.dt, cfg.nearest_point_num, GS, &s.mpc)) != AMK_OK) return st;
+    if (cfg.keyframes.max_frame_count > 0) {
+        amk_kfmap_params kp = cfg.keyframes;
+        auto all_zero = [](const double *T) { bool z = true; for (int e = 0; e < 16; ++e) z = z && T[e] == 0.0; return z; };
+        // mParamTbc: the map's own field when it is set, else the depth configuration's (one extrinsic serves both in the
+        // reference, FrameKDMap.cpp:15), else camera frame = body frame
+        if (all_zero(kp.Tbc)) std::memcpy(kp.Tbc, cfg.depth.Tbc, sizeof kp.Tbc);
+        if (all_zero(kp.Tbc)) kp.Tbc[0] = kp.Tbc[5] = kp.Tbc[10] = kp.Tbc[15] = 1.0;
+        if ((st = amk_kfmap_create(GS, cfg.max_points, cfg.max_edge_points, &kp, &s.map)) != AMK_OK) return st;
+    }
+    const size_t S = GS, N = amk_mpc_horizon(s.mpc);
+    AMK_HIP(alloc_all(s.ref_path, S * N * 10, s.u, S * 4, s.x0array, S * N * 14, s.flags, S * 4, s.state_quad, S * cfg.step.mpc_max_iter * 10, s.pos_x, S));
+    return AMK_OK;
+}
+// submit()'s first refusals: what is wrong with a frame's own arguments, whichever slot it goes to
+int frame_args(const amk_pipeline_config &c, const amk_pipeline_frame *f) {
+    if (f->d_depth) {   // a frame that starts at the depth image
+        if (!f->d_Twb || f->depth_rows <= 0 || f->depth_cols <= 0 || (f->depth_type != AMK_DEPTH_U16 && f->depth_type != AMK_DEPTH_F32))
+            return AMK_ERR_INVALID_ARG;
+        int w = 0, h = 0;
+        if (amk_depth_out_size(f->depth_rows, f->depth_cols, c.depth.resize_scale, &w, &h) != AMK_OK) return AMK_ERR_INVALID_ARG;
+        if ((long long)w * h > c.max_points || (long long)w * h > c.max_edge_points) return AMK_ERR_INVALID_ARG;
+        if ((long long)w * h > AMK_EDGE_MAX_PIXELS) return AMK_ERR_UNSUPPORTED;
+    } else if (!f->d_cloud || !f->d_edge) return AMK_ERR_INVALID_ARG;
+    if (!f->d_odom && (!f->d_state_quad || !f->d_pos_x || !f->d_ref_path_init)) return AMK_ERR_INVALID_ARG;
+    return (f->n_keyframes < 0 || f->n_keyframes > AMK_MAX_FRAMES - 1) ? AMK_ERR_INVALID_ARG : AMK_OK;
+}
+// The record of a checked frame that a slot keeps until its gang is launched
+amk_pipeline::Staged staged(const amk_pipeline_frame &f) {
+    amk_pipeline::Staged o;
+    o.frame = f;
+    if (f.n_keyframes > 0) {
+        o.kf_obstacle.assign(f.kf_obstacle, f.kf_obstacle + f.n_keyframes);
+        o.kf_edge.assign(f.kf_edge, f.kf_edge + f.n_keyframes);
+    }
+    o.has_camera = f.camera != nullptr;
+    if (f.camera) o.camera = *f.camera;
+    o.input_ready = (hipEvent_t)f.input_ready;
+    o.frame.kf_obstacle = o.frame.kf_edge = nullptr; o.frame.camera = nullptr;   // (the caller's host storage: a launch reads the copies)
+    return o;
+}
 }  // namespace
 
 extern "C" {
-
 int amk_pipeline_create(const amk_pipeline_config *cfg, amk_pipeline **out) {
     if (!cfg || !out || cfg->n_slots <= 0 || cfg->n_slots > AMK_PIPELINE_MAX_SLOTS || cfg->n_scenes <= 0 ||
         cfg->max_points <= 0 || cfg->max_edge_points <= 0 || cfg->gang < 0 || cfg->gang > AMK_PIPELINE_MAX_GANG ||
@@ -456,48 +533,11 @@ int amk_pipeline_create(const amk_pipeline_config *cfg, amk_pipeline **out) {
     if (p->depth > AMK_PIPELINE_MAX_DEPTH) p->depth = AMK_PIPELINE_MAX_DEPTH;
     p->gang = cfg->gang > 0 ? cfg->gang : 1;
     p->slots.resize(cfg->n_slots);
-    const int GS = p->gang * cfg->n_scenes;
-    int st = AMK_OK;
-    for (auto &s : p->slots) {
-        hipError_t e;
-        if ((e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking)) != hipSuccess) {
-            st = amk::hip_fail(e);
-            break;
+    for (auto &s : p->slots)
+        if (const int st = create_slot(p, s); st != AMK_OK) {
+            amk_pipeline_destroy(p);
+            return st;
         }
-        s.done.assign(p->depth, nullptr);
-        for (auto &ev : s.done)
-            if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) break;
-        if (e != hipSuccess) {
-            st = amk::hip_fail(e);
-            break;
-        }
-        if ((st = amk_kd_create(GS, cfg->max_points, &s.obstacle)) != AMK_OK) break;
-        if ((st = amk_kd_create(GS, cfg->max_edge_points, &s.edge)) != AMK_OK) break;
-        if ((st = amk_mpc_create(cfg->T, cfg->dt, cfg->nearest_point_num, GS, &s.mpc)) != AMK_OK) break;
-        if (cfg->keyframes.max_frame_count > 0) {
-            amk_kfmap_params kp = cfg->keyframes;
-            auto all_zero = [](const double *T) { bool z = true; for (int e = 0; e < 16; ++e) z = z && T[e] == 0.0; return z; };
-            // mParamTbc: the map's own field when it is set, else the depth configuration's (one extrinsic serves both in the
-            // reference, FrameKDMap.cpp:15), else camera frame = body frame
-            if (all_zero(kp.Tbc)) std::memcpy(kp.Tbc, cfg->depth.Tbc, sizeof kp.Tbc);
-            if (all_zero(kp.Tbc)) kp.Tbc[0] = kp.Tbc[5] = kp.Tbc[10] = kp.Tbc[15] = 1.0;
-            if ((st = amk_kfmap_create(GS, cfg->max_points, cfg->max_edge_points, &kp, &s.map)) != AMK_OK) break;
-        }
-        const size_t S = GS, N = amk_mpc_horizon(s.mpc);
-        if ((e = s.ref_path.alloc(S * N * 10)) != hipSuccess || (e = s.u.alloc(S * 4)) != hipSuccess ||
-            (e = s.x0array.alloc(S * N * 14)) != hipSuccess || (e = s.flags.alloc(S * 4)) != hipSuccess) {
-            st = amk::hip_fail(e);
-            break;
-        }
-        if ((e = s.state_quad.alloc(S * cfg->step.mpc_max_iter * 10)) != hipSuccess || (e = s.pos_x.alloc(S)) != hipSuccess) {
-            st = amk::hip_fail(e);
-            break;
-        }
-    }
-    if (st != AMK_OK) {
-        amk_pipeline_destroy(p);
-        return st;
-    }
     *out = p;
     return AMK_OK;
 }
@@ -520,43 +560,27 @@ int amk_pipeline_destroy(amk_pipeline *p) {
 
 int amk_pipeline_slots(const amk_pipeline *p) { return p ? (int)p->slots.size() : -1; }
 int amk_pipeline_gang(const amk_pipeline *p) { return p ? p->gang : -1; }
-
-amk_mpc *amk_pipeline_mpc(amk_pipeline *p, int slot) {
-    return (p && slot >= 0 && slot < (int)p->slots.size()) ? p->slots[slot].mpc : nullptr;
-}
-amk_kfmap *amk_pipeline_kfmap(amk_pipeline *p, int slot) {
-    return (p && slot >= 0 && slot < (int)p->slots.size()) ? p->slots[slot].map : nullptr;
-}
+amk_mpc *amk_pipeline_mpc(amk_pipeline *p, int slot) { const Slot *s = slot_at(p, slot); return s ? s->mpc : nullptr; }
+amk_kfmap *amk_pipeline_kfmap(amk_pipeline *p, int slot) { const Slot *s = slot_at(p, slot); return s ? s->map : nullptr; }
+void *amk_pipeline_stream(amk_pipeline *p, int slot) { const Slot *s = slot_at(p, slot); return s ? (void *)s->stream : nullptr; }
 amk_kd *amk_pipeline_kd(amk_pipeline *p, int slot, int which) {
-    if (!p || slot < 0 || slot >= (int)p->slots.size()) return nullptr;
-    return which == 0 ? p->slots[slot].obstacle : (which == 1 ? p->slots[slot].edge : nullptr);
-}
-void *amk_pipeline_stream(amk_pipeline *p, int slot) {
-    return (p && slot >= 0 && slot < (int)p->slots.size()) ? (void *)p->slots[slot].stream : nullptr;
+    const Slot *s = slot_at(p, slot);
+    return !s ? nullptr : (which == 0 ? s->obstacle : (which == 1 ? s->edge : nullptr));
 }
 
 int amk_pipeline_submit(amk_pipeline *p, const amk_pipeline_frame *f, int *ticket_out) {
     if (!p || !f) return AMK_ERR_INVALID_ARG;
-    if (f->d_depth) {   // a frame that starts at the depth image
-        if (!f->d_Twb || f->depth_rows <= 0 || f->depth_cols <= 0 || (f->depth_type != AMK_DEPTH_U16 && f->depth_type != AMK_DEPTH_F32))
-            return AMK_ERR_INVALID_ARG;
-        int w = 0, h = 0;
-        if (amk_depth_out_size(f->depth_rows, f->depth_cols, p->cfg.depth.resize_scale, &w, &h) != AMK_OK) return AMK_ERR_INVALID_ARG;
-        if ((long long)w * h > p->cfg.max_points || (long long)w * h > p->cfg.max_edge_points) return AMK_ERR_INVALID_ARG;
-        if ((long long)w * h > AMK_EDGE_MAX_PIXELS) return AMK_ERR_UNSUPPORTED;
-    } else if (!f->d_cloud || !f->d_edge) return AMK_ERR_INVALID_ARG;
-    if (!f->d_odom && (!f->d_state_quad || !f->d_pos_x || !f->d_ref_path_init)) return AMK_ERR_INVALID_ARG;
+    if (const int st = frame_args(p->cfg, f); st != AMK_OK) return st;
     const int si = p->next, ns = (int)p->slots.size();
-    auto &s = p->slots[si];
-    if (f->n_keyframes < 0 || f->n_keyframes > AMK_MAX_FRAMES - 1) return AMK_ERR_INVALID_ARG;
+    Slot &s = p->slots[si];
     // the slot's own map: no caller keyframes; cloud frames bring mCurFrame.Twc AND the camera model -- the reference always runs
     // PtIsInFrame (FrameKDMap.cpp:339-345); without a camera every reference point would count as inside the current frame and
     // the keyframes would never be merged
     if (s.map && (f->n_keyframes > 0 || (!f->d_depth && (!f->d_Twc_cur || !f->camera)))) return AMK_ERR_INVALID_ARG;
     if (s.map && !s.open.empty()) {   // the map step takes ONE camera model per launch (position 0's): a gang must agree on it
         const amk_pipeline::Staged &o = s.open[0];
-        if ((o.depth != nullptr) != (f->d_depth != nullptr)) return AMK_ERR_INVALID_ARG;
-        if (f->d_depth && (o.depth_rows != f->depth_rows || o.depth_cols != f->depth_cols)) return AMK_ERR_INVALID_ARG;
+        if ((o.frame.d_depth != nullptr) != (f->d_depth != nullptr)) return AMK_ERR_INVALID_ARG;
+        if (f->d_depth && (o.frame.depth_rows != f->depth_rows || o.frame.depth_cols != f->depth_cols)) return AMK_ERR_INVALID_ARG;
         if (!f->d_depth && std::memcmp(&o.camera, f->camera, sizeof(amk_frame_camera)) != 0) return AMK_ERR_INVALID_ARG;
     }
     if (f->n_keyframes > 0) {
@@ -576,26 +600,16 @@ int amk_pipeline_submit(amk_pipeline *p, const amk_pipeline_frame *f, int *ticke
     // the event about to be re-recorded belongs to the launch issued `depth` launches ago.  depth 1 = at most one launch per
     // slot on the device (every launch then pays the host's reaction time between its predecessor's end and its own start).
     if (s.open.empty() && s.count - s.waited >= p->depth) {
-        static const bool trace_host = [] { const char *e = std::getenv("AMK_PIPELINE_TRACE"); return e && e[0] == '1'; }();
-        const auto t0 = std::chrono::steady_clock::now();
+        Stopwatch watch;
         const int ws = wait_event(s.done[s.count % p->depth]);
-        if (trace_host)
-            fprintf(stderr, "amk_pipeline submit: waited %.0f us for the launch issued %d launches ago on slot %d\n",
-                    std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(), p->depth, si);
+        if (Stopwatch::on())
+            fprintf(stderr, "amk_pipeline submit: waited %.0f us for the launch issued %d launches ago on slot %d\n", watch.lap(), p->depth, si);
         if (ws != AMK_OK) return ws;
         s.waited = s.count - p->depth + 1;
     }
     const int g = (int)s.open.size();
     s.point_stride = stride;
-    // staged: the frame's inputs are read when its gang is launched (they stay the caller's until then)
-    s.open.push_back(amk_pipeline::Staged{f->d_cloud, f->d_edge, f->d_cloud_counts, f->d_edge_counts, f->d_state_quad, f->d_pos_x,
-                                           f->d_ref_path_init, f->d_u_out, f->keep_warm_start, (hipEvent_t)f->input_ready,
-                                           f->d_odom, f->odom_age, f->d_cmd_out, f->d_depth, f->depth_type, f->depth_rows, f->depth_cols, f->d_Twb,
-                                           {}, {}, f->d_Twc_cur, f->camera != nullptr, f->camera ? *f->camera : amk_frame_camera{}, f->d_global_goal});
-    if (f->n_keyframes > 0) {
-        s.open.back().kf_obstacle.assign(f->kf_obstacle, f->kf_obstacle + f->n_keyframes);
-        s.open.back().kf_edge.assign(f->kf_edge, f->kf_edge + f->n_keyframes);
-    }
+    s.open.push_back(staged(*f));
     if (ticket_out) *ticket_out = g * ns + si;
     ++p->submitted;
     if ((int)s.open.size() == p->gang) return launch_slot(p, s);
@@ -603,54 +617,42 @@ int amk_pipeline_submit(amk_pipeline *p, const amk_pipeline_frame *f, int *ticke
 }
 
 int amk_pipeline_wait(amk_pipeline *p, int ticket) {
-    if (!p || ticket < 0 || ticket >= (int)p->slots.size() * p->gang) return AMK_ERR_INVALID_ARG;
-    auto &s = p->slots[ticket % (int)p->slots.size()];
-    if (!s.open.empty()) {   // a partly filled gang: launch it now
-        const int st = launch_slot(p, s);
-        if (st != AMK_OK) return st;
+    Slot *s = slot_of(p, ticket);
+    if (!s) return AMK_ERR_INVALID_ARG;
+    if (const int st = launch_slot(p, *s); st != AMK_OK) return st;   // a partly filled gang: launch it now
+    if (s->waited < s->count) {   // the newest event implies all earlier ones (in-order stream)
+        if (const int ws = wait_event(s->done[(s->count - 1) % p->depth]); ws != AMK_OK) return ws;
+        s->waited = s->count;
     }
-    if (s.waited < s.count) {   // the newest event implies all earlier ones (in-order stream)
-        const int ws = wait_event(s.done[(s.count - 1) % p->depth]);
-        if (ws != AMK_OK) return ws;
-        s.waited = s.count;
-    }
-    return s.fail_status;   // AMK_OK unless the slot's newest launch failed half-way (its frames were dropped)
+    return s->fail_status;   // AMK_OK unless the slot's newest launch failed half-way (its frames were dropped)
 }
 
 int amk_pipeline_wait_stream(amk_pipeline *p, int ticket, void *stream) {
-    if (!p || ticket < 0 || ticket >= (int)p->slots.size() * p->gang) return AMK_ERR_INVALID_ARG;
-    auto &s = p->slots[ticket % (int)p->slots.size()];
-    if (!s.open.empty()) {
-        const int st = launch_slot(p, s);
-        if (st != AMK_OK) return st;
-    }
-    if (s.count > 0) AMK_HIP(hipStreamWaitEvent((hipStream_t)stream, s.done[(s.count - 1) % p->depth], 0));
-    return s.fail_status;
+    Slot *s = slot_of(p, ticket);
+    if (!s) return AMK_ERR_INVALID_ARG;
+    if (const int st = launch_slot(p, *s); st != AMK_OK) return st;
+    if (s->count > 0) AMK_HIP(hipStreamWaitEvent((hipStream_t)stream, s->done[(s->count - 1) % p->depth], 0));
+    return s->fail_status;
 }
 
 int amk_pipeline_query(amk_pipeline *p, int ticket) {  // 1 = finished (or idle), 0 = still running or staged, -1 error
-    if (!p || ticket < 0 || ticket >= (int)p->slots.size() * p->gang) return -1;
-    auto &s = p->slots[ticket % (int)p->slots.size()];
-    if (!s.open.empty()) return 0;
-    if (s.fail_status != AMK_OK) return -1;   // the slot's newest launch failed half-way: its frames were dropped (wait() tells why)
-    if (s.waited >= s.count) return 1;
-    const hipError_t e = hipEventQuery(s.done[(s.count - 1) % p->depth]);
-    if (e == hipSuccess) { s.waited = s.count; return 1; }
+    Slot *s = slot_of(p, ticket);
+    if (!s) return -1;
+    if (!s->open.empty()) return 0;
+    if (s->fail_status != AMK_OK) return -1;   // the slot's newest launch failed half-way: its frames were dropped (wait() tells why)
+    if (s->waited >= s->count) return 1;
+    const hipError_t e = hipEventQuery(s->done[(s->count - 1) % p->depth]);
+    if (e == hipSuccess) { s->waited = s->count; return 1; }
     return e == hipErrorNotReady ? 0 : -1;
 }
 
 int amk_pipeline_drain(amk_pipeline *p) {
     if (!p) return AMK_ERR_INVALID_ARG;
     int first_error = AMK_OK;   // every slot is launched and waited for even when one fails: drain() leaves nothing in flight
-    for (auto &s : p->slots) {   // every open gang first: a launch must not wait for the slots before it to finish
-        if (s.open.empty()) continue;
-        const int st = launch_slot(p, s);
-        if (st != AMK_OK && first_error == AMK_OK) first_error = st;
-    }
-    for (int i = 0; i < (int)p->slots.size(); ++i) {
-        const int st = amk_pipeline_wait(p, i);
-        if (st != AMK_OK && first_error == AMK_OK) first_error = st;
-    }
+    for (auto &s : p->slots)   // every open gang first: a launch must not wait for the slots before it to finish
+        if (const int st = launch_slot(p, s); st != AMK_OK && first_error == AMK_OK) first_error = st;
+    for (int i = 0; i < (int)p->slots.size(); ++i)
+        if (const int st = amk_pipeline_wait(p, i); st != AMK_OK && first_error == AMK_OK) first_error = st;
     return first_error;
 }
 
@@ -663,15 +665,13 @@ int amk__pipeline_inject_failure(amk_pipeline *p, int stage) {
 }
 
 int amk_pipeline_outputs(amk_pipeline *p, int ticket, double **d_u, double **d_x0array, int **d_flags, double **d_ref_path) {
-    if (!p || ticket < 0 || ticket >= (int)p->slots.size() * p->gang) return AMK_ERR_INVALID_ARG;
-    const int ns = (int)p->slots.size(), g = ticket / ns;
-    auto &s = p->slots[ticket % ns];
-    const size_t S = p->cfg.n_scenes, N = amk_mpc_horizon(s.mpc), o = (size_t)g * S;
-    if (d_u) *d_u = s.u.p + o * 4;
-    if (d_x0array) *d_x0array = s.x0array.p + o * N * 14;
-    if (d_flags) *d_flags = s.flags.p + o * 4;
-    if (d_ref_path) *d_ref_path = s.ref_path.p + o * N * 10;
+    Slot *s = slot_of(p, ticket);
+    if (!s) return AMK_ERR_INVALID_ARG;
+    const size_t S = p->cfg.n_scenes, N = amk_mpc_horizon(s->mpc), o = (size_t)(ticket / (int)p->slots.size()) * S;
+    if (d_u) *d_u = s->u.p + o * 4;
+    if (d_x0array) *d_x0array = s->x0array.p + o * N * 14;
+    if (d_flags) *d_flags = s->flags.p + o * 4;
+    if (d_ref_path) *d_ref_path = s->ref_path.p + o * N * 10;
     return AMK_OK;
 }
-
 }  // extern "C"

@@ -433,3 +433,77 @@ def test_task_mode_clock_model_and_odometry_age(use_odom_est, age, iter_time):
     pt.wait(t); got = pt.outputs(t); pt.close()
     assert np.array_equal(got["u"], want["u"]) and np.array_equal(got["flags"], want["flags"]) and np.array_equal(got["ref_path"], want["ref_path"])
     assert np.array_equal(cmd.cpu().numpy(), flight.command(got["u"], got["flags"], x, prm))
+
+
+def test_gang_of_a_cloud_frame_and_a_depth_task_frame():
+    """A gang whose positions differ in kind: position 0 a host-mode cloud frame (state_quad, pos_x, ref_path_init, u_out), position 1
+    a TASK-mode frame that starts at the depth image (odom, ref_path_init, cmd_out, depth, Twb).  The launch then mixes, per
+    position, the caller's clouds with the slot's own, gathered inputs with the prologue's, and kept scenes with rebuilt ones.
+    Every frame returns, bit for bit, what it returns alone on a gang-1 pipeline of the same configuration -- also in a second
+    period, in which position 1 runs on the path, the Twc and the warm start that the slot kept for it."""
+    import torch
+    from avoid_mpc_amd import flight
+    from avoid_mpc_amd.host import Pipeline, depth_params
+    from tests import _flight, _oracle
+    prm = synth.MpcParams(T=0.33, K=3)
+    S, n, periods = 3, 1500, 2
+    cam = dict(_flight.DEPTH_CAM, resize_scale=10.0)                 # 320 x 240 / 10: 768 pixels <= 1500
+    dp = depth_params(cam["pixel2meter"], cam["depth_min"], cam["depth_max"], cam["resize_scale"], cam["fx"], cam["fy"], cam["cx"],
+                      cam["cy"], cam["Tbc"])
+    dev = torch.device("cuda", torch.cuda.current_device())
+    dbl = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(dev)
+    # position 0: a fresh set of scenes per period, 1500 obstacle and 1500 edge points each
+    cloud_frames = []
+    for t in range(periods):
+        scenes = [synth.make_scene(10 * n, 7100 + 31 * t + s, prm) for s in range(S)]
+        sq, px = flight.period_inputs(np.stack([np.concatenate([sc["pos"], [sc["yaw"]], sc["vel"], sc["acc"]]) for sc in scenes]),
+                                      np.stack([sc["ref_path"] for sc in scenes]), prm, shift=False)
+        cloud_frames.append(dict(clouds=torch.from_numpy(np.stack([sc["cloud"][:n] for sc in scenes])).to(dev),
+                                 edges=torch.from_numpy(np.stack([sc["edge"] for sc in scenes])).to(dev), state_quad=dbl(sq),
+                                 pos_x=dbl(px), ref_path_init=dbl(np.stack([sc["ref_path"] for sc in scenes]))))
+    # position 1: three robots in their own worlds, one nominal period further on in the second frame
+    seeds = [11, 12, 13]
+    worlds = [flight.FlightWorld(sd, prm, 1000) for sd in seeds]
+    st = [flight.initial_state(sd, prm) for sd in seeds]
+    x = np.stack([a for a, _ in st]); ref0 = np.stack([b for _, b in st])
+    depth_frames = []
+    for t in range(periods):
+        fr = [_flight._depth_frame(worlds[i], x[i], cam) for i in range(S)]
+        assert all(len(_oracle.depth_oracle(img, cam, Twb)[0]) > 0 for img, Twb in fr)   # (an empty frame would keep an index that was never built)
+        depth_frames.append(dict(depth=torch.from_numpy(np.stack([d for d, _ in fr]).view(np.int16)).to(dev),
+                                 Twb=dbl(np.stack([T for _, T in fr])), odom=dbl(x), ref_path_init=dbl(ref0) if t == 0 else None,
+                                 keep_warm_start=t > 0))
+        x = x.copy(); x[:, 0] += prm.speed * prm.dt
+
+    def run(gang, positions):
+        """`positions`: per position of the gang, its frames over the periods -> results[position][period]"""
+        pl = Pipeline(1, S, n, n, prm, queue_depth=1, gang=gang, depth=dp)
+        res = [[] for _ in positions]
+        for t in range(periods):
+            outs, tickets = [], []
+            for frames in positions:
+                task = "odom" in frames[t]
+                outs.append(torch.zeros((S, 3 if task else 4), dtype=torch.float64, device=dev))
+                kw = dict(cmd_out=outs[-1]) if task else dict(u_out=outs[-1])
+                tickets.append(pl.submit(frames[t].get("clouds"), frames[t].get("edges"), **kw,
+                                         **{k: v for k, v in frames[t].items() if k not in ("clouds", "edges")}))
+            assert tickets == list(range(len(positions)))                  # one slot: ticket = position in the gang
+            pl.drain()
+            for r, tk, out, frames in zip(res, tickets, outs, positions):
+                o = pl.outputs(tk)
+                if "odom" in frames[t]:
+                    o["cmd"] = out.cpu().numpy()
+                else:
+                    o["u"] = out.cpu().numpy()     # (a gang-1 host-mode frame's control goes to u_out ONLY)
+                r.append(o)
+        pl.close()
+        return res
+
+    got = run(2, [cloud_frames, depth_frames])
+    want = [run(1, [cloud_frames])[0], run(1, [depth_frames])[0]]
+    for pos in range(2):
+        for t in range(periods):
+            assert sorted(got[pos][t]) == sorted(want[pos][t]) == sorted(["u", "flags", "x0array", "ref_path"] + ["cmd"] * pos)
+            for name in got[pos][t]:
+                assert np.array_equal(got[pos][t][name], want[pos][t][name]), (pos, t, name)
+    assert np.abs(got[1][0]["cmd"]).max() > 0 and not np.array_equal(got[1][0]["u"], got[1][1]["u"])   # (the frames ran, and differ)
