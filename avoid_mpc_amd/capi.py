@@ -45,7 +45,7 @@ SYMBOLS = [
     "amk_mpc_hess_sparsity", "amk_mpc_eval", "amk_mpc_eval_host", "amk_mpc_np", "amk_mpc_eval_gamma",
     "amk_mpc_eval_gamma_host", "amk_step_batch", "amk_step_batch_frames", "amk_step_batch_host",
     "amk_pipeline_create", "amk_pipeline_destroy", "amk_pipeline_slots", "amk_pipeline_gang", "amk_pipeline_mpc", "amk_pipeline_kd",
-    "amk_pipeline_kfmap",
+    "amk_pipeline_kfmap", "amk_pipeline_queue_mode",
     "amk_pipeline_stream", "amk_pipeline_submit", "amk_pipeline_wait", "amk_pipeline_query", "amk_pipeline_drain",
     "amk_pipeline_outputs", "amk_pipeline_wait_stream",
     "amk_shard_scene_range", "amk_shard_unique_id", "amk_shard_create", "amk_shard_destroy", "amk_shard_rank",
@@ -110,6 +110,8 @@ class FrameCamera(C.Structure):
 
 
 AMK_DEPTH_U16, AMK_DEPTH_F32 = 0, 1
+AMK_QUEUES_POOLED, AMK_QUEUES_PRIORITY = 0, 1   # amk_pipeline_queue_mode
+AMK_PIPELINE_MAX_OWN_QUEUES = 24
 
 _lib = None
 
@@ -196,7 +198,10 @@ def load():
         "amk_pipeline_submit": (i, [vp, C.POINTER(PipelineFrame), C.POINTER(i)]),
         "amk_pipeline_wait": (i, [vp, i]),
         "amk_pipeline_wait_stream": (i, [vp, i, vp]),
+        "amk_pipeline_queue_mode": (i, [vp, i]),
         "amk__pipeline_inject_failure": (i, [vp, i]),   # internal (tests)
+        "amk__pipeline_queue_policy": (i, [i, i, i, i, vp, vp]),   # internal (tests): pool, n_slots, n_classes, forced -> mode [n], class [n]
+        "amk__pipeline_overlap_probe": (i, [vp, i, vp]),   # internal (tests): start / end clocks [n_slots][2] uint64 of one fixed-length kernel per slot
         "amk_pipeline_query": (i, [vp, i]),
         "amk_pipeline_drain": (i, [vp]),
         "amk_pipeline_outputs": (i, [vp, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),

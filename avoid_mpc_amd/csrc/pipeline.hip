@@ -33,6 +33,7 @@ struct amk_pipeline {
     };
     struct Slot {
         hipStream_t stream = nullptr;
+        int queue_mode = AMK_QUEUES_POOLED;   // how `stream` was really created (amk_pipeline_queue_mode)
         std::vector<hipEvent_t> done;   // ring of queue_depth events: done[k % depth] marks the end of the slot's k-th launch
         long long count = 0;            // gang launches issued on this slot
         long long waited = 0;           // launches known to have finished
@@ -58,6 +59,7 @@ struct amk_pipeline {
     long long submitted = 0;
     int inject_failure = 0;             // tests only (amk__pipeline_inject_failure): the next launch fails at this stage
 };
+extern "C" int amk__pipeline_queue_policy(int pool, int n_slots, int n_classes, int forced, int *mode_out, int *class_out);
 
 namespace {
 // The small inputs of the frames of a gang into the slot's contiguous buffers, and their fresh warm starts, in ONE launch
@@ -465,11 +467,43 @@ int launch_slot(amk_pipeline *p, Slot &s) {
     if (&s == &p->slots[p->next]) p->next = (p->next + 1) % (int)p->slots.size();
     return st;
 }
+// Hardware queues.  The runtime multiplexes a process's streams onto a pool of GPU_MAX_HW_QUEUES hardware queues (4 unless the
+// host exported more before its first HIP call), and two streams on one queue serialise: 10 slots on 4 queues keep 4 chains in
+// flight, not 10.  The runtime keeps one such pool per stream priority class, so a pipeline whose slots
+// are spread over the classes obtains a queue per slot without the host's help -- amk__pipeline_queue_policy says how, per slot.
+// (A stream with a CU mask, hipExtStreamCreateWithCUMask, also gets a queue outside the pool, but it is a BLOCKING stream: it
+// synchronises with the null stream, which a pipeline's slots must not -- profiles/pipeline_queues_ab.txt section 2.)
+int env_int(const char *name, int absent) {
+    const char *e = std::getenv(name);
+    const int v = e ? std::atoi(e) : 0;
+    return v > 0 ? v : absent;
+}
+int forced_queue_mode() {   // AMK_PIPELINE_QUEUES=pooled|priority (A/B runs, tests); anything else: automatic (-1)
+    const char *e = std::getenv("AMK_PIPELINE_QUEUES");
+    if (!e) return -1;
+    return !std::strcmp(e, "pooled") ? AMK_QUEUES_POOLED : !std::strcmp(e, "priority") ? AMK_QUEUES_PRIORITY : -1;
+}
+int g_fail_queue_creation = 0;   // tests only (amk__pipeline_inject_failure(NULL, 3)): the next create's priority stream calls fail
+// The slot's stream in the mode the policy gave it; a creation call that fails leaves the slot with a pooled stream.
+int create_stream(Slot &s, int mode, int priority, bool fail) {
+    s.stream = nullptr;
+    s.queue_mode = AMK_QUEUES_POOLED;
+    if (mode == AMK_QUEUES_PRIORITY) {
+        if (!fail && hipStreamCreateWithPriority(&s.stream, hipStreamNonBlocking, priority) == hipSuccess) {
+            s.queue_mode = AMK_QUEUES_PRIORITY;
+            return AMK_OK;
+        }
+        (void)hipGetLastError();   // (the failed call's sticky record)
+        s.stream = nullptr;
+    }
+    AMK_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+    return AMK_OK;
+}
 // A slot's stream, events, handles and buffers; what a failure leaves behind is amk_pipeline_destroy's
-int create_slot(const amk_pipeline *p, Slot &s) {
+int create_slot(const amk_pipeline *p, Slot &s, int queue_mode, int priority, bool fail_queue) {
     const amk_pipeline_config &cfg = p->cfg;
     const int GS = p->gang * cfg.n_scenes;
-    AMK_HIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+    if (const int st = create_stream(s, queue_mode, priority, fail_queue); st != AMK_OK) return st;
     s.done.assign(p->depth, nullptr);
     for (auto &ev : s.done) AMK_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     int st;
@@ -533,13 +567,54 @@ int amk_pipeline_create(const amk_pipeline_config *cfg, amk_pipeline **out) {
     if (p->depth > AMK_PIPELINE_MAX_DEPTH) p->depth = AMK_PIPELINE_MAX_DEPTH;
     p->gang = cfg->gang > 0 ? cfg->gang : 1;
     p->slots.resize(cfg->n_slots);
-    for (auto &s : p->slots)
-        if (const int st = create_slot(p, s); st != AMK_OK) {
+    // one hardware queue per slot where the runtime's pool is too small for it (queue_policy, above)
+    int least = 0, greatest = 0;   // numerically: greatest <= least (lower numbers are higher priorities)
+    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess || least < greatest) least = greatest = 0;
+    int mode[AMK_PIPELINE_MAX_SLOTS], cls[AMK_PIPELINE_MAX_SLOTS];
+    amk__pipeline_queue_policy(env_int("GPU_MAX_HW_QUEUES", 4), cfg->n_slots, least - greatest + 1, forced_queue_mode(), mode, cls);
+    const bool fail_queue = g_fail_queue_creation != 0;
+    g_fail_queue_creation = 0;
+    for (int i = 0; i < cfg->n_slots; ++i)
+        if (const int st = create_slot(p, p->slots[i], mode[i], greatest + cls[i], fail_queue); st != AMK_OK) {
             amk_pipeline_destroy(p);
             return st;
         }
     *out = p;
     return AMK_OK;
+}
+
+// The policy itself (pure; internal, exported for its test): how each of n_slots slots gets its stream when the runtime's pool
+// holds `pool` hardware queues per priority class and the device has n_classes classes.  forced: AMK_QUEUES_* or -1 (automatic).
+//   pooled     every slot takes a stream from the pool.  Automatic mode picks it when the pool has a queue for every slot and
+//              one for the host's own stream (pool >= n_slots + 1) -- the configuration the documentation asks the host for --
+//              and when the pool already holds AMK_PIPELINE_MAX_OWN_QUEUES queues (nothing may be added).
+//   priority   the slots cycle over the classes (0 = the highest priority) in the order normal, low, high, so that every class's
+//              own pool serves at most `pool` slots; slots beyond n_classes x pool, or beyond AMK_PIPELINE_MAX_OWN_QUEUES, are
+//              pooled (they share).  The order matters, because the dispatcher honours the classes: a slot of a higher class
+//              takes the CUs first, and the host's round robin then waits for the slots of the lower ones.  Of the six orders
+//              this one leaves the high class the fewest slots and is the fastest on the bench's cold line by 6 - 13 %
+//              (profiles/pipeline_queues_ab.txt section 3).
+// mode_out / class_out: [n_slots].  Returns the number of slots that are not pooled.
+int amk__pipeline_queue_policy(int pool, int n_slots, int n_classes, int forced, int *mode_out, int *class_out) {
+    if (pool < 1 || n_slots < 1 || !mode_out || !class_out) return -1;
+    if (n_classes < 1) n_classes = 1;
+    int mode = forced;
+    if (mode != AMK_QUEUES_POOLED && mode != AMK_QUEUES_PRIORITY)
+        mode = (pool >= n_slots + 1 || pool >= AMK_PIPELINE_MAX_OWN_QUEUES) ? AMK_QUEUES_POOLED : AMK_QUEUES_PRIORITY;
+    int own = 0;
+    if (mode == AMK_QUEUES_PRIORITY) own = (int)std::min<long long>(std::min(n_slots, AMK_PIPELINE_MAX_OWN_QUEUES), (long long)n_classes * pool);
+    const int normal = (n_classes - 1) / 2;   // the class of a stream created without a priority (the range is symmetric about it)
+    for (int i = 0; i < n_slots; ++i) {
+        mode_out[i] = i < own ? AMK_QUEUES_PRIORITY : AMK_QUEUES_POOLED;
+        // the cycle: normal, the lower classes, then the higher ones from just above normal up to the highest
+        const int k = i % n_classes;
+        class_out[i] = i < own ? (k < n_classes - normal ? normal + k : n_classes - 1 - k) : normal;
+    }
+    return own;
+}
+
+int amk_pipeline_queue_mode(const amk_pipeline *p, int slot) {
+    return (p && slot >= 0 && slot < (int)p->slots.size()) ? p->slots[slot].queue_mode : -1;
 }
 
 int amk_pipeline_destroy(amk_pipeline *p) {
@@ -657,8 +732,10 @@ int amk_pipeline_drain(amk_pipeline *p) {
 }
 
 // tests only: the next launch of this pipeline fails at stage 1 (after the gather of the small inputs, before the index
-// builds) or 2 (after the builds, before the control step) with AMK_ERR_HIP
+// builds) or 2 (after the builds, before the control step) with AMK_ERR_HIP.  Stage 3, with p == NULL: in the next
+// amk_pipeline_create every priority / dedicated stream creation call fails (the slots fall back to pooled streams).
 int amk__pipeline_inject_failure(amk_pipeline *p, int stage) {
+    if (!p && stage == 3) { g_fail_queue_creation = 1; return AMK_OK; }   // (no pipeline yet: the next amk_pipeline_create's)
     if (!p || stage < 0 || stage > 2) return AMK_ERR_INVALID_ARG;
     p->inject_failure = stage;
     return AMK_OK;

@@ -506,6 +506,10 @@ class Pipeline:
         """GetPtCloud of one scene of the slot's keyframe map (synchronises the device) -> (xyz [n, 3], frame_sizes [F])."""
         return self.kfmap(slot).points(scene)
 
+    def queue_mode(self, slot):
+        """amk_pipeline_queue_mode: how the slot's stream was really created (capi.AMK_QUEUES_POOLED / _PRIORITY)."""
+        return self.lib.amk_pipeline_queue_mode(self.h, int(slot))
+
     def mpc(self, slot):
         return self._mpc[slot]
 

@@ -391,9 +391,18 @@ int amk_step_batch_host(amk_kd *obstacle, amk_kd *edge, amk_mpc *mpc, const amk_
  * A pipeline owns n_slots slots = {HIP stream, obstacle + edge amk_kd, amk_mpc, reference-path buffer, outputs}; submit()
  * enqueues on the next slot (round robin) -- per frame the reference's sequence FrameKDMap::AddVertex (FrameKDMap.cpp:34-52: the two
  * InitializeNew) -> AvoidanceStateMachine::Step TASK branch (AvoidanceStateMachine.cpp:322-355) -- and returns at once;
- * it blocks only when queue_depth steps of that slot are still unfinished.  The host should export GPU_MAX_HW_QUEUES >= n_slots
- * before the first HIP call (ROCm multiplexes streams onto 4 hardware queues by default; two streams on one queue
- * serialise).  Input buffers belong to the caller and must stay valid until the slot has finished.  They must also be
+ * it blocks only when queue_depth steps of that slot are still unfinished.  Hardware queues: ROCm multiplexes a process's
+ * streams onto GPU_MAX_HW_QUEUES hardware queues (4 by default) and two streams on one queue serialise.  The host no longer has
+ * to export that variable: when it names fewer than n_slots + 1 queues (absent = 4), amk_pipeline_create creates the slots'
+ * streams over the device's stream priority classes (the runtime keeps a pool of queues per class), cycling normal, low, high,
+ * so that no class's pool serves more slots than it holds; slots beyond classes x pool share.  That recovers part of the loss,
+ * not all of it (the dispatcher honours the classes: 10 slots x gang 4 reach 0.55 M steps/s, against 0.43 M with shared queues
+ * and 0.60 M with GPU_MAX_HW_QUEUES=32 -- DESIGN.md section 7), so a host that can export GPU_MAX_HW_QUEUES >= n_slots + 1 (at
+ * most 32) before its first HIP call still should: it gets ordinary streams, as before.  The pipeline never adds more than
+ * AMK_PIPELINE_MAX_OWN_QUEUES (24) queues to the process, and a creation call that fails leaves that slot with an ordinary
+ * stream.  AMK_PIPELINE_QUEUES=pooled|priority forces one way for every pipeline of the process (A/B runs);
+ * amk_pipeline_queue_mode reports what a slot got.  Every slot's stream is a non-blocking stream either way.
+ * Input buffers belong to the caller and must stay valid until the slot has finished.  They must also be
  * COMPLETE: a slot runs on its own non-blocking stream, which is not ordered against the stream that produced the inputs, and
  * with a gang the inputs are only read when the gang is launched (the G-th submit, wait or drain).  Either synchronise the
  * producing stream before submit(), or record an event on it and pass it as amk_pipeline_frame.input_ready -- the slot's stream
@@ -429,6 +438,9 @@ typedef struct amk_task_params {
 #define AMK_PIPELINE_DEFAULT_DEPTH 3
 #define AMK_PIPELINE_MAX_DEPTH 64
 #define AMK_PIPELINE_MAX_GANG 8
+#define AMK_PIPELINE_MAX_OWN_QUEUES 24   /* hardware queues the pipeline's streams may add to the process */
+#define AMK_QUEUES_POOLED 0              /* amk_pipeline_queue_mode: hipStreamCreateWithFlags (the runtime's pool)              */
+#define AMK_QUEUES_PRIORITY 1            /* hipStreamCreateWithPriority, the slots spread over the priority classes            */
 /* FrameKDMap's keyframe parameters (the batched map itself: amk_kfmap_*, below) */
 typedef struct amk_kfmap amk_kfmap;
 typedef struct amk_kfmap_params {
@@ -532,6 +544,7 @@ int amk_pipeline_create(const amk_pipeline_config *cfg, amk_pipeline **out);
 int amk_pipeline_destroy(amk_pipeline *p);
 int amk_pipeline_slots(const amk_pipeline *p);
 int amk_pipeline_gang(const amk_pipeline *p);       /* frames per launch (>= 1)                                            */
+int amk_pipeline_queue_mode(const amk_pipeline *p, int slot);   /* AMK_QUEUES_*: how the slot's stream was really created; -1: no such slot */
 /* The slot's handles, to configure them (weights, limits, tie order, precision ...) and its stream.                       */
 amk_mpc *amk_pipeline_mpc(amk_pipeline *p, int slot);
 amk_kd *amk_pipeline_kd(amk_pipeline *p, int slot, int which /* 0 obstacle, 1 edge */);
