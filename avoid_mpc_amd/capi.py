@@ -53,6 +53,7 @@ SYMBOLS = [
     "amk_shard_rccl_info", "amk_shard_wait",
     "amk_depth_out_size", "amk_depth_to_cloud", "amk_depth_to_cloud_host",
     "amk_depth_to_edge_cloud", "amk_depth_to_edge_cloud_host",
+    "amk_depth_clouds_work_bytes", "amk_depth_to_clouds", "amk_depth_to_clouds_host",
 ]
 
 
@@ -245,6 +246,11 @@ def load():
         "amk_depth_to_cloud_host": (i, [vp, i, i, i, C.c_longlong, i, C.POINTER(DepthParams), vp, vp, i, C.c_longlong, vp]),
         "amk_depth_to_edge_cloud": (i, [vp, i, i, i, C.c_longlong, i, C.POINTER(DepthParams), vp, vp, i, C.c_longlong, vp, vp]),
         "amk_depth_to_edge_cloud_host": (i, [vp, i, i, i, C.c_longlong, i, C.POINTER(DepthParams), vp, vp, i, C.c_longlong, vp]),
+        "amk_depth_clouds_work_bytes": (i, [i, i, d, i, C.POINTER(C.c_longlong)]),
+        "amk_depth_to_clouds": (i, [vp, i, i, i, C.c_longlong, i, C.POINTER(DepthParams), vp, vp, vp, C.c_longlong, vp, vp, C.c_longlong, vp,
+                                    i, vp, C.c_longlong, vp]),
+        "amk_depth_to_clouds_host": (i, [vp, i, i, i, C.c_longlong, i, C.POINTER(DepthParams), vp, vp, vp, C.c_longlong, vp, vp, C.c_longlong,
+                                         vp, i]),
     }
     sig["amk__kd_set_mode"] = (i, [vp, i])  # internal: 0 bucketed index, 1 streaming scan
     sig["amk__sweep_set_target"] = (None, [i])  # internal (tests, A/B): the pool's sweep against 1 a fine hashed grid of the current frame (default), 0 the frame's own index
@@ -252,6 +258,7 @@ def load():
     sig["amk__frames_force_wide"] = (None, [i])  # internal (tests): 1 the multi-frame step's merge re-reads its candidates every round whatever the map's size
     sig["amk__mpc_ref_states"] = (i, [vp, vp, ll])  # internal (tests): host copy of the P vectors the last step's newest pass handed to the solve
     sig["amk__kfmap_slots_host"] = (i, [vp, vp, vp, vp, vp, vp])  # internal (tests): cur_slot [S], kf_n [S], kf_slots [S][P], fmap [F][S], need [S] of a keyframe map
+    sig["amk__depth_set_band_rows"] = (i, [i])  # internal (tests, measurements): amk_depth_to_clouds tiled with bands of this many rows at any image size; 0 automatic
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)
         if fn is None:

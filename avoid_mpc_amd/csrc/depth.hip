@@ -2,10 +2,13 @@
 // (AM/src/FrameKDMap.cpp:90-130 with GetInvDepthImg :76-89 and UV2Camera :131-138; AM = roswrapper/ros/src/avoid_mpc
 // in the reference tree).  SURVEY.md section 8 row f2: the per-pixel streaming step right before the tree build.
 //
-// One block per scene.  Only the 2x2 raw pixels under each down-scaled pixel are read (4 % of a 640x480 image at
+// amk_depth_to_cloud / amk_depth_to_edge_cloud: one block per scene (the edge cloud up to AMK_EDGE_MAX_PIXELS pixels);
+// amk_depth_to_clouds: both clouds, above that size on one block per band of rows (depth_band_kernel).
+// Only the 2x2 raw pixels under each down-scaled pixel are read (4 % of a 640x480 image at
 // resize_scale 10): the reference inverts the whole image and then lets cv::resize pick the same four taps.
 // The kept pixels are appended in row-major order (ballot + popcount prefix per wave, LDS combine per block),
 // which is the order the reference's emplace_back produces and therefore the index space of the KD tree.
+#include <algorithm>
 #include <cstring>
 
 #include "amk_common.h"
@@ -225,6 +228,186 @@ __global__ __launch_bounds__(kDepthThreads) void depth_to_cloud_kernel(const T *
     if (tid == 0) counts[s] = base;
 }
 
+// ---- Both clouds of a down-scaled image of any size (amk_depth_to_clouds): grid (bands, scenes), one block per band of R whole
+// down-scaled rows of one scene.  Whole rows keep band order = row-major pixel order.  A band decides its rows [r0, r1) from a halo
+// of 3 rows on each side, all in LDS: quantised depth over [r0 - 3, r1 + 3), its erosion over [r0 - 2, r1 + 2), the Sobel magnitude
+// over [r0 - 1, r1 + 1) -- W * (4 R + 14) bytes.  Every range is clipped to the IMAGE: a row of a neighbouring band is a real row
+// (recomputed here), a row outside the image is what the one-block kernel above makes of it (an ignored erosion tap, a replicated
+// Sobel tap, a zero magnitude).
+// Two launches of the same body.  EMIT = false writes {kept obstacle pixels, edge points} of the band into band_counts[scene][band].
+// EMIT = true sums the counts of the bands before its own (no block waits for another: what crosses bands crosses the launch
+// boundary), learns from the scene's obstacle total whether the scene is empty, redoes the band and appends its points at its offsets.
+template <typename T, bool EMIT>
+__global__ __launch_bounds__(kDepthThreads) void depth_band_kernel(const T *__restrict__ depth, long long scene_stride, DepthGeom g,
+                                                                   int R, const double *__restrict__ Twb,
+                                                                   const double *__restrict__ Twc, float *__restrict__ cloud,
+                                                                   long long cloud_scene_stride, int *__restrict__ counts,
+                                                                   float *__restrict__ edge_cloud, long long edge_scene_stride,
+                                                                   int *__restrict__ edge_counts, int point_stride,
+                                                                   int2 *__restrict__ band_counts) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char band_smem[];
+    const int b = blockIdx.x, nb = gridDim.x, s = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int W = g.W, H = g.H;
+    const int r0 = b * R, r1 = min(H, r0 + R);
+    unsigned char *quant = band_smem;                        // image row r at row r - (r0 - 3)
+    unsigned char *ero = band_smem + (size_t)(R + 6) * W;    //               at row r - (r0 - 2)
+    short *mag = reinterpret_cast<short *>(band_smem + (size_t)(2 * R + 10) * W);   //  at row r - (r0 - 1)
+    const T *img = depth + (long long)s * scene_stride;
+    __shared__ double Mb[12], Mc[12];   // rows 0..2 of Twb * Tbc (obstacle points) and of Twc * Tbc (edge points)
+    __shared__ int wave_tot[kDepthThreads / 64];
+    __shared__ int red[kDepthThreads / 64][4];
+    int obs_base = 0, edge_base = 0;
+    bool want_edges = true;
+    if (EMIT) {
+        const int2 *bc = band_counts + (size_t)s * nb;
+        int acc[4] = {0, 0, 0, 0};   // obstacle / edge points of the bands before this one, of the whole scene
+        for (int j = tid; j < nb; j += kDepthThreads) {
+            const int2 v = bc[j];
+            acc[0] += j < b ? v.x : 0;
+            acc[1] += j < b ? v.y : 0;
+            acc[2] += v.x;
+            acc[3] += v.y;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            for (int off = 32; off > 0; off >>= 1) acc[k] += __shfl_xor(acc[k], off, 64);
+            if (lane == 0) red[wv][k] = acc[k];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
+        const bool empty = acc[2] == 0;   // cloud->empty(): BuildEdgeCloud is not reached (:126-128)
+        if (b == 0 && tid == 0) {
+            counts[s] = acc[2];
+            edge_counts[s] = empty ? 0 : acc[3];
+        }
+        const int2 mine = bc[b];
+        if (empty || (mine.x == 0 && mine.y == 0)) return;   // (block-uniform)
+        obs_base = acc[0]; edge_base = acc[1];
+        want_edges = mine.y > 0;
+        pose_times_tbc(Twb + 16 * s, g, Mb);   // (mat4Twb * mParamTbc), :119-120
+        pose_times_tbc(Twc + 16 * s, g, Mc);   // (mCurFrame.Twc * mParamTbc), :209
+        __syncthreads();
+    }
+    const double range = g.dmax - g.dmin;
+    // inverse depth once per pixel: the quantised layer over the band and its halo, and ProcessDepth's points of the band's own rows
+    const int qlo = want_edges ? max(r0 - 3, 0) : r0, qhi = want_edges ? min(r1 + 3, H) : r1, nq = (qhi - qlo) * W;
+    float *out = cloud + (long long)s * cloud_scene_stride;
+    int n_obs = 0;
+    for (int p0 = 0; p0 < nq; p0 += kDepthThreads) {
+        const int p = p0 + tid;
+        bool keep = false;
+        float px = 0.f, py = 0.f, pz = 0.f;
+        if (p < nq) {
+            const int row = qlo + p / W, col = p % W;
+            const float inv = small_inv(img, row, col, g);
+            const double invd = (double)inv;
+            if (row >= r0 && row < r1 && !(invd < 1e-2)) {                  // :113-115
+                const double d = 1.0 / invd;                                // :116
+                if (d > g.dmin && d < g.dmax) {                             // :117
+                    if (EMIT) {
+                        const double xc = ((double)col - g.cx) * d / g.fx;  // UV2Camera :133-136
+                        const double yc = ((double)row - g.cy) * d / g.fy;
+                        px = (float)(((Mb[0] * xc + Mb[1] * yc) + Mb[2] * d) + Mb[3]);
+                        py = (float)(((Mb[4] * xc + Mb[5] * yc) + Mb[6] * d) + Mb[7]);
+                        pz = (float)(((Mb[8] * xc + Mb[9] * yc) + Mb[10] * d) + Mb[11]);
+                    }
+                    keep = true;
+                }
+            }
+            quant[(row - r0 + 3) * W + col] =
+                invd > 1e-2 ? (unsigned char)((double)(1 / inv) / range * (double)200.0f) : (unsigned char)255;  // :183-191
+        }
+        if (EMIT) obs_base = append_round(keep, px, py, pz, out, point_stride, obs_base, wave_tot);
+        else n_obs += keep ? 1 : 0;
+    }
+    __syncthreads();
+    int n_edge = 0;
+    if (want_edges) {
+        const int elo = max(r0 - 2, 0), ne = (min(r1 + 2, H) - elo) * W;
+        for (int p = tid; p < ne; p += kDepthThreads) {   // cv::erode 3x3, taps outside the IMAGE ignored
+            const int r = elo + p / W, c = p % W;
+            int m = 255;
+            for (int dr = -1; dr <= 1; ++dr)
+                for (int dc = -1; dc <= 1; ++dc) {
+                    const int rr = r + dr, cc = c + dc;
+                    if (rr >= 0 && rr < H && cc >= 0 && cc < W) m = min(m, (int)quant[(rr - r0 + 3) * W + cc]);
+                }
+            ero[(r - r0 + 2) * W + c] = (unsigned char)m;
+        }
+        __syncthreads();
+        auto epx = [&](int r, int c) { return (int)ero[(min(max(r, 0), H - 1) - r0 + 2) * W + min(max(c, 0), W - 1)]; };  // BORDER_REPLICATE
+        auto sobx = [&](int r, int c) {
+            return (epx(r - 1, c + 1) + 2 * epx(r, c + 1) + epx(r + 1, c + 1)) - (epx(r - 1, c - 1) + 2 * epx(r, c - 1) + epx(r + 1, c - 1));
+        };
+        auto soby = [&](int r, int c) {
+            return (epx(r + 1, c - 1) + 2 * epx(r + 1, c) + epx(r + 1, c + 1)) - (epx(r - 1, c - 1) + 2 * epx(r - 1, c) + epx(r - 1, c + 1));
+        };
+        const int mlo = max(r0 - 1, 0), nm = (min(r1 + 1, H) - mlo) * W;
+        for (int p = tid; p < nm; p += kDepthThreads) {
+            const int r = mlo + p / W, c = p % W;
+            mag[(r - r0 + 1) * W + c] = (short)(abs(sobx(r, c)) + abs(soby(r, c)));
+        }
+        __syncthreads();
+        auto mg = [&](int r, int c) { return (r < 0 || r >= H || c < 0 || c >= W) ? 0 : (int)mag[(r - r0 + 1) * W + c]; };
+        float *eout = edge_cloud + (long long)s * edge_scene_stride;
+        const int nown = (r1 - r0) * W;
+        for (int p0 = 0; p0 < nown; p0 += kDepthThreads) {
+            const int p = p0 + tid;
+            bool keep = false;
+            float px = 0.f, py = 0.f, pz = 0.f;
+            if (p < nown) {
+                const int r = r0 + p / W, c = p % W, m = mg(r, c);
+                bool edge = false;
+                if (m > 0) {
+                    const int xs = sobx(r, c), ys = soby(r, c);
+                    const int x = abs(xs), y = abs(ys) << 15, tg22x = x * 13573;
+                    if (y < tg22x) edge = m > mg(r, c - 1) && m >= mg(r, c + 1);
+                    else if (y > tg22x + (x << 16)) edge = m > mg(r - 1, c) && m >= mg(r + 1, c);
+                    else {
+                        const int sg = ((xs ^ ys) < 0) ? -1 : 1;
+                        edge = m > mg(r - 1, c - sg) && m > mg(r + 1, c + sg);
+                    }
+                }
+                if (edge) {
+                    double d = (double)(float)ero[(r - r0 + 2) * W + c];   // :199
+                    d = d * range / 200.0;                                 // :200
+                    if (!(d > g.dmax || d < g.dmin)) {                     // :201-203
+                        if (EMIT) {
+                            const double xc = ((double)c - g.cx) * d / g.fx, yc = ((double)r - g.cy) * d / g.fy;
+                            px = (float)(((Mc[0] * xc + Mc[1] * yc) + Mc[2] * d) + Mc[3]);
+                            py = (float)(((Mc[4] * xc + Mc[5] * yc) + Mc[6] * d) + Mc[7]);
+                            pz = (float)(((Mc[8] * xc + Mc[9] * yc) + Mc[10] * d) + Mc[11]);
+                        }
+                        keep = true;
+                    }
+                }
+            }
+            if (EMIT) edge_base = append_round(keep, px, py, pz, eout, point_stride, edge_base, wave_tot);
+            else n_edge += keep ? 1 : 0;
+        }
+    }
+    if (!EMIT) {
+        for (int off = 32; off > 0; off >>= 1) {
+            n_obs += __shfl_xor(n_obs, off, 64);
+            n_edge += __shfl_xor(n_edge, off, 64);
+        }
+        if (lane == 0) { red[wv][0] = n_obs; red[wv][1] = n_edge; }
+        __syncthreads();
+        if (tid == 0)
+            band_counts[(size_t)s * nb + b] = make_int2((red[0][0] + red[1][0]) + (red[2][0] + red[3][0]),
+                                                        (red[0][1] + red[1][1]) + (red[2][1] + red[3][1]));
+    }
+}
+
+// Band height.  All three layers of a band take W * (4 R + 14) bytes of LDS; within 64 KiB less the kernel's few static words that is
+// R <= band_rows_max(W): 16+ up to W = 812, 4 at AMK_DEPTH_MAX_WIDTH.  The call takes min(16, that): 49 920 B at W = 640, so two
+// workgroups still share a CU's LDS.
+constexpr int kBandLdsBudget = 64 * 1024 - 512;
+constexpr int kBandRowsAuto = 16;
+int band_rows_max(int W) { return (kBandLdsBudget / W - 14) / 4; }
+int g_forced_band_rows = 0;   // amk__depth_set_band_rows (tests): > 0 forces the tiled path with this band height
+
 int make_geom(int rows, int cols, const amk_depth_params *p, DepthGeom &g) {
     if (!p || rows <= 0 || cols <= 0 || !(p->resize_scale > 0)) return AMK_ERR_INVALID_ARG;
     g.rows = rows; g.cols = cols;
@@ -294,6 +477,107 @@ int amk_depth_to_edge_cloud(const void *d_depth, int depth_type, int rows, int c
         hipLaunchKernelGGL(depth_to_edge_kernel<float>, dim3(n_scenes), dim3(kDepthThreads), lds, (hipStream_t)stream,
                            (const float *)d_depth, scene_stride, g, d_Twc, d_cloud, point_stride, cloud_scene_stride, d_counts);
     AMK_HIP(hipGetLastError());
+    return AMK_OK;
+}
+
+// tests only (exported, not in the header): force amk_depth_to_clouds onto the tiled kernels with bands of this many rows (clipped to
+// what the LDS holds at the image's width) at any image size; 0 = automatic
+int amk__depth_set_band_rows(int band_rows) {
+    if (band_rows < 0) return AMK_ERR_INVALID_ARG;
+    g_forced_band_rows = band_rows;
+    return AMK_OK;
+}
+
+// {obstacle, edge} count of every band of every scene, for the smallest band (one row): covers any band height
+int amk_depth_clouds_work_bytes(int rows, int cols, double resize_scale, int n_scenes, long long *bytes_out) {
+    int w = 0, h = 0;
+    if (!bytes_out || n_scenes <= 0) return AMK_ERR_INVALID_ARG;
+    if (const int st = amk_depth_out_size(rows, cols, resize_scale, &w, &h); st != AMK_OK) return st;
+    *bytes_out = (long long)sizeof(int2) * h * n_scenes;
+    return AMK_OK;
+}
+
+int amk_depth_to_clouds(const void *d_depth, int depth_type, int rows, int cols, long long scene_stride, int n_scenes,
+                        const amk_depth_params *params, const double *d_Twb, const double *d_Twc, float *d_cloud,
+                        long long cloud_scene_stride, int *d_counts, float *d_edge, long long edge_scene_stride,
+                        int *d_edge_counts, int point_stride, void *d_work, long long work_bytes, void *stream) {
+    if (!d_depth || !d_Twb || !d_Twc || !d_cloud || !d_counts || !d_edge || !d_edge_counts || !d_work || n_scenes <= 0 ||
+        point_stride < 3)
+        return AMK_ERR_INVALID_ARG;
+    if (depth_type != AMK_DEPTH_U16 && depth_type != AMK_DEPTH_F32) return AMK_ERR_UNSUPPORTED;
+    DepthGeom g;
+    int st = make_geom(rows, cols, params, g);
+    if (st != AMK_OK) return st;
+    const long long cap = (long long)g.W * g.H * point_stride;
+    if (scene_stride < (long long)rows * cols || cloud_scene_stride < cap || edge_scene_stride < cap) return AMK_ERR_INVALID_ARG;
+    if (work_bytes < (long long)sizeof(int2) * g.H * n_scenes) return AMK_ERR_INVALID_ARG;
+    if (g.W > AMK_DEPTH_MAX_WIDTH) return AMK_ERR_UNSUPPORTED;
+    const int forced = g_forced_band_rows;
+    const bool one_block = forced <= 0 && (long long)g.W * g.H <= AMK_EDGE_MAX_PIXELS;
+    if (!one_block && n_scenes > 65535) return AMK_ERR_UNSUPPORTED;   // (scenes are the grid's second dimension)
+    if (amk_device_count() <= 0) return AMK_ERR_NO_DEVICE;
+    if (one_block) {   // the one-block kernels, as the two calls launch them
+        st = amk_depth_to_cloud(d_depth, depth_type, rows, cols, scene_stride, n_scenes, params, d_Twb, d_cloud, point_stride,
+                                cloud_scene_stride, d_counts, stream);
+        if (st != AMK_OK) return st;
+        return amk_depth_to_edge_cloud(d_depth, depth_type, rows, cols, scene_stride, n_scenes, params, d_Twc, d_edge, point_stride,
+                                       edge_scene_stride, d_edge_counts, stream);
+    }
+    const int R = std::min(forced > 0 ? forced : kBandRowsAuto, band_rows_max(g.W));
+    const dim3 grid((g.H + R - 1) / R, n_scenes);
+    const size_t lds = (size_t)g.W * (4 * R + 14);
+    int2 *bc = (int2 *)d_work;
+    const hipStream_t hs = (hipStream_t)stream;
+#define AMK_BAND_LAUNCH(T, EMIT)                                                                                                   \
+    hipLaunchKernelGGL((depth_band_kernel<T, EMIT>), grid, dim3(kDepthThreads), lds, hs, (const T *)d_depth, scene_stride, g, R,   \
+                       d_Twb, d_Twc, d_cloud, cloud_scene_stride, d_counts, d_edge, edge_scene_stride, d_edge_counts, point_stride, bc)
+    if (depth_type == AMK_DEPTH_U16) {
+        AMK_BAND_LAUNCH(unsigned short, false);
+        AMK_BAND_LAUNCH(unsigned short, true);
+    } else {
+        AMK_BAND_LAUNCH(float, false);
+        AMK_BAND_LAUNCH(float, true);
+    }
+#undef AMK_BAND_LAUNCH
+    AMK_HIP(hipGetLastError());
+    return AMK_OK;
+}
+
+int amk_depth_to_clouds_host(const void *h_depth, int depth_type, int rows, int cols, long long scene_stride, int n_scenes,
+                             const amk_depth_params *params, const double *h_Twb, const double *h_Twc, float *h_cloud,
+                             long long cloud_scene_stride, int *h_counts, float *h_edge, long long edge_scene_stride,
+                             int *h_edge_counts, int point_stride) {
+    if (!h_depth || !h_Twb || !h_Twc || !h_cloud || !h_counts || !h_edge || !h_edge_counts || n_scenes <= 0 || scene_stride <= 0 ||
+        cloud_scene_stride <= 0 || edge_scene_stride <= 0)
+        return AMK_ERR_INVALID_ARG;
+    if (depth_type != AMK_DEPTH_U16 && depth_type != AMK_DEPTH_F32) return AMK_ERR_UNSUPPORTED;
+    long long work_bytes = 0;
+    if (const int st = amk_depth_clouds_work_bytes(rows, cols, params ? params->resize_scale : 0.0, n_scenes, &work_bytes); st != AMK_OK)
+        return st;
+    if (amk_device_count() <= 0) return AMK_ERR_NO_DEVICE;
+    const size_t esz = depth_type == AMK_DEPTH_U16 ? 2 : 4;
+    amk::DevBuf<unsigned char> img, work;
+    amk::DevBuf<double> pose;   // [2][S][16]: Twb, Twc
+    amk::DevBuf<float> cloud, edge;
+    amk::DevBuf<int> cnt;       // [2][S]: obstacle, edge
+    AMK_HIP(img.alloc((size_t)scene_stride * n_scenes * esz));
+    AMK_HIP(work.alloc((size_t)work_bytes));
+    AMK_HIP(pose.alloc((size_t)32 * n_scenes));
+    AMK_HIP(cloud.alloc((size_t)cloud_scene_stride * n_scenes));
+    AMK_HIP(edge.alloc((size_t)edge_scene_stride * n_scenes));
+    AMK_HIP(cnt.alloc((size_t)2 * n_scenes));
+    AMK_HIP(hipMemcpy(img.p, h_depth, (size_t)scene_stride * n_scenes * esz, hipMemcpyHostToDevice));
+    AMK_HIP(hipMemcpy(pose.p, h_Twb, sizeof(double) * 16 * n_scenes, hipMemcpyHostToDevice));
+    AMK_HIP(hipMemcpy(pose.p + (size_t)16 * n_scenes, h_Twc, sizeof(double) * 16 * n_scenes, hipMemcpyHostToDevice));
+    const int st = amk_depth_to_clouds(img.p, depth_type, rows, cols, scene_stride, n_scenes, params, pose.p,
+                                       pose.p + (size_t)16 * n_scenes, cloud.p, cloud_scene_stride, cnt.p, edge.p, edge_scene_stride,
+                                       cnt.p + n_scenes, point_stride, work.p, work_bytes, nullptr);
+    if (st != AMK_OK) return st;
+    AMK_HIP(hipDeviceSynchronize());
+    AMK_HIP(hipMemcpy(h_counts, cnt.p, sizeof(int) * n_scenes, hipMemcpyDeviceToHost));
+    AMK_HIP(hipMemcpy(h_edge_counts, cnt.p + n_scenes, sizeof(int) * n_scenes, hipMemcpyDeviceToHost));
+    AMK_HIP(hipMemcpy(h_cloud, cloud.p, sizeof(float) * (size_t)cloud_scene_stride * n_scenes, hipMemcpyDeviceToHost));
+    AMK_HIP(hipMemcpy(h_edge, edge.p, sizeof(float) * (size_t)edge_scene_stride * n_scenes, hipMemcpyDeviceToHost));
     return AMK_OK;
 }
 

@@ -47,6 +47,7 @@ struct amk_pipeline {
         amk::DevBuf<float> dcloud, dedge;      // [G S][max_points][3], [G S][max_edge_points][3]
         amk::DevBuf<int> dcount, decount;      // [G S]
         amk::DevBuf<double> Twc;               // [G S][16]
+        amk::DevBuf<unsigned char> dwork;      // amk_depth_to_clouds' workspace: the positions of a gang run on one stream, so one serves them
         bool ref_inited[AMK_PIPELINE_MAX_GANG] = {};   // TASK mode: position g holds an mRefPath (a frame with d_ref_path_init ran
                                         // there, and no launch has failed half-way since)
         amk_kfmap *map = nullptr;       // amk_pipeline_config.keyframes.max_frame_count > 0: the slot's keyframe map (gang x n_scenes scenes)
@@ -256,7 +257,7 @@ struct Launch {
     const amk_pipeline_frame &frame(int g) const { return s.open[g].frame; }
     int wait_for_inputs(), restart_robots(), gather_inputs(), depth_stage();   // the stages, in launch_gang's order
     int build_indices(Stopwatch &watch), control_step(), finish();
-    int ensure_depth_buffers(), depth_camera(amk_frame_camera *cam);   // (parts of depth_stage and control_step)
+    int ensure_depth_buffers(long long work_bytes), depth_camera(amk_frame_camera *cam);   // (parts of depth_stage and control_step)
 };
 int Launch::wait_for_inputs() {   // inputs produced on the caller's streams: ordered on the device, not by the host
     for (const auto &o : s.open)
@@ -310,13 +311,24 @@ int Launch::gather_inputs() {
     return AMK_OK;
 }
 // The slot's own clouds, counts and Twc, allocated by its first depth frame -- or again after an attempt that ran out of memory
-// half-way: all five buffers or none.  Every scene's Twc starts from the identity.
-int Launch::ensure_depth_buffers() {
-    if (s.dcloud.p && s.dedge.p && s.dcount.p && s.decount.p && s.Twc.p) return AMK_OK;
+// half-way: all six buffers or none.  Every scene's Twc starts from the identity.  The workspace of amk_depth_to_clouds
+// is the only one that depends on the image: a later frame with more rows gets a larger one (hipFree waits for the device, so no
+// launch in flight still reads the old one; the other five, and with them every scene's Twc, stay).
+int Launch::ensure_depth_buffers(long long work_bytes) {
+    const auto release_all = [this] { s.dcloud.release(); s.dedge.release(); s.dcount.release(); s.decount.release(); s.Twc.release(); s.dwork.release(); };
+    if (s.dcloud.p && s.dedge.p && s.dcount.p && s.decount.p && s.Twc.p && s.dwork.p) {
+        if ((long long)s.dwork.n >= work_bytes) return AMK_OK;
+        if (const hipError_t e = s.dwork.alloc((size_t)work_bytes); e != hipSuccess) {
+            release_all();
+            return amk::hip_fail(e);
+        }
+        return AMK_OK;
+    }
     const size_t GS = (size_t)G * S;
-    const hipError_t e = alloc_all(s.dcloud, GS * c.max_points * 3, s.dedge, GS * c.max_edge_points * 3, s.dcount, GS, s.decount, GS, s.Twc, GS * 16);
+    const hipError_t e = alloc_all(s.dcloud, GS * c.max_points * 3, s.dedge, GS * c.max_edge_points * 3, s.dcount, GS, s.decount, GS, s.Twc, GS * 16,
+                                   s.dwork, (size_t)work_bytes);
     if (e != hipSuccess) {
-        s.dcloud.release(); s.dedge.release(); s.dcount.release(); s.decount.release(); s.Twc.release();
+        release_all();
         return amk::hip_fail(e);
     }
     hipLaunchKernelGGL(pipeline_twc_init_kernel, dim3((unsigned)((GS * 16 + 255) / 256)), dim3(256), 0, st, s.Twc.p, (int)GS);
@@ -333,16 +345,16 @@ int Launch::depth_stage() {
             continue;
         }
         if (s.point_stride != 3) return AMK_ERR_INVALID_ARG;   // the slot's own clouds are packed xyz
-        if (const int rc = ensure_depth_buffers(); rc != AMK_OK) return rc;
+        long long work_bytes = 0;
+        if (const int rc = amk_depth_clouds_work_bytes(f.depth_rows, f.depth_cols, c.depth.resize_scale, S, &work_bytes); rc != AMK_OK) return rc;
+        if (const int rc = ensure_depth_buffers(work_bytes); rc != AMK_OK) return rc;
         any_depth = true;
         const size_t o = (size_t)g * S;
         float *dc = s.dcloud.p + o * c.max_points * 3, *de = s.dedge.p + o * c.max_edge_points * 3;
         const long long img = (long long)f.depth_rows * f.depth_cols;
-        int rc = amk_depth_to_cloud(f.d_depth, f.depth_type, f.depth_rows, f.depth_cols, img, S, &c.depth, f.d_Twb, dc, 3,
-                                    (long long)c.max_points * 3, s.dcount.p + o, st);
-        if (rc != AMK_OK) return rc;
-        rc = amk_depth_to_edge_cloud(f.d_depth, f.depth_type, f.depth_rows, f.depth_cols, img, S, &c.depth, s.Twc.p + o * 16, de, 3,
-                                     (long long)c.max_edge_points * 3, s.decount.p + o, st);
+        const int rc = amk_depth_to_clouds(f.d_depth, f.depth_type, f.depth_rows, f.depth_cols, img, S, &c.depth, f.d_Twb, s.Twc.p + o * 16, dc,
+                                           (long long)c.max_points * 3, s.dcount.p + o, de, (long long)c.max_edge_points * 3, s.decount.p + o, 3,
+                                           s.dwork.p, (long long)s.dwork.n, st);
         if (rc != AMK_OK) return rc;
         hipLaunchKernelGGL(pipeline_twc_update_kernel, dim3((S * 16 + 255) / 256), dim3(256), 0, st, f.d_Twb, s.dcount.p + o, s.Twc.p + o * 16, S, c.depth);
         AMK_HIP(hipGetLastError());
@@ -531,7 +543,7 @@ int frame_args(const amk_pipeline_config &c, const amk_pipeline_frame *f) {
         int w = 0, h = 0;
         if (amk_depth_out_size(f->depth_rows, f->depth_cols, c.depth.resize_scale, &w, &h) != AMK_OK) return AMK_ERR_INVALID_ARG;
         if ((long long)w * h > c.max_points || (long long)w * h > c.max_edge_points) return AMK_ERR_INVALID_ARG;
-        if ((long long)w * h > AMK_EDGE_MAX_PIXELS) return AMK_ERR_UNSUPPORTED;
+        if (w > AMK_DEPTH_MAX_WIDTH) return AMK_ERR_UNSUPPORTED;   // (amk_depth_to_clouds: any number of pixels, bands of whole rows)
     } else if (!f->d_cloud || !f->d_edge) return AMK_ERR_INVALID_ARG;
     if (!f->d_odom && (!f->d_state_quad || !f->d_pos_x || !f->d_ref_path_init)) return AMK_ERR_INVALID_ARG;
     return (f->n_keyframes < 0 || f->n_keyframes > AMK_MAX_FRAMES - 1) ? AMK_ERR_INVALID_ARG : AMK_OK;

@@ -716,3 +716,32 @@ def depth_to_cloud(depth, params, Twb, point_stride=3, stream=None, edge=False):
                   int(point_stride), cap * point_stride, capi.dptr(counts), capi.stream_ptr(stream)),
                "amk_depth_to_edge_cloud" if edge else "amk_depth_to_cloud")
     return cloud, counts
+
+
+def depth_to_clouds(depth, params, Twb, Twc, point_stride=3, stream=None):
+    """AddVertex's image half for a batch, FrameKDMap::ProcessDepth followed by FrameKDMap::BuildEdgeCloud, in one call and for
+    down-scaled images of any size (amk_depth_to_clouds): depth [S, rows, cols] uint16 / float32 device tensor, Twb and Twc
+    (mCurFrame.Twc: the previous frame's Twb * Tbc) [S, 4, 4] float64 -> (cloud, counts, edge, edge_counts), clouds float32
+    [S, W*H, point_stride] of which the first counts[s] points of a scene are written, counts int32 [S]."""
+    assert depth.dim() == 3 and depth.dtype in (torch.uint16, torch.int16, torch.float32) and depth.is_contiguous()
+    S, rows, cols = (int(v) for v in depth.shape)
+    for T in (Twb, Twc):
+        assert T.dtype == torch.float64 and tuple(T.shape) == (S, 4, 4) and T.is_contiguous()
+    lib = capi.load()
+    w, h, nbytes = C.c_int(), C.c_int(), C.c_longlong()
+    capi.check(lib.amk_depth_out_size(rows, cols, params.resize_scale, C.byref(w), C.byref(h)), "amk_depth_out_size")
+    capi.check(lib.amk_depth_clouds_work_bytes(rows, cols, params.resize_scale, S, C.byref(nbytes)), "amk_depth_clouds_work_bytes")
+    cap = w.value * h.value
+    cloud = torch.zeros((S, cap, point_stride), dtype=torch.float32, device=depth.device)
+    edge = torch.zeros((S, cap, point_stride), dtype=torch.float32, device=depth.device)
+    counts = torch.empty(S, dtype=torch.int32, device=depth.device)
+    edge_counts = torch.empty(S, dtype=torch.int32, device=depth.device)
+    work = torch.empty((nbytes.value + 7) // 8, dtype=torch.int64, device=depth.device)
+    if stream is not None:
+        work.record_stream(stream)   # dropped at return: its memory must not be reused before the launches on `stream` are through
+    kind = capi.AMK_DEPTH_F32 if depth.dtype == torch.float32 else capi.AMK_DEPTH_U16
+    capi.check(lib.amk_depth_to_clouds(capi.dptr(depth), kind, rows, cols, rows * cols, S, C.byref(params), capi.dptr(Twb), capi.dptr(Twc),
+                                       capi.dptr(cloud), cap * point_stride, capi.dptr(counts), capi.dptr(edge), cap * point_stride,
+                                       capi.dptr(edge_counts), int(point_stride), capi.dptr(work), work.numel() * 8,
+                                       capi.stream_ptr(stream)), "amk_depth_to_clouds")
+    return cloud, counts, edge, edge_counts

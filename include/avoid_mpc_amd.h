@@ -516,7 +516,8 @@ typedef struct amk_pipeline_frame {
     /* device with amk_pipeline_config.depth -- the edge cloud through the slot's own mCurFrame.Twc (the PREVIOUS frame's        */
     /* Twb * Tbc of the same position, identity at first, as the reference: :50,209) -- then both index builds; a scene whose  */
     /* frame yields no obstacle point keeps its previous frame and its Twc (:39-41).  The down-scaled image must fit the       */
-    /* pipeline's capacities: (cols / resize_scale) * (rows / resize_scale) <= max_points and <= max_edge_points.              */
+    /* pipeline's capacities: (cols / resize_scale) * (rows / resize_scale) <= max_points and <= max_edge_points; its width     */
+    /* cols / resize_scale is at most AMK_DEPTH_MAX_WIDTH, else AMK_ERR_UNSUPPORTED (one amk_depth_to_clouds per frame).       */
     const void *d_depth;           /* [S][rows][cols] uint16 / float32 (depth_type: AMK_DEPTH_U16 / AMK_DEPTH_F32) or NULL */
     int depth_type, depth_rows, depth_cols, reserved;
     const double *d_Twb;           /* [S][16] world <- body, row-major (DepthCallback, AvoidanceStateMachine.cpp:153-164) */
@@ -781,8 +782,8 @@ int amk_depth_to_cloud_host(const void *h_depth, int depth_type, int rows, int c
  *                  Twb * Tbc (it is updated only after ProcessDepth, :50).  Pass Twb of the current frame instead to
  *                  get what the authors presumably meant.
  * The edge cloud of a scene is empty when its obstacle cloud is (:126-128).  Down-scaled images of more than
- * AMK_EDGE_MAX_PIXELS pixels: AMK_ERR_UNSUPPORTED.  Bit-exact against oracle/depth_oracle.c; parity with OpenCV's
- * own erode / Canny is unpinned.                                                          */
+ * AMK_EDGE_MAX_PIXELS pixels: AMK_ERR_UNSUPPORTED (amk_depth_to_clouds below takes any size).  Bit-exact against
+ * oracle/depth_oracle.c; parity with OpenCV's own erode / Canny is unpinned.             */
 #define AMK_EDGE_MAX_PIXELS 16000
 int amk_depth_to_edge_cloud(const void *d_depth, int depth_type, int rows, int cols, long long scene_stride,
                             int n_scenes, const amk_depth_params *params, const double *d_Twc, float *d_cloud,
@@ -790,6 +791,34 @@ int amk_depth_to_edge_cloud(const void *d_depth, int depth_type, int rows, int c
 int amk_depth_to_edge_cloud_host(const void *h_depth, int depth_type, int rows, int cols, long long scene_stride,
                                  int n_scenes, const amk_depth_params *params, const double *h_Twc, float *h_cloud,
                                  int point_stride, long long cloud_scene_stride, int *h_counts);
+
+/* Depth image -> both clouds in one call: AddVertex's image half, ProcessDepth followed by BuildEdgeCloud
+ * (FrameKDMap.cpp:90-130,176-214), for down-scaled images of ANY size.  For every scene d_cloud / d_counts hold, bit
+ * for bit and in the same order, what amk_depth_to_cloud(..., d_Twb, ...) writes, and d_edge / d_edge_counts what
+ * amk_depth_to_edge_cloud(..., d_Twc, ...) writes (d_Twc = mCurFrame.Twc, the PREVIOUS frame's Twb * Tbc: the stale pose
+ * is kept; the edge cloud of a scene is empty when its obstacle cloud is).  Only the first counts[s] points of a
+ * scene are written.
+ * Down-scaled images of at most AMK_EDGE_MAX_PIXELS pixels run the two kernels of those calls.  Larger ones are cut
+ * into bands of whole down-scaled rows, one workgroup per band and scene, in two launches: the first counts the
+ * kept pixels and the edge points of every band into the workspace, the second sums the counts of the bands before
+ * its own and writes its points there, so the order is the row-major pixel order at any size and no atomic decides
+ * it.  A band holds its rows and a halo of 3 on each side in LDS (quantised depth, erosion, Sobel magnitude), which
+ * bounds the down-scaled WIDTH: more than AMK_DEPTH_MAX_WIDTH columns: AMK_ERR_UNSUPPORTED (and so are more than 65 535 scenes
+ * in one call above AMK_EDGE_MAX_PIXELS pixels: the scenes are the grid's second dimension).
+ *   d_work / work_bytes   the caller's workspace, at least amk_depth_clouds_work_bytes(rows, cols, resize_scale,
+ *                         n_scenes) bytes (host arithmetic, needs no GPU; covers any band height), 8-byte aligned.
+ * Stream-ordered and re-entrant: no allocation, no hidden state.  amk_depth_to_clouds_host takes host pointers,
+ * allocates its own workspace and synchronises (one upload of the image for both clouds).                       */
+#define AMK_DEPTH_MAX_WIDTH 2048
+int amk_depth_clouds_work_bytes(int rows, int cols, double resize_scale, int n_scenes, long long *bytes_out);
+int amk_depth_to_clouds(const void *d_depth, int depth_type, int rows, int cols, long long scene_stride, int n_scenes,
+                        const amk_depth_params *params, const double *d_Twb, const double *d_Twc, float *d_cloud,
+                        long long cloud_scene_stride, int *d_counts, float *d_edge, long long edge_scene_stride,
+                        int *d_edge_counts, int point_stride, void *d_work, long long work_bytes, void *stream);
+int amk_depth_to_clouds_host(const void *h_depth, int depth_type, int rows, int cols, long long scene_stride,
+                             int n_scenes, const amk_depth_params *params, const double *h_Twb, const double *h_Twc,
+                             float *h_cloud, long long cloud_scene_stride, int *h_counts, float *h_edge,
+                             long long edge_scene_stride, int *h_edge_counts, int point_stride);
 
 #ifdef __cplusplus
 }

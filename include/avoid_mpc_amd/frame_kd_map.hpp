@@ -121,14 +121,26 @@ public:
     }
 
     // AddVertex(mat4Twb, depth) of the reference (FrameKDMap.cpp:34-51), the depth image as a raw buffer:
-    // ProcessDepth + BuildEdgeCloud (with the stale pose, as the reference), two fresh trees, swap, Twc = Twb * Tbc.
+    // ProcessDepth + BuildEdgeCloud (with the stale pose, as the reference) in one amk_depth_to_clouds_host -- any image size up to
+    // AMK_DEPTH_MAX_WIDTH down-scaled columns --, two fresh trees, swap, Twc = Twb * Tbc.
     struct XYZ { float x, y, z; };
     struct XYZCloud { std::vector<XYZ> points; };
     void AddVertex(const double *Twb, const void *depth, int depthType, int rows, int cols) {
         auto cloud = std::make_shared<XYZCloud>(), edgeCloud = std::make_shared<XYZCloud>();
-        ProcessDepth(depth, depthType, rows, cols, Twb, *cloud);
-        if (cloud->points.empty()) return;                                         // :39-41
-        BuildEdgeCloud(depth, depthType, rows, cols, mTwc, *edgeCloud);            // ProcessDepth's tail, :130
+        int w = 0, h = 0;
+        amk_throw(amk_depth_out_size(rows, cols, depthParams.resize_scale, &w, &h), "amk_depth_out_size");
+        mParamWidth = w; mParamHeight = h;                                         // :106-107
+        // both clouds from one upload of the image, at any image size (amk_depth_to_clouds); the edge cloud through mTwc
+        std::vector<float> xyz((size_t)w * h * 3), exyz((size_t)w * h * 3);
+        int n = 0, ne = 0;
+        amk_throw(amk_depth_to_clouds_host(depth, depthType, rows, cols, (long long)rows * cols, 1, &depthParams, Twb, mTwc, xyz.data(),
+                                           (long long)w * h * 3, &n, exyz.data(), (long long)w * h * 3, &ne, 3),
+                  "amk_depth_to_clouds_host");
+        if (n == 0) return;                                                        // :39-41
+        cloud->points.resize((size_t)n);
+        for (int i = 0; i < n; ++i) cloud->points[i] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
+        edgeCloud->points.resize((size_t)ne);                                      // ProcessDepth's tail, :130
+        for (int i = 0; i < ne; ++i) edgeCloud->points[i] = {exyz[3 * i], exyz[3 * i + 1], exyz[3 * i + 2]};
         AddVertex(cloud, edgeCloud);
         for (int i = 0; i < 4; ++i)                                                // mCurFrame.Twc = mat4Twb * mParamTbc, :50
             for (int j = 0; j < 4; ++j) {
