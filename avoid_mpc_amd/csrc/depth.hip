@@ -4,12 +4,16 @@
 //
 // amk_depth_to_cloud / amk_depth_to_edge_cloud: one block per scene (the edge cloud up to AMK_EDGE_MAX_PIXELS pixels);
 // amk_depth_to_clouds: both clouds, above that size on one block per band of rows (depth_band_kernel).
+// Every rule of the reference is written once, as a device helper (obstacle_depth, quantise, to_world, EdgeLayers); the three
+// kernels are control flow over them and differ only in which image rows a block holds in LDS (one exception, for its measured
+// cost: the keep test behind depth_to_edge_kernel's `any` flag is written out there).
 // Only the 2x2 raw pixels under each down-scaled pixel are read (4 % of a 640x480 image at
 // resize_scale 10): the reference inverts the whole image and then lets cv::resize pick the same four taps.
 // The kept pixels are appended in row-major order (ballot + popcount prefix per wave, LDS combine per block),
 // which is the order the reference's emplace_back produces and therefore the index space of the KD tree.
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 
 #include "amk_common.h"
 
@@ -94,9 +98,84 @@ __device__ __forceinline__ int append_round(bool keep, float px, float py, float
     return base + tot;
 }
 
-// FrameKDMap::BuildEdgeCloud (FrameKDMap.cpp:176-214) for one scene per block; the whole down-scaled frame lives in
-// LDS: quantised depth (u8), its 3x3 erosion (u8), Sobel L1 magnitude (i16).  cv::Canny(., 0.1, 0.3) on 8-bit data =
-// non-maximum suppression of the non-zero magnitudes (both thresholds floor to 0: every survivor is a strong edge).
+// ProcessDepth's test of one down-scaled pixel (:113-117): is it an obstacle point, and at which depth.  A NaN passes the first
+// comparison and fails the other two, as in the reference.
+__device__ __forceinline__ bool obstacle_depth(double invd, const DepthGeom &g, double &d) {
+    d = 1.0 / invd;                                                // :116
+    return !(invd < 1e-2) && d > g.dmin && d < g.dmax;             // :113-115, :117
+}
+
+// BuildEdgeCloud's 8-bit depth (:183-191)
+__device__ __forceinline__ unsigned char quantise(float inv, double range) {
+    return (double)inv > 1e-2 ? (unsigned char)((double)(1 / inv) / range * (double)200.0f) : (unsigned char)255;
+}
+
+// UV2Camera (:133-136), then M * (xc, yc, d, 1) with M = rows 0..2 of pose * Tbc; pcl::PointXYZ is float32 (:122)
+__device__ __forceinline__ void to_world(const double *M, int row, int col, double d, const DepthGeom &g, float &px, float &py,
+                                         float &pz) {
+    const double xc = ((double)col - g.cx) * d / g.fx, yc = ((double)row - g.cy) * d / g.fy;
+    px = (float)(((M[0] * xc + M[1] * yc) + M[2] * d) + M[3]);
+    py = (float)(((M[4] * xc + M[5] * yc) + M[6] * d) + M[7]);
+    pz = (float)(((M[8] * xc + M[9] * yc) + M[10] * d) + M[11]);
+}
+
+// FrameKDMap::BuildEdgeCloud (FrameKDMap.cpp:176-214) on three LDS layers of the down-scaled W x H image: quantised depth (u8), its
+// 3x3 erosion (u8), Sobel L1 magnitude (i16).  Each layer holds a range of IMAGE rows: image row r is the layer's row r - (its first
+// row q0 / e0 / m0).  cv::Canny(., 0.1, 0.3) on 8-bit data = non-maximum suppression of the non-zero magnitudes (both thresholds floor
+// to 0: every survivor is a strong edge).
+struct EdgeLayers {
+    unsigned char *quant, *ero;
+    short *mag;
+    int W, H, q0, e0, m0;
+    __device__ __forceinline__ int epx(int r, int c) const {   // BORDER_REPLICATE
+        return (int)ero[(min(max(r, 0), H - 1) - e0) * W + min(max(c, 0), W - 1)];
+    }
+    __device__ __forceinline__ int sobx(int r, int c) const {
+        return (epx(r - 1, c + 1) + 2 * epx(r, c + 1) + epx(r + 1, c + 1)) - (epx(r - 1, c - 1) + 2 * epx(r, c - 1) + epx(r + 1, c - 1));
+    }
+    __device__ __forceinline__ int soby(int r, int c) const {
+        return (epx(r + 1, c - 1) + 2 * epx(r + 1, c) + epx(r + 1, c + 1)) - (epx(r - 1, c - 1) + 2 * epx(r - 1, c) + epx(r - 1, c + 1));
+    }
+    __device__ __forceinline__ int mg(int r, int c) const { return (r < 0 || r >= H || c < 0 || c >= W) ? 0 : (int)mag[(r - m0) * W + c]; }
+    // cv::erode 3x3 of image rows [lo, hi), taps outside the IMAGE ignored (every thread of the block)
+    __device__ __forceinline__ void erode(int lo, int hi) const {
+        const int n = (hi - lo) * W;
+        for (int p = threadIdx.x; p < n; p += kDepthThreads) {
+            const int r = lo + p / W, c = p % W;
+            int m = 255;
+            for (int dr = -1; dr <= 1; ++dr)
+                for (int dc = -1; dc <= 1; ++dc) {
+                    const int rr = r + dr, cc = c + dc;
+                    if (rr >= 0 && rr < H && cc >= 0 && cc < W) m = min(m, (int)quant[(rr - q0) * W + cc]);
+                }
+            ero[(r - e0) * W + c] = (unsigned char)m;
+        }
+    }
+    __device__ __forceinline__ void magnitude(int lo, int hi) const {
+        const int n = (hi - lo) * W;
+        for (int p = threadIdx.x; p < n; p += kDepthThreads) {
+            const int r = lo + p / W, c = p % W;
+            mag[(r - m0) * W + c] = (short)(abs(sobx(r, c)) + abs(soby(r, c)));
+        }
+    }
+    __device__ __forceinline__ bool is_edge(int r, int c) const {   // Canny's non-maximum suppression
+        const int m = mag[(r - m0) * W + c];   // (r, c) is a pixel of the image
+        if (m <= 0) return false;
+        const int xs = sobx(r, c), ys = soby(r, c);
+        const int x = abs(xs), y = abs(ys) << 15, tg22x = x * 13573;
+        if (y < tg22x) return m > mg(r, c - 1) && m >= mg(r, c + 1);
+        if (y > tg22x + (x << 16)) return m > mg(r - 1, c) && m >= mg(r + 1, c);
+        const int sg = ((xs ^ ys) < 0) ? -1 : 1;
+        return m > mg(r - 1, c - sg) && m > mg(r + 1, c + sg);
+    }
+    __device__ __forceinline__ bool edge_depth(int r, int c, double range, const DepthGeom &g, double &d) const {
+        d = (double)(float)ero[(r - e0) * W + c];   // :199
+        d = d * range / 200.0;                      // :200
+        return !(d > g.dmax || d < g.dmin);         // :201-203
+    }
+};
+
+// The edge cloud of one scene per block, the whole down-scaled frame in LDS.
 template <typename T>
 __global__ __launch_bounds__(kDepthThreads) void depth_to_edge_kernel(const T *__restrict__ depth, long long scene_stride,
                                                                       DepthGeom g, const double *__restrict__ Twc,
@@ -106,8 +185,7 @@ __global__ __launch_bounds__(kDepthThreads) void depth_to_edge_kernel(const T *_
     extern __shared__ __attribute__((aligned(16))) unsigned char edge_smem[];
     const int s = blockIdx.x, tid = threadIdx.x;
     const int W = g.W, H = g.H, npix = W * H;
-    unsigned char *quant = edge_smem, *ero = edge_smem + npix;
-    short *mag = reinterpret_cast<short *>(edge_smem + 2 * ((npix + 1) & ~1));
+    const EdgeLayers L{edge_smem, edge_smem + npix, reinterpret_cast<short *>(edge_smem + 2 * ((npix + 1) & ~1)), W, H, 0, 0, 0};
     const T *img = depth + (long long)s * scene_stride;
     float *out = cloud + (long long)s * cloud_scene_stride;
     __shared__ double M[12];
@@ -121,11 +199,11 @@ __global__ __launch_bounds__(kDepthThreads) void depth_to_edge_kernel(const T *_
     for (int p = tid; p < npix; p += kDepthThreads) {
         const float inv = small_inv(img, p / W, p % W, g);
         const double invd = (double)inv;
-        if (!(invd < 1e-2)) {               // would ProcessDepth keep this pixel? (:113-117)
+        if (!(invd < 1e-2)) {               // obstacle_depth's test written out: through the helper this kernel measured 0.6 % slower
             const double d = 1.0 / invd;
             any = any || (d > g.dmin && d < g.dmax);
         }
-        quant[p] = invd > 1e-2 ? (unsigned char)((double)(1 / inv) / range * (double)200.0f) : (unsigned char)255;  // :183-191
+        L.quant[p] = quantise(inv, range);
     }
     if (any) any_obstacle = 1;
     __syncthreads();
@@ -133,55 +211,21 @@ __global__ __launch_bounds__(kDepthThreads) void depth_to_edge_kernel(const T *_
         if (tid == 0) counts[s] = 0;
         return;
     }
-    for (int p = tid; p < npix; p += kDepthThreads) {   // cv::erode 3x3, out-of-image taps ignored
-        const int r = p / W, c = p % W;
-        int m = 255;
-        for (int dr = -1; dr <= 1; ++dr)
-            for (int dc = -1; dc <= 1; ++dc) {
-                const int rr = r + dr, cc = c + dc;
-                if (rr >= 0 && rr < H && cc >= 0 && cc < W) m = min(m, (int)quant[rr * W + cc]);
-            }
-        ero[p] = (unsigned char)m;
-    }
+    L.erode(0, H);
     __syncthreads();
-    auto epx = [&](int r, int c) { return (int)ero[min(max(r, 0), H - 1) * W + min(max(c, 0), W - 1)]; };  // BORDER_REPLICATE
-    auto sobx = [&](int r, int c) {
-        return (epx(r - 1, c + 1) + 2 * epx(r, c + 1) + epx(r + 1, c + 1)) - (epx(r - 1, c - 1) + 2 * epx(r, c - 1) + epx(r + 1, c - 1));
-    };
-    auto soby = [&](int r, int c) {
-        return (epx(r + 1, c - 1) + 2 * epx(r + 1, c) + epx(r + 1, c + 1)) - (epx(r - 1, c - 1) + 2 * epx(r - 1, c) + epx(r - 1, c + 1));
-    };
-    for (int p = tid; p < npix; p += kDepthThreads) mag[p] = (short)(abs(sobx(p / W, p % W)) + abs(soby(p / W, p % W)));
+    L.magnitude(0, H);
     __syncthreads();
-    auto mg = [&](int r, int c) { return (r < 0 || r >= H || c < 0 || c >= W) ? 0 : (int)mag[r * W + c]; };
     int base = 0;
     for (int p0 = 0; p0 < npix; p0 += kDepthThreads) {
         const int p = p0 + tid;
         bool keep = false;
         float px = 0.f, py = 0.f, pz = 0.f;
         if (p < npix) {
-            const int r = p / W, c = p % W, m = mag[p];
-            bool edge = false;
-            if (m > 0) {
-                const int xs = sobx(r, c), ys = soby(r, c);
-                const int x = abs(xs), y = abs(ys) << 15, tg22x = x * 13573;
-                if (y < tg22x) edge = m > mg(r, c - 1) && m >= mg(r, c + 1);
-                else if (y > tg22x + (x << 16)) edge = m > mg(r - 1, c) && m >= mg(r + 1, c);
-                else {
-                    const int sg = ((xs ^ ys) < 0) ? -1 : 1;
-                    edge = m > mg(r - 1, c - sg) && m > mg(r + 1, c + sg);
-                }
-            }
-            if (edge) {
-                double d = (double)(float)ero[p];   // :199
-                d = d * range / 200.0;              // :200
-                if (!(d > g.dmax || d < g.dmin)) {  // :201-203
-                    const double xc = ((double)c - g.cx) * d / g.fx, yc = ((double)r - g.cy) * d / g.fy;
-                    px = (float)(((M[0] * xc + M[1] * yc) + M[2] * d) + M[3]);
-                    py = (float)(((M[4] * xc + M[5] * yc) + M[6] * d) + M[7]);
-                    pz = (float)(((M[8] * xc + M[9] * yc) + M[10] * d) + M[11]);
-                    keep = true;
-                }
+            const int r = p / W, c = p % W;
+            double d;
+            if (L.is_edge(r, c) && L.edge_depth(r, c, range, g, d)) {
+                to_world(M, r, c, d, g, px, py, pz);
+                keep = true;
             }
         }
         base = append_round(keep, px, py, pz, out, point_stride, base, wave_tot);
@@ -210,17 +254,10 @@ __global__ __launch_bounds__(kDepthThreads) void depth_to_cloud_kernel(const T *
         float px = 0.f, py = 0.f, pz = 0.f;
         if (p < npix) {
             const int row = p / g.W, col = p % g.W;
-            const double invd = (double)small_inv(img, row, col, g);
-            if (!(invd < 1e-2)) {                                       // :113-115
-                const double d = 1.0 / invd;                            // :116
-                if (d > g.dmin && d < g.dmax) {                         // :117
-                    const double xc = ((double)col - g.cx) * d / g.fx;  // UV2Camera :133-136
-                    const double yc = ((double)row - g.cy) * d / g.fy;
-                    px = (float)(((M[0] * xc + M[1] * yc) + M[2] * d) + M[3]);   // pcl::PointXYZ is float32 (:122)
-                    py = (float)(((M[4] * xc + M[5] * yc) + M[6] * d) + M[7]);
-                    pz = (float)(((M[8] * xc + M[9] * yc) + M[10] * d) + M[11]);
-                    keep = true;
-                }
+            double d;
+            if (obstacle_depth((double)small_inv(img, row, col, g), g, d)) {
+                to_world(M, row, col, d, g, px, py, pz);
+                keep = true;
             }
         }
         base = append_round(keep, px, py, pz, out, point_stride, base, wave_tot);
@@ -232,8 +269,8 @@ __global__ __launch_bounds__(kDepthThreads) void depth_to_cloud_kernel(const T *
 // down-scaled rows of one scene.  Whole rows keep band order = row-major pixel order.  A band decides its rows [r0, r1) from a halo
 // of 3 rows on each side, all in LDS: quantised depth over [r0 - 3, r1 + 3), its erosion over [r0 - 2, r1 + 2), the Sobel magnitude
 // over [r0 - 1, r1 + 1) -- W * (4 R + 14) bytes.  Every range is clipped to the IMAGE: a row of a neighbouring band is a real row
-// (recomputed here), a row outside the image is what the one-block kernel above makes of it (an ignored erosion tap, a replicated
-// Sobel tap, a zero magnitude).
+// (recomputed here), a row outside the image is what EdgeLayers makes of it for the one-block kernel too (an ignored erosion tap, a
+// replicated Sobel tap, a zero magnitude).
 // Two launches of the same body.  EMIT = false writes {kept obstacle pixels, edge points} of the band into band_counts[scene][band].
 // EMIT = true sums the counts of the bands before its own (no block waits for another: what crosses bands crosses the launch
 // boundary), learns from the scene's obstacle total whether the scene is empty, redoes the band and appends its points at its offsets.
@@ -249,9 +286,8 @@ __global__ __launch_bounds__(kDepthThreads) void depth_band_kernel(const T *__re
     const int b = blockIdx.x, nb = gridDim.x, s = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int W = g.W, H = g.H;
     const int r0 = b * R, r1 = min(H, r0 + R);
-    unsigned char *quant = band_smem;                        // image row r at row r - (r0 - 3)
-    unsigned char *ero = band_smem + (size_t)(R + 6) * W;    //               at row r - (r0 - 2)
-    short *mag = reinterpret_cast<short *>(band_smem + (size_t)(2 * R + 10) * W);   //  at row r - (r0 - 1)
+    const EdgeLayers L{band_smem, band_smem + (size_t)(R + 6) * W, reinterpret_cast<short *>(band_smem + (size_t)(2 * R + 10) * W),
+                       W, H, r0 - 3, r0 - 2, r0 - 1};
     const T *img = depth + (long long)s * scene_stride;
     __shared__ double Mb[12], Mc[12];   // rows 0..2 of Twb * Tbc (obstacle points) and of Twc * Tbc (edge points)
     __shared__ int wave_tot[kDepthThreads / 64];
@@ -301,22 +337,12 @@ __global__ __launch_bounds__(kDepthThreads) void depth_band_kernel(const T *__re
         if (p < nq) {
             const int row = qlo + p / W, col = p % W;
             const float inv = small_inv(img, row, col, g);
-            const double invd = (double)inv;
-            if (row >= r0 && row < r1 && !(invd < 1e-2)) {                  // :113-115
-                const double d = 1.0 / invd;                                // :116
-                if (d > g.dmin && d < g.dmax) {                             // :117
-                    if (EMIT) {
-                        const double xc = ((double)col - g.cx) * d / g.fx;  // UV2Camera :133-136
-                        const double yc = ((double)row - g.cy) * d / g.fy;
-                        px = (float)(((Mb[0] * xc + Mb[1] * yc) + Mb[2] * d) + Mb[3]);
-                        py = (float)(((Mb[4] * xc + Mb[5] * yc) + Mb[6] * d) + Mb[7]);
-                        pz = (float)(((Mb[8] * xc + Mb[9] * yc) + Mb[10] * d) + Mb[11]);
-                    }
-                    keep = true;
-                }
+            L.quant[(row - L.q0) * W + col] = quantise(inv, range);   // (first: the emit kernel stays within 64 VGPRs this way)
+            double d;
+            if (row >= r0 && row < r1 && obstacle_depth((double)inv, g, d)) {
+                if (EMIT) to_world(Mb, row, col, d, g, px, py, pz);
+                keep = true;
             }
-            quant[(row - r0 + 3) * W + col] =
-                invd > 1e-2 ? (unsigned char)((double)(1 / inv) / range * (double)200.0f) : (unsigned char)255;  // :183-191
         }
         if (EMIT) obs_base = append_round(keep, px, py, pz, out, point_stride, obs_base, wave_tot);
         else n_obs += keep ? 1 : 0;
@@ -324,32 +350,10 @@ __global__ __launch_bounds__(kDepthThreads) void depth_band_kernel(const T *__re
     __syncthreads();
     int n_edge = 0;
     if (want_edges) {
-        const int elo = max(r0 - 2, 0), ne = (min(r1 + 2, H) - elo) * W;
-        for (int p = tid; p < ne; p += kDepthThreads) {   // cv::erode 3x3, taps outside the IMAGE ignored
-            const int r = elo + p / W, c = p % W;
-            int m = 255;
-            for (int dr = -1; dr <= 1; ++dr)
-                for (int dc = -1; dc <= 1; ++dc) {
-                    const int rr = r + dr, cc = c + dc;
-                    if (rr >= 0 && rr < H && cc >= 0 && cc < W) m = min(m, (int)quant[(rr - r0 + 3) * W + cc]);
-                }
-            ero[(r - r0 + 2) * W + c] = (unsigned char)m;
-        }
+        L.erode(max(r0 - 2, 0), min(r1 + 2, H));
         __syncthreads();
-        auto epx = [&](int r, int c) { return (int)ero[(min(max(r, 0), H - 1) - r0 + 2) * W + min(max(c, 0), W - 1)]; };  // BORDER_REPLICATE
-        auto sobx = [&](int r, int c) {
-            return (epx(r - 1, c + 1) + 2 * epx(r, c + 1) + epx(r + 1, c + 1)) - (epx(r - 1, c - 1) + 2 * epx(r, c - 1) + epx(r + 1, c - 1));
-        };
-        auto soby = [&](int r, int c) {
-            return (epx(r + 1, c - 1) + 2 * epx(r + 1, c) + epx(r + 1, c + 1)) - (epx(r - 1, c - 1) + 2 * epx(r - 1, c) + epx(r - 1, c + 1));
-        };
-        const int mlo = max(r0 - 1, 0), nm = (min(r1 + 1, H) - mlo) * W;
-        for (int p = tid; p < nm; p += kDepthThreads) {
-            const int r = mlo + p / W, c = p % W;
-            mag[(r - r0 + 1) * W + c] = (short)(abs(sobx(r, c)) + abs(soby(r, c)));
-        }
+        L.magnitude(max(r0 - 1, 0), min(r1 + 1, H));
         __syncthreads();
-        auto mg = [&](int r, int c) { return (r < 0 || r >= H || c < 0 || c >= W) ? 0 : (int)mag[(r - r0 + 1) * W + c]; };
         float *eout = edge_cloud + (long long)s * edge_scene_stride;
         const int nown = (r1 - r0) * W;
         for (int p0 = 0; p0 < nown; p0 += kDepthThreads) {
@@ -357,30 +361,11 @@ __global__ __launch_bounds__(kDepthThreads) void depth_band_kernel(const T *__re
             bool keep = false;
             float px = 0.f, py = 0.f, pz = 0.f;
             if (p < nown) {
-                const int r = r0 + p / W, c = p % W, m = mg(r, c);
-                bool edge = false;
-                if (m > 0) {
-                    const int xs = sobx(r, c), ys = soby(r, c);
-                    const int x = abs(xs), y = abs(ys) << 15, tg22x = x * 13573;
-                    if (y < tg22x) edge = m > mg(r, c - 1) && m >= mg(r, c + 1);
-                    else if (y > tg22x + (x << 16)) edge = m > mg(r - 1, c) && m >= mg(r + 1, c);
-                    else {
-                        const int sg = ((xs ^ ys) < 0) ? -1 : 1;
-                        edge = m > mg(r - 1, c - sg) && m > mg(r + 1, c + sg);
-                    }
-                }
-                if (edge) {
-                    double d = (double)(float)ero[(r - r0 + 2) * W + c];   // :199
-                    d = d * range / 200.0;                                 // :200
-                    if (!(d > g.dmax || d < g.dmin)) {                     // :201-203
-                        if (EMIT) {
-                            const double xc = ((double)c - g.cx) * d / g.fx, yc = ((double)r - g.cy) * d / g.fy;
-                            px = (float)(((Mc[0] * xc + Mc[1] * yc) + Mc[2] * d) + Mc[3]);
-                            py = (float)(((Mc[4] * xc + Mc[5] * yc) + Mc[6] * d) + Mc[7]);
-                            pz = (float)(((Mc[8] * xc + Mc[9] * yc) + Mc[10] * d) + Mc[11]);
-                        }
-                        keep = true;
-                    }
+                const int r = r0 + p / W, c = p % W;
+                double d;
+                if (L.is_edge(r, c) && L.edge_depth(r, c, range, g, d)) {
+                    if (EMIT) to_world(Mc, r, c, d, g, px, py, pz);
+                    keep = true;
                 }
             }
             if (EMIT) edge_base = append_round(keep, px, py, pz, eout, point_stride, edge_base, wave_tot);
@@ -409,11 +394,8 @@ int band_rows_max(int W) { return (kBandLdsBudget / W - 14) / 4; }
 int g_forced_band_rows = 0;   // amk__depth_set_band_rows (tests): > 0 forces the tiled path with this band height
 
 int make_geom(int rows, int cols, const amk_depth_params *p, DepthGeom &g) {
-    if (!p || rows <= 0 || cols <= 0 || !(p->resize_scale > 0)) return AMK_ERR_INVALID_ARG;
+    if (!p || amk_depth_out_size(rows, cols, p->resize_scale, &g.W, &g.H) != AMK_OK) return AMK_ERR_INVALID_ARG;
     g.rows = rows; g.cols = cols;
-    g.W = (int)((double)cols / p->resize_scale);   // mParamWidth = cols / mParamDepthScale (int <- double, :106)
-    g.H = (int)((double)rows / p->resize_scale);
-    if (g.W <= 0 || g.H <= 0) return AMK_ERR_INVALID_ARG;
     g.scale_x = 1.0 / ((double)g.W / (double)cols);  // cv::resize: inv_scale = dsize / ssize; scale = 1 / inv_scale
     g.scale_y = 1.0 / ((double)g.H / (double)rows);
     g.pixel2meter = p->pixel2meter; g.dmin = p->depth_min; g.dmax = p->depth_max;
@@ -423,13 +405,117 @@ int make_geom(int rows, int cols, const amk_depth_params *p, DepthGeom &g) {
     return AMK_OK;
 }
 
+// A checked batch of depth images on the device: what every launch needs besides its pose and its cloud
+struct Frames {
+    const void *depth;
+    int type, n_scenes, point_stride;
+    long long scene_stride;
+    DepthGeom g;
+};
+
+// The refusals the three device entry points share, in the order that decides which of two faults answers.  `pointers`: none of the
+// call's pointers is null; `cloud_scene_stride`: the smallest of the call's cloud strides.
+int check_frames(bool pointers, const void *d_depth, int depth_type, int rows, int cols, long long scene_stride, int n_scenes,
+                 const amk_depth_params *params, int point_stride, long long cloud_scene_stride, Frames &f) {
+    if (!pointers || !d_depth || n_scenes <= 0 || point_stride < 3) return AMK_ERR_INVALID_ARG;
+    if (depth_type != AMK_DEPTH_U16 && depth_type != AMK_DEPTH_F32) return AMK_ERR_UNSUPPORTED;
+    if (const int st = make_geom(rows, cols, params, f.g); st != AMK_OK) return st;
+    if (scene_stride < (long long)rows * cols || cloud_scene_stride < (long long)f.g.W * f.g.H * point_stride)
+        return AMK_ERR_INVALID_ARG;
+    f.depth = d_depth; f.type = depth_type; f.n_scenes = n_scenes; f.point_stride = point_stride; f.scene_stride = scene_stride;
+    return AMK_OK;
+}
+
+// The pixel-type dispatch: launch(img) with the batch's images as a pointer to their pixel type; then the launch's status
+template <typename Launch>
+int with_pixels(const Frames &f, Launch &&launch) {
+    if (f.type == AMK_DEPTH_U16) launch((const unsigned short *)f.depth);
+    else launch((const float *)f.depth);
+    AMK_HIP(hipGetLastError());
+    return AMK_OK;
+}
+
+// One cloud of a call: its pose [S][16] (Twb for the obstacle cloud, Twc for the edge cloud), its points [S][scene_stride], its counts [S]
+struct Cloud {
+    const double *T;
+    float *points;
+    long long scene_stride;
+    int *counts;
+};
+
+int launch_cloud(const Frames &f, const Cloud &c, hipStream_t stream) {
+    return with_pixels(f, [&](auto *img) {
+        hipLaunchKernelGGL(depth_to_cloud_kernel, dim3(f.n_scenes), dim3(kDepthThreads), 0, stream, img, f.scene_stride, f.g, c.T,
+                           c.points, f.point_stride, c.scene_stride, c.counts);
+    });
+}
+
+int launch_edge(const Frames &f, const Cloud &c, hipStream_t stream) {
+    const size_t npix = (size_t)f.g.W * f.g.H, lds = 2 * ((npix + 1) & ~(size_t)1) + 2 * npix;  // quant, eroded (u8), magnitude (i16)
+    return with_pixels(f, [&](auto *img) {
+        hipLaunchKernelGGL(depth_to_edge_kernel, dim3(f.n_scenes), dim3(kDepthThreads), lds, stream, img, f.scene_stride, f.g, c.T,
+                           c.points, f.point_stride, c.scene_stride, c.counts);
+    });
+}
+
+// {obstacle, edge} count of every band of every scene, for the smallest band (one row): covers any band height
+long long work_bytes_for(int H, int n_scenes) { return (long long)sizeof(int2) * H * n_scenes; }
+
+// The host-memory variants, `host` holding the caller's pointers.  Refuses what all three refuse (`work_status`, the caller's answer about its workspace of `work_bytes`,
+// stands behind the pixel type and before the device); uploads the images and the N poses; runs device(images, clouds, workspace) on
+// the null stream and waits; downloads the N clouds and their counts.
+template <int N, typename Device>
+int on_device_copies(const void *h_depth, int depth_type, long long scene_stride, int n_scenes, const Cloud (&host)[N],
+                     int work_status, long long work_bytes, Device &&device) {
+    bool pointers = h_depth != nullptr;
+    for (const Cloud &c : host) pointers = pointers && c.T && c.points && c.counts;
+    if (!pointers || n_scenes <= 0) return AMK_ERR_INVALID_ARG;
+    if (depth_type != AMK_DEPTH_U16 && depth_type != AMK_DEPTH_F32) return AMK_ERR_UNSUPPORTED;
+    if (work_status != AMK_OK) return work_status;
+    if (amk_device_count() <= 0) return AMK_ERR_NO_DEVICE;
+    const size_t img_bytes = (size_t)scene_stride * n_scenes * (depth_type == AMK_DEPTH_U16 ? 2 : 4);
+    amk::DevBuf<unsigned char> img, work;
+    amk::DevBuf<double> pose[N];
+    amk::DevBuf<float> points[N];
+    amk::DevBuf<int> counts[N];
+    Cloud dev[N];
+    AMK_HIP(img.alloc(img_bytes));
+    AMK_HIP(work.alloc((size_t)work_bytes));
+    AMK_HIP(hipMemcpy(img.p, h_depth, img_bytes, hipMemcpyHostToDevice));
+    for (int i = 0; i < N; ++i) {
+        AMK_HIP(pose[i].alloc((size_t)16 * n_scenes));
+        AMK_HIP(points[i].alloc((size_t)host[i].scene_stride * n_scenes));
+        AMK_HIP(counts[i].alloc(n_scenes));
+        AMK_HIP(hipMemcpy(pose[i].p, host[i].T, sizeof(double) * 16 * n_scenes, hipMemcpyHostToDevice));
+        dev[i] = {pose[i].p, points[i].p, host[i].scene_stride, counts[i].p};
+    }
+    if (const int st = device(img.p, dev, work.p); st != AMK_OK) return st;
+    AMK_HIP(hipDeviceSynchronize());
+    for (int i = 0; i < N; ++i) {
+        AMK_HIP(hipMemcpy(host[i].counts, counts[i].p, sizeof(int) * n_scenes, hipMemcpyDeviceToHost));
+        AMK_HIP(hipMemcpy(host[i].points, points[i].p, sizeof(float) * (size_t)host[i].scene_stride * n_scenes, hipMemcpyDeviceToHost));
+    }
+    return AMK_OK;
+}
+
+// amk_depth_to_cloud_host / amk_depth_to_edge_cloud_host: one cloud through `fn`, their device call
+int one_cloud_on_host(decltype(&amk_depth_to_cloud) fn, const void *h_depth, int depth_type, int rows, int cols, long long scene_stride,
+                      int n_scenes, const amk_depth_params *params, const double *h_T, float *h_cloud, int point_stride,
+                      long long cloud_scene_stride, int *h_counts) {
+    const Cloud host[1] = {{h_T, h_cloud, cloud_scene_stride, h_counts}};
+    return on_device_copies(h_depth, depth_type, scene_stride, n_scenes, host, AMK_OK, 0, [&](const void *img, const Cloud *c, void *) {
+        return fn(img, depth_type, rows, cols, scene_stride, n_scenes, params, c->T, c->points, point_stride, c->scene_stride, c->counts,
+                  nullptr);
+    });
+}
+
 }  // namespace
 
 extern "C" {
 
 int amk_depth_out_size(int rows, int cols, double resize_scale, int *out_w, int *out_h) {
     if (rows <= 0 || cols <= 0 || !(resize_scale > 0) || !out_w || !out_h) return AMK_ERR_INVALID_ARG;
-    *out_w = (int)((double)cols / resize_scale);
+    *out_w = (int)((double)cols / resize_scale);   // mParamWidth = cols / mParamDepthScale (int <- double, :106)
     *out_h = (int)((double)rows / resize_scale);
     return (*out_w > 0 && *out_h > 0) ? AMK_OK : AMK_ERR_INVALID_ARG;
 }
@@ -437,47 +523,24 @@ int amk_depth_out_size(int rows, int cols, double resize_scale, int *out_w, int 
 int amk_depth_to_cloud(const void *d_depth, int depth_type, int rows, int cols, long long scene_stride, int n_scenes,
                        const amk_depth_params *params, const double *d_Twb, float *d_cloud, int point_stride,
                        long long cloud_scene_stride, int *d_counts, void *stream) {
-    if (!d_depth || !d_Twb || !d_cloud || !d_counts || n_scenes <= 0 || point_stride < 3) return AMK_ERR_INVALID_ARG;
-    if (depth_type != AMK_DEPTH_U16 && depth_type != AMK_DEPTH_F32) return AMK_ERR_UNSUPPORTED;
-    DepthGeom g;
-    int st = make_geom(rows, cols, params, g);
-    if (st != AMK_OK) return st;
-    if (scene_stride < (long long)rows * cols || cloud_scene_stride < (long long)g.W * g.H * point_stride)
-        return AMK_ERR_INVALID_ARG;
+    Frames f;
+    if (const int st = check_frames(d_Twb && d_cloud && d_counts, d_depth, depth_type, rows, cols, scene_stride, n_scenes, params,
+                                    point_stride, cloud_scene_stride, f); st != AMK_OK)
+        return st;
     if (amk_device_count() <= 0) return AMK_ERR_NO_DEVICE;
-    if (depth_type == AMK_DEPTH_U16)
-        hipLaunchKernelGGL(depth_to_cloud_kernel<unsigned short>, dim3(n_scenes), dim3(kDepthThreads), 0, (hipStream_t)stream,
-                           (const unsigned short *)d_depth, scene_stride, g, d_Twb, d_cloud, point_stride, cloud_scene_stride,
-                           d_counts);
-    else
-        hipLaunchKernelGGL(depth_to_cloud_kernel<float>, dim3(n_scenes), dim3(kDepthThreads), 0, (hipStream_t)stream,
-                           (const float *)d_depth, scene_stride, g, d_Twb, d_cloud, point_stride, cloud_scene_stride, d_counts);
-    AMK_HIP(hipGetLastError());
-    return AMK_OK;
+    return launch_cloud(f, {d_Twb, d_cloud, cloud_scene_stride, d_counts}, (hipStream_t)stream);
 }
 
 int amk_depth_to_edge_cloud(const void *d_depth, int depth_type, int rows, int cols, long long scene_stride, int n_scenes,
                             const amk_depth_params *params, const double *d_Twc, float *d_cloud, int point_stride,
                             long long cloud_scene_stride, int *d_counts, void *stream) {
-    if (!d_depth || !d_Twc || !d_cloud || !d_counts || n_scenes <= 0 || point_stride < 3) return AMK_ERR_INVALID_ARG;
-    if (depth_type != AMK_DEPTH_U16 && depth_type != AMK_DEPTH_F32) return AMK_ERR_UNSUPPORTED;
-    DepthGeom g;
-    int st = make_geom(rows, cols, params, g);
-    if (st != AMK_OK) return st;
-    if (scene_stride < (long long)rows * cols || cloud_scene_stride < (long long)g.W * g.H * point_stride)
-        return AMK_ERR_INVALID_ARG;
-    if ((long long)g.W * g.H > AMK_EDGE_MAX_PIXELS) return AMK_ERR_UNSUPPORTED;
+    Frames f;
+    if (const int st = check_frames(d_Twc && d_cloud && d_counts, d_depth, depth_type, rows, cols, scene_stride, n_scenes, params,
+                                    point_stride, cloud_scene_stride, f); st != AMK_OK)
+        return st;
+    if ((long long)f.g.W * f.g.H > AMK_EDGE_MAX_PIXELS) return AMK_ERR_UNSUPPORTED;
     if (amk_device_count() <= 0) return AMK_ERR_NO_DEVICE;
-    const size_t npix = (size_t)g.W * g.H, lds = 2 * ((npix + 1) & ~(size_t)1) + 2 * npix;  // quant, eroded (u8), magnitude (i16)
-    if (depth_type == AMK_DEPTH_U16)
-        hipLaunchKernelGGL(depth_to_edge_kernel<unsigned short>, dim3(n_scenes), dim3(kDepthThreads), lds, (hipStream_t)stream,
-                           (const unsigned short *)d_depth, scene_stride, g, d_Twc, d_cloud, point_stride, cloud_scene_stride,
-                           d_counts);
-    else
-        hipLaunchKernelGGL(depth_to_edge_kernel<float>, dim3(n_scenes), dim3(kDepthThreads), lds, (hipStream_t)stream,
-                           (const float *)d_depth, scene_stride, g, d_Twc, d_cloud, point_stride, cloud_scene_stride, d_counts);
-    AMK_HIP(hipGetLastError());
-    return AMK_OK;
+    return launch_edge(f, {d_Twc, d_cloud, cloud_scene_stride, d_counts}, (hipStream_t)stream);
 }
 
 // tests only (exported, not in the header): force amk_depth_to_clouds onto the tiled kernels with bands of this many rows (clipped to
@@ -488,12 +551,11 @@ int amk__depth_set_band_rows(int band_rows) {
     return AMK_OK;
 }
 
-// {obstacle, edge} count of every band of every scene, for the smallest band (one row): covers any band height
 int amk_depth_clouds_work_bytes(int rows, int cols, double resize_scale, int n_scenes, long long *bytes_out) {
     int w = 0, h = 0;
     if (!bytes_out || n_scenes <= 0) return AMK_ERR_INVALID_ARG;
     if (const int st = amk_depth_out_size(rows, cols, resize_scale, &w, &h); st != AMK_OK) return st;
-    *bytes_out = (long long)sizeof(int2) * h * n_scenes;
+    *bytes_out = work_bytes_for(h, n_scenes);
     return AMK_OK;
 }
 
@@ -501,126 +563,62 @@ int amk_depth_to_clouds(const void *d_depth, int depth_type, int rows, int cols,
                         const amk_depth_params *params, const double *d_Twb, const double *d_Twc, float *d_cloud,
                         long long cloud_scene_stride, int *d_counts, float *d_edge, long long edge_scene_stride,
                         int *d_edge_counts, int point_stride, void *d_work, long long work_bytes, void *stream) {
-    if (!d_depth || !d_Twb || !d_Twc || !d_cloud || !d_counts || !d_edge || !d_edge_counts || !d_work || n_scenes <= 0 ||
-        point_stride < 3)
-        return AMK_ERR_INVALID_ARG;
-    if (depth_type != AMK_DEPTH_U16 && depth_type != AMK_DEPTH_F32) return AMK_ERR_UNSUPPORTED;
-    DepthGeom g;
-    int st = make_geom(rows, cols, params, g);
-    if (st != AMK_OK) return st;
-    const long long cap = (long long)g.W * g.H * point_stride;
-    if (scene_stride < (long long)rows * cols || cloud_scene_stride < cap || edge_scene_stride < cap) return AMK_ERR_INVALID_ARG;
-    if (work_bytes < (long long)sizeof(int2) * g.H * n_scenes) return AMK_ERR_INVALID_ARG;
+    Frames f;
+    if (const int st = check_frames(d_Twb && d_Twc && d_cloud && d_counts && d_edge && d_edge_counts && d_work, d_depth, depth_type, rows,
+                                    cols, scene_stride, n_scenes, params, point_stride, std::min(cloud_scene_stride, edge_scene_stride), f);
+        st != AMK_OK)
+        return st;
+    const DepthGeom &g = f.g;
+    if (work_bytes < work_bytes_for(g.H, n_scenes)) return AMK_ERR_INVALID_ARG;
     if (g.W > AMK_DEPTH_MAX_WIDTH) return AMK_ERR_UNSUPPORTED;
     const int forced = g_forced_band_rows;
     const bool one_block = forced <= 0 && (long long)g.W * g.H <= AMK_EDGE_MAX_PIXELS;
     if (!one_block && n_scenes > 65535) return AMK_ERR_UNSUPPORTED;   // (scenes are the grid's second dimension)
     if (amk_device_count() <= 0) return AMK_ERR_NO_DEVICE;
+    const hipStream_t hs = (hipStream_t)stream;
     if (one_block) {   // the one-block kernels, as the two calls launch them
-        st = amk_depth_to_cloud(d_depth, depth_type, rows, cols, scene_stride, n_scenes, params, d_Twb, d_cloud, point_stride,
-                                cloud_scene_stride, d_counts, stream);
-        if (st != AMK_OK) return st;
-        return amk_depth_to_edge_cloud(d_depth, depth_type, rows, cols, scene_stride, n_scenes, params, d_Twc, d_edge, point_stride,
-                                       edge_scene_stride, d_edge_counts, stream);
+        if (const int st = launch_cloud(f, {d_Twb, d_cloud, cloud_scene_stride, d_counts}, hs); st != AMK_OK) return st;
+        return launch_edge(f, {d_Twc, d_edge, edge_scene_stride, d_edge_counts}, hs);
     }
     const int R = std::min(forced > 0 ? forced : kBandRowsAuto, band_rows_max(g.W));
     const dim3 grid((g.H + R - 1) / R, n_scenes);
     const size_t lds = (size_t)g.W * (4 * R + 14);
-    int2 *bc = (int2 *)d_work;
-    const hipStream_t hs = (hipStream_t)stream;
-#define AMK_BAND_LAUNCH(T, EMIT)                                                                                                   \
-    hipLaunchKernelGGL((depth_band_kernel<T, EMIT>), grid, dim3(kDepthThreads), lds, hs, (const T *)d_depth, scene_stride, g, R,   \
-                       d_Twb, d_Twc, d_cloud, cloud_scene_stride, d_counts, d_edge, edge_scene_stride, d_edge_counts, point_stride, bc)
-    if (depth_type == AMK_DEPTH_U16) {
-        AMK_BAND_LAUNCH(unsigned short, false);
-        AMK_BAND_LAUNCH(unsigned short, true);
-    } else {
-        AMK_BAND_LAUNCH(float, false);
-        AMK_BAND_LAUNCH(float, true);
-    }
-#undef AMK_BAND_LAUNCH
-    AMK_HIP(hipGetLastError());
-    return AMK_OK;
+    return with_pixels(f, [&](auto *img) {
+        using T = std::decay_t<decltype(*img)>;
+        for (auto *kernel : {depth_band_kernel<T, false>, depth_band_kernel<T, true>})   // count, then emit
+            hipLaunchKernelGGL(kernel, grid, dim3(kDepthThreads), lds, hs, img, scene_stride, g, R, d_Twb, d_Twc, d_cloud,
+                               cloud_scene_stride, d_counts, d_edge, edge_scene_stride, d_edge_counts, point_stride, (int2 *)d_work);
+    });
+}
+
+int amk_depth_to_cloud_host(const void *h_depth, int depth_type, int rows, int cols, long long scene_stride, int n_scenes,
+                            const amk_depth_params *params, const double *h_Twb, float *h_cloud, int point_stride,
+                            long long cloud_scene_stride, int *h_counts) {
+    return one_cloud_on_host(amk_depth_to_cloud, h_depth, depth_type, rows, cols, scene_stride, n_scenes, params, h_Twb, h_cloud,
+                             point_stride, cloud_scene_stride, h_counts);
+}
+
+int amk_depth_to_edge_cloud_host(const void *h_depth, int depth_type, int rows, int cols, long long scene_stride,
+                                 int n_scenes, const amk_depth_params *params, const double *h_Twc, float *h_cloud,
+                                 int point_stride, long long cloud_scene_stride, int *h_counts) {
+    return one_cloud_on_host(amk_depth_to_edge_cloud, h_depth, depth_type, rows, cols, scene_stride, n_scenes, params, h_Twc, h_cloud,
+                             point_stride, cloud_scene_stride, h_counts);
 }
 
 int amk_depth_to_clouds_host(const void *h_depth, int depth_type, int rows, int cols, long long scene_stride, int n_scenes,
                              const amk_depth_params *params, const double *h_Twb, const double *h_Twc, float *h_cloud,
                              long long cloud_scene_stride, int *h_counts, float *h_edge, long long edge_scene_stride,
                              int *h_edge_counts, int point_stride) {
-    if (!h_depth || !h_Twb || !h_Twc || !h_cloud || !h_counts || !h_edge || !h_edge_counts || n_scenes <= 0 || scene_stride <= 0 ||
-        cloud_scene_stride <= 0 || edge_scene_stride <= 0)
-        return AMK_ERR_INVALID_ARG;
-    if (depth_type != AMK_DEPTH_U16 && depth_type != AMK_DEPTH_F32) return AMK_ERR_UNSUPPORTED;
+    if (scene_stride <= 0 || cloud_scene_stride <= 0 || edge_scene_stride <= 0) return AMK_ERR_INVALID_ARG;
+    const Cloud host[2] = {{h_Twb, h_cloud, cloud_scene_stride, h_counts}, {h_Twc, h_edge, edge_scene_stride, h_edge_counts}};
     long long work_bytes = 0;
-    if (const int st = amk_depth_clouds_work_bytes(rows, cols, params ? params->resize_scale : 0.0, n_scenes, &work_bytes); st != AMK_OK)
-        return st;
-    if (amk_device_count() <= 0) return AMK_ERR_NO_DEVICE;
-    const size_t esz = depth_type == AMK_DEPTH_U16 ? 2 : 4;
-    amk::DevBuf<unsigned char> img, work;
-    amk::DevBuf<double> pose;   // [2][S][16]: Twb, Twc
-    amk::DevBuf<float> cloud, edge;
-    amk::DevBuf<int> cnt;       // [2][S]: obstacle, edge
-    AMK_HIP(img.alloc((size_t)scene_stride * n_scenes * esz));
-    AMK_HIP(work.alloc((size_t)work_bytes));
-    AMK_HIP(pose.alloc((size_t)32 * n_scenes));
-    AMK_HIP(cloud.alloc((size_t)cloud_scene_stride * n_scenes));
-    AMK_HIP(edge.alloc((size_t)edge_scene_stride * n_scenes));
-    AMK_HIP(cnt.alloc((size_t)2 * n_scenes));
-    AMK_HIP(hipMemcpy(img.p, h_depth, (size_t)scene_stride * n_scenes * esz, hipMemcpyHostToDevice));
-    AMK_HIP(hipMemcpy(pose.p, h_Twb, sizeof(double) * 16 * n_scenes, hipMemcpyHostToDevice));
-    AMK_HIP(hipMemcpy(pose.p + (size_t)16 * n_scenes, h_Twc, sizeof(double) * 16 * n_scenes, hipMemcpyHostToDevice));
-    const int st = amk_depth_to_clouds(img.p, depth_type, rows, cols, scene_stride, n_scenes, params, pose.p,
-                                       pose.p + (size_t)16 * n_scenes, cloud.p, cloud_scene_stride, cnt.p, edge.p, edge_scene_stride,
-                                       cnt.p + n_scenes, point_stride, work.p, work_bytes, nullptr);
-    if (st != AMK_OK) return st;
-    AMK_HIP(hipDeviceSynchronize());
-    AMK_HIP(hipMemcpy(h_counts, cnt.p, sizeof(int) * n_scenes, hipMemcpyDeviceToHost));
-    AMK_HIP(hipMemcpy(h_edge_counts, cnt.p + n_scenes, sizeof(int) * n_scenes, hipMemcpyDeviceToHost));
-    AMK_HIP(hipMemcpy(h_cloud, cloud.p, sizeof(float) * (size_t)cloud_scene_stride * n_scenes, hipMemcpyDeviceToHost));
-    AMK_HIP(hipMemcpy(h_edge, edge.p, sizeof(float) * (size_t)edge_scene_stride * n_scenes, hipMemcpyDeviceToHost));
-    return AMK_OK;
-}
-
-static int depth_host_common(int edge, const void *h_depth, int depth_type, int rows, int cols, long long scene_stride,
-                             int n_scenes, const amk_depth_params *params, const double *h_T, float *h_cloud,
-                             int point_stride, long long cloud_scene_stride, int *h_counts) {
-    if (!h_depth || !h_T || !h_cloud || !h_counts || n_scenes <= 0) return AMK_ERR_INVALID_ARG;
-    if (depth_type != AMK_DEPTH_U16 && depth_type != AMK_DEPTH_F32) return AMK_ERR_UNSUPPORTED;
-    if (amk_device_count() <= 0) return AMK_ERR_NO_DEVICE;
-    const size_t esz = depth_type == AMK_DEPTH_U16 ? 2 : 4;
-    amk::DevBuf<unsigned char> img;
-    amk::DevBuf<double> pose;
-    amk::DevBuf<float> cloud;
-    amk::DevBuf<int> cnt;
-    AMK_HIP(img.alloc((size_t)scene_stride * n_scenes * esz));
-    AMK_HIP(pose.alloc((size_t)16 * n_scenes));
-    AMK_HIP(cloud.alloc((size_t)cloud_scene_stride * n_scenes));
-    AMK_HIP(cnt.alloc(n_scenes));
-    AMK_HIP(hipMemcpy(img.p, h_depth, (size_t)scene_stride * n_scenes * esz, hipMemcpyHostToDevice));
-    AMK_HIP(hipMemcpy(pose.p, h_T, sizeof(double) * 16 * n_scenes, hipMemcpyHostToDevice));
-    int st = edge ? amk_depth_to_edge_cloud(img.p, depth_type, rows, cols, scene_stride, n_scenes, params, pose.p, cloud.p,
-                                            point_stride, cloud_scene_stride, cnt.p, nullptr)
-                  : amk_depth_to_cloud(img.p, depth_type, rows, cols, scene_stride, n_scenes, params, pose.p, cloud.p,
-                                       point_stride, cloud_scene_stride, cnt.p, nullptr);
-    if (st != AMK_OK) return st;
-    AMK_HIP(hipDeviceSynchronize());
-    AMK_HIP(hipMemcpy(h_counts, cnt.p, sizeof(int) * n_scenes, hipMemcpyDeviceToHost));
-    AMK_HIP(hipMemcpy(h_cloud, cloud.p, sizeof(float) * (size_t)cloud_scene_stride * n_scenes, hipMemcpyDeviceToHost));
-    return AMK_OK;
-}
-
-int amk_depth_to_edge_cloud_host(const void *h_depth, int depth_type, int rows, int cols, long long scene_stride,
-                                 int n_scenes, const amk_depth_params *params, const double *h_Twc, float *h_cloud,
-                                 int point_stride, long long cloud_scene_stride, int *h_counts) {
-    return depth_host_common(1, h_depth, depth_type, rows, cols, scene_stride, n_scenes, params, h_Twc, h_cloud,
-                             point_stride, cloud_scene_stride, h_counts);
-}
-
-int amk_depth_to_cloud_host(const void *h_depth, int depth_type, int rows, int cols, long long scene_stride, int n_scenes,
-                            const amk_depth_params *params, const double *h_Twb, float *h_cloud, int point_stride,
-                            long long cloud_scene_stride, int *h_counts) {
-    return depth_host_common(0, h_depth, depth_type, rows, cols, scene_stride, n_scenes, params, h_Twb, h_cloud,
-                             point_stride, cloud_scene_stride, h_counts);
+    const int work_status = amk_depth_clouds_work_bytes(rows, cols, params ? params->resize_scale : 0.0, n_scenes, &work_bytes);
+    return on_device_copies(h_depth, depth_type, scene_stride, n_scenes, host, work_status, work_bytes,
+                            [&](const void *img, const Cloud *c, void *work) {
+                                return amk_depth_to_clouds(img, depth_type, rows, cols, scene_stride, n_scenes, params, c[0].T, c[1].T,
+                                                           c[0].points, c[0].scene_stride, c[0].counts, c[1].points, c[1].scene_stride,
+                                                           c[1].counts, point_stride, work, work_bytes, nullptr);
+                            });
 }
 
 }  // extern "C"

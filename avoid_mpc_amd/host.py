@@ -698,19 +698,25 @@ def depth_params(pixel2meter=1.0, depth_min=0.1, depth_max=100.0, resize_scale=1
     return p
 
 
-def depth_to_cloud(depth, params, Twb, point_stride=3, stream=None, edge=False):
-    """FrameKDMap::ProcessDepth (edge=True: FrameKDMap::BuildEdgeCloud, Twb then = mCurFrame.Twc) for a batch: depth [S, rows, cols] uint16 / float32 device tensor, Twb [S, 4, 4]
-    float64 -> (cloud float32 [S, W*H, point_stride], counts int32 [S]); the cloud feeds KdBatch.build(cloud, counts)."""
+def _depth_batch(depth, params, poses):
+    """What depth_to_cloud and depth_to_clouds start with: the checked shapes of a batch and the library's answer about its
+    down-scaled size -> (lib, S, rows, cols, capacity of a cloud in points, AMK_DEPTH_* of the pixels)."""
     assert depth.dim() == 3 and depth.dtype in (torch.uint16, torch.int16, torch.float32) and depth.is_contiguous()
     S, rows, cols = (int(v) for v in depth.shape)
-    assert Twb.dtype == torch.float64 and tuple(Twb.shape) == (S, 4, 4) and Twb.is_contiguous()
+    for T in poses:
+        assert T.dtype == torch.float64 and tuple(T.shape) == (S, 4, 4) and T.is_contiguous()
     lib = capi.load()
     w, h = C.c_int(), C.c_int()
     capi.check(lib.amk_depth_out_size(rows, cols, params.resize_scale, C.byref(w), C.byref(h)), "amk_depth_out_size")
-    cap = w.value * h.value
+    return lib, S, rows, cols, w.value * h.value, capi.AMK_DEPTH_F32 if depth.dtype == torch.float32 else capi.AMK_DEPTH_U16
+
+
+def depth_to_cloud(depth, params, Twb, point_stride=3, stream=None, edge=False):
+    """FrameKDMap::ProcessDepth (edge=True: FrameKDMap::BuildEdgeCloud, Twb then = mCurFrame.Twc) for a batch: depth [S, rows, cols] uint16 / float32 device tensor, Twb [S, 4, 4]
+    float64 -> (cloud float32 [S, W*H, point_stride], counts int32 [S]); the cloud feeds KdBatch.build(cloud, counts)."""
+    lib, S, rows, cols, cap, kind = _depth_batch(depth, params, (Twb,))
     cloud = torch.zeros((S, cap, point_stride), dtype=torch.float32, device=depth.device)
     counts = torch.empty(S, dtype=torch.int32, device=depth.device)
-    kind = capi.AMK_DEPTH_F32 if depth.dtype == torch.float32 else capi.AMK_DEPTH_U16
     fn = lib.amk_depth_to_edge_cloud if edge else lib.amk_depth_to_cloud
     capi.check(fn(capi.dptr(depth), kind, rows, cols, rows * cols, S, C.byref(params), capi.dptr(Twb), capi.dptr(cloud),
                   int(point_stride), cap * point_stride, capi.dptr(counts), capi.stream_ptr(stream)),
@@ -723,15 +729,9 @@ def depth_to_clouds(depth, params, Twb, Twc, point_stride=3, stream=None):
     down-scaled images of any size (amk_depth_to_clouds): depth [S, rows, cols] uint16 / float32 device tensor, Twb and Twc
     (mCurFrame.Twc: the previous frame's Twb * Tbc) [S, 4, 4] float64 -> (cloud, counts, edge, edge_counts), clouds float32
     [S, W*H, point_stride] of which the first counts[s] points of a scene are written, counts int32 [S]."""
-    assert depth.dim() == 3 and depth.dtype in (torch.uint16, torch.int16, torch.float32) and depth.is_contiguous()
-    S, rows, cols = (int(v) for v in depth.shape)
-    for T in (Twb, Twc):
-        assert T.dtype == torch.float64 and tuple(T.shape) == (S, 4, 4) and T.is_contiguous()
-    lib = capi.load()
-    w, h, nbytes = C.c_int(), C.c_int(), C.c_longlong()
-    capi.check(lib.amk_depth_out_size(rows, cols, params.resize_scale, C.byref(w), C.byref(h)), "amk_depth_out_size")
+    lib, S, rows, cols, cap, kind = _depth_batch(depth, params, (Twb, Twc))
+    nbytes = C.c_longlong()
     capi.check(lib.amk_depth_clouds_work_bytes(rows, cols, params.resize_scale, S, C.byref(nbytes)), "amk_depth_clouds_work_bytes")
-    cap = w.value * h.value
     cloud = torch.zeros((S, cap, point_stride), dtype=torch.float32, device=depth.device)
     edge = torch.zeros((S, cap, point_stride), dtype=torch.float32, device=depth.device)
     counts = torch.empty(S, dtype=torch.int32, device=depth.device)
@@ -739,7 +739,6 @@ def depth_to_clouds(depth, params, Twb, Twc, point_stride=3, stream=None):
     work = torch.empty((nbytes.value + 7) // 8, dtype=torch.int64, device=depth.device)
     if stream is not None:
         work.record_stream(stream)   # dropped at return: its memory must not be reused before the launches on `stream` are through
-    kind = capi.AMK_DEPTH_F32 if depth.dtype == torch.float32 else capi.AMK_DEPTH_U16
     capi.check(lib.amk_depth_to_clouds(capi.dptr(depth), kind, rows, cols, rows * cols, S, C.byref(params), capi.dptr(Twb), capi.dptr(Twc),
                                        capi.dptr(cloud), cap * point_stride, capi.dptr(counts), capi.dptr(edge), cap * point_stride,
                                        capi.dptr(edge_counts), int(point_stride), capi.dptr(work), work.numel() * 8,

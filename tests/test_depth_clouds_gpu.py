@@ -9,11 +9,10 @@ import numpy as np
 import pytest
 
 from tests import _oracle
+from tests._depth import TBC, poses as _poses, wall_scene as _wall_scene
 from tests.test_depth_oracle import YAML
 
 pytestmark = pytest.mark.gpu
-
-TBC = np.array([[0, 0, 1, 0.1], [-1, 0, 0, 0.0], [0, -1, 0, 0.05], [0, 0, 0, 1.0]])
 
 
 @pytest.fixture(scope="module")
@@ -32,25 +31,6 @@ def band_rows():
         yield lambda r: lib.amk__depth_set_band_rows(int(r))
     finally:
         lib.amk__depth_set_band_rows(0)
-
-
-def _poses(rng, S):
-    out = np.zeros((S, 4, 4))
-    for s in range(S):
-        th = rng.uniform(-np.pi, np.pi)
-        out[s] = [[np.cos(th), -np.sin(th), 0, rng.uniform(-5, 5)], [np.sin(th), np.cos(th), 0, rng.uniform(-5, 5)],
-                  [0, 0, 1, rng.uniform(0.5, 3)], [0, 0, 0, 1]]
-    return out
-
-
-def _wall_scene(rng, shape, dtype):
-    """As in test_depth_gpu.test_edge_cloud_bit_exact_vs_oracle: a wall with noise, a near box, 2 % invalid pixels."""
-    rows, cols = shape
-    d = np.full(shape, 20.0) + rng.normal(0, 0.02, shape)
-    r0, c0 = rng.integers(2, rows // 2), rng.integers(2, cols // 2)
-    d[r0:r0 + rows // 3, c0:c0 + cols // 3] = rng.uniform(2, 8)
-    d[rng.random(shape) < 0.02] = 0.0
-    return np.round(d * 1000).astype(np.uint16) if dtype == np.uint16 else d.astype(np.float32)
 
 
 def _references(imgs, prm, Twb, Twc):
@@ -107,6 +87,23 @@ def test_above_the_one_block_limit(dtype, stride, torch_cuda):
     _assert_equal(got, refs)
     assert got[1][2] == 0 and got[3][2] == 0
     assert min(got[3][s] for s in (0, 1, 3)) > 10 and min(got[1][s] for s in (0, 1, 3)) > 0
+
+
+@pytest.mark.parametrize("shape", [(125, 128), (127, 126), (7, 2047)])
+def test_at_the_edge_of_the_dispatch(shape, band_rows, torch_cuda):
+    """Scale 1, float32, S = 2, the automatic band height: 125 x 128 = 16 000 pixels, the last size on the one-block pair (its LDS
+    layers at their largest); 127 x 126 = 16 002, the first tiled size; 7 x 2047 = 14 329, an odd pixel count on one block (the
+    magnitude layer starts at (npix + 1) & ~1) at the widest odd row.  3 x 5333 = 15 999 would be the odd count next to the limit,
+    but its width is above AMK_DEPTH_MAX_WIDTH: the call refuses it (test_refusals)."""
+    rng = np.random.default_rng(12)
+    S = 2
+    imgs = np.stack([_wall_scene(rng, shape, np.float32) for _ in range(S)])
+    prm = dict(YAML, pixel2meter=1.0, resize_scale=1.0, Tbc=TBC)
+    Twb, Twc = _poses(rng, S), _poses(rng, S)
+    refs = _references(imgs, prm, Twb, Twc)
+    assert all(len(rc) > 0 and len(re) > 10 for rc, re, _ in refs), [(len(rc), len(re)) for rc, re, _ in refs]
+    band_rows(0)
+    _assert_equal(_run(torch_cuda, imgs, prm, Twb, Twc), refs, shape)
 
 
 BORDER_H, BORDER_W = 37, 53
@@ -239,6 +236,7 @@ def test_refusals(torch_cuda):
     assert call(kind=7) == capi.AMK_ERR_UNSUPPORTED
     # a 4 x 2049 image at scale 1: W > AMK_DEPTH_MAX_WIDTH (its buffers fit in the ones above)
     assert call(rows=4, cols=2049, scene_stride=4 * 2049) == capi.AMK_ERR_UNSUPPORTED
+    assert call(rows=3, cols=5333, scene_stride=3 * 5333) == capi.AMK_ERR_UNSUPPORTED   # (15 999 pixels: one block's worth, too wide)
     torch.cuda.synchronize()
     for t in (cloud, edge, cnt, ecnt):
         assert bool((t == -7).all())

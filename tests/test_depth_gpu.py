@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from tests import _oracle
+from tests._depth import TBC, poses as _poses, wall_scene
 from tests.test_depth_oracle import YAML, scene
 
 pytestmark = pytest.mark.gpu
@@ -15,15 +16,6 @@ def torch_cuda():
     import torch
     assert torch.cuda.is_available()
     return torch
-
-
-def _poses(rng, S):
-    out = np.zeros((S, 4, 4))
-    for s in range(S):
-        th = rng.uniform(-np.pi, np.pi)
-        out[s] = [[np.cos(th), -np.sin(th), 0, rng.uniform(-5, 5)], [np.sin(th), np.cos(th), 0, rng.uniform(-5, 5)],
-                  [0, 0, 1, rng.uniform(0.5, 3)], [0, 0, 0, 1]]
-    return out
 
 
 @pytest.mark.parametrize("dtype", [np.uint16, np.float32])
@@ -37,8 +29,7 @@ def test_bit_exact_vs_oracle(dtype, shape, scale, stride, torch_cuda):
     imgs, p2m = zip(*[scene(rng, *shape, dtype) for _ in range(S)])
     imgs = np.stack(imgs)
     imgs[S - 1] = 0                                   # an empty frame
-    Tbc = np.array([[0, 0, 1, 0.1], [-1, 0, 0, 0.0], [0, -1, 0, 0.05], [0, 0, 0, 1.0]])
-    prm = dict(YAML, pixel2meter=p2m[0], resize_scale=scale, Tbc=Tbc)
+    prm = dict(YAML, pixel2meter=p2m[0], resize_scale=scale, Tbc=TBC)
     Twb = _poses(rng, S)
     dev = torch.from_numpy(imgs.view(np.int16) if dtype == np.uint16 else imgs).cuda()
     cloud, counts = depth_to_cloud(dev, depth_params(**prm), torch.from_numpy(Twb).cuda(), point_stride=stride)
@@ -103,18 +94,9 @@ def test_edge_cloud_bit_exact_vs_oracle(dtype, shape, scale, stride, torch_cuda)
     from avoid_mpc_amd.host import depth_params, depth_to_cloud
     rng = np.random.default_rng(4)
     S = 5
-    rows, cols = shape
-    imgs = []
-    for s in range(S):
-        d = np.full(shape, 20.0) + rng.normal(0, 0.02, shape)
-        r0, c0 = rng.integers(2, rows // 2), rng.integers(2, cols // 2)
-        d[r0:r0 + rows // 3, c0:c0 + cols // 3] = rng.uniform(2, 8)
-        d[rng.random(shape) < 0.02] = 0.0
-        imgs.append(np.round(d * 1000).astype(np.uint16) if dtype == np.uint16 else d.astype(np.float32))
-    imgs = np.stack(imgs)
+    imgs = np.stack([wall_scene(rng, shape, dtype) for _ in range(S)])
     imgs[S - 1] = 0                                   # no obstacle point -> no edge cloud either
-    Tbc = np.array([[0, 0, 1, 0.1], [-1, 0, 0, 0.0], [0, -1, 0, 0.05], [0, 0, 0, 1.0]])
-    prm = dict(YAML, pixel2meter=1e-3 if dtype == np.uint16 else 1.0, resize_scale=scale, Tbc=Tbc)
+    prm = dict(YAML, pixel2meter=1e-3 if dtype == np.uint16 else 1.0, resize_scale=scale, Tbc=TBC)
     Twc = _poses(rng, S)
     dev = torch.from_numpy(imgs.view(np.int16) if dtype == np.uint16 else imgs).cuda()
     cloud, counts = depth_to_cloud(dev, depth_params(**prm), torch.from_numpy(Twc).cuda(), point_stride=stride, edge=True)
