@@ -258,6 +258,7 @@ def load():
     sig["amk__frames_force_wide"] = (None, [i])  # internal (tests): 1 the multi-frame step's merge re-reads its candidates every round whatever the map's size
     sig["amk__mpc_ref_states"] = (i, [vp, vp, ll])  # internal (tests): host copy of the P vectors the last step's newest pass handed to the solve
     sig["amk__kfmap_slots_host"] = (i, [vp, vp, vp, vp, vp, vp])  # internal (tests): cur_slot [S], kf_n [S], kf_slots [S][P], fmap [F][S], need [S] of a keyframe map
+    sig["amk__mpc_dynamics"] = (i, [vp, vp, d, vp, vp, vp, vp])  # internal (tests), host only, no device: tau[4], drag[3], dt -> A [10][10], B [10][4], c [10], dtau [3][150] or NULL
     sig["amk__depth_set_band_rows"] = (i, [i])  # internal (tests, measurements): amk_depth_to_clouds tiled with bands of this many rows at any image size; 0 automatic
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)

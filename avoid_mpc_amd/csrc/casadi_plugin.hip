@@ -33,7 +33,7 @@ namespace {
 struct Plugin {
     amk_mpc *mpc = nullptr;
     int N = 0, K = 0, nx = 0, np = 0, ng = 0, nref = 0, nnz_j = 0, nnz_h = 0;
-    double tail[34];  // gains, taus, weights, radius last pushed into the handle
+    double tail[amk::NlpDims::kTail];  // gains, taus, weights, radius last pushed into the handle
     bool have_tail = false;
     std::vector<casadi_int> sp_x, sp_p, sp_g, sp_scalar, sp_jac, sp_hess;
     std::vector<double> f, grad, g, jac, hess, gx, gp, zx, zp, zg;
@@ -91,10 +91,11 @@ Plugin &plugin() {
 int push_tail(Plugin &P, const double *p) {
     const double *t = p + P.nref;
     if (P.have_tail && std::memcmp(t, P.tail, sizeof P.tail) == 0) return AMK_OK;
-    int st = amk_mpc_setup_gains(P.mpc, t);
-    if (st == AMK_OK) st = amk_mpc_setup_tau(P.mpc, t + 4);
-    if (st == AMK_OK) st = amk_mpc_setup_weights(P.mpc, t + 8);
-    if (st == AMK_OK) st = amk_mpc_set_drone_radius(P.mpc, t[33]);
+    using D = amk::NlpDims;
+    int st = amk_mpc_setup_gains(P.mpc, t + D::kTailGain);
+    if (st == AMK_OK) st = amk_mpc_setup_tau(P.mpc, t + D::kTailTau);
+    if (st == AMK_OK) st = amk_mpc_setup_weights(P.mpc, t + D::kTailW);
+    if (st == AMK_OK) st = amk_mpc_set_drone_radius(P.mpc, t[D::kTailRadius]);
     if (st == AMK_OK) {
         std::memcpy(P.tail, t, sizeof P.tail);
         P.have_tail = true;

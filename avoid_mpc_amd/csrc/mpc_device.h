@@ -20,6 +20,7 @@
 #pragma once
 #include "amk_common.h"
 #include "fast_math.h"
+#include "mpc_model.h"   // SD, UD, kGz, rows_of_A / rows_of_B, pv_of / pv_inv, SceneRecord, NlpDims: shared with the host
 
 namespace amk {
 
@@ -32,9 +33,6 @@ constexpr bool kTrace = true;
 #define AMK_CLK() 0LL
 constexpr bool kTrace = false;
 #endif
-
-constexpr int SD = AMK_S_DIM;  // 10
-constexpr int UD = AMK_U_DIM;  // 4
 
 // parameter block in device memory (doubles)
 constexpr int PRM_W = 0;        // weights[25]: Qgoal[10] Qpen[10] Qu[4] lambda
@@ -118,22 +116,6 @@ constexpr int DPP_XOR2 = 0x4E;         // quad_perm:[2,3,0,1]
 constexpr int DPP_HALF_MIRROR = 0x141; // lane i <-> 7-i inside each 8 lanes
 constexpr int DPP_MIRROR = 0x140;      // lane i <-> 15-i inside each row of 16
 
-// nonzero rows of column j of A / column a of B (fixed by the model: p <- v <- a chains per axis,
-// yaw <- yaw_dot; mpc_obstacle_casadi.py:106-122).  Returns count, rows in r[3].
-__device__ __forceinline__ int rows_of_A(int j, int r[3]) {
-    if (j < 4) { r[0] = j; return 1; }                     // p_x,p_y,p_z,yaw: identity column
-    if (j < 7) { r[0] = j - 4; r[1] = j; return 2; }       // v_a: rows p_a, v_a
-    r[0] = j - 7; r[1] = j - 3; r[2] = j; return 3;        // a_a: rows p_a, v_a, a_a
-}
-__device__ __forceinline__ int rows_of_B(int a, int r[3]) {
-    if (a == 3) { r[0] = 3; return 1; }                    // yaw_dot -> yaw
-    r[0] = a; r[1] = 4 + a; r[2] = 7 + a; return 3;        // a_cmd -> p_a, v_a, a_a
-}
-
-// position/velocity slots of the 10-state, and the inverse map (-1 = not in the 6-block)
-__device__ __forceinline__ int pv_of(int i) { return i < 3 ? i : i + 1; }   // 0..5 -> {0,1,2,4,5,6}
-__device__ __forceinline__ int pv_inv(int s) { return s < 3 ? s : (s >= 4 && s <= 6 ? s - 1 : -1); }
-
 // ---- Riccati plan: which LDS cells each lane combines in "round A" of a backward stage.  The affine
 // dynamics are constant, so every entry of A'PA, B'PB, B'PA, A'p, A'lam, B'p, B'lam is a fixed <= 9-term
 // linear combination of entries of P / p / lam; the host enumerates the terms once per handle
@@ -175,8 +157,8 @@ struct SolveSched {
 };
 
 struct SceneIO {
-    const double *ref;   // [N][10] reference states            (P[10 : 10+10N])
-    const double *obs;   // [N][K][3] obstacle points           (P[10+10N : ...])
+    const double *ref;   // [N][10] reference states            (SceneRecord::ref)
+    const double *obs;   // [N][K][3] obstacle points           (SceneRecord::obs)
 };
 
 }  // namespace amk

@@ -6,7 +6,9 @@ namespace AMK_RNS {
 using namespace amk;
 typedef AMK_REAL real;
 #define RL(x) ((real)(x))
-constexpr real kGz = RL(9.81);   // mpc_obstacle_casadi.py:39
+#if AMK_REAL_F32
+constexpr real kGz = RL(amk::kGz);   // the model's constant (mpc_model.h) in this namespace's arithmetic
+#endif
 constexpr int YB = amk::kTermRecord;  // doubles per collision term in the global scratch: y1, y2, 1/rho, g'/g
 
 // ---- cross-lane reductions on DPP (no LDS crossbar): quad_perm for lane^1 / lane^2, row_half_mirror and
@@ -797,6 +799,23 @@ __device__ __forceinline__ real next_mu(real mu, real mu_min, real kappa_mu) {
     return m < RL(10.0) * mu_min ? mu_min : m;                       // no short last level
 }
 
+// What every pass over a scene opens with (the solve, and the two NLP evaluation kernels of mpc_eval.hip): the first prm_len
+// parameters, x_init, the target and the rotation of every reference yaw into LDS.  No barrier: the caller's.
+__device__ __forceinline__ void load_scene(real *sm, const LdsMap &L, int N, const double *prm_g, int prm_len, const double *x_init,
+                                           const double *target, const SceneIO &io) {
+    const int lane = threadIdx.x;
+    for (int e = lane; e < prm_len; e += 64) sm[L.prm + e] = (real)prm_g[e];
+    if (lane < SD) {
+        sm[L.xinit + lane] = (real)x_init[lane];
+        sm[L.target + lane] = (real)target[lane];
+    }
+    if (lane < N - 1) {  // rot of ref yaw, :174-185
+        const real yaw = (real)io.ref[lane * SD + 3];
+        sm[L.cy + lane] = cos(yaw);
+        sm[L.sy + lane] = sin(-yaw);
+    }
+}
+
 // The whole solve for one scene.  w0/w_out: decision vector [X_0,U_0,...,U_{N-1},X_N] in global
 // memory (warm start in, solution out; may alias).  info[4] as in the C ABI.  ybuf: [N][K][YB] doubles of scratch.
 // Statement by statement the algorithm of DESIGN.md section 5, as the CPU restatement of the tests (one difference in bookkeeping only: an accepted first
@@ -825,16 +844,7 @@ __device__ __forceinline__ void solve_scene(real *sm, const LdsMap &L, int N, in
     const int lane = threadIdx.x;
     const real o_tol = (real)opt.tol, o_mu_init = (real)opt.mu_init, o_bound_push = (real)opt.bound_push, o_bound_frac = (real)opt.bound_frac, o_kappa_mu = (real)opt.kappa_mu, o_tau_min = (real)opt.tau_min, o_eta_phi = (real)opt.eta_phi, o_s_max = (real)opt.s_max, o_kappa_sigma = (real)opt.kappa_sigma;
     const real o_kappa_eps = (real)opt.kappa_eps, o_maj = (real)opt.maj;
-    for (int e = lane; e < PRM_LDS_LEN; e += 64) sm[L.prm + e] = (real)prm_g[e];
-    if (lane < SD) {
-        sm[L.xinit + lane] = (real)x_init[lane];
-        sm[L.target + lane] = (real)target[lane];
-    }
-    if (lane < N - 1) {  // rot of ref yaw, :174-185
-        const real yaw = (real)io.ref[lane * SD + 3];
-        sm[L.cy + lane] = cos(yaw);
-        sm[L.sy + lane] = sin(-yaw);
-    }
+    load_scene(sm, L, N, prm_g, PRM_LDS_LEN, x_init, target, io);
     __syncthreads();
     const real *prm = sm + L.prm;
     for (int e = lane; e < 56 + 10 + 40; e += 64) sm[L.M + e] = RL(0.0);  // structurally-zero outputs stay zero

@@ -1,6 +1,9 @@
 // Host-side handle of a batch of ObstacleAvoidanceMPC objects (AM/include/HighLvlMpc.h:4-33) and the
 // device workspace of the fused control step.  Shared by mpc_solve.hip and step.hip.
 #pragma once
+#include <initializer_list>
+#include <type_traits>
+#include <utility>
 #include <vector>
 #include "mpc_device.h"
 
@@ -9,6 +12,7 @@ struct amk_mpc {
     int N = 0, K = 0, S = 0, nx = 0, nref = 0;
     int run_scenes = 0;       // internal (amk_pipeline, a gang that is not full): launches cover scenes [0, run_scenes); 0 = all S
     int launch_scenes() const { return run_scenes > 0 && run_scenes < S ? run_scenes : S; }
+    amk::NlpDims dims() const { return {N, K}; }   // nx and nref above are dims().nx() and SceneRecord{N, K}.len()
     double h_prm[amk::PRM_LEN];
     double drag[3] = {0.0, 0.0, 0.0};   // amk_mpc_set_drag_coefficient: v' = a - drag .* v (host-side: only A, B, c see it)
     amk::SolveOpts opt;
@@ -22,7 +26,7 @@ struct amk_mpc {
     amk::DevBuf<int> plan_meta;     // [PLAN_ITEMS] PlanItemMeta + [64] LaneRole
     // staging for amk_mpc_eval_host
     amk::DevBuf<double> ev_w, ev_ref, ev_out;
-    // amk_mpc_eval_gamma: d(A, B, c)/d tau ([3][150], recomputed when tau changes) and its host staging
+    // amk_mpc_eval_gamma: d(A, B, c)/d tau (mpc_model.h DtauBlock, recomputed when tau changes) and its host staging
     amk::DevBuf<double> ev_dtau, ev_gam;
     double ev_dtau_tau[4] = {0, 0, 0, 0};
     bool ev_dtau_valid = false;
@@ -50,7 +54,38 @@ struct amk_mpc {
     amk::DevBuf<int> sh_flags;
 };
 
+// Internal (not in include/avoid_mpc_amd.h; tests/test_mpc_model.py), host only, needs no device: the model's A [10][10], B [10][4],
+// c [10] at tau[4], drag[3], dt, and with dtau (mpc_model.h DtauBlock, [3][150]; null: not wanted) their derivatives in tau_0..2.
+// With dtau, A, B, c are the value part of the dual-number run.  The handle's dynamics and amk_mpc_eval_gamma both come from here.
+extern "C" int amk__mpc_dynamics(const double *tau, const double *drag, double dt, double *A, double *B, double *c, double *dtau);
+
 namespace amk {
+// The horizons with a kernel instantiation of their own (N baked in: LDS offsets become immediates, as the reference bakes N into its
+// plugin) -- the BASELINE configs'.  Every other horizon runs the generic instantiation, NT = 0.  This list is the only place they are named.
+using BakedHorizons = std::integer_sequence<int, 10, 20, 30>;
+template <class F, int... NT>
+void with_horizon(int N, F &&f, std::integer_sequence<int, NT...>) {
+    if (!((N == NT && (f(std::integral_constant<int, NT>{}), true)) || ...)) f(std::integral_constant<int, 0>{});
+}
+// calls f(std::integral_constant<int, NT>) with the instantiation that serves horizon N
+template <class F>
+void with_horizon(int N, F &&f) { with_horizon(N, f, BakedHorizons{}); }
+
+// The *_host conveniences of the MPC: copy `in` to the device, launch, wait, copy `out` back.  A copy whose host side is null is
+// skipped (an input not given, an output not wanted).
+struct HostCopy { void *dst; const void *src; size_t bytes; };
+template <class Launch>
+int staged_call(std::initializer_list<HostCopy> in, Launch &&launch, hipError_t (*wait)(), std::initializer_list<HostCopy> out) {
+    for (const HostCopy &c : in)
+        if (c.src) AMK_HIP(hipMemcpy(c.dst, c.src, c.bytes, hipMemcpyHostToDevice));
+    const int st = launch();
+    if (st != AMK_OK) return st;
+    AMK_HIP(wait());
+    for (const HostCopy &c : out)
+        if (c.dst) AMK_HIP(hipMemcpy(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost));
+    return AMK_OK;
+}
+
 // amk_mpc::run_scenes for the length of a scope (amk_pipeline's control step): whichever way the scope is left, it is 0 again
 struct RunScenes {
     amk_mpc *m;

@@ -13,57 +13,17 @@
 
 using namespace amk;
 
+extern "C" int amk__mpc_dynamics(const double *tau, const double *drag, double dt, double *A, double *B, double *c, double *dtau) {
+    if (!tau || !drag || !A || !B || !c) return AMK_ERR_INVALID_ARG;
+    mpc_dynamics(tau, drag, dt, A, B, c, dtau);
+    return AMK_OK;
+}
+
 namespace {
 
-// ---- host-side model: RK4 x 4 of the quadrotor ODE (mpc_obstacle_casadi.py:106-122, 338-357) probed for
-// its affine form F(x,u) = A x + B u + c (exactly affine with the drag term off, the repo default
-// mpc_parameters.yaml:4).
-// Drag (mpc_obstacle_casadi.py:95-105, yaml use_drag_coefficient): `rotmat * diag(k, k, k) * rotmat.T * v` read as matrix products is
-// k v whatever the attitude (R (k I) R' = k I) -- linear in the state, so F stays affine with the same sparsity (amk_mpc_set_drag_coefficient).
-void ode_host(const double *x, const double *u, const double *tau, const double *drag, double *xd) {
-    xd[0] = x[4]; xd[1] = x[5]; xd[2] = x[6];
-    xd[3] = u[3];
-    xd[4] = x[7] - drag[0] * x[4]; xd[5] = x[8] - drag[1] * x[5]; xd[6] = x[9] - drag[2] * x[6];
-    xd[7] = (u[0] - x[7]) * tau[0];
-    xd[8] = (u[1] - x[8]) * tau[1];
-    xd[9] = (u[2] - kGz - x[9]) * tau[2];
-}
-
-void rk4_host(const double *x, const double *u, const double *tau, const double *drag, double dt, double *xn) {
-    const int M = 4;
-    const double DT = dt / M;
-    double X[SD], k1[SD], k2[SD], k3[SD], k4[SD], t[SD];
-    std::memcpy(X, x, sizeof X);
-    for (int m = 0; m < M; ++m) {
-        ode_host(X, u, tau, drag, k1);
-        for (int i = 0; i < SD; ++i) { k1[i] *= DT; t[i] = X[i] + 0.5 * k1[i]; }
-        ode_host(t, u, tau, drag, k2);
-        for (int i = 0; i < SD; ++i) { k2[i] *= DT; t[i] = X[i] + 0.5 * k2[i]; }
-        ode_host(t, u, tau, drag, k3);
-        for (int i = 0; i < SD; ++i) { k3[i] *= DT; t[i] = X[i] + k3[i]; }
-        ode_host(t, u, tau, drag, k4);
-        for (int i = 0; i < SD; ++i) { k4[i] *= DT; X[i] = X[i] + (k1[i] + 2 * k2[i] + 2 * k3[i] + k4[i]) / 6; }
-    }
-    std::memcpy(xn, X, sizeof X);
-}
-
+// the handle's A, B, c from its tau, drag and dt: the model's affine probe (mpc_model.h; exactly affine, the drag term included)
 void refresh_dynamics(amk_mpc *m) {
-    double *A = m->h_prm + PRM_A, *B = m->h_prm + PRM_B, *c = m->h_prm + PRM_C;
-    const double *tau = m->h_prm + PRM_TAU;
-    double z10[SD] = {0}, z4[UD] = {0}, e10[SD], e4[UD], f[SD];
-    rk4_host(z10, z4, tau, m->drag, m->dt, c);
-    for (int j = 0; j < SD; ++j) {
-        std::memset(e10, 0, sizeof e10);
-        e10[j] = 1.0;
-        rk4_host(e10, z4, tau, m->drag, m->dt, f);
-        for (int i = 0; i < SD; ++i) A[i * SD + j] = f[i] - c[i];
-    }
-    for (int j = 0; j < UD; ++j) {
-        std::memset(e4, 0, sizeof e4);
-        e4[j] = 1.0;
-        rk4_host(z10, e4, tau, m->drag, m->dt, f);
-        for (int i = 0; i < SD; ++i) B[i * UD + j] = f[i] - c[i];
-    }
+    amk__mpc_dynamics(m->h_prm + PRM_TAU, m->drag, m->dt, m->h_prm + PRM_A, m->h_prm + PRM_B, m->h_prm + PRM_C, nullptr);
 }
 
 // Enumerates, for every entry of A'PA, B'PB(+R), B'PA, A'p, A'lam, B'p(+r_bar), B'lam(+r), the <= 9 source cells
@@ -160,7 +120,6 @@ int build_plan(amk_mpc *m, std::vector<double> &coef, std::vector<int> &meta) {
     int *lm = meta.data() + (size_t)PLAN_ITEMS * (PLAN_TERMS + 4);
     double *lc = coef.data() + (size_t)PLAN_ITEMS * (PLAN_TERMS + 1);
     std::vector<int> free_lanes;
-    auto pv_inv_h = [](int s) { return s < 3 ? s : (s >= 4 && s <= 6 ? s - 1 : -1); };
     for (int lane = 0; lane < 64; ++lane) {
         int *r = lm + lane * LANE_META_INTS;
         // defaults: idle lane (zero columns, zero base, writes to the dummy cell)
@@ -175,14 +134,13 @@ int build_plan(amk_mpc *m, std::vector<double> &coef, std::vector<int> &meta) {
         r[0] = L.G + i; r[1] = 10; r[2] = L.G + j; r[3] = 10;
         int nb = 0;
         r[4 + nb] = L.M + lane; r[7 + nb] = 0; ++nb;
-        const int bi = (i == 0 || i == 1) ? 0 : ((i == 4 || i == 5) ? 1 : -1);
-        const int bj = (j == 0 || j == 1) ? 0 : ((j == 4 || j == 5) ? 1 : -1);
-        if (bi >= 0 && bi == bj) {  // rotated 2x2 blocks of Q_k, stage k-1: rotQ[(k-1)*6 + .]
-            r[4 + nb] = L.rotQ - 6 + bi * 3 + ((i == 1 || i == 5) ? 1 : 0) + ((j == 1 || j == 5) ? 1 : 0); r[7 + nb] = 6; ++nb;
+        const RotEntry rot = rot_entry(i, j);
+        if (rot.block >= 0) {  // rotated 2x2 blocks of Q_k, stage k-1: rotQ[(k-1)*6 + .]
+            r[4 + nb] = L.rotQ - 6 + rot.block * 3 + rot.which; r[7 + nb] = 6; ++nb;
         } else if (i == j) {
             lc[lane * 2 + 0] = 2.0 * m->h_prm[PRM_W + 10 + i];
         }
-        const int pi = pv_inv_h(i), pj = pv_inv_h(j);
+        const int pi = pv_inv(i), pj = pv_inv(j);
         if (pi >= 0 && pj >= 0) {   // collision Hessian, stage k-1: H6[(k-1)*21 + .]
             r[4 + nb] = L.H6 - 21 + (pi >= pj ? pi * (pi + 1) / 2 + pj : pj * (pj + 1) / 2 + pi); r[7 + nb] = 21; ++nb;
         }
@@ -270,13 +228,14 @@ __device__ __forceinline__ void solve_kernel_body(int Nrt, int K, int nref, int 
     const bool resume = dstate == 2;
     const int N = NT > 0 ? NT : Nrt;
     const LdsMap L(N);
+    const SceneRecord rec{N, K};
     const double *P = ref_states + (size_t)s * nref;
     SceneIO io;
-    io.ref = P + SD;
-    io.obs = P + SD + SD * N;
-    const double *target = P + SD + SD * N + 3 * K * N;
+    io.ref = rec.ref(P);
+    io.obs = rec.obs(P);
+    const double *target = rec.target(P);
     double *w = w0 + (size_t)s * nx;
-    solve_scene(sm, L, N, K, prm, opt, P, target, io, w, w, info ? info + 4 * s : nullptr, plan_coef, plan_meta,
+    solve_scene(sm, L, N, K, prm, opt, P + rec.x_init(), target, io, w, w, info ? info + 4 * s : nullptr, plan_coef, plan_meta,
                 ybuf + (size_t)s * N * (K > 0 ? K : 1) * kTermRecord, gains + (size_t)s * N * GAIN_STAGE, s == 0 ? trace : nullptr,
                 resume, sched.budget, sched.rec ? sched.rec + (size_t)s * (8 * N + 8) : nullptr);
     __syncthreads();
@@ -287,9 +246,9 @@ __device__ __forceinline__ void solve_kernel_body(int Nrt, int K, int nref, int 
     }
     if (lane < UD) u_out[4 * s + lane] = sm[L.U + lane];  // sol[10..13]  HighLvlMpc.cpp:124-128
     if (x0array)                                           // rows [X_k,U_k], k < N  :130-136
-        for (int e = lane; e < 14 * N; e += 64) {
-            const int k = e / 14, i = e % 14;
-            x0array[(size_t)s * 14 * N + e] = i < SD ? sm[L.X + k * SD + i] : sm[L.U + k * UD + (i - SD)];
+        for (int e = lane; e < NlpDims::kStage * N; e += 64) {
+            const int k = e / NlpDims::kStage, i = e % NlpDims::kStage;
+            x0array[(size_t)s * NlpDims::kStage * N + e] = i < SD ? sm[L.X + k * SD + i] : sm[L.U + k * UD + (i - SD)];
         }
     if (ref_path)  // mRefPath[i] = x0Array[i][0:10], AvoidanceStateMachine.cpp:338-342
         for (int e = lane; e < SD * N; e += 64) ref_path[(size_t)s * SD * N + e] = sm[L.X + e];
@@ -320,6 +279,13 @@ __global__ __launch_bounds__(64, AMK_SOLVE_WAVES) void mpc_solve_kernel_f32(AMK_
     solve_kernel_body<float, NT>(AMK_SOLVE_PASS);
 }
 
+// the fp64 instantiation that serves horizon N (amk_mpc_create, amk__solve_occupancy)
+static const void *solve_kernel_f64(int N) {
+    const void *f = nullptr;
+    with_horizon(N, [&](auto nt) { f = (const void *)mpc_solve_kernel<decltype(nt)::value>; });
+    return f;
+}
+
 namespace amk {
 int launch_solve(amk_mpc *m, const double *d_ref_states, double *d_u, double *d_x0array, int *d_info, const int *d_done,
                  double *d_ref_path, int *d_step_flags, hipStream_t stream, int budget, int max_passes) {
@@ -330,27 +296,16 @@ int launch_solve(amk_mpc *m, const double *d_ref_states, double *d_u, double *d_
         sched = SolveSched{budget > 0 ? budget : 0, max_passes, m->resume_rec.p, const_cast<int *>(d_done)};
     }
     TimedLaunch tl(KC_SOLVE, stream);
-#define AMK_LAUNCH_SOLVE(KERNEL, NT, LDS)                                                                            \
-    hipLaunchKernelGGL(KERNEL<NT>, dim3(m->launch_scenes()), dim3(64), LDS, stream, m->N, m->K, m->nref, m->nx, m->prm.p, m->opt,      \
-                       d_ref_states, m->w0.p, d_u, d_x0array, d_info, g_trace, d_done, d_ref_path, d_step_flags,         \
-                       m->plan_coef.p, m->plan_meta.p, m->ybuf.p, m->gains.p, sched)
-    if (m->precision == 32) {  // fp32 arithmetic, half the scratchpad
-        const size_t lds = m->lds_bytes / 2;
-        switch (m->N) {
-            case 10: AMK_LAUNCH_SOLVE(mpc_solve_kernel_f32, 10, lds); break;
-            case 20: AMK_LAUNCH_SOLVE(mpc_solve_kernel_f32, 20, lds); break;
-            case 30: AMK_LAUNCH_SOLVE(mpc_solve_kernel_f32, 30, lds); break;
-            default: AMK_LAUNCH_SOLVE(mpc_solve_kernel_f32, 0, lds); break;
-        }
-    } else {
-        switch (m->N) {  // the BASELINE horizons get their own instantiation; anything else runs the generic one
-            case 10: AMK_LAUNCH_SOLVE(mpc_solve_kernel, 10, m->lds_bytes); break;
-            case 20: AMK_LAUNCH_SOLVE(mpc_solve_kernel, 20, m->lds_bytes); break;
-            case 30: AMK_LAUNCH_SOLVE(mpc_solve_kernel, 30, m->lds_bytes); break;
-            default: AMK_LAUNCH_SOLVE(mpc_solve_kernel, 0, m->lds_bytes); break;
-        }
-    }
-#undef AMK_LAUNCH_SOLVE
+    with_horizon(m->N, [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        auto launch = [&](auto kernel, size_t lds) {
+            hipLaunchKernelGGL(kernel, dim3(m->launch_scenes()), dim3(64), lds, stream, m->N, m->K, m->nref, m->nx, m->prm.p, m->opt,
+                               d_ref_states, m->w0.p, d_u, d_x0array, d_info, g_trace, d_done, d_ref_path, d_step_flags,
+                               m->plan_coef.p, m->plan_meta.p, m->ybuf.p, m->gains.p, sched);
+        };
+        if (m->precision == 32) launch(mpc_solve_kernel_f32<NT>, m->lds_bytes / 2);  // fp32 arithmetic, half the scratchpad
+        else launch(mpc_solve_kernel<NT>, m->lds_bytes);
+    });
     AMK_HIP(hipGetLastError());
     return AMK_OK;
 }
@@ -372,8 +327,7 @@ extern "C" int amk__plan_dump(amk_mpc *m, int *h_meta, int n_ints) {
 // internal: resident solve blocks per CU as the runtime computes it (diagnostics)
 extern "C" int amk__solve_occupancy(amk_mpc *m) {
     int nb = -1;
-    const void *f = m->N == 10 ? (const void *)mpc_solve_kernel<10> : m->N == 20 ? (const void *)mpc_solve_kernel<20>
-                  : m->N == 30 ? (const void *)mpc_solve_kernel<30> : (const void *)mpc_solve_kernel<0>;
+    const void *f = solve_kernel_f64(m->N);
     hipFuncAttributes fa;
     if (hipFuncGetAttributes(&fa, f) == hipSuccess)
         printf("solve kernel N=%d: numRegs %d, sharedSizeBytes %zu, localSizeBytes %zu, maxDynamicShared %d, lds request %zu\n", m->N,
@@ -392,8 +346,8 @@ int amk_mpc_create(double T, double dt, int nearest_point_num, int n_scenes, amk
     if (amk_device_count() <= 0) return AMK_ERR_NO_DEVICE;
     amk_mpc *m = new amk_mpc();
     m->T = T; m->dt = dt; m->N = N; m->K = nearest_point_num; m->S = n_scenes;
-    m->nx = 10 + 14 * N;
-    m->nref = 20 + 10 * N + 3 * m->K * N;
+    m->nx = m->dims().nx();
+    m->nref = SceneRecord{N, m->K}.len();
     std::memset(m->h_prm, 0, sizeof m->h_prm);
     // constructor defaults, HighLvlMpc.cpp:13-16,53-56
     const double wdef[25] = {100, 100, 100, 300, 1, 1, 1, 0., 0., 0., 0.0, 10, 10, 30, 0, 1, 1, 0., 0., 0., 1., 1., 1., 1., 1.};
@@ -421,11 +375,9 @@ int amk_mpc_create(double T, double dt, int nearest_point_num, int n_scenes, amk
         (e = m->gains.alloc((size_t)n_scenes * N * GAIN_STAGE)) != hipSuccess ||
         (e = hipMemset(m->gains.p, 0, sizeof(double) * (size_t)n_scenes * N * GAIN_STAGE)) != hipSuccess ||
         (e = hipMemset(m->w0.p, 0, sizeof(double) * (size_t)n_scenes * m->nx)) != hipSuccess ||
-        (e = hipFuncSetAttribute(N == 10   ? (const void *)mpc_solve_kernel<10>
-                                 : N == 20 ? (const void *)mpc_solve_kernel<20>
-                                 : N == 30 ? (const void *)mpc_solve_kernel<30>
-                                           : (const void *)mpc_solve_kernel<0>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->lds_bytes)) != hipSuccess) {
+        // the dynamic-LDS limit is raised on the fp64 kernel only, as it always was: the fp32 kernels ask for half of lds_bytes, and
+        // neither comes near the 64 KB a kernel may ask for without it (LdsMap(AMK_MAX_HORIZON) is under 30 KB of doubles)
+        (e = hipFuncSetAttribute(solve_kernel_f64(N), hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->lds_bytes)) != hipSuccess) {
         delete m;
         return amk::hip_fail(e);
     }
@@ -459,7 +411,7 @@ int amk_mpc_setup_tau(amk_mpc *m, const double *tau) {
     refresh_dynamics(m);
     return upload_params(m);
 }
-// The reference's use_drag_coefficient switch in the one reading under which it is well defined (see ode_host): v' = a - k .* v.
+// The reference's use_drag_coefficient switch in the one reading under which it is well defined (see mpc_model.h: ode): v' = a - k .* v.
 // Changes A (the v <- v and p <- v entries) and nothing of its sparsity; the Riccati plan is rebuilt from the new values.
 int amk_mpc_set_drag_coefficient(amk_mpc *m, double kx, double ky, double kz) {
     if (!m || !(kx >= 0.0 && ky >= 0.0 && kz >= 0.0) || !(kx < 1e3 && ky < 1e3 && kz < 1e3)) return AMK_ERR_INVALID_ARG;
@@ -533,21 +485,18 @@ int amk_mpc_reset_warm_start(amk_mpc *m, void *stream) {
 
 int amk_mpc_solve_host(amk_mpc *m, const double *h_ref_states, double *h_u, double *h_x0array, int *h_info, int faster) {
     if (!m || !h_ref_states || !h_u) return AMK_ERR_INVALID_ARG;
-    const size_t S = m->S;
+    const size_t S = m->S, nx0 = (size_t)NlpDims::kStage * m->N;
     if (!m->st_ref.p) {
         AMK_HIP(m->st_ref.alloc(S * m->nref));
-        AMK_HIP(m->st_u.alloc(S * 4));
-        AMK_HIP(m->st_x0.alloc(S * 14 * m->N));
+        AMK_HIP(m->st_u.alloc(S * UD));
+        AMK_HIP(m->st_x0.alloc(S * nx0));
         AMK_HIP(m->st_info.alloc(S * 4));
     }
-    AMK_HIP(hipMemcpy(m->st_ref.p, h_ref_states, sizeof(double) * S * m->nref, hipMemcpyHostToDevice));
-    int st = amk_mpc_solve(m, m->st_ref.p, m->st_u.p, m->st_x0.p, m->st_info.p, faster, nullptr);
-    if (st != AMK_OK) return st;
-    AMK_HIP(hipDeviceSynchronize());
-    AMK_HIP(hipMemcpy(h_u, m->st_u.p, sizeof(double) * S * 4, hipMemcpyDeviceToHost));
-    if (h_x0array) AMK_HIP(hipMemcpy(h_x0array, m->st_x0.p, sizeof(double) * S * 14 * m->N, hipMemcpyDeviceToHost));
-    if (h_info) AMK_HIP(hipMemcpy(h_info, m->st_info.p, sizeof(int) * S * 4, hipMemcpyDeviceToHost));
-    return AMK_OK;
+    return staged_call({{m->st_ref.p, h_ref_states, sizeof(double) * S * m->nref}},
+                       [&] { return amk_mpc_solve(m, m->st_ref.p, m->st_u.p, m->st_x0.p, m->st_info.p, faster, nullptr); },
+                       hipDeviceSynchronize,
+                       {{h_u, m->st_u.p, sizeof(double) * S * UD}, {h_x0array, m->st_x0.p, sizeof(double) * S * nx0},
+                        {h_info, m->st_info.p, sizeof(int) * S * 4}});
 }
 
 }  // extern "C"

@@ -164,13 +164,14 @@ __device__ __forceinline__ void pack_ref_states(int tid, int nthr, int s, int N,
         if (tid == 0) done[s] = 1;
         return;
     }
+    const SceneRecord R{N, K};
     double *P = ref_states + (size_t)s * nref;
     const double *sq = state_quad + ((size_t)s * max_iter + iter) * SD;
-    if (tid < SD) P[tid] = sq[tid];
-    for (int e = tid; e < SD * N; e += nthr) P[SD + e] = rp[e];
+    if (tid < SD) P[R.x_init() + tid] = sq[tid];
+    for (int e = tid; e < SD * N; e += nthr) P[R.ref() + e] = rp[e];
     for (int e = tid; e < 3 * K * N; e += nthr) {
         const int i = e / (3 * K), j = (e / 3) % K;
-        P[SD + SD * N + e] = (j < cnt(i)) ? (double)knn_pts[(size_t)s * N * K * 3 + e] : 10000.0;  // :223-226
+        P[R.obs() + e] = (j < cnt(i)) ? (double)knn_pts[(size_t)s * N * K * 3 + e] : 10000.0;  // :223-226
     }
     if (tid < SD) {
         const double *last = rp + (N - 1) * SD;
@@ -182,7 +183,7 @@ __device__ __forceinline__ void pack_ref_states(int tid, int nthr, int s, int N,
             v += dX;
         }
         if (tid == 1) v = 0.;
-        P[SD + SD * N + 3 * K * N + tid] = v;
+        P[R.target() + tid] = v;
     }
 }
 

@@ -1,5 +1,6 @@
 """GPU: the plugin's NLP functions on the device (amk_mpc_eval) against the oracle's
-restatement of mpc_obstacle_casadi.py:153-219 at random points, for the three BASELINE sizes.
+restatement of mpc_obstacle_casadi.py:153-219 at random points, for the three BASELINE sizes and three horizons that run the generic
+instantiation; amk_mpc_eval_gamma against amk_mpc_eval there.
 
 Tolerance (fp64): same formulas, different summation order (LDS atomics / wave reductions) and ocml vs libm exp/log:
 1e-9 relative to the largest entry of each output (measured ~1e-13)."""
@@ -20,9 +21,12 @@ RTOL = 1e-9
 
 
 def _points(cfg, S, seed):
-    """S random (w, P-prefix) pairs around a plausible flight state, obstacles close enough to matter."""
     c = synth.CONFIGS[cfg]
-    prm = synth.MpcParams(T=c["T"], K=c["K"])
+    return _points_at(synth.MpcParams(T=c["T"], K=c["K"]), S, seed)
+
+
+def _points_at(prm, S, seed):
+    """S random (w, P-prefix) pairs around a plausible flight state, obstacles close enough to matter."""
     N, K = prm.N, prm.K
     rng = np.random.default_rng(seed)
     nref = 20 + 10 * N + 3 * K * N
@@ -102,6 +106,56 @@ def compare_eval_with_oracle(prm, W, R):
 def test_eval_matches_oracle(cfg):
     prm, W, R = _points(cfg, 24, 5)
     compare_eval_with_oracle(prm, W, R)
+
+
+# Horizons without an instantiation of their own (the generic one, NT = 0: LDS offsets at run-time N): 2 is the smallest
+# amk_mpc_create accepts -- one path stage, one 25-entry Hessian block; 7 is odd, so every take() of LdsMap rounds; 32 is AMK_MAX_HORIZON
+GENERIC = [(2, 1), (7, 3), (32, 2)]
+
+
+def _generic_prm(N, K):
+    prm = synth.MpcParams(T=N * 0.033 + 1e-4, K=K)   # as tests/test_mpc_gpu.py test_generic_horizon_kernel_matches_oracle makes it
+    assert prm.N == N
+    return prm
+
+
+@pytest.mark.parametrize("N,K", GENERIC)
+def test_eval_matches_oracle_at_generic_horizons(N, K):
+    prm, W, R = _points_at(_generic_prm(N, K), 3, 11)
+    print(N, K, compare_eval_with_oracle(prm, W, R))
+
+
+@pytest.mark.parametrize("N,K", GENERIC)
+def test_eval_gamma_agrees_with_eval_at_generic_horizons(N, K):
+    """amk_mpc_eval_gamma (through amk_mpc_eval_gamma_host) against amk_mpc_eval's own outputs: grad_x gamma = lam_f grad f + J' lam_g to
+    1e-12 relative (tests/test_casadi_plugin_gpu.py's bound for the same identity), and the x_init block of grad_p gamma = -lam_g[0:10]
+    exactly (g[0:10] = X_0 - x_init)."""
+    import ctypes as C
+    import torch
+    from avoid_mpc_amd.host import MpcBatch
+    S = 3
+    prm, W, R = _points_at(_generic_prm(N, K), S, 12)
+    nx, ng, npar = 10 + 14 * N, 10 + 10 * N, R.shape[1] + 34
+    m = MpcBatch(prm.T, prm.dt, prm.K, S); m.configure(prm)
+    rng = np.random.default_rng(13)
+    lam_f = np.linspace(0.5, 2.0, S); lam_g = rng.normal(size=(S, ng))
+    out = m.eval(torch.from_numpy(W).cuda(), torch.from_numpy(R).cuda(), None, want=("grad_f", "jac_g"))
+    torch.cuda.synchronize()
+    grad_f, jac = out["grad_f"].cpu().numpy(), out["jac_g"].cpu().numpy()
+    jc, jr = m.sparsity("jac_g")
+    gx = np.zeros((S, nx)); gp = np.zeros((S, npar))
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    assert m.lib.amk_mpc_np(m.h) == npar
+    assert m.lib.amk_mpc_eval_gamma_host(m.h, vp(W), vp(R), vp(lam_f), vp(lam_g), vp(gx), vp(gp)) == 0
+    for s in range(S):
+        Jd = np.zeros((ng, nx))
+        for col in range(nx):
+            Jd[jr[jc[col]:jc[col + 1]], col] = jac[s][jc[col]:jc[col + 1]]
+        ref = lam_f[s] * grad_f[s] + Jd.T @ lam_g[s]
+        err = np.abs(gx[s] - ref).max() / np.abs(ref).max()
+        print(N, K, s, err)
+        assert err <= 1e-12
+        assert np.array_equal(gp[s, :10], -lam_g[s, :10])
 
 
 def test_eval_host_and_null_outputs():
