@@ -33,6 +33,26 @@ const int *mpco_last_info(void *h);
 
 #define MAXK 64
 
+/* Optional per-pass decision log of stepo_run / stepo_run_frames (tests/_step_loop_cases.py): one record of STEPO_LOG_W doubles for
+ * every pass that BEGINS, the pass that leaves through :333-335 included:
+ *   [0] the nearest distance PlanWapionts compared with safety_distance (sqrt(DBL_MAX): nothing answered)
+ *   [1] min over the reference points that got neighbours of |sqrt(d2[0]) - safety_distance| (DBL_MAX: none did), after the snap;
+ *       the points whose sqrt(d2[0]) EQUALS safety_distance are left out of it and counted in [6]
+ *   [2] needReplan  [3] isSafety  [4] reference point 0 was snapped  [5] the pass left the loop before its solve
+ * stepo_set_decision_log(buf, max_passes) arms it for the following runs (NULL: off); stepo_decision_log_count() = records of the
+ * last run. */
+#define STEPO_LOG_W 7
+static double *g_dlog = NULL;
+static int g_dlog_cap = 0, g_dlog_n = 0;
+void stepo_set_decision_log(double *buf, int max_passes) { g_dlog = buf; g_dlog_cap = buf ? max_passes : 0; g_dlog_n = 0; }
+int stepo_decision_log_count(void) { return g_dlog_n; }
+static void dlog_put(double nearest, double row_margin, int need, int safe, int snapped, int left, int on_edge) {
+    if (g_dlog && g_dlog_n < g_dlog_cap) {
+        double *r = g_dlog + (size_t)STEPO_LOG_W * g_dlog_n++;
+        r[0] = nearest; r[1] = row_margin; r[2] = need; r[3] = safe; r[4] = snapped; r[5] = left; r[6] = on_edge;
+    }
+}
+
 /* QueryNearest for a single-frame map.  Fast path (cur frame has >= k points and the query is
  * inside the camera frustum, FrameKDMap.cpp:339-345) and slow path (k' = min(k, size), :298) end in
  * the same SearchForNearest call except for k' -- both are restated; `in_frame` selects. */
@@ -109,14 +129,18 @@ int stepo_run(void *kd_obs, void *kd_edge, void *mpc, int K, double speed, doubl
     double *x0 = (double *)calloc((size_t)14 * N, sizeof(double));
     double *obst = (double *)malloc(sizeof(double) * 3 * K * N);
     int is_safety = 1, solves = 0, status = -1, iters = 0;
+    g_dlog_n = 0;
     memset(u, 0, sizeof(double) * 4);
     for (int iter = 0; iter < mpc_max_iter; ++iter) {
         const double *sq = state_quad + 10 * iter; /* GetCurStateQuad(start + decay), :330 */
         /* PlanWapionts :259-281 (only ref point 0) */
         is_safety = 1;
+        double log_nd, log_rm = DBL_MAX;
+        int snapped = 0, on_edge = 0;
         {
             double *p1 = ref_path;
             double nd = map_nearest_distance(kd_obs, p1);
+            log_nd = nd;
             if (!(nd > safety_distance)) {
                 double ep[1][3], ed[1];
                 int cnt = map_query(kd_edge, p1, 1, 1, ep, ed);
@@ -124,6 +148,7 @@ int stepo_run(void *kd_obs, void *kd_edge, void *mpc, int K, double speed, doubl
                 else {
                     p1[0] = ep[0][0]; p1[1] = ep[0][1]; p1[2] = ep[0][2];
                     is_safety = 1;
+                    snapped = 1;
                 }
             }
         }
@@ -138,7 +163,13 @@ int stepo_run(void *kd_obs, void *kd_edge, void *mpc, int K, double speed, doubl
                 else { o[0] = o[1] = o[2] = 10000; } /* :223-226 */
             }
             if (cnt == 0 || sqrt(d2[0]) <= safety_distance) need_replan = 1; /* :228-231 */
+            if (cnt > 0) {
+                const double m = fabs(sqrt(d2[0]) - safety_distance);
+                if (m == 0) ++on_edge;
+                else if (m < log_rm) log_rm = m;
+            }
         }
+        dlog_put(log_nd, log_rm, need_replan, is_safety, snapped, !need_replan && iter > 0 && is_safety, on_edge);
         if (!need_replan && iter > 0 && is_safety) break; /* :333-335 */
         /* GetRefStates :236-257 */
         memcpy(ref_states, sq, sizeof(double) * 10);
@@ -265,18 +296,22 @@ int stepo_run_frames(void **kd_obs, void **kd_edge, int F, const double *Twc, co
     double *x0 = (double *)calloc((size_t)14 * N, sizeof(double));
     double *obst = (double *)malloc(sizeof(double) * 3 * K * N);
     int is_safety = 1, solves = 0, status = -1, iters = 0;
+    g_dlog_n = 0;
     memset(u, 0, sizeof(double) * 4);
     for (int iter = 0; iter < mpc_max_iter; ++iter) {
         const double *sq = state_quad + 10 * iter;
         is_safety = 1;
+        double log_nd, log_rm = DBL_MAX;
+        int snapped = 0, on_edge = 0;
         {
             double *p1 = ref_path;
             double nd = mapf_nearest_distance(kd_obs, F, p1);
+            log_nd = nd;
             if (!(nd > safety_distance)) {
                 double ep[1][3], ed[1];
                 int cnt = mapf_query(kd_edge, F, p1, 1, Twc, cam, ep, ed);
                 if (cnt == 0) is_safety = 0;
-                else { p1[0] = ep[0][0]; p1[1] = ep[0][1]; p1[2] = ep[0][2]; }
+                else { p1[0] = ep[0][0]; p1[1] = ep[0][1]; p1[2] = ep[0][2]; snapped = 1; }
             }
         }
         int need_replan = 0;
@@ -289,7 +324,13 @@ int stepo_run_frames(void **kd_obs, void **kd_edge, int F, const double *Twc, co
                 else { o[0] = o[1] = o[2] = 10000; }
             }
             if (cnt == 0 || sqrt(d2[0]) <= safety_distance) need_replan = 1;
+            if (cnt > 0) {
+                const double m = fabs(sqrt(d2[0]) - safety_distance);
+                if (m == 0) ++on_edge;
+                else if (m < log_rm) log_rm = m;
+            }
         }
+        dlog_put(log_nd, log_rm, need_replan, is_safety, snapped, !need_replan && iter > 0 && is_safety, on_edge);
         if (!need_replan && iter > 0 && is_safety) break;
         memcpy(ref_states, sq, sizeof(double) * 10);
         memcpy(ref_states + 10, ref_path, sizeof(double) * 10 * N);
