@@ -6,7 +6,6 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
-#include <functional>
 #include <vector>
 
 #include "../../include/avoid_mpc_amd.h"
@@ -70,6 +69,8 @@ struct TimedLaunch {  // RAII: records an event before and after the enclosed la
 };
 
 }  // namespace amk
+
+#include "host_stage.h"
 
 struct amk_kd;
 struct amk_mpc;
@@ -156,15 +157,34 @@ int step_batch_map(amk_kd *obs_pool, amk_kd *edge_pool, int n_frames, const int 
                    const amk_frame_camera *cam, amk_mpc *mpc, const amk_step_params *prm, const double *d_state_quad,
                    const double *d_pos_x, double *d_ref_path, double *d_u, double *d_x0array, int *d_flags, hipStream_t stream,
                    bool exact);
-// map_query.hip, for kfmap.hip: QueryNearest / GetNearestDistance over a pool, and the staging of their *_host variants
+// map_query.hip, for kfmap.hip: QueryNearest / GetNearestDistance over a pool
 int map_query_nearest(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_Twc, const amk_frame_camera *cam,
                       const double *d_queries, int query_stride, int n_queries, int k, float *d_pts, double *d_sqdist, int *d_frame,
                       int *d_counts, hipStream_t stream, bool exact);
 int map_nearest_distance(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_queries, int query_stride,
                          int n_queries, double *d_dist, hipStream_t stream);
-int map_query_host(int S, const double *h_queries, int query_stride, int n_queries, int k, const double *h_Twc, float *h_pts,
-                   double *h_sqdist, int *h_frame, int *h_counts, double *h_dist,
-                   const std::function<int(const double *, const double *, float *, double *, int *, int *, double *)> &launch);
+inline bool query_args_ok(const double *queries, int query_stride, int n_queries) { return queries && query_stride >= 3 && n_queries >= 1; }
+// Their *_host variants and amk_kd_query_frames_host: queries (and poses) staged through `stage`, launch(d) -- the entry's device
+// call, d[i] = MapQuerySlot i, null where the host pointer is -- enqueued on the null stream between two device-wide waits (a
+// build or an update enqueued on any stream is seen), results copied back.  A convenience for single-robot hosts and tests,
+// not a hot path.  Any output may be NULL.
+enum MapQuerySlot { MQ_QUERIES, MQ_TWC, MQ_PTS, MQ_SQDIST, MQ_FRAME, MQ_COUNTS, MQ_DIST };
+template <class Launch>
+int map_query_host(HostStage &stage, int S, const double *h_queries, int query_stride, int n_queries, int k, const double *h_Twc,
+                   float *h_pts, double *h_sqdist, int *h_frame, int *h_counts, double *h_dist, Launch &&launch) {
+    if (S < 1 || !query_args_ok(h_queries, query_stride, n_queries) || k < 1) return AMK_ERR_INVALID_ARG;
+    if (k > AMK_MAX_K) return AMK_ERR_UNSUPPORTED;
+    const size_t rows = (size_t)S * n_queries, nq = (rows - 1) * query_stride + 3;
+    return stage.call({to_device(h_queries, sizeof(double) * nq), if_given(to_device(h_Twc, sizeof(double) * S * 16)),
+                       if_given(to_host(h_pts, sizeof(float) * rows * k * 3)), if_given(to_host(h_sqdist, sizeof(double) * rows * k)),
+                       if_given(to_host(h_frame, sizeof(int) * rows * k)), if_given(to_host(h_counts, sizeof(int) * rows)),
+                       if_given(to_host(h_dist, sizeof(double) * rows))},
+                      [&](const HostStage::Dev *d) {
+                          AMK_HIP(hipDeviceSynchronize());
+                          return launch(d);
+                      },
+                      hipDeviceSynchronize);
+}
 // kfmap.hip, for pipeline.hip: AddVertex for the frames of a gang (see there)
 int kfmap_add_vertex_gang(amk_kfmap *m, int n_frames, int frame_scenes, const float *const *d_xyz, const int *const *d_counts,
                           const float *const *d_edge_xyz, const int *const *d_edge_counts, int point_stride, const double *const *d_Twc,
@@ -217,17 +237,9 @@ struct amk_kd {
     amk::DevBuf<int> sw_src;          // [2 + 1][rows]          pool scene the row's grid was built from, -1: none (row 2: always -1)
     int sw_rows = 0, sw_flip = 0;
     double sw_inv_h = 0.0;            // the lattice of the grids held (1 / cell edge)
-    // staging for the *_host conveniences: a private stream and one pinned host block, so that a single-query
-    // SearchForNearest costs one small H2D copy, one launch, one D2H copy and a wait on THIS stream only (a device-wide
+    // staging of the *_host conveniences.  amk_kd_search_host goes through the pinned block and the private stream, so that a
+    // single-query SearchForNearest costs one small H2D copy, one launch, one D2H copy and a wait on THAT stream only (a device-wide
     // synchronisation would stall every other stream of the process: a ROS node calls this ~100 times per control period)
-    hipStream_t hstream = nullptr;
-    void *hpin = nullptr;
-    size_t hpin_bytes = 0;
-    amk::DevBuf<unsigned char> stage_out;
+    amk::HostStage stage;
     int async_pending = 0;  // a stream-ordered build / sweep was enqueued since the last synchronisation
-    amk::DevBuf<float> stage_xyz;
-    amk::DevBuf<int> stage_counts;
-    amk::DevBuf<double> stage_q, stage_d2;
-    amk::DevBuf<int> stage_idx, stage_cnt;
-    amk::DevBuf<float> stage_pts;
 };

@@ -461,52 +461,31 @@ int launch_edge(const Frames &f, const Cloud &c, hipStream_t stream) {
 // {obstacle, edge} count of every band of every scene, for the smallest band (one row): covers any band height
 long long work_bytes_for(int H, int n_scenes) { return (long long)sizeof(int2) * H * n_scenes; }
 
-// The host-memory variants, `host` holding the caller's pointers.  Refuses what all three refuse (`work_status`, the caller's answer about its workspace of `work_bytes`,
-// stands behind the pixel type and before the device); uploads the images and the N poses; runs device(images, clouds, workspace) on
-// the null stream and waits; downloads the N clouds and their counts.
-template <int N, typename Device>
-int on_device_copies(const void *h_depth, int depth_type, long long scene_stride, int n_scenes, const Cloud (&host)[N],
-                     int work_status, long long work_bytes, Device &&device) {
-    bool pointers = h_depth != nullptr;
-    for (const Cloud &c : host) pointers = pointers && c.T && c.points && c.counts;
+// What the three host-memory variants refuse before anything is staged (`work_status`, the caller's answer about its workspace,
+// stands behind the pixel type and before the device)
+int refuse_host_call(bool pointers, int depth_type, int n_scenes, int work_status) {
     if (!pointers || n_scenes <= 0) return AMK_ERR_INVALID_ARG;
     if (depth_type != AMK_DEPTH_U16 && depth_type != AMK_DEPTH_F32) return AMK_ERR_UNSUPPORTED;
     if (work_status != AMK_OK) return work_status;
-    if (amk_device_count() <= 0) return AMK_ERR_NO_DEVICE;
-    const size_t img_bytes = (size_t)scene_stride * n_scenes * (depth_type == AMK_DEPTH_U16 ? 2 : 4);
-    amk::DevBuf<unsigned char> img, work;
-    amk::DevBuf<double> pose[N];
-    amk::DevBuf<float> points[N];
-    amk::DevBuf<int> counts[N];
-    Cloud dev[N];
-    AMK_HIP(img.alloc(img_bytes));
-    AMK_HIP(work.alloc((size_t)work_bytes));
-    AMK_HIP(hipMemcpy(img.p, h_depth, img_bytes, hipMemcpyHostToDevice));
-    for (int i = 0; i < N; ++i) {
-        AMK_HIP(pose[i].alloc((size_t)16 * n_scenes));
-        AMK_HIP(points[i].alloc((size_t)host[i].scene_stride * n_scenes));
-        AMK_HIP(counts[i].alloc(n_scenes));
-        AMK_HIP(hipMemcpy(pose[i].p, host[i].T, sizeof(double) * 16 * n_scenes, hipMemcpyHostToDevice));
-        dev[i] = {pose[i].p, points[i].p, host[i].scene_stride, counts[i].p};
-    }
-    if (const int st = device(img.p, dev, work.p); st != AMK_OK) return st;
-    AMK_HIP(hipDeviceSynchronize());
-    for (int i = 0; i < N; ++i) {
-        AMK_HIP(hipMemcpy(host[i].counts, counts[i].p, sizeof(int) * n_scenes, hipMemcpyDeviceToHost));
-        AMK_HIP(hipMemcpy(host[i].points, points[i].p, sizeof(float) * (size_t)host[i].scene_stride * n_scenes, hipMemcpyDeviceToHost));
-    }
-    return AMK_OK;
+    return amk_device_count() <= 0 ? AMK_ERR_NO_DEVICE : AMK_OK;
 }
 
-// amk_depth_to_cloud_host / amk_depth_to_edge_cloud_host: one cloud through `fn`, their device call
+size_t image_bytes(int depth_type, long long scene_stride, int n_scenes) { return (size_t)scene_stride * n_scenes * (depth_type == AMK_DEPTH_U16 ? 2 : 4); }
+
+// amk_depth_to_cloud_host / amk_depth_to_edge_cloud_host: one cloud through `fn`, their device call, on the null stream
 int one_cloud_on_host(decltype(&amk_depth_to_cloud) fn, const void *h_depth, int depth_type, int rows, int cols, long long scene_stride,
                       int n_scenes, const amk_depth_params *params, const double *h_T, float *h_cloud, int point_stride,
                       long long cloud_scene_stride, int *h_counts) {
-    const Cloud host[1] = {{h_T, h_cloud, cloud_scene_stride, h_counts}};
-    return on_device_copies(h_depth, depth_type, scene_stride, n_scenes, host, AMK_OK, 0, [&](const void *img, const Cloud *c, void *) {
-        return fn(img, depth_type, rows, cols, scene_stride, n_scenes, params, c->T, c->points, point_stride, c->scene_stride, c->counts,
-                  nullptr);
-    });
+    if (const int st = refuse_host_call(h_depth && h_T && h_cloud && h_counts, depth_type, n_scenes, AMK_OK); st != AMK_OK) return st;
+    enum { IMAGES, POSES, COUNTS, POINTS };
+    amk::HostStage stage;
+    return stage.call({amk::to_device(h_depth, image_bytes(depth_type, scene_stride, n_scenes)), amk::to_device(h_T, sizeof(double) * 16 * n_scenes),
+                       amk::to_host(h_counts, sizeof(int) * n_scenes), amk::to_host(h_cloud, sizeof(float) * (size_t)cloud_scene_stride * n_scenes)},
+                      [&](const amk::HostStage::Dev *d) {
+                          return fn(d[IMAGES], depth_type, rows, cols, scene_stride, n_scenes, params, d[POSES], d[POINTS], point_stride,
+                                    cloud_scene_stride, d[COUNTS], nullptr);
+                      },
+                      hipDeviceSynchronize);
 }
 
 }  // namespace
@@ -610,15 +589,23 @@ int amk_depth_to_clouds_host(const void *h_depth, int depth_type, int rows, int 
                              long long cloud_scene_stride, int *h_counts, float *h_edge, long long edge_scene_stride,
                              int *h_edge_counts, int point_stride) {
     if (scene_stride <= 0 || cloud_scene_stride <= 0 || edge_scene_stride <= 0) return AMK_ERR_INVALID_ARG;
-    const Cloud host[2] = {{h_Twb, h_cloud, cloud_scene_stride, h_counts}, {h_Twc, h_edge, edge_scene_stride, h_edge_counts}};
     long long work_bytes = 0;
     const int work_status = amk_depth_clouds_work_bytes(rows, cols, params ? params->resize_scale : 0.0, n_scenes, &work_bytes);
-    return on_device_copies(h_depth, depth_type, scene_stride, n_scenes, host, work_status, work_bytes,
-                            [&](const void *img, const Cloud *c, void *work) {
-                                return amk_depth_to_clouds(img, depth_type, rows, cols, scene_stride, n_scenes, params, c[0].T, c[1].T,
-                                                           c[0].points, c[0].scene_stride, c[0].counts, c[1].points, c[1].scene_stride,
-                                                           c[1].counts, point_stride, work, work_bytes, nullptr);
-                            });
+    if (const int st = refuse_host_call(h_depth && h_Twb && h_Twc && h_cloud && h_counts && h_edge && h_edge_counts, depth_type, n_scenes, work_status);
+        st != AMK_OK)
+        return st;
+    enum { IMAGES, TWB, TWC, WORK, COUNTS, POINTS, EDGE_COUNTS, EDGE_POINTS };
+    amk::HostStage stage;
+    return stage.call({amk::to_device(h_depth, image_bytes(depth_type, scene_stride, n_scenes)), amk::to_device(h_Twb, sizeof(double) * 16 * n_scenes),
+                       amk::to_device(h_Twc, sizeof(double) * 16 * n_scenes), amk::scratch((size_t)work_bytes),
+                       amk::to_host(h_counts, sizeof(int) * n_scenes), amk::to_host(h_cloud, sizeof(float) * (size_t)cloud_scene_stride * n_scenes),
+                       amk::to_host(h_edge_counts, sizeof(int) * n_scenes), amk::to_host(h_edge, sizeof(float) * (size_t)edge_scene_stride * n_scenes)},
+                      [&](const amk::HostStage::Dev *d) {
+                          return amk_depth_to_clouds(d[IMAGES], depth_type, rows, cols, scene_stride, n_scenes, params, d[TWB], d[TWC], d[POINTS],
+                                                     cloud_scene_stride, d[COUNTS], d[EDGE_POINTS], edge_scene_stride, d[EDGE_COUNTS], point_stride,
+                                                     d[WORK], work_bytes, nullptr);
+                      },
+                      hipDeviceSynchronize);
 }
 
 }  // extern "C"

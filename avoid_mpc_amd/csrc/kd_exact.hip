@@ -309,24 +309,21 @@ int amk_kd_exact_status(amk_kd *kd, int *d_status, void *stream) {
 
 int amk_kd_exact_status_host(amk_kd *kd, int *h_status) {   // synchronises
     if (!kd || !h_status) return AMK_ERR_INVALID_ARG;
-    amk::DevBuf<int> d;
-    AMK_HIP(d.alloc(kd->n_scenes));
-    const int st = amk_kd_exact_status(kd, d.p, nullptr);
-    if (st != AMK_OK) return st;
-    AMK_HIP(hipDeviceSynchronize());
-    AMK_HIP(hipMemcpy(h_status, d.p, sizeof(int) * kd->n_scenes, hipMemcpyDeviceToHost));
-    return AMK_OK;
+    return kd->stage.call({amk::to_host(h_status, sizeof(int) * kd->n_scenes)},
+                          [&](const amk::HostStage::Dev *d) { return amk_kd_exact_status(kd, d[0], nullptr); }, hipDeviceSynchronize);
 }
 
 // internal (tests): number of nodes of every scene's tree (-1: not available), after synchronising
 // A handle in AMK_TIES_AUTO: 0 for a scene whose tree has not been built for the current cloud (no tree, no nodes).
 int amk__kd_exact_nodes(amk_kd *kd, int *h_nodes) {
     if (!kd || !h_nodes || !kd->exact.allocated()) return AMK_ERR_INVALID_ARG;
-    AMK_HIP(hipDeviceSynchronize());
-    AMK_HIP(hipMemcpy(h_nodes, kd->exact.n_nodes(), sizeof(int) * kd->n_scenes, hipMemcpyDeviceToHost));
-    if (kd->tie_order == AMK_TIES_AUTO) {
-        std::vector<int> built((size_t)kd->n_scenes, 0);
-        if (kd->au_active) AMK_HIP(hipMemcpy(built.data(), kd->au_built(), sizeof(int) * kd->n_scenes, hipMemcpyDeviceToHost));
+    const bool lazy = kd->tie_order == AMK_TIES_AUTO, cleared = lazy && kd->au_active;   // (au_state exists and belongs to this cloud)
+    std::vector<int> built((size_t)kd->n_scenes, 0);
+    if (const int st = amk::read_back({{h_nodes, kd->exact.n_nodes(), sizeof(int) * kd->n_scenes},
+                                       {cleared ? built.data() : nullptr, cleared ? kd->au_built() : nullptr, sizeof(int) * kd->n_scenes}});
+        st != AMK_OK)
+        return st;
+    if (lazy) {
         for (int s = 0; s < kd->n_scenes; ++s)
             if (!built[s]) h_nodes[s] = 0;
     }
@@ -338,9 +335,7 @@ int amk__kd_exact_nodes(amk_kd *kd, int *h_nodes) {
 // lower-level build kernel leaves its per-wavefront phase clocks
 int amk__kd_exact_trace(amk_kd *kd, unsigned *h, int n) {
     if (!kd || !h || !kd->exact.allocated()) return AMK_ERR_INVALID_ARG;
-    AMK_HIP(hipDeviceSynchronize());
-    AMK_HIP(hipMemcpy(h, kd->exact.at<unsigned>(amk::ExactStore::SA), sizeof(unsigned) * n, hipMemcpyDeviceToHost));
-    return AMK_OK;
+    return amk::read_back({{h, kd->exact.at<unsigned>(amk::ExactStore::SA), sizeof(unsigned) * n}});
 }
 #endif
 

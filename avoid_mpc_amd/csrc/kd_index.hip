@@ -367,22 +367,13 @@ __global__ __launch_bounds__(256) void kd_tie_flags_kernel(amk::GridPtrs gpt, co
 extern "C" int amk_kd_points_host(amk_kd *kd, float *h_xyz, int *h_sizes) {
     if (!kd || !h_xyz || !h_sizes) return AMK_ERR_INVALID_ARG;
     AMK_HIP(hipDeviceSynchronize());
-    {
-        const int st = ensure_soa(kd, nullptr);
-        if (st != AMK_OK) return st;
-        AMK_HIP(hipDeviceSynchronize());
+    if (const int st = ensure_soa(kd, nullptr); st != AMK_OK) return st;
+    int st = amk::read_back({{h_sizes, kd->size.p, sizeof(int) * kd->n_scenes}});
+    for (int s = 0; s < kd->n_scenes && st == AMK_OK; ++s) {
+        const size_t at = (size_t)s * kd->cap;
+        st = amk::planes_to_xyz(kd->x.p + at, kd->y.p + at, kd->z.p + at, h_sizes[s], h_xyz + (size_t)s * kd->max_points * 3);
     }
-    AMK_HIP(hipMemcpy(h_sizes, kd->size.p, sizeof(int) * kd->n_scenes, hipMemcpyDeviceToHost));
-    std::vector<float> plane((size_t)kd->cap);
-    for (int s = 0; s < kd->n_scenes; ++s) {
-        const int n = h_sizes[s];
-        const float *src[3] = {kd->x.p, kd->y.p, kd->z.p};
-        for (int c = 0; c < 3; ++c) {
-            if (n > 0) AMK_HIP(hipMemcpy(plane.data(), src[c] + (size_t)s * kd->cap, sizeof(float) * n, hipMemcpyDeviceToHost));
-            for (int i = 0; i < n; ++i) h_xyz[((size_t)s * kd->max_points + i) * 3 + c] = plane[i];
-        }
-    }
-    return AMK_OK;
+    return st;
 }
 
 // internal (tests / benchmarks): 0 = bucketed index (default), 1 = streaming scan
@@ -449,8 +440,6 @@ int amk_kd_create(int n_scenes, int max_points, amk_kd **out) {
 }
 
 int amk_kd_destroy(amk_kd *kd) {
-    if (kd && kd->hpin) (void)hipHostFree(kd->hpin);
-    if (kd && kd->hstream) (void)hipStreamDestroy(kd->hstream);
     if (!kd) return AMK_ERR_INVALID_ARG;
     delete kd;
     return AMK_OK;
@@ -582,29 +571,24 @@ int amk_kd_build_host(amk_kd *kd, const float *h_xyz, int point_stride, long lon
     if (!kd || (!h_xyz && kd->max_points > 0) || point_stride < 3) return AMK_ERR_INVALID_ARG;
     const long long min_stride = (long long)kd->max_points * point_stride;
     if (scene_stride < min_stride && kd->n_scenes > 1) return AMK_ERR_INVALID_ARG;
-    const size_t tot = (size_t)(kd->n_scenes - 1) * scene_stride + (size_t)min_stride;
-    if (kd->stage_xyz.n < tot) AMK_HIP(kd->stage_xyz.alloc(tot > 0 ? tot : 1));
-    if (h_counts) {  // only the points every scene holds (the caller's buffer need not extend to the capacity)
-        for (int s = 0; s < kd->n_scenes; ++s) {
-            if (h_counts[s] < 0 || h_counts[s] > kd->max_points) return AMK_ERR_INVALID_ARG;
-            const size_t nf = (size_t)h_counts[s] * point_stride;
-            if (nf) AMK_HIP(hipMemcpy(kd->stage_xyz.p + (size_t)s * scene_stride, h_xyz + (size_t)s * scene_stride,
-                                      nf * sizeof(float), hipMemcpyHostToDevice));
-        }
-    } else if (tot) {
-        AMK_HIP(hipMemcpy(kd->stage_xyz.p, h_xyz, tot * sizeof(float), hipMemcpyHostToDevice));
-    }
-    const int *d_counts = nullptr;
-    if (h_counts) {
-        if (kd->stage_counts.n < (size_t)kd->n_scenes) AMK_HIP(kd->stage_counts.alloc(kd->n_scenes));
-        AMK_HIP(hipMemcpy(kd->stage_counts.p, h_counts, sizeof(int) * kd->n_scenes, hipMemcpyHostToDevice));
-        d_counts = kd->stage_counts.p;
-    }
-    int st = amk_kd_build(kd, kd->stage_xyz.p, point_stride, scene_stride, d_counts, nullptr);
-    if (st != AMK_OK) return st;
-    AMK_HIP(hipDeviceSynchronize());
-    kd->async_pending = 0;
-    return AMK_OK;
+    const size_t S = kd->n_scenes, tot = (S - 1) * scene_stride + (size_t)min_stride;
+    for (size_t s = 0; h_counts && s < S; ++s)
+        if (h_counts[s] < 0 || h_counts[s] > kd->max_points) return AMK_ERR_INVALID_ARG;
+    enum { XYZ, COUNTS };
+    // with counts, only the points every scene holds go over (the caller's buffer need not extend to the capacity): the launch copies them
+    const int st = kd->stage.call(
+        {!h_counts && tot > 0 ? amk::to_device(h_xyz, sizeof(float) * tot) : amk::scratch(sizeof(float) * (tot > 0 ? tot : 1)),
+         amk::if_given(amk::to_device(h_counts, sizeof(int) * S))},
+        [&](const amk::HostStage::Dev *d) {
+            float *d_xyz = d[XYZ];
+            for (size_t s = 0; h_counts && s < S; ++s)
+                if (const size_t nf = (size_t)h_counts[s] * point_stride)
+                    AMK_HIP(hipMemcpy(d_xyz + s * scene_stride, h_xyz + s * scene_stride, nf * sizeof(float), hipMemcpyHostToDevice));
+            return amk_kd_build(kd, d_xyz, point_stride, scene_stride, d[COUNTS], nullptr);
+        },
+        hipDeviceSynchronize);
+    if (st == AMK_OK) kd->async_pending = 0;
+    return st;
 }
 
 int amk_kd_search_host(amk_kd *kd, const double *h_queries, int n_queries, int k, int *h_indices, double *h_sqdist,
@@ -612,37 +596,30 @@ int amk_kd_search_host(amk_kd *kd, const double *h_queries, int n_queries, int k
     if (!kd || !h_queries || n_queries <= 0 || k <= 0) return AMK_ERR_INVALID_ARG;
     if (k > AMK_MAX_K || n_queries > AMK_MAX_QUERIES) return AMK_ERR_UNSUPPORTED;
     if (kd->mode == 0 && kd->tie_order == AMK_TIES_AUTO && k + 1 > AMK_MAX_K) return AMK_ERR_UNSUPPORTED;   // (before anything is staged)
-    const size_t rows = (size_t)kd->n_scenes * n_queries;
-    // one device block and one pinned host block: [queries | sqdist | indices | counts | pts]
-    const size_t o_q = 0, o_d2 = o_q + rows * 3 * sizeof(double), o_idx = o_d2 + rows * k * sizeof(double),
-                 o_cnt = o_idx + rows * k * sizeof(int), o_pts = o_cnt + rows * sizeof(int),
-                 total = o_pts + rows * k * 3 * sizeof(float);
-    if (!kd->hstream) AMK_HIP(hipStreamCreateWithFlags(&kd->hstream, hipStreamNonBlocking));
-    if (kd->stage_out.n < total) AMK_HIP(kd->stage_out.alloc(total));
-    if (kd->hpin_bytes < total) {
-        if (kd->hpin) (void)hipHostFree(kd->hpin);
-        kd->hpin = nullptr;
-        kd->hpin_bytes = 0;
-        AMK_HIP(hipHostMalloc(&kd->hpin, total, hipHostMallocDefault));
-        kd->hpin_bytes = total;
-    }
     if (kd->async_pending) {  // a build / sweep enqueued on some other stream: order behind it once
         AMK_HIP(hipDeviceSynchronize());
         kd->async_pending = 0;
     }
-    unsigned char *hp = static_cast<unsigned char *>(kd->hpin), *dp = kd->stage_out.p;
-    memcpy(hp + o_q, h_queries, rows * 3 * sizeof(double));
-    AMK_HIP(hipMemcpyAsync(dp + o_q, hp + o_q, rows * 3 * sizeof(double), hipMemcpyHostToDevice, kd->hstream));
-    int st = amk_kd_search(kd, reinterpret_cast<const double *>(dp + o_q), n_queries, k, reinterpret_cast<int *>(dp + o_idx),
-                           reinterpret_cast<double *>(dp + o_d2), reinterpret_cast<float *>(dp + o_pts),
-                           reinterpret_cast<int *>(dp + o_cnt), kd->hstream);
-    if (st != AMK_OK) return st;
-    AMK_HIP(hipMemcpyAsync(hp + o_d2, dp + o_d2, total - o_d2, hipMemcpyDeviceToHost, kd->hstream));
-    AMK_HIP(hipStreamSynchronize(kd->hstream));
-    if (h_indices) memcpy(h_indices, hp + o_idx, rows * k * sizeof(int));
-    if (h_sqdist) memcpy(h_sqdist, hp + o_d2, rows * k * sizeof(double));
-    if (h_pts) memcpy(h_pts, hp + o_pts, rows * k * 3 * sizeof(float));
-    if (h_counts) memcpy(h_counts, hp + o_cnt, rows * sizeof(int));
+    const size_t rows = (size_t)kd->n_scenes * n_queries;
+    enum { QUERIES, SQDIST, INDICES, COUNTS, PTS };
+    return kd->stage.call_pinned({amk::to_device(h_queries, rows * 3 * sizeof(double)), amk::to_host(h_sqdist, rows * k * sizeof(double)),
+                                  amk::to_host(h_indices, rows * k * sizeof(int)), amk::to_host(h_counts, rows * sizeof(int)),
+                                  amk::to_host(h_pts, rows * k * 3 * sizeof(float))},
+                                 [&](const amk::HostStage::Dev *d, hipStream_t stream) {
+                                     return amk_kd_search(kd, d[QUERIES], n_queries, k, d[INDICES], d[SQDIST], d[PTS], d[COUNTS], stream);
+                                 });
+}
+
+// Internal (not in include/avoid_mpc_amd.h; tests/test_host_stage.py), host only, needs no device: where HostStage puts n slots of
+// bytes[i] -- offsets[n], and total = the block that holds them
+int amk__stage_layout(const long long *bytes, int n, long long *offsets, long long *total) {
+    if (n < 0 || !total || (n > 0 && (!bytes || !offsets))) return AMK_ERR_INVALID_ARG;
+    size_t end = 0;
+    for (int i = 0; i < n; ++i) {
+        if (bytes[i] < 0) return AMK_ERR_INVALID_ARG;
+        offsets[i] = (long long)amk::stage_next(end, (size_t)bytes[i]);
+    }
+    *total = (long long)end;
     return AMK_OK;
 }
 

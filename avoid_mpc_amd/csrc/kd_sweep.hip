@@ -596,9 +596,9 @@ extern "C" int amk_kd_keyframe_sweep_host(amk_kd *keyframe, amk_kd *current, dou
                                           int *h_outliers, int *h_rebuilt) {
     int st = amk_kd_keyframe_sweep(keyframe, current, th_dist, th_count, nullptr, nullptr, nullptr);
     if (st != AMK_OK) return st;
-    AMK_HIP(hipDeviceSynchronize());
     std::vector<int> tmp((size_t)keyframe->n_scenes * 2);
-    AMK_HIP(hipMemcpy(tmp.data(), keyframe->sweep_cnt.p, sizeof(int) * tmp.size(), hipMemcpyDeviceToHost));
+    st = amk::read_back({{tmp.data(), keyframe->sweep_cnt.p, sizeof(int) * tmp.size()}});
+    if (st != AMK_OK) return st;
     for (int s = 0; s < keyframe->n_scenes; ++s) {
         if (h_outliers) h_outliers[s] = tmp[2 * s];
         if (h_rebuilt) h_rebuilt[s] = tmp[2 * s + 1];

@@ -41,6 +41,7 @@ struct amk_kfmap {
     amk::DevBuf<int> fmap;       // [F][S] query vector: pool scene of frame f, -1 absent
     int tie_order = AMK_TIES_LOWEST_INDEX;   // amk_kfmap_set_tie_order; AMK_TIES_NANOFLANN: the pools hold a tree per scene (kd_pool_exact_build)
     bool had_frame = false;      // an AddVertex was enqueued (never cleared): the tie order can no longer change
+    amk::HostStage stage;        // staging of the map's *_host entries
 };
 
 namespace {
@@ -382,26 +383,24 @@ int amk_kfmap_set_tie_order(amk_kfmap *m, int mode) {
 // absent frame or a map in the default mode.  Synchronises the device.
 int amk_kfmap_exact_status_host(amk_kfmap *m, int *h_obs, int *h_edge) {
     if (!m) return AMK_ERR_INVALID_ARG;
-    AMK_HIP(hipDeviceSynchronize());
     const size_t S = m->S, F = m->F, PS = (size_t)m->P * S;
+    const bool exact = m->tie_order == AMK_TIES_NANOFLANN;
     std::vector<int> fm(S * F), st(PS);
-    AMK_HIP(hipMemcpy(fm.data(), m->fmap.p, sizeof(int) * S * F, hipMemcpyDeviceToHost));
-    amk::DevBuf<int> d;
-    if (m->tie_order == AMK_TIES_NANOFLANN) AMK_HIP(d.alloc(PS));
+    if (const int rc = read_back({{fm.data(), m->fmap.p, sizeof(int) * S * F}}); rc != AMK_OK) return rc;
     amk_kd *pools[2] = {m->obs, m->edge};
     int *outs[2] = {h_obs, h_edge};
     for (int h = 0; h < 2; ++h) {
         if (!outs[h]) continue;
-        if (m->tie_order == AMK_TIES_NANOFLANN) {
-            const int rc = amk::kd_pool_exact_status(pools[h], d.p, nullptr);
+        if (exact) {
+            const int rc = m->stage.call({to_host(st.data(), sizeof(int) * PS)},
+                                         [&](const HostStage::Dev *d) { return amk::kd_pool_exact_status(pools[h], d[0], nullptr); },
+                                         hipDeviceSynchronize);
             if (rc != AMK_OK) return rc;
-            AMK_HIP(hipDeviceSynchronize());
-            AMK_HIP(hipMemcpy(st.data(), d.p, sizeof(int) * PS, hipMemcpyDeviceToHost));
         }
         for (size_t s = 0; s < S; ++s)
             for (size_t f = 0; f < F; ++f) {
                 const int p = fm[f * S + s];
-                outs[h][s * F + f] = (p < 0 || m->tie_order != AMK_TIES_NANOFLANN) ? AMK_EXACT_OFF : st[p];
+                outs[h][s * F + f] = (p < 0 || !exact) ? AMK_EXACT_OFF : st[p];
             }
     }
     return AMK_OK;
@@ -499,17 +498,18 @@ int amk_kfmap_nearest_distance(amk_kfmap *m, const double *d_queries, int query_
 int amk_kfmap_query_nearest_host(amk_kfmap *m, const amk_frame_camera *cam, const double *h_queries, int query_stride, int n_queries,
                                  int k, int query_edge, float *h_pts, double *h_sqdist, int *h_frame, int *h_counts) {
     if (!m) return AMK_ERR_INVALID_ARG;
-    return amk::map_query_host(m->S, h_queries, query_stride, n_queries, k, nullptr, h_pts, h_sqdist, h_frame, h_counts, nullptr,
-                               [&](const double *dq, const double *, float *dp, double *dd, int *df, int *dc, double *) {
-                                   return amk_kfmap_query_nearest(m, cam, dq, query_stride, n_queries, k, query_edge, dp, dd, df, dc, nullptr);
+    return amk::map_query_host(m->stage, m->S, h_queries, query_stride, n_queries, k, nullptr, h_pts, h_sqdist, h_frame, h_counts, nullptr,
+                               [&](const HostStage::Dev *d) {
+                                   return amk_kfmap_query_nearest(m, cam, d[MQ_QUERIES], query_stride, n_queries, k, query_edge, d[MQ_PTS],
+                                                                  d[MQ_SQDIST], d[MQ_FRAME], d[MQ_COUNTS], nullptr);
                                });
 }
 
 int amk_kfmap_nearest_distance_host(amk_kfmap *m, const double *h_queries, int query_stride, int n_queries, double *h_dist) {
     if (!m || !h_dist) return AMK_ERR_INVALID_ARG;
-    return amk::map_query_host(m->S, h_queries, query_stride, n_queries, 1, nullptr, nullptr, nullptr, nullptr, nullptr, h_dist,
-                               [&](const double *dq, const double *, float *, double *, int *, int *, double *dd) {
-                                   return amk_kfmap_nearest_distance(m, dq, query_stride, n_queries, dd, nullptr);
+    return amk::map_query_host(m->stage, m->S, h_queries, query_stride, n_queries, 1, nullptr, nullptr, nullptr, nullptr, nullptr, h_dist,
+                               [&](const HostStage::Dev *d) {
+                                   return amk_kfmap_nearest_distance(m, d[MQ_QUERIES], query_stride, n_queries, d[MQ_DIST], nullptr);
                                });
 }
 
@@ -533,20 +533,15 @@ int amk_kfmap_points_host(amk_kfmap *m, int scene, float *h_xyz, long long capac
     if (!h_xyz && capacity_points == 0) return AMK_OK;   // the size probe
     if (capacity_points < total) return AMK_ERR_INVALID_ARG;
     if (total > 0 && !m->obs->x.p) return AMK_ERR_INVALID_ARG;   // (cannot occur: the planes are reserved at creation)
-    std::vector<float> plane;
     long long o = 0;
-    for (int f = 0; f < m->F; ++f) {
-        const int n = sz[f];
-        if (n <= 0) continue;
-        plane.resize((size_t)n);
-        const float *src[3] = {m->obs->x.p, m->obs->y.p, m->obs->z.p};
-        for (int c = 0; c < 3; ++c) {
-            AMK_HIP(hipMemcpy(plane.data(), src[c] + (size_t)fm[f] * m->obs->cap, sizeof(float) * n, hipMemcpyDeviceToHost));
-            for (int i = 0; i < n; ++i) h_xyz[(size_t)(o + i) * 3 + c] = plane[i];
-        }
-        o += n;
+    int st = AMK_OK;
+    for (int f = 0; f < m->F && st == AMK_OK; ++f) {
+        if (sz[f] <= 0) continue;
+        const size_t at = (size_t)fm[f] * m->obs->cap;
+        st = planes_to_xyz(m->obs->x.p + at, m->obs->y.p + at, m->obs->z.p + at, sz[f], h_xyz + (size_t)o * 3);
+        o += sz[f];
     }
-    return AMK_OK;
+    return st;
 }
 
 // Introspection (tests, diagnostics): per scene the number of keyframes, the number of frames of the query vector, the
@@ -554,13 +549,12 @@ int amk_kfmap_points_host(amk_kfmap *m, int scene, float *h_xyz, long long capac
 // every query frame (-1 beyond the scene's map).  Synchronises the device.
 int amk_kfmap_state_host(amk_kfmap *m, int *h_n_keyframes, int *h_n_query_frames, int *h_last_outliers, int *h_frame_sizes) {
     if (!m) return AMK_ERR_INVALID_ARG;
-    AMK_HIP(hipDeviceSynchronize());
     const size_t S = m->S;
     std::vector<int> nk(S), fm(S * m->F), out(S), sz((size_t)m->P * S);
-    AMK_HIP(hipMemcpy(nk.data(), m->kf_n.p, sizeof(int) * S, hipMemcpyDeviceToHost));
-    AMK_HIP(hipMemcpy(fm.data(), m->fmap.p, sizeof(int) * S * m->F, hipMemcpyDeviceToHost));
-    AMK_HIP(hipMemcpy(out.data(), m->outliers.p, sizeof(int) * S, hipMemcpyDeviceToHost));
-    AMK_HIP(hipMemcpy(sz.data(), m->obs->size.p, sizeof(int) * sz.size(), hipMemcpyDeviceToHost));
+    if (const int st = read_back({{nk.data(), m->kf_n.p, sizeof(int) * S}, {fm.data(), m->fmap.p, sizeof(int) * S * m->F},
+                                  {out.data(), m->outliers.p, sizeof(int) * S}, {sz.data(), m->obs->size.p, sizeof(int) * sz.size()}});
+        st != AMK_OK)
+        return st;
     for (size_t s = 0; s < S; ++s) {
         if (h_n_keyframes) h_n_keyframes[s] = nk[s];
         if (h_last_outliers) h_last_outliers[s] = out[s];
@@ -579,14 +573,9 @@ int amk_kfmap_state_host(amk_kfmap *m, int *h_n_keyframes, int *h_n_query_frames
 // need [S] as the kernels left them (any pointer may be NULL).  Synchronises the device.
 int amk__kfmap_slots_host(amk_kfmap *m, int *h_cur_slot, int *h_kf_n, int *h_kf_slots, int *h_fmap, int *h_need) {
     if (!m) return AMK_ERR_INVALID_ARG;
-    AMK_HIP(hipDeviceSynchronize());
-    const size_t S = m->S;
-    if (h_cur_slot) AMK_HIP(hipMemcpy(h_cur_slot, m->cur_slot.p, sizeof(int) * S, hipMemcpyDeviceToHost));
-    if (h_kf_n) AMK_HIP(hipMemcpy(h_kf_n, m->kf_n.p, sizeof(int) * S, hipMemcpyDeviceToHost));
-    if (h_kf_slots) AMK_HIP(hipMemcpy(h_kf_slots, m->kf_slots.p, sizeof(int) * S * m->P, hipMemcpyDeviceToHost));
-    if (h_fmap) AMK_HIP(hipMemcpy(h_fmap, m->fmap.p, sizeof(int) * S * m->F, hipMemcpyDeviceToHost));
-    if (h_need) AMK_HIP(hipMemcpy(h_need, m->need.p, sizeof(int) * S, hipMemcpyDeviceToHost));
-    return AMK_OK;
+    const size_t B = sizeof(int) * m->S;   // bytes of one int per scene
+    return read_back({{h_cur_slot, m->cur_slot.p, B}, {h_kf_n, m->kf_n.p, B}, {h_kf_slots, m->kf_slots.p, B * m->P}, {h_fmap, m->fmap.p, B * m->F},
+                      {h_need, m->need.p, B}});
 }
 
 }  // extern "C"

@@ -190,10 +190,6 @@ int launch_query(const QueryFrames &qf, int S, const double *d_queries, int quer
     return AMK_OK;
 }
 
-int query_args_ok(const double *d_queries, int query_stride, int n_queries) {
-    return d_queries && query_stride >= 3 && n_queries >= 1;
-}
-
 // a caller's list of frame handles -> the kernel's argument (status: the header's rules, before anything is launched)
 int frames_of_handles(amk_kd *const *frames, int n_frames, QueryFrames &qf, int &S) {
     if (!frames || n_frames < 1) return AMK_ERR_INVALID_ARG;
@@ -244,41 +240,6 @@ int map_nearest_distance(amk_kd *pool, int n_frames, const int *d_fmap, int S, c
     return launch_query<true>(frames_of_pool(pool, n_frames, d_fmap, S), S, d_queries, query_stride, n_queries, 1, nullptr, nullptr,
                               nullptr, nullptr, nullptr, nullptr, d_dist, stream);
 }
-
-// The *_host variants: queries (and poses) staged through device memory, `launch` enqueued on the null stream between two
-// device-wide waits (a build or an update enqueued on any stream is seen), results copied back.  Allocates per call: a
-// convenience for single-robot hosts and tests, not a hot path.  Any output may be NULL.
-int map_query_host(int S, const double *h_queries, int query_stride, int n_queries, int k, const double *h_Twc, float *h_pts,
-                   double *h_sqdist, int *h_frame, int *h_counts, double *h_dist,
-                   const std::function<int(const double *, const double *, float *, double *, int *, int *, double *)> &launch) {
-    if (S < 1 || !query_args_ok(h_queries, query_stride, n_queries) || k < 1) return AMK_ERR_INVALID_ARG;
-    if (k > AMK_MAX_K) return AMK_ERR_UNSUPPORTED;
-    const size_t rows = (size_t)S * n_queries, nq = (rows - 1) * query_stride + 3;
-    DevBuf<double> q, twc, d2, dist;
-    DevBuf<float> pts;
-    DevBuf<int> frame, counts;
-    AMK_HIP(q.alloc(nq));
-    AMK_HIP(hipMemcpy(q.p, h_queries, sizeof(double) * nq, hipMemcpyHostToDevice));
-    if (h_Twc) {
-        AMK_HIP(twc.alloc((size_t)S * 16));
-        AMK_HIP(hipMemcpy(twc.p, h_Twc, sizeof(double) * S * 16, hipMemcpyHostToDevice));
-    }
-    if (h_pts) AMK_HIP(pts.alloc(rows * k * 3));
-    if (h_sqdist) AMK_HIP(d2.alloc(rows * k));
-    if (h_frame) AMK_HIP(frame.alloc(rows * k));
-    if (h_counts) AMK_HIP(counts.alloc(rows));
-    if (h_dist) AMK_HIP(dist.alloc(rows));
-    AMK_HIP(hipDeviceSynchronize());
-    const int st = launch(q.p, twc.p, pts.p, d2.p, frame.p, counts.p, dist.p);
-    if (st != AMK_OK) return st;
-    AMK_HIP(hipDeviceSynchronize());
-    if (h_pts) AMK_HIP(hipMemcpy(h_pts, pts.p, sizeof(float) * rows * k * 3, hipMemcpyDeviceToHost));
-    if (h_sqdist) AMK_HIP(hipMemcpy(h_sqdist, d2.p, sizeof(double) * rows * k, hipMemcpyDeviceToHost));
-    if (h_frame) AMK_HIP(hipMemcpy(h_frame, frame.p, sizeof(int) * rows * k, hipMemcpyDeviceToHost));
-    if (h_counts) AMK_HIP(hipMemcpy(h_counts, counts.p, sizeof(int) * rows, hipMemcpyDeviceToHost));
-    if (h_dist) AMK_HIP(hipMemcpy(h_dist, dist.p, sizeof(double) * rows, hipMemcpyDeviceToHost));
-    return AMK_OK;
-}
 }  // namespace amk
 
 extern "C" {
@@ -313,9 +274,11 @@ int amk_kd_query_frames_host(amk_kd *const *frames, int n_frames, const double *
     QueryFrames qf;
     int S = 0;
     if (const int st = frames_of_handles(frames, n_frames, qf, S); st != AMK_OK) return st;
-    return amk::map_query_host(S, h_queries, query_stride, n_queries, k, h_Twc, h_pts, h_sqdist, h_frame, h_counts, nullptr,
-                               [&](const double *dq, const double *dT, float *dp, double *dd, int *df, int *dc, double *) {
-                                   return amk_kd_query_frames(frames, n_frames, dT, cam, dq, query_stride, n_queries, k, dp, dd, df, dc, nullptr);
+    amk::HostStage stage;   // frees at return: these frames belong to no one handle
+    return amk::map_query_host(stage, S, h_queries, query_stride, n_queries, k, h_Twc, h_pts, h_sqdist, h_frame, h_counts, nullptr,
+                               [&](const amk::HostStage::Dev *d) {
+                                   return amk_kd_query_frames(frames, n_frames, d[amk::MQ_TWC], cam, d[amk::MQ_QUERIES], query_stride, n_queries, k,
+                                                              d[amk::MQ_PTS], d[amk::MQ_SQDIST], d[amk::MQ_FRAME], d[amk::MQ_COUNTS], nullptr);
                                });
 }
 

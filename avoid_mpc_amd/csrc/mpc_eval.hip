@@ -262,17 +262,6 @@ __global__ __launch_bounds__(64) void mpc_eval_gamma_kernel(int Nrt, int K, int 
     }
 }
 
-// the device staging the two *_host conveniences share: w, the scene records, amk_mpc_eval's lam_f and its five outputs
-int ensure_eval_staging(amk_mpc *m) {
-    if (m->ev_w.p) return AMK_OK;
-    const NlpDims D = m->dims();
-    const size_t S = m->S;
-    AMK_HIP(m->ev_w.alloc(S * D.nx()));
-    AMK_HIP(m->ev_ref.alloc(S * m->nref));
-    AMK_HIP(m->ev_out.alloc(S * (2 + D.nx() + D.ng() + D.nnz_jac() + D.nnz_hess())));
-    return AMK_OK;
-}
-
 hipError_t wait_null_stream() { return hipStreamSynchronize(nullptr); }
 
 }  // namespace
@@ -366,36 +355,30 @@ int amk_mpc_eval_gamma_host(amk_mpc *m, const double *h_w, const double *h_ref_s
                             const double *h_lam_g, double *h_grad_x, double *h_grad_p) {
     if (!m || !h_w || !h_ref_states) return AMK_ERR_INVALID_ARG;
     const NlpDims D = m->dims();
-    const size_t S = m->S, nx = D.nx(), ng = D.ng(), np = D.np(), B = sizeof(double);
-    int st = ensure_eval_staging(m);
-    if (st != AMK_OK) return st;
-    if (!m->ev_gam.p) AMK_HIP(m->ev_gam.alloc(S * (1 + ng + nx + np)));
-    double *lf = m->ev_gam.p, *lgm = lf + S, *gx = lgm + S * ng, *gp = gx + S * nx;
-    return staged_call({{m->ev_w.p, h_w, B * S * nx}, {m->ev_ref.p, h_ref_states, B * S * m->nref}, {lf, h_lam_f, B * S},
-                        {lgm, h_lam_g, B * S * ng}},
-                       [&] {
-                           return amk_mpc_eval_gamma(m, m->ev_w.p, m->ev_ref.p, h_lam_f ? lf : nullptr, h_lam_g ? lgm : nullptr,
-                                                     h_grad_x ? gx : nullptr, h_grad_p ? gp : nullptr, nullptr);
-                       },
-                       wait_null_stream, {{h_grad_x, gx, B * S * nx}, {h_grad_p, gp, B * S * np}});
+    const size_t B = sizeof(double) * m->S;   // bytes of one double per scene
+    enum { W, REF, LAM_F, LAM_G, GRAD_X, GRAD_P };
+    return m->stage.call({to_device(h_w, B * D.nx()), to_device(h_ref_states, B * m->nref), if_given(to_device(h_lam_f, B)),
+                          if_given(to_device(h_lam_g, B * D.ng())), if_given(to_host(h_grad_x, B * D.nx())),
+                          if_given(to_host(h_grad_p, B * D.np()))},
+                         [&](const HostStage::Dev *d) {
+                             return amk_mpc_eval_gamma(m, d[W], d[REF], d[LAM_F], d[LAM_G], d[GRAD_X], d[GRAD_P], nullptr);
+                         },
+                         wait_null_stream);
 }
 
 int amk_mpc_eval_host(amk_mpc *m, const double *h_w, const double *h_ref_states, const double *h_lam_f, double *h_f,
                       double *h_grad_f, double *h_g, double *h_jac_g, double *h_hess_l) {
     if (!m || !h_w || !h_ref_states) return AMK_ERR_INVALID_ARG;
     const NlpDims D = m->dims();
-    const size_t S = m->S, nx = D.nx(), ng = D.ng(), nj = D.nnz_jac(), nh = D.nnz_hess(), B = sizeof(double);
-    int st = ensure_eval_staging(m);
-    if (st != AMK_OK) return st;
-    double *lam = m->ev_out.p, *f = lam + S, *gr = f + S, *g = gr + S * nx, *jac = g + S * ng, *hs = jac + S * nj;
-    return staged_call({{m->ev_w.p, h_w, B * S * nx}, {m->ev_ref.p, h_ref_states, B * S * m->nref}, {lam, h_lam_f, B * S}},
-                       [&] {
-                           return amk_mpc_eval(m, m->ev_w.p, m->ev_ref.p, h_lam_f ? lam : nullptr, h_f ? f : nullptr,
-                                               h_grad_f ? gr : nullptr, h_g ? g : nullptr, h_jac_g ? jac : nullptr,
-                                               h_hess_l ? hs : nullptr, nullptr);
-                       },
-                       wait_null_stream,
-                       {{h_f, f, B * S}, {h_grad_f, gr, B * S * nx}, {h_g, g, B * S * ng}, {h_jac_g, jac, B * S * nj}, {h_hess_l, hs, B * S * nh}});
+    const size_t B = sizeof(double) * m->S;   // bytes of one double per scene
+    enum { W, REF, LAM_F, F, GRAD_F, G, JAC_G, HESS_L };
+    return m->stage.call({to_device(h_w, B * D.nx()), to_device(h_ref_states, B * m->nref), if_given(to_device(h_lam_f, B)),
+                          if_given(to_host(h_f, B)), if_given(to_host(h_grad_f, B * D.nx())), if_given(to_host(h_g, B * D.ng())),
+                          if_given(to_host(h_jac_g, B * D.nnz_jac())), if_given(to_host(h_hess_l, B * D.nnz_hess()))},
+                         [&](const HostStage::Dev *d) {
+                             return amk_mpc_eval(m, d[W], d[REF], d[LAM_F], d[F], d[GRAD_F], d[G], d[JAC_G], d[HESS_L], nullptr);
+                         },
+                         wait_null_stream);
 }
 
 }  // extern "C"

@@ -1,7 +1,6 @@
 // Host-side handle of a batch of ObstacleAvoidanceMPC objects (AM/include/HighLvlMpc.h:4-33) and the
 // device workspace of the fused control step.  Shared by mpc_solve.hip and step.hip.
 #pragma once
-#include <initializer_list>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -24,15 +23,10 @@ struct amk_mpc {
     amk::DevBuf<double> gains; // [S][N][GAIN_STAGE = 32] Riccati feedback gains, structural zeros left out (scratch of one interior-point iteration)
     amk::DevBuf<double> plan_coef;  // item coefficients + lane-role constants of the Riccati plan (mpc_device.h)
     amk::DevBuf<int> plan_meta;     // [PLAN_ITEMS] PlanItemMeta + [64] LaneRole
-    // staging for amk_mpc_eval_host
-    amk::DevBuf<double> ev_w, ev_ref, ev_out;
-    // amk_mpc_eval_gamma: d(A, B, c)/d tau (mpc_model.h DtauBlock, recomputed when tau changes) and its host staging
-    amk::DevBuf<double> ev_dtau, ev_gam;
+    // amk_mpc_eval_gamma: d(A, B, c)/d tau (mpc_model.h DtauBlock, recomputed when tau changes)
+    amk::DevBuf<double> ev_dtau;
     double ev_dtau_tau[4] = {0, 0, 0, 0};
     bool ev_dtau_valid = false;
-    // staging for amk_mpc_solve_host
-    amk::DevBuf<double> st_ref, st_u, st_x0;
-    amk::DevBuf<int> st_info;
     // control-step workspace (allocated by the first amk_step_batch)
     amk::DevBuf<float> knn_pts;     // [S][N][K][3] neighbours of every reference point
     amk::DevBuf<double> knn_d2;     // [S][N][K]
@@ -49,9 +43,7 @@ struct amk_mpc {
     amk::DevBuf<double> mf_knn_d2, mf_edge_d2;    // [F][S][N][K],    [F][S]
     amk::DevBuf<char> mf_exact;                   // step_frames.hip: FrameExact, when a frame is in AMK_TIES_NANOFLANN mode
     std::vector<char> mf_exact_host;
-    // staging for amk_step_batch_host
-    amk::DevBuf<double> sh_sq, sh_posx, sh_ref, sh_u, sh_x0;
-    amk::DevBuf<int> sh_flags;
+    amk::HostStage stage;   // staging of the *_host entries: the two evals, the solve, amk_step_batch_host
 };
 
 // Internal (not in include/avoid_mpc_amd.h; tests/test_mpc_model.py), host only, needs no device: the model's A [10][10], B [10][4],
@@ -70,21 +62,6 @@ void with_horizon(int N, F &&f, std::integer_sequence<int, NT...>) {
 // calls f(std::integral_constant<int, NT>) with the instantiation that serves horizon N
 template <class F>
 void with_horizon(int N, F &&f) { with_horizon(N, f, BakedHorizons{}); }
-
-// The *_host conveniences of the MPC: copy `in` to the device, launch, wait, copy `out` back.  A copy whose host side is null is
-// skipped (an input not given, an output not wanted).
-struct HostCopy { void *dst; const void *src; size_t bytes; };
-template <class Launch>
-int staged_call(std::initializer_list<HostCopy> in, Launch &&launch, hipError_t (*wait)(), std::initializer_list<HostCopy> out) {
-    for (const HostCopy &c : in)
-        if (c.src) AMK_HIP(hipMemcpy(c.dst, c.src, c.bytes, hipMemcpyHostToDevice));
-    const int st = launch();
-    if (st != AMK_OK) return st;
-    AMK_HIP(wait());
-    for (const HostCopy &c : out)
-        if (c.dst) AMK_HIP(hipMemcpy(c.dst, c.src, c.bytes, hipMemcpyDeviceToHost));
-    return AMK_OK;
-}
 
 // amk_mpc::run_scenes for the length of a scope (amk_pipeline's control step): whichever way the scope is left, it is 0 again
 struct RunScenes {

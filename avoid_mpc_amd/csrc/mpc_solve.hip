@@ -486,17 +486,11 @@ int amk_mpc_reset_warm_start(amk_mpc *m, void *stream) {
 int amk_mpc_solve_host(amk_mpc *m, const double *h_ref_states, double *h_u, double *h_x0array, int *h_info, int faster) {
     if (!m || !h_ref_states || !h_u) return AMK_ERR_INVALID_ARG;
     const size_t S = m->S, nx0 = (size_t)NlpDims::kStage * m->N;
-    if (!m->st_ref.p) {
-        AMK_HIP(m->st_ref.alloc(S * m->nref));
-        AMK_HIP(m->st_u.alloc(S * UD));
-        AMK_HIP(m->st_x0.alloc(S * nx0));
-        AMK_HIP(m->st_info.alloc(S * 4));
-    }
-    return staged_call({{m->st_ref.p, h_ref_states, sizeof(double) * S * m->nref}},
-                       [&] { return amk_mpc_solve(m, m->st_ref.p, m->st_u.p, m->st_x0.p, m->st_info.p, faster, nullptr); },
-                       hipDeviceSynchronize,
-                       {{h_u, m->st_u.p, sizeof(double) * S * UD}, {h_x0array, m->st_x0.p, sizeof(double) * S * nx0},
-                        {h_info, m->st_info.p, sizeof(int) * S * 4}});
+    enum { REF, U, X0, INFO };
+    return m->stage.call({to_device(h_ref_states, sizeof(double) * S * m->nref), to_host(h_u, sizeof(double) * S * UD),
+                          to_host(h_x0array, sizeof(double) * S * nx0), to_host(h_info, sizeof(int) * S * 4)},
+                         [&](const HostStage::Dev *d) { return amk_mpc_solve(m, d[REF], d[U], d[X0], d[INFO], faster, nullptr); },
+                         hipDeviceSynchronize);
 }
 
 }  // extern "C"

@@ -325,10 +325,8 @@ extern "C" void amk__diag_skip(int mask) { g_diag_skip = mask; }
 // solve: the first min(n, S nref) doubles of the workspace, after a device-wide wait.  No step has run yet: AMK_ERR_INVALID_ARG.
 extern "C" int amk__mpc_ref_states(amk_mpc *mpc, double *h_out, long long n) {
     if (!mpc || !h_out || n < 0 || !mpc->ref_states.p) return AMK_ERR_INVALID_ARG;
-    AMK_HIP(hipDeviceSynchronize());
     const long long have = (long long)mpc->S * mpc->nref;
-    AMK_HIP(hipMemcpy(h_out, mpc->ref_states.p, sizeof(double) * (size_t)(n < have ? n : have), hipMemcpyDeviceToHost));
-    return AMK_OK;
+    return read_back({{h_out, mpc->ref_states.p, sizeof(double) * (size_t)(n < have ? n : have)}});
 }
 
 extern "C" int amk_step_batch(amk_kd *obstacle, amk_kd *edge, amk_mpc *mpc, const amk_step_params *prm,
@@ -447,26 +445,15 @@ extern "C" int amk_step_batch_host(amk_kd *obstacle, amk_kd *edge, amk_mpc *mpc,
     if (!mpc || !prm || !h_state_quad || !h_pos_x || !h_ref_path || !h_u || !h_flags) return AMK_ERR_INVALID_ARG;
     if (!step_params_ok(mpc, prm)) return AMK_ERR_INVALID_ARG;
     const size_t S = mpc->S, N = mpc->N, mi = prm->mpc_max_iter;
-    if (mpc->sh_sq.n < S * mi * SD) AMK_HIP(mpc->sh_sq.alloc(S * AMK_MAX_OUTER_ITER * SD));
-    if (!mpc->sh_ref.p) {
-        AMK_HIP(mpc->sh_posx.alloc(S));
-        AMK_HIP(mpc->sh_ref.alloc(S * N * SD));
-        AMK_HIP(mpc->sh_u.alloc(S * 4));
-        AMK_HIP(mpc->sh_x0.alloc(S * N * 14));
-        AMK_HIP(mpc->sh_flags.alloc(S * 4));
-    }
-    AMK_HIP(hipMemcpy(mpc->sh_sq.p, h_state_quad, sizeof(double) * S * mi * SD, hipMemcpyHostToDevice));
-    AMK_HIP(hipMemcpy(mpc->sh_posx.p, h_pos_x, sizeof(double) * S, hipMemcpyHostToDevice));
-    AMK_HIP(hipMemcpy(mpc->sh_ref.p, h_ref_path, sizeof(double) * S * N * SD, hipMemcpyHostToDevice));
-    int st = amk_step_batch(obstacle, edge, mpc, prm, mpc->sh_sq.p, mpc->sh_posx.p, mpc->sh_ref.p, mpc->sh_u.p,
-                            mpc->sh_x0.p, mpc->sh_flags.p, nullptr);
-    if (st != AMK_OK) return st;
-    AMK_HIP(hipDeviceSynchronize());
-    AMK_HIP(hipMemcpy(h_ref_path, mpc->sh_ref.p, sizeof(double) * S * N * SD, hipMemcpyDeviceToHost));
-    AMK_HIP(hipMemcpy(h_u, mpc->sh_u.p, sizeof(double) * S * 4, hipMemcpyDeviceToHost));
-    if (h_x0array) AMK_HIP(hipMemcpy(h_x0array, mpc->sh_x0.p, sizeof(double) * S * N * 14, hipMemcpyDeviceToHost));
-    AMK_HIP(hipMemcpy(h_flags, mpc->sh_flags.p, sizeof(int) * S * 4, hipMemcpyDeviceToHost));
-    return AMK_OK;
+    enum { STATE_QUAD, POS_X, REF_PATH, U, X0ARRAY, FLAGS };
+    return mpc->stage.call({to_device(h_state_quad, sizeof(double) * S * mi * SD), to_device(h_pos_x, sizeof(double) * S),
+                            both_ways(h_ref_path, sizeof(double) * S * N * SD), to_host(h_u, sizeof(double) * S * 4),
+                            to_host(h_x0array, sizeof(double) * S * N * 14), to_host(h_flags, sizeof(int) * S * 4)},
+                           [&](const HostStage::Dev *d) {
+                               return amk_step_batch(obstacle, edge, mpc, prm, d[STATE_QUAD], d[POS_X], d[REF_PATH], d[U], d[X0ARRAY],
+                                                     d[FLAGS], nullptr);
+                           },
+                           hipDeviceSynchronize);
 }
 
 #ifdef AMK_KNN_COUNT
