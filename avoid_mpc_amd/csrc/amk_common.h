@@ -164,6 +164,19 @@ int map_query_nearest(amk_kd *pool, int n_frames, const int *d_fmap, int S, cons
 int map_nearest_distance(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_queries, int query_stride,
                          int n_queries, double *d_dist, hipStream_t stream);
 inline bool query_args_ok(const double *queries, int query_stride, int n_queries) { return queries && query_stride >= 3 && n_queries >= 1; }
+// kd_radius.hip / map_query.hip: the argument rules every radius search shares (include/avoid_mpc_amd.h), checked before anything
+// is staged or launched.  any_list: a list output was given; any_out: an output at all
+inline int radius_args_status(const double *queries, int query_stride, int n_queries, double radius_sq, int max_results, bool any_list,
+                              bool any_out) {
+    if (!query_args_ok(queries, query_stride, n_queries) || !(radius_sq >= 0.0) || max_results < 0 || !any_out) return AMK_ERR_INVALID_ARG;
+    if (max_results > AMK_MAX_K) return AMK_ERR_UNSUPPORTED;
+    if (max_results == 0 && any_list) return AMK_ERR_INVALID_ARG;
+    return AMK_OK;
+}
+inline double radius_clamped(double radius_sq) { return radius_sq < DBL_MAX ? radius_sq : DBL_MAX; }   // +inf: every usable point
+// map_query.hip, for kfmap.hip: the radius search over a pool
+int map_radius_search(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_queries, int query_stride, int n_queries,
+                      double radius_sq, int max_results, float *d_pts, double *d_sqdist, int *d_frame, int *d_counts, hipStream_t stream);
 // Their *_host variants and amk_kd_query_frames_host: queries (and poses) staged through `stage`, launch(d) -- the entry's device
 // call, d[i] = MapQuerySlot i, null where the host pointer is -- enqueued on the null stream between two device-wide waits (a
 // build or an update enqueued on any stream is seen), results copied back.  A convenience for single-robot hosts and tests,
@@ -179,6 +192,26 @@ int map_query_host(HostStage &stage, int S, const double *h_queries, int query_s
                        if_given(to_host(h_pts, sizeof(float) * rows * k * 3)), if_given(to_host(h_sqdist, sizeof(double) * rows * k)),
                        if_given(to_host(h_frame, sizeof(int) * rows * k)), if_given(to_host(h_counts, sizeof(int) * rows)),
                        if_given(to_host(h_dist, sizeof(double) * rows))},
+                      [&](const HostStage::Dev *d) {
+                          AMK_HIP(hipDeviceSynchronize());
+                          return launch(d);
+                      },
+                      hipDeviceSynchronize);
+}
+// The *_host variants of the map's radius searches: the same staging (slots MQ_QUERIES, MQ_PTS ... MQ_COUNTS) under the radius
+// search's argument rules
+template <class Launch>
+int map_radius_host(HostStage &stage, int S, const double *h_queries, int query_stride, int n_queries, double radius_sq, int max_results,
+                    float *h_pts, double *h_sqdist, int *h_frame, int *h_counts, Launch &&launch) {
+    if (S < 1) return AMK_ERR_INVALID_ARG;
+    if (const int st = radius_args_status(h_queries, query_stride, n_queries, radius_sq, max_results, h_pts || h_sqdist || h_frame,
+                                          h_pts || h_sqdist || h_frame || h_counts);
+        st != AMK_OK)
+        return st;
+    const size_t rows = (size_t)S * n_queries, nq = (rows - 1) * query_stride + 3, k = (size_t)max_results;
+    return stage.call({to_device(h_queries, sizeof(double) * nq), scratch(0), if_given(to_host(h_pts, sizeof(float) * rows * k * 3)),
+                       if_given(to_host(h_sqdist, sizeof(double) * rows * k)), if_given(to_host(h_frame, sizeof(int) * rows * k)),
+                       if_given(to_host(h_counts, sizeof(int) * rows))},
                       [&](const HostStage::Dev *d) {
                           AMK_HIP(hipDeviceSynchronize());
                           return launch(d);

@@ -712,6 +712,151 @@ __device__ __forceinline__ void grid_knn(const GridScene &gs, double qx, double 
 #endif
 }
 
+// nanoflann's radiusSearch (AM/include/nanoflann_two.hpp:345-413,1611-1639) on the bucketed index, one wavefront per query:
+// returns (in every lane) the number of usable points with squared distance < r2 -- strict, as RadiusResultSet::addPoint tests
+// it; never capped, never clipped by the list -- and, when k > 0, leaves the k nearest of them in lane i < k as grid_knn
+// does: (ld, li, lpos), ties by index, empty slots (DBL_MAX, kNoIndex, 0).  r2 in [0, DBL_MAX]: d < r2 then implies the
+// usable-point rule d < DBL_MAX (false for NaN, inf and overflow), and r2 = DBL_MAX means every usable point.
+//
+// A FIXED-radius question, like grid_outlier_thread's: a point within sqrt(r2) of q lies in a cell that the cube [q - rho, q + rho]^3
+// touches (cell_of is monotone per axis, clamping included: a query outside the bounding box works), so exactly those cells are
+// visited, no rings and no stop rule.  The (row, tile) items of the cube go one per lane, 64 at a time; a row (iy, iz) is clipped
+// to the ball's x extent through its slab distances as grid_knn clips to tau, here against the fixed r2, and a row farther than
+// the ball is skipped.  The runs of an item batch are flattened into 64-candidate windows by grid_knn's announce / running-max
+// scheme.  A query with a NaN or infinite coordinate walks nothing; neither does a scene that was never built (zeroed geometry).
+__device__ __forceinline__ int grid_radius(const GridScene &gs, double qx, double qy, double qz, double r2, int k, double &ld,
+                                           int &li, int &lpos, GridWaveLds *ws) {
+    const int lane = threadIdx.x & 63;
+    const double b[3] = {gs.gp[0], gs.gp[1], gs.gp[2]};
+    const double h = gs.gp[3], inv_h = gs.gp[4];
+    const int g[3] = {(int)gs.gp[5], (int)gs.gp[6], (int)gs.gp[7]};
+    const double q[3] = {qx, qy, qz};
+    ld = DBL_MAX;
+    li = kNoIndex;
+    lpos = 0;
+    int count = 0;
+    const bool qbad = !(fabs(qx) <= DBL_MAX && fabs(qy) <= DBL_MAX && fabs(qz) <= DBL_MAX);
+    if (qbad || g[0] * g[1] * g[2] <= 0) return 0;   // (wave-uniform)
+    // rounding slack of the cell boundaries, as in grid_knn; the cube's half edge: sqrt(r2) widened by it (a point whose computed
+    // distance is < r2 may be sqrt(r2) + an ulp away along one axis)
+    const double slack = 1e-9 * h + 1e-12 * (fabs(qx) + fabs(qy) + fabs(qz) + fabs(b[0]) + fabs(b[1]) + fabs(b[2]));
+    const double rho = sqrt(r2) * (1.0 + 1e-12) + slack;
+    int c[3], lo[3], hi[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        c[a] = cell_of(q[a], b[a], inv_h, g[a]);
+        lo[a] = cell_of(q[a] - rho, b[a], inv_h, g[a]);
+        hi[a] = cell_of(q[a] + rho, b[a], inv_h, g[a]);
+    }
+    double tau = DBL_MAX;  // the k-th kept distance (k > 0)
+    int win = 0;           // number of the candidate window being fetched (tags ws->mark)
+    ws->mark[lane] = 0;
+    const int ny = hi[1] - lo[1] + 1, nz = hi[2] - lo[2] + 1;
+    const int nitems = ny * nz * gs.nt;
+    // item -> (row, tile) and row -> (iy, iz) through float reciprocals, exact while nitems < 4e6 (grid_knn)
+    const float inv_nt = 1.0f / (float)gs.nt, inv_ny = 1.0f / (float)ny;
+    for (int row0 = 0; row0 < nitems; row0 += 64) {
+        const int item = row0 + lane;
+        int sA = 0, lA = 0;
+        if (item < nitems) {
+            const int j = (int)(((float)item + 0.5f) * inv_nt);
+            const int *cst = gs.cs + (size_t)(item - j * gs.nt) * (kGridMaxCells + 2);
+            const int jz = (int)(((float)j + 0.5f) * inv_ny);
+            const int iy = lo[1] + (j - jz * ny), iz = lo[2] + jz;
+            const int dy = iy - c[1], dz = iz - c[2];
+            // the slab distances use the faces between the row and the query's cell only: never a boundary face, behind which
+            // the points the sampled box missed are clamped
+            const double ey = dy < 0 ? q[1] - (b[1] + (double)(iy + 1) * h) : (dy > 0 ? (b[1] + (double)iy * h) - q[1] : 0.0);
+            const double ez = dz < 0 ? q[2] - (b[2] + (double)(iz + 1) * h) : (dz > 0 ? (b[2] + (double)iz * h) - q[2] : 0.0);
+            const double fy = fmax(0.0, ey - slack), fz = fmax(0.0, ez - slack);
+            const double rem = r2 * (1.0 + 1e-12) - (fy * fy + fz * fz);
+            if (rem >= 0.0) {   // (else the whole row is out of reach; NaN = inf - inf: every distance to the row overflows)
+                const double rx = sqrt(rem) * (1.0 + 1e-12) + slack;
+                const int x0 = max(lo[0], cell_of(q[0] - rx, b[0], inv_h, g[0]));
+                const int x1 = min(hi[0], cell_of(q[0] + rx, b[0], inv_h, g[0]));
+                if (x0 <= x1) {
+                    const int rowbase = (iz * g[1] + iy) * g[0];
+                    sA = cst[rowbase + x0];
+                    lA = cst[rowbase + x1 + 1] - sA;
+                }
+            }
+        }
+        if (__ballot(lA > 0) == 0) continue;  // nothing but empty buckets in these rows
+        // flatten the <= 64 runs into one index space so that every lane gets a point (grid_knn's scheme, one run per item)
+        const int incl = wave_incl_scan_i32(lA);
+        const int total = __builtin_amdgcn_readlane(incl, 63);
+        const int mypre = incl - lA, mylen = lA;
+        ws->item[lane] = make_int4(mypre, lA, sA, 0);
+        auto fetch = [&](int w0, double &d, int &ic, int &ip) {
+            ++win;
+            const int rel = mypre - w0;
+            // every lane stores (the silent ones into the spare slot) and the wave is fenced before it reads: see grid_knn
+            ws->mark[(mylen > 0 && rel >= 0 && rel < 64) ? rel : 64] = (win << 6) | lane;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const unsigned long long before = __ballot(mylen > 0 && mypre <= w0);
+            const int carry = 63 - __clzll((long long)before);   // (w0 < total: some non-empty item holds w0)
+            const int mk = ws->mark[lane];
+            const int o = max(wave_incl_scan_max_i32((mk >> 6) == win ? (mk & 63) + 1 : 0) - 1, carry);
+            const int t = w0 + lane;
+            d = __builtin_nan("");
+            ic = kNoIndex;
+            ip = 0;
+            if (t < total) {
+                const int4 it = ws->item[o];
+                const int pos = it.z + (t - it.x);
+                const float4 p4 = gs.pt[pos];
+                d = sq_dist(qx, qy, qz, p4.x, p4.y, p4.z);
+                ic = __float_as_int(p4.w);
+                ip = pos;
+            }
+        };
+        double d, dn;
+        int ic, icn, ip, ipn;
+        fetch(0, d, ic, ip);
+        for (int t0 = 0; t0 < total; t0 += 64) {
+            if (t0 + 64 < total) fetch(t0 + 64, dn, icn, ipn);  // next window in flight while this one is counted and merged
+            const bool in = d < r2;   // strict; false for NaN (no candidate) -- and d < r2 <= DBL_MAX: usable
+            count += __popcll(__ballot(in));
+            if (k > 0) {
+                // the list: grid_knn's lane-held sorted insertion, offered only candidates inside the ball that beat (or tie) the k-th kept
+                bool live = in && d <= tau;
+                for (;;) {
+                    const unsigned long long m = __ballot(live);
+                    if (!m) break;
+                    int src = __ffsll((long long)m) - 1;
+                    if (m & (m - 1)) {   // several: (one of) the nearest by the high word of the distance (any order gives the same list)
+                        const int hk = live ? __double2hiint(d) : 0x7FFFFFFF;
+                        const int hmin = grid_wave_min_i32(hk);
+                        src = __ffsll((long long)__ballot(hk == hmin)) - 1;
+                    }
+                    const double dc = readlane_f64(d, src);
+                    const int icc = __builtin_amdgcn_readlane(ic, src);
+                    const int ipc = __builtin_amdgcn_readlane(ip, src);
+                    // rank of the candidate in (distance, index) order among the kept entries
+                    const bool lt = (lane < k) & ((ld < dc) | ((ld == dc) & (li < icc)));
+                    const int pos = __popcll(__ballot(lt));
+                    if (pos < k) {
+                        const double up_d = wave_shr1_f64(ld);
+                        const int up_i = wave_shr1_i32(li), up_p = wave_shr1_i32(lpos);
+                        const bool above = lane > pos, here = lane == pos;   // selects, not branches
+                        ld = here ? dc : (above ? up_d : ld);
+                        li = here ? icc : (above ? up_i : li);
+                        lpos = here ? ipc : (above ? up_p : lpos);
+                        tau = readlane_f64(ld, k - 1);
+                    }
+                    live = live && lane != src && d <= tau;
+                }
+            }
+            d = dn;
+            ic = icn;
+            ip = ipn;
+        }
+    }
+    return count;
+}
+
 // 1-NN squared distance of q, one THREAD per query (the n-queries-on-n-points keyframe sweep,
 // AM/src/FrameKDMap.cpp:466-476): same ring walk and stopping rule as grid_knn with k = 1, scalar per lane.
 // Returns DBL_MAX when the index holds no point with a finite distance to q.

@@ -52,6 +52,33 @@ __device__ __forceinline__ void frame_list(const GridScene &gs, const ExactPtrs 
     nd = (lane < k && li != kNoIndex) ? ld : DBL_MAX;
 }
 
+// Folds one frame's sorted list (frame_list's nd / rec, frame number f) into the running list held one entry per lane < k: the
+// frame's entries are offered best first, an entry ranks behind every kept one at the same or a smaller distance (kept entries came
+// from an earlier frame or are earlier neighbours of this one: the tie rule), and the fold ends at the first entry that ranks
+// behind the k-th kept one.
+__device__ __forceinline__ void fold_frame_list(double nd, const float4 &rec, int f, int k, int lane, double &rd, float &rx, float &ry,
+                                                float &rz, int &rf) {
+    for (int e = 0; e < k; ++e) {     // this frame's entries, best first
+        const double dc = readlane_f64(nd, e);
+        if (!(dc < DBL_MAX)) break;
+        // rank among the kept entries: behind every one at the same or a smaller distance
+        const int pos = __popcll(__ballot((lane < k) & (rd <= dc)));
+        if (pos >= k) break;          // (the entries behind it are no nearer)
+        const float cx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rec.x), e));
+        const float cy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rec.y), e));
+        const float cz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rec.z), e));
+        const double up_d = wave_shr1_f64(rd);
+        const float up_x = wave_shr1_f32(rx), up_y = wave_shr1_f32(ry), up_z = wave_shr1_f32(rz);
+        const int up_f = wave_shr1_i32(rf);
+        const bool above = lane > pos, here = lane == pos;   // selects, not branches
+        rd = here ? dc : (above ? up_d : rd);
+        rx = here ? cx : (above ? up_x : rx);
+        ry = here ? cy : (above ? up_y : ry);
+        rz = here ? cz : (above ? up_z : rz);
+        rf = here ? f : (above ? up_f : rf);
+    }
+}
+
 // DIST: GetNearestDistance -- the same walk with k = 1 and no fast path; out_dist = sqrt of the best squared distance
 template <bool MAP, bool DIST, bool EXACT>
 __device__ __forceinline__ void map_query_row(const QueryFrames &qf, const ExactPtrs &ex, int n_scenes, const double *__restrict__ queries,
@@ -110,25 +137,7 @@ __device__ __forceinline__ void map_query_row(const QueryFrames &qf, const Exact
             double nd;
             float4 rec;
             frame_list<EXACT>(gs, ex, m, qx, qy, qz, k, lane, &wl[w], nd, rec);
-            for (int e = 0; e < k; ++e) {     // this frame's entries, best first
-                const double dc = readlane_f64(nd, e);
-                if (!(dc < DBL_MAX)) break;
-                // rank among the kept entries: behind every one at the same or a smaller distance
-                const int pos = __popcll(__ballot((lane < k) & (rd <= dc)));
-                if (pos >= k) break;          // (the entries behind it are no nearer)
-                const float cx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rec.x), e));
-                const float cy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rec.y), e));
-                const float cz = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rec.z), e));
-                const double up_d = wave_shr1_f64(rd);
-                const float up_x = wave_shr1_f32(rx), up_y = wave_shr1_f32(ry), up_z = wave_shr1_f32(rz);
-                const int up_f = wave_shr1_i32(rf);
-                const bool above = lane > pos, here = lane == pos;   // selects, not branches
-                rd = here ? dc : (above ? up_d : rd);
-                rx = here ? cx : (above ? up_x : rx);
-                ry = here ? cy : (above ? up_y : ry);
-                rz = here ? cz : (above ? up_z : rz);
-                rf = here ? f : (above ? up_f : rf);
-            }
+            fold_frame_list(nd, rec, f, k, lane, rd, rx, ry, rz, rf);
         }
         cnt = __popcll(__ballot((lane < k) & (rd < DBL_MAX)));
     }
@@ -190,8 +199,9 @@ int launch_query(const QueryFrames &qf, int S, const double *d_queries, int quer
     return AMK_OK;
 }
 
-// a caller's list of frame handles -> the kernel's argument (status: the header's rules, before anything is launched)
-int frames_of_handles(amk_kd *const *frames, int n_frames, QueryFrames &qf, int &S) {
+// a caller's list of frame handles -> the kernel's argument (status: the header's rules, before anything is launched).
+// default_ties_only: the multi-frame kNN queries answer in the default tie order only; radius results have no tie-order modes
+int frames_of_handles(amk_kd *const *frames, int n_frames, QueryFrames &qf, int &S, bool default_ties_only = true) {
     if (!frames || n_frames < 1) return AMK_ERR_INVALID_ARG;
     if (n_frames > AMK_MAX_FRAMES) return AMK_ERR_UNSUPPORTED;
     for (int f = 0; f < n_frames; ++f)
@@ -200,7 +210,7 @@ int frames_of_handles(amk_kd *const *frames, int n_frames, QueryFrames &qf, int 
     S = frames[0]->n_scenes;
     qf.map = FrameMap{n_frames, nullptr, S};
     for (int f = 0; f < n_frames; ++f) {
-        if (frames[f]->mode != 0 || frames[f]->tie_order != AMK_TIES_LOWEST_INDEX) return AMK_ERR_UNSUPPORTED;
+        if (frames[f]->mode != 0 || (default_ties_only && frames[f]->tie_order != AMK_TIES_LOWEST_INDEX)) return AMK_ERR_UNSUPPORTED;
         qf.g[f] = grid_ptrs(frames[f]);
         qf.size[f] = frames[f]->size.p;
     }
@@ -213,6 +223,64 @@ QueryFrames frames_of_pool(amk_kd *pool, int n_frames, const int *d_fmap, int S)
     qf.g[0] = grid_ptrs(pool);
     qf.size[0] = pool->size.p;
     return qf;
+}
+
+// Radius search over the frames (amk_kfmap_radius_search / amk_kd_radius_search_frames): one wavefront per (scene, query) walks
+// every frame its scene holds -- no fast path, no PtIsInFrame, no size rule: those belong to QueryNearest -- with grid_radius; the
+// counts add up, each frame's list is folded into the running list as above (equal distances keep the earlier frame, then the
+// lower index within a frame).
+template <bool MAP>
+__global__ __launch_bounds__(256) void map_radius_kernel(QueryFrames qf, int n_scenes, const double *__restrict__ queries,
+                                                         int query_stride, int n_queries, double r2, int k,
+                                                         float *__restrict__ out_pts, double *__restrict__ out_d2,
+                                                         int *__restrict__ out_frame, int *__restrict__ out_cnt) {
+    __shared__ GridWaveLds wl[4];
+    const WaveSlot ws = wave_slot(n_queries);
+    const int s = ws.s, w = ws.w, lane = ws.lane, q = ws.unit;
+    if (s >= n_scenes || q >= n_queries) return;
+    const size_t row = (size_t)s * n_queries + q;
+    const double *qp = queries + row * query_stride;
+    const double qx = qp[0], qy = qp[1], qz = qp[2];
+    const int F = MAP ? qf.map.held(s, lane) : qf.map.n;
+    const GridPtrs pool = qf.g[0];   // (map mode: one set of pool pointers stays live over the loop)
+    double rd = DBL_MAX;             // the running list: lane i < k holds the i-th best (distance, point, frame) so far
+    float rx = 0.f, ry = 0.f, rz = 0.f;
+    int rf = -1, cnt = 0;
+    for (int f = 0; f < F; ++f) {
+        const int m = MAP ? qf.map.pool_scene(f, s) : s;
+        if (m < 0) continue;         // (map mode: this scene's map has no frame f)
+        const GridScene gs = (MAP ? pool : qf.g[f]).scene(m);
+        double ld;
+        int li, lpos;
+        cnt += grid_radius(gs, qx, qy, qz, r2, k, ld, li, lpos, &wl[w]);
+        if (k > 0) {
+            const float4 rec = gs.pt[lpos];   // (lpos = 0 for empty slots: a valid address)
+            fold_frame_list((lane < k && li != kNoIndex) ? ld : DBL_MAX, rec, f, k, lane, rd, rx, ry, rz, rf);
+        }
+    }
+    if (lane == 0 && out_cnt) out_cnt[row] = cnt;
+    if (lane < k) {
+        const bool ok = rd < DBL_MAX;
+        const size_t o = row * k + lane;
+        if (out_d2) out_d2[o] = ok ? rd : DBL_MAX;
+        if (out_frame) out_frame[o] = ok ? rf : -1;
+        if (out_pts) {
+            out_pts[o * 3 + 0] = ok ? rx : 0.f;
+            out_pts[o * 3 + 1] = ok ? ry : 0.f;
+            out_pts[o * 3 + 2] = ok ? rz : 0.f;
+        }
+    }
+}
+
+int launch_radius(const QueryFrames &qf, int S, const double *d_queries, int query_stride, int n_queries, double radius_sq, int max_results,
+                  float *d_pts, double *d_sqdist, int *d_frame, int *d_counts, hipStream_t stream) {
+    const long long blocks = search_blocks(S, n_queries);
+    if (blocks > 0x7fffffffll) return AMK_ERR_UNSUPPORTED;
+    auto kernel = qf.map.fmap ? map_radius_kernel<true> : map_radius_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, stream, qf, S, d_queries, query_stride, n_queries,
+                       radius_clamped(radius_sq), max_results, d_pts, d_sqdist, d_frame, d_counts);
+    AMK_HIP(hipGetLastError());
+    return AMK_OK;
 }
 
 }  // namespace
@@ -239,6 +307,16 @@ int map_nearest_distance(amk_kd *pool, int n_frames, const int *d_fmap, int S, c
     if (!pool || !d_fmap || n_frames < 1 || S < 1 || !query_args_ok(d_queries, query_stride, n_queries) || !d_dist) return AMK_ERR_INVALID_ARG;
     return launch_query<true>(frames_of_pool(pool, n_frames, d_fmap, S), S, d_queries, query_stride, n_queries, 1, nullptr, nullptr,
                               nullptr, nullptr, nullptr, nullptr, d_dist, stream);
+}
+int map_radius_search(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_queries, int query_stride, int n_queries,
+                      double radius_sq, int max_results, float *d_pts, double *d_sqdist, int *d_frame, int *d_counts, hipStream_t stream) {
+    if (!pool || !d_fmap || n_frames < 1 || S < 1) return AMK_ERR_INVALID_ARG;
+    if (const int st = radius_args_status(d_queries, query_stride, n_queries, radius_sq, max_results, d_pts || d_sqdist || d_frame,
+                                          d_pts || d_sqdist || d_frame || d_counts);
+        st != AMK_OK)
+        return st;
+    return launch_radius(frames_of_pool(pool, n_frames, d_fmap, S), S, d_queries, query_stride, n_queries, radius_sq, max_results, d_pts,
+                         d_sqdist, d_frame, d_counts, stream);
 }
 }  // namespace amk
 
@@ -280,6 +358,34 @@ int amk_kd_query_frames_host(amk_kd *const *frames, int n_frames, const double *
                                    return amk_kd_query_frames(frames, n_frames, d[amk::MQ_TWC], cam, d[amk::MQ_QUERIES], query_stride, n_queries, k,
                                                               d[amk::MQ_PTS], d[amk::MQ_SQDIST], d[amk::MQ_FRAME], d[amk::MQ_COUNTS], nullptr);
                                });
+}
+
+int amk_kd_radius_search_frames(amk_kd *const *frames, int n_frames, const double *d_queries, int query_stride, int n_queries,
+                                double radius_sq, int max_results, float *d_pts, double *d_sqdist, int *d_frame, int *d_counts,
+                                void *stream) {
+    if (const int st = radius_args_status(d_queries, query_stride, n_queries, radius_sq, max_results, d_pts || d_sqdist || d_frame,
+                                          d_pts || d_sqdist || d_frame || d_counts);
+        st != AMK_OK)
+        return st;
+    QueryFrames qf;
+    int S = 0;
+    if (const int st = frames_of_handles(frames, n_frames, qf, S, false); st != AMK_OK) return st;
+    return launch_radius(qf, S, d_queries, query_stride, n_queries, radius_sq, max_results, d_pts, d_sqdist, d_frame, d_counts,
+                         (hipStream_t)stream);
+}
+
+int amk_kd_radius_search_frames_host(amk_kd *const *frames, int n_frames, const double *h_queries, int query_stride, int n_queries,
+                                     double radius_sq, int max_results, float *h_pts, double *h_sqdist, int *h_frame, int *h_counts) {
+    QueryFrames qf;
+    int S = 0;
+    if (const int st = frames_of_handles(frames, n_frames, qf, S, false); st != AMK_OK) return st;
+    amk::HostStage stage;   // frees at return: these frames belong to no one handle
+    return amk::map_radius_host(stage, S, h_queries, query_stride, n_queries, radius_sq, max_results, h_pts, h_sqdist, h_frame, h_counts,
+                                [&](const amk::HostStage::Dev *d) {
+                                    return amk_kd_radius_search_frames(frames, n_frames, d[amk::MQ_QUERIES], query_stride, n_queries, radius_sq,
+                                                                       max_results, d[amk::MQ_PTS], d[amk::MQ_SQDIST], d[amk::MQ_FRAME],
+                                                                       d[amk::MQ_COUNTS], nullptr);
+                                });
 }
 
 }  // extern "C"

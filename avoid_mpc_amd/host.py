@@ -86,6 +86,24 @@ class KdBatch:
                                           capi.dptr(out["counts"]), capi.stream_ptr(stream)), "amk_kd_search")
         return out
 
+    def radius_search(self, queries, radius_sq, max_results, want_pts=True, stream=None, out=None):
+        """amk_kd_radius_search: nanoflann's radiusSearch for queries float64 [S, Q, >= 3] (the first three of every row are read).
+        radius_sq: a SQUARED distance, the test is strict (d2 < radius_sq); counts [S, Q] is the full number of usable points within
+        the radius whatever max_results; the lists hold the nearest max_results of them, ascending, ties by cloud index, empty slots
+        -1 / DBL_MAX / 0.  max_results = 0: the pure count (no lists).  -> dict(indices, sqdist, pts, counts)"""
+        Q, stride = _check_queries(queries, self.S)
+        k, dev = int(max_results), queries.device
+        if out is None:
+            lists = k > 0
+            out = dict(indices=torch.empty((self.S, Q, k), dtype=torch.int32, device=dev) if lists else None,
+                       sqdist=torch.empty((self.S, Q, k), dtype=torch.float64, device=dev) if lists else None,
+                       pts=torch.empty((self.S, Q, k, 3), dtype=torch.float32, device=dev) if lists and want_pts else None,
+                       counts=torch.empty((self.S, Q), dtype=torch.int32, device=dev))
+        capi.check(self.lib.amk_kd_radius_search(self.h, capi.dptr(queries), stride, Q, float(radius_sq), k, capi.dptr(out["indices"]),
+                                                 capi.dptr(out["sqdist"]), capi.dptr(out["pts"]), capi.dptr(out["counts"]),
+                                                 _stream_arg(stream)), "amk_kd_radius_search")
+        return out
+
     def keyframe_sweep(self, current, th_dist, th_count, stream=None):
         """KeyframeThreadWorker's sweep: self = last keyframe, rebuilt from its outliers w.r.t. `current`.
         -> (outliers int32 [S], rebuilt int32 [S]) device tensors"""
@@ -116,6 +134,20 @@ class KdBatch:
         vp = lambda a: a.ctypes.data_as(C.c_void_p)
         capi.check(self.lib.amk_kd_search_host(self.h, vp(q), Q, int(k), vp(idx), vp(d2), vp(pts), vp(cnt)),
                    "amk_kd_search_host")
+        return dict(indices=idx, sqdist=d2, pts=pts, counts=cnt)
+
+
+    def radius_search_host(self, queries, radius_sq, max_results):
+        """amk_kd_radius_search_host: radius_search with numpy buffers (queries [S, Q, >= 3]); synchronises."""
+        q = np.ascontiguousarray(queries, np.float64)
+        assert q.ndim == 3 and q.shape[0] == self.S and q.shape[2] >= 3
+        Q, k = q.shape[1], int(max_results)
+        idx = np.zeros((self.S, Q, k), np.int32); d2 = np.zeros((self.S, Q, k), np.float64)
+        pts = np.zeros((self.S, Q, k, 3), np.float32); cnt = np.zeros((self.S, Q), np.int32)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        lst = (lambda a: vp(a)) if k > 0 else (lambda a: None)   # max_results = 0 is the pure count: no list pointers
+        capi.check(self.lib.amk_kd_radius_search_host(self.h, vp(q), int(q.shape[2]), Q, float(radius_sq), k, lst(idx), lst(d2), lst(pts),
+                                                      vp(cnt)), "amk_kd_radius_search_host")
         return dict(indices=idx, sqdist=d2, pts=pts, counts=cnt)
 
 
@@ -303,6 +335,26 @@ def nearest_distance_frames(handles, queries, stream=None, out=None):
     return out
 
 
+def _radius_out(S, Q, k, dev):
+    """outputs of the multi-frame radius searches; max_results = 0 is the pure count: no lists"""
+    out = _query_out(S, Q, k, dev)
+    return out if k > 0 else dict(pts=None, sqdist=None, frame=None, counts=out["counts"])
+
+
+def radius_search_frames(handles, queries, radius_sq, max_results, stream=None, out=None):
+    """amk_kd_radius_search_frames: the radius search over a list of KdBatch handles (obstacle OR edge, index 0 = current frame);
+    counts sum over the frames, the lists merge by (squared distance, frame, cloud index).  -> dict(pts, sqdist, frame, counts)"""
+    F, S = len(handles), handles[0].S
+    Q, stride = _check_queries(queries, S)
+    if out is None:
+        out = _radius_out(S, Q, int(max_results), queries.device)
+    ha = (C.c_void_p * F)(*[h.h for h in handles])
+    capi.check(capi.load().amk_kd_radius_search_frames(ha, F, capi.dptr(queries), stride, Q, float(radius_sq), int(max_results),
+                                                       capi.dptr(out["pts"]), capi.dptr(out["sqdist"]), capi.dptr(out["frame"]),
+                                                       capi.dptr(out["counts"]), _stream_arg(stream)), "amk_kd_radius_search_frames")
+    return out
+
+
 class KfMap:
     """amk_kfmap: FrameKDMap's keyframe list for S scenes on the device (FrameKDMap.cpp:29-74,233-252,428-488)."""
 
@@ -365,6 +417,19 @@ class KfMap:
         capi.check(self.lib.amk_kfmap_query_nearest(self.h, C.byref(cam) if cam is not None else None, capi.dptr(queries), stride, Q, int(k),
                                                     int(bool(edge)), capi.dptr(out["pts"]), capi.dptr(out["sqdist"]), capi.dptr(out["frame"]),
                                                     capi.dptr(out["counts"]), _stream_arg(stream)), "amk_kfmap_query_nearest")
+        return out
+
+    def radius_search(self, queries, radius_sq, max_results, edge=False, stream=None, out=None):
+        """amk_kfmap_radius_search: nanoflann's radiusSearch for queries float64 [S, Q, >= 3] over every frame each scene's query
+        vector holds (no fast path, no frustum test, no size rule).  radius_sq is a squared distance, the test is strict; counts is
+        the full number over the frames; the lists hold the nearest max_results, ordered by (squared distance, frame, cloud index).
+        -> dict(pts [S,Q,k,3] f32, sqdist [S,Q,k] f64, frame [S,Q,k] i32, counts [S,Q] i32); max_results = 0: counts only"""
+        Q, stride = _check_queries(queries, self.S)
+        if out is None:
+            out = _radius_out(self.S, Q, int(max_results), queries.device)
+        capi.check(self.lib.amk_kfmap_radius_search(self.h, capi.dptr(queries), stride, Q, float(radius_sq), int(max_results), int(bool(edge)),
+                                                    capi.dptr(out["pts"]), capi.dptr(out["sqdist"]), capi.dptr(out["frame"]),
+                                                    capi.dptr(out["counts"]), _stream_arg(stream)), "amk_kfmap_radius_search")
         return out
 
     def nearest_distance(self, queries, stream=None, out=None):

@@ -205,6 +205,41 @@ int amk_kd_build_host(amk_kd *kd, const float *h_xyz, int point_stride, long lon
 int amk_kd_search_host(amk_kd *kd, const double *h_queries, int n_queries, int k, int *h_indices,
                        double *h_sqdist, float *h_pts, int *h_counts);
 
+/* Radius search: nanoflann's radiusSearch (nanoflann_two.hpp:1611-1639, RadiusResultSet :345-413) on every scene's index --
+ * which points lie within a radius of a position, and how many.  The reference never calls it (KDTreeTwo wraps findNeighbors
+ * only): this is the surface of the index it was modelled on, not Avoid-MPC's.  Queries are read at
+ * d_queries[(s*n_queries + q)*query_stride + {0,1,2}] (query_stride 3 = packed, 10 = the rows of mRefPath, 14 = the rows of
+ * x0array); n_queries >= 1 with no AMK_MAX_QUERIES cap; query_stride >= 3.
+ *   radius_sq   a SQUARED distance, as nanoflann's L2 radius is.  It must be >= 0 and not NaN (else AMK_ERR_INVALID_ARG); +inf
+ *               and anything >= DBL_MAX mean every usable point.  The test is strict: a result has squared distance < radius_sq,
+ *               a point at exactly radius_sq is not a result (RadiusResultSet::addPoint) -- radius_sq = 0 finds nothing, not
+ *               even a point the query coincides with.
+ *   d_counts    [S][n_queries] int: the number of usable points within the radius, radiusSearch's return value.  The count is never
+ *               capped: it is always the full number, whatever max_results.  A point is usable under the rule of amk_kd_search
+ *               (squared distance < DBL_MAX: false for NaN, inf and overflow); a query with a NaN or infinite coordinate gets
+ *               count 0 and every slot empty; an empty scene answers 0.
+ *   lists       d_indices [S][n_queries][max_results] int, d_sqdist [..][max_results] double, d_pts [..][max_results][3] float:
+ *               the min(count, max_results) NEAREST results, ascending by squared distance (the distances of amk_kd_search,
+ *               bit for bit), equal distances by cloud index.  nanoflann sorts radius results with std::sort on the distance
+ *               alone, so its order among equals is unspecified and the tie-order modes do not apply: a handle in
+ *               AMK_TIES_NANOFLANN / AMK_TIES_AUTO answers identically to the default, and the exact tree is not consulted.
+ *               Slots beyond the results hold -1 / DBL_MAX / (0,0,0).  Each list output may be NULL, and so may d_counts,
+ *               but not all four.
+ *   max_results 0 <= max_results <= AMK_MAX_K.  max_results == 0 requires every list pointer NULL (else AMK_ERR_INVALID_ARG): it
+ *               is the pure count.  > AMK_MAX_K: AMK_ERR_UNSUPPORTED; < 0: AMK_ERR_INVALID_ARG.
+ * The size rule does not apply: KDTreeTwo's count rule (kd_tree_two.h:119-124) belongs to SearchForNearest, and this is the
+ * index's own query -- a cloud of one point, or of exactly max_results points, answers normally.
+ * Every error is returned before anything is launched, the outputs untouched.  A handle in scan mode (internal, tests) returns
+ * AMK_ERR_UNSUPPORTED.  The call is stream-ordered like amk_kd_search and allocates nothing.
+ * Not offered (AMK_ERR_* or simply absent): per-query radii, uncapped result lists (a CSR output), radius queries inside
+ * amk_step_batch, AMK_TIES_* semantics for radius results, scan-mode handles.                                              */
+int amk_kd_radius_search(amk_kd *kd, const double *d_queries, int query_stride, int n_queries, double radius_sq,
+                         int max_results, int *d_indices, double *d_sqdist, float *d_pts, int *d_counts, void *stream);
+/* Same with host buffers: stages through the handle's own block (as amk_kd_search_host) and synchronises.  h_queries holds at
+ * least (S * n_queries - 1) * query_stride + 3 doubles.                                                                    */
+int amk_kd_radius_search_host(amk_kd *kd, const double *h_queries, int query_stride, int n_queries, double radius_sq,
+                              int max_results, int *h_indices, double *h_sqdist, float *h_pts, int *h_counts);
+
 /* ------------------------------------------------------------------------------------------ */
 /* MPC: batch of ObstacleAvoidanceMPC                          HighLvlMpc.h:4-33, .cpp:5-137    */
 /* ------------------------------------------------------------------------------------------ */
@@ -701,6 +736,31 @@ int amk_kd_nearest_distance_frames(amk_kd *const *frames, int n_frames, const do
 int amk_kd_query_frames_host(amk_kd *const *frames, int n_frames, const double *h_Twc, const struct amk_frame_camera *cam,
                              const double *h_queries, int query_stride, int n_queries, int k, float *h_pts, double *h_sqdist,
                              int *h_frame, int *h_counts);
+/* Radius search over the frames: amk_kd_radius_search (see there: radius_sq, the strict test, the uncapped count, max_results,
+ * the errors) over every frame a scene holds -- a keyframe map's query vector, or a caller's list of frame handles.  This is
+ * nanoflann's query, not FrameKDMap::QueryNearest: there is no fast path and no PtIsInFrame, and no size rule -- every frame the
+ * scene holds contributes, whatever its size.
+ *   d_counts [S][n_queries]               the SUM over the frames of the usable points within the radius (never capped)
+ *   d_pts / d_sqdist / d_frame [S][n_queries][max_results]   the min(count, max_results) nearest of all frames, ascending by
+ *               squared distance; equal distances keep the earlier frame, then the lower cloud index within a frame; d_frame is
+ *               the position in the query vector (0 = current frame).  Slots beyond the results hold (0,0,0) / DBL_MAX / -1.
+ *               Each output may be NULL, not all; max_results == 0 (the pure count) requires the three lists NULL.
+ *   query_edge  != 0: the frames' edge clouds, else their obstacle clouds
+ * A scene with no frame yet answers 0.  The map's tie order (amk_kfmap_set_tie_order) does not apply, nor does that of the
+ * handles of a list; scan-mode handles and n_frames > AMK_MAX_FRAMES return AMK_ERR_UNSUPPORTED before anything is launched.
+ * Stream-ordered, nothing allocated, no map state changed; ordering against amk_kfmap_add_vertex / _update / _reset and index
+ * builds as stated for the map's own queries above.  The *_host variants stage through device memory and synchronise the device. */
+int amk_kfmap_radius_search(amk_kfmap *map, const double *d_queries, int query_stride, int n_queries, double radius_sq,
+                            int max_results, int query_edge, float *d_pts, double *d_sqdist, int *d_frame, int *d_counts,
+                            void *stream);
+int amk_kfmap_radius_search_host(amk_kfmap *map, const double *h_queries, int query_stride, int n_queries, double radius_sq,
+                                 int max_results, int query_edge, float *h_pts, double *h_sqdist, int *h_frame, int *h_counts);
+int amk_kd_radius_search_frames(amk_kd *const *frames, int n_frames, const double *d_queries, int query_stride, int n_queries,
+                                double radius_sq, int max_results, float *d_pts, double *d_sqdist, int *d_frame, int *d_counts,
+                                void *stream);
+int amk_kd_radius_search_frames_host(amk_kd *const *frames, int n_frames, const double *h_queries, int query_stride, int n_queries,
+                                     double radius_sq, int max_results, float *h_pts, double *h_sqdist, int *h_frame,
+                                     int *h_counts);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Scenes sharded over the GPUs of a node (one process per GPU), RCCL over xGMI                 */

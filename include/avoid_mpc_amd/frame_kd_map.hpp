@@ -208,6 +208,34 @@ public:
         }
     }
 
+    // Not in the reference (it never calls nanoflann's radiusSearch): every point of the map within a radius of `point`, over the
+    // frames of the query vector -- no fast path, no PtIsInFrame, every frame contributes whatever its size.  radius_sq is a
+    // SQUARED distance, the test is strict.  Returns their number (the full number, whatever max_results) and fills the nearest
+    // min(count, max_results), ascending; equal distances keep the earlier frame, then the lower index within a frame.
+    size_t QueryRadius(const Vector3d &point, double radius_sq, int max_results, std::vector<Vector3d> &nearestPoints,
+                       std::vector<double> &distances, bool queryEdge = false) {
+        struct PtDists { Vector3d pt; double dist; };
+        std::vector<PtDists> pointsDist;
+        size_t count = 0;
+        std::lock_guard<std::mutex> lock(mMtxKdTree);
+        for (auto &fr : mVecQueryVector) {
+            PtCloudKdPtr pc = queryEdge ? fr.edgeCloud : fr.pointCloud;
+            if (!pc) continue;
+            count += pc->RadiusSearch(vx(point), vy(point), vz(point), radius_sq, max_results);
+            for (size_t j = 0; j < pc->squared_distances.size(); ++j)
+                pointsDist.push_back({Vector3d(pc->closest_pts[j].x, pc->closest_pts[j].y, pc->closest_pts[j].z),
+                                      pc->squared_distances[j]});
+        }
+        nearestPoints.clear();
+        distances.clear();
+        std::stable_sort(pointsDist.begin(), pointsDist.end(), [](const PtDists &a, const PtDists &b) { return a.dist < b.dist; });
+        for (int i = 0; i < max_results && i < (int)pointsDist.size(); ++i) {
+            nearestPoints.push_back(pointsDist[i].pt);
+            distances.push_back(pointsDist[i].dist);
+        }
+        return count;
+    }
+
     // One pass of KeyframeThreadWorker's body (:443-486) -- the caller owns the 30 ms cadence and the
     // "new frame arrived" flag.  dronePos / bodyX: translation of Twb = Twc * Tbc^-1 and the world
     // direction of the body x axis (first column of Rwb), what DroneBehindPts (:233-252) derives.

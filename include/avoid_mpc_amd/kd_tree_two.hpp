@@ -133,6 +133,31 @@ public:
                 out_sqdist[i].push_back((num_t)d2[(size_t)i * n + j]);
             }
     }
+    // Not in the reference (KDTreeTwo wraps findNeighbors only): nanoflann's radiusSearch (nanoflann_two.hpp:1611-1639) on this tree.
+    // radius_sq is a SQUARED distance and the test is strict (d2 < radius_sq).  Returns the number of points within the radius --
+    // the full number, whatever max_results -- and fills closest_pts / squared_distances / indices with the nearest
+    // min(count, max_results) of them, ascending, equal distances by index.  max_results = 0: the pure count.  The size rule of
+    // SearchForNearest does not apply: a cloud of one point, or of exactly max_results points, answers normally.
+    size_t RadiusSearch(num_t x, num_t y, num_t z, double radius_sq, int max_results) {
+        closest_pts.clear();
+        squared_distances.clear();
+        indices.clear();
+        if (cloud.pts.size() == 0) return 0;
+        if (max_results < 0 || max_results > AMK_MAX_K) throw std::runtime_error("KDTreeTwo::RadiusSearch: max_results outside [0, AMK_MAX_K]");
+        const double q[3] = {(double)x, (double)y, (double)z};
+        const int n = max_results;
+        std::vector<int> idx(n);
+        std::vector<double> d2(n);
+        int count = 0;
+        amk_throw(amk_kd_radius_search_host(kd_, q, 3, 1, radius_sq, n, n ? idx.data() : nullptr, n ? d2.data() : nullptr, nullptr, &count),
+                  "amk_kd_radius_search_host");
+        for (int i = 0; i < n && i < count; i++) {
+            closest_pts.push_back(cloud.pts[idx[i]]);
+            squared_distances.push_back((num_t)d2[i]);
+            indices.push_back(idx[i]);
+        }
+        return (size_t)count;
+    }
     PointCloudTwo<num_t> const &GetPointCloud() { return cloud; }
     std::vector<int> const &GetColors() { return colors; }
     amk_kd *handle() { return kd_; }  // for batched / fused use through the C ABI
