@@ -218,6 +218,37 @@ int map_radius_host(HostStage &stage, int S, const double *h_queries, int query_
                       },
                       hipDeviceSynchronize);
 }
+// kd_segment.hip / map_query.hip: the argument rules every segment search shares (include/avoid_mpc_amd.h, "Segment search"),
+// checked before anything is staged or launched: a path is n_points >= 2 positions, the rest as for the radius searches
+inline int segment_args_status(const double *path, int point_stride, int n_points, double radius_sq, int max_results, bool any_list,
+                               bool any_out) {
+    if (n_points < 2) return AMK_ERR_INVALID_ARG;
+    return radius_args_status(path, point_stride, n_points, radius_sq, max_results, any_list, any_out);
+}
+// map_query.hip, for kfmap.hip: the segment search over a pool
+int map_segment_search(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_path, int point_stride, int n_points,
+                       double radius_sq, int max_results, float *d_pts, double *d_sqdist, double *d_t, int *d_frame, int *d_counts,
+                       hipStream_t stream);
+// The *_host variants of the map's segment searches: map_radius_host's staging with the path in MQ_QUERIES and t in MQ_DIST; the
+// outputs have a row per LEG
+template <class Launch>
+int map_segment_host(HostStage &stage, int S, const double *h_path, int point_stride, int n_points, double radius_sq, int max_results,
+                     float *h_pts, double *h_sqdist, double *h_t, int *h_frame, int *h_counts, Launch &&launch) {
+    if (S < 1) return AMK_ERR_INVALID_ARG;
+    if (const int st = segment_args_status(h_path, point_stride, n_points, radius_sq, max_results, h_pts || h_sqdist || h_t || h_frame,
+                                           h_pts || h_sqdist || h_t || h_frame || h_counts);
+        st != AMK_OK)
+        return st;
+    const size_t np = ((size_t)S * n_points - 1) * point_stride + 3, rows = (size_t)S * (n_points - 1), k = (size_t)max_results;
+    return stage.call({to_device(h_path, sizeof(double) * np), scratch(0), if_given(to_host(h_pts, sizeof(float) * rows * k * 3)),
+                       if_given(to_host(h_sqdist, sizeof(double) * rows * k)), if_given(to_host(h_frame, sizeof(int) * rows * k)),
+                       if_given(to_host(h_counts, sizeof(int) * rows)), if_given(to_host(h_t, sizeof(double) * rows * k))},
+                      [&](const HostStage::Dev *d) {
+                          AMK_HIP(hipDeviceSynchronize());
+                          return launch(d);
+                      },
+                      hipDeviceSynchronize);
+}
 // kfmap.hip, for pipeline.hip: AddVertex for the frames of a gang (see there)
 int kfmap_add_vertex_gang(amk_kfmap *m, int n_frames, int frame_scenes, const float *const *d_xyz, const int *const *d_counts,
                           const float *const *d_edge_xyz, const int *const *d_edge_counts, int point_stride, const double *const *d_Twc,

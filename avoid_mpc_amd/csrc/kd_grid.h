@@ -857,6 +857,215 @@ __device__ __forceinline__ int grid_radius(const GridScene &gs, double qx, doubl
     return count;
 }
 
+// One leg a -> b of a path (include/avoid_mpc_amd.h, "Segment search"): the per-leg values, wave-uniform.  fp64 with contraction
+// off, sums left to right as sq_dist forms them.  ONE reciprocal per leg instead of a division per candidate: the leg is the
+// wavefront's, so this is scalar-unit work done once, and the candidates pay a product.  ok: every coordinate of both endpoints
+// and L2 are finite (a leg that is not gets count 0); a == b gives ab = 0 and an infinite inv that no candidate ever uses.
+struct SegLeg { double a[3], b[3], ab[3], inv; bool ok; };
+__device__ __forceinline__ SegLeg seg_leg(const double *pa, const double *pb) {
+#pragma clang fp contract(off)
+    SegLeg g;
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        g.a[i] = pa[i];
+        g.b[i] = pb[i];
+        g.ab[i] = g.b[i] - g.a[i];
+        ok = ok && fabs(g.a[i]) <= DBL_MAX && fabs(g.b[i]) <= DBL_MAX;   // false for NaN and inf
+    }
+    const double L2 = (g.ab[0] * g.ab[0] + g.ab[1] * g.ab[1]) + g.ab[2] * g.ab[2];
+    g.inv = 1.0 / L2;
+    g.ok = ok && L2 <= DBL_MAX;
+    return g;
+}
+// Squared distance of the stored point p to the leg and, in t, where along the leg the closest approach c lies: t clamped to
+// [0, 1] by comparisons (a NaN dot gives 0), c = a + t * ab per component (one product, one sum) below 1 and b itself at 1.
+// A degenerate leg has dot == 0 (or NaN), so t = 0, c = a and the result is sq_dist(a, p) bit for bit.
+__device__ __forceinline__ double seg_dist(const SegLeg &g, float px, float py, float pz, double &t) {
+#pragma clang fp contract(off)
+    const double p0 = (double)px, p1 = (double)py, p2 = (double)pz;
+    const double ap0 = p0 - g.a[0], ap1 = p1 - g.a[1], ap2 = p2 - g.a[2];
+    const double dot = (ap0 * g.ab[0] + ap1 * g.ab[1]) + ap2 * g.ab[2];
+    double tt = dot > 0.0 ? dot * g.inv : 0.0;
+    tt = tt < 1.0 ? tt : 1.0;
+    const bool inside = tt < 1.0;
+    const double c0 = inside ? g.a[0] + tt * g.ab[0] : g.b[0];
+    const double c1 = inside ? g.a[1] + tt * g.ab[1] : g.b[1];
+    const double c2 = inside ? g.a[2] + tt * g.ab[2] : g.b[2];
+    const double e0 = c0 - p0, e1 = c1 - p1, e2 = c2 - p2;
+    t = tt;
+    return (e0 * e0 + e1 * e1) + e2 * e2;
+}
+
+// Segment search on the bucketed index, one wavefront per leg: returns (in every lane) the number of usable points whose
+// seg_dist to the leg is < r2 -- strict, never capped, never clipped by the list -- and, when k > 0, leaves the k nearest of
+// them in lane i < k as grid_radius does, with the position t of the closest approach as a further payload: (ld, li, lpos, lt),
+// ties by index, empty slots (DBL_MAX, kNoIndex, 0, 0.0).  r2 in [0, DBL_MAX].
+//
+// A fixed-radius walk like grid_radius, around a segment instead of a point: no rings, no stop rule.  With [qlo, qhi] the leg's
+// bounding box, the cells visited are those the box [qlo - rho, qhi + rho] touches (cell_of is monotone per axis, clamping
+// included: a leg partly or wholly outside the bounding box of the cloud works); their (row, tile) items go one per lane, 64 at
+// a time.  A row (iy, iz) is skipped, and its run of cells clipped in x, through its slab distances to the leg's y and z
+// INTERVALS -- the faces between the row and the cells the leg spans only, never a boundary face, behind which the points the
+// sampled box missed are clamped -- against the fixed r2.  This clips against the leg's bounding box, not against the leg: a thin
+// capsule lying diagonally in a wide box evaluates every record of that box.
+//
+// The slack, derived for this walk (u = 2^-53):
+//  * the closest approach.  ab_i = fl(b_i - a_i), then c_i = fl(a_i + fl(t * ab_i)) with 0 <= t < 1, or b_i itself: three
+//    roundings, each relative to a quantity of at most |a_i| + |b_i|, so c_i lies within delta_i = 4u (|a_i| + |b_i|) of the
+//    interval [qlo_i, qhi_i] -- whatever t is, so the rounding of dot, inv and t does not enter.
+//  * the distance.  e_i = fl(c_i - p_i) and d2 = fl-sum of the three squares, all terms non-negative: d2 >= (1 - 4u) sum e_i^2,
+//    so d2 < r2 gives |c_i - p_i| < sqrt(r2) (1 + 4u) per axis, and e_x^2 < r2 (1 + 4u) - (e_y^2 + e_z^2).  A point that counts
+//    therefore has p_i within sqrt(r2) (1 + 4u) + delta_i of [qlo_i, qhi_i] on every axis.
+//  * the cell faces, as in grid_knn: a record of cell i has floor((p - bbmin) * inv_h) = i after clamping, the face is formed as
+//    bbmin + i * h; with at most 1024 cells per axis both sides are off by less than 4e-13 h + 4u |bbmin|, and the differences
+//    qlo - face, face - qhi add u (|a| + |b| + |bbmin| + 1024 h).
+//  slack = 1e-9 h + 1e-12 (sum |a_i| + sum |b_i| + sum |bbmin_i|) exceeds the sum of these by more than a factor of 1000 (1e-12
+//  against 4u = 4.5e-16), and the factors (1 + 1e-12) on r2 and on the square roots cover the (1 + 4u) and sqrt's own rounding.
+//  The slab distances are moreover shrunk by (1 - 1e-12) before they are squared, so that a square which overflows belongs to
+//  a row whose every distance overflows; a row is skipped only when the squares exceed r2 (1 + 1e-12), and inf - inf leaves the
+//  row unclipped.
+__device__ __forceinline__ int grid_segment(const GridScene &gs, const SegLeg &leg, double r2, int k, double &ld, int &li, int &lpos,
+                                            double &lt, GridWaveLds *ws) {
+    const int lane = threadIdx.x & 63;
+    const double b[3] = {gs.gp[0], gs.gp[1], gs.gp[2]};
+    const double h = gs.gp[3], inv_h = gs.gp[4];
+    const int g[3] = {(int)gs.gp[5], (int)gs.gp[6], (int)gs.gp[7]};
+    ld = DBL_MAX;
+    li = kNoIndex;
+    lpos = 0;
+    lt = 0.0;
+    int count = 0;
+    if (!leg.ok || g[0] * g[1] * g[2] <= 0) return 0;   // (wave-uniform)
+    const double slack = 1e-9 * h + 1e-12 * (fabs(leg.a[0]) + fabs(leg.a[1]) + fabs(leg.a[2]) + fabs(leg.b[0]) + fabs(leg.b[1]) +
+                                             fabs(leg.b[2]) + fabs(b[0]) + fabs(b[1]) + fabs(b[2]));
+    const double r2s = r2 * (1.0 + 1e-12);   // (inf at r2 = DBL_MAX: no row is skipped)
+    const double rho = sqrt(r2) * (1.0 + 1e-12) + slack;
+    double qlo[3], qhi[3];
+    int clo[3], chi[3], lo[3], hi[3];   // the cells the leg spans; the cells the widened box touches
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        qlo[a] = fmin(leg.a[a], leg.b[a]);
+        qhi[a] = fmax(leg.a[a], leg.b[a]);
+        clo[a] = cell_of(qlo[a], b[a], inv_h, g[a]);
+        chi[a] = cell_of(qhi[a], b[a], inv_h, g[a]);
+        lo[a] = cell_of(qlo[a] - rho, b[a], inv_h, g[a]);
+        hi[a] = cell_of(qhi[a] + rho, b[a], inv_h, g[a]);
+    }
+    double tau = DBL_MAX;  // the k-th kept distance (k > 0)
+    int win = 0;           // number of the candidate window being fetched (tags ws->mark)
+    ws->mark[lane] = 0;
+    const int ny = hi[1] - lo[1] + 1, nz = hi[2] - lo[2] + 1;
+    const int nitems = ny * nz * gs.nt;
+    // item -> (row, tile) and row -> (iy, iz) through float reciprocals, exact while nitems < 4e6 (grid_knn)
+    const float inv_nt = 1.0f / (float)gs.nt, inv_ny = 1.0f / (float)ny;
+    for (int row0 = 0; row0 < nitems; row0 += 64) {
+        const int item = row0 + lane;
+        int sA = 0, lA = 0;
+        if (item < nitems) {
+            const int j = (int)(((float)item + 0.5f) * inv_nt);
+            const int *cst = gs.cs + (size_t)(item - j * gs.nt) * (kGridMaxCells + 2);
+            const int jz = (int)(((float)j + 0.5f) * inv_ny);
+            const int iy = lo[1] + (j - jz * ny), iz = lo[2] + jz;
+            // iy < clo: the row's upper face iy + 1 <= clo <= g - 1 is an interior face, and so is iy > chi's lower face iy >= 1
+            const double ey = iy < clo[1] ? qlo[1] - (b[1] + (double)(iy + 1) * h) : (iy > chi[1] ? (b[1] + (double)iy * h) - qhi[1] : 0.0);
+            const double ez = iz < clo[2] ? qlo[2] - (b[2] + (double)(iz + 1) * h) : (iz > chi[2] ? (b[2] + (double)iz * h) - qhi[2] : 0.0);
+            const double fy = fmax(0.0, ey - slack) * (1.0 - 1e-12), fz = fmax(0.0, ez - slack) * (1.0 - 1e-12);
+            const double far2 = fy * fy + fz * fz;
+            if (!(far2 > r2s)) {   // (else the whole row is out of reach)
+                const double rem = r2s - far2;   // NaN = inf - inf: no clip
+                int x0 = lo[0], x1 = hi[0];
+                if (rem == rem) {
+                    const double rx = sqrt(rem) * (1.0 + 1e-12) + slack;
+                    x0 = max(x0, cell_of(qlo[0] - rx, b[0], inv_h, g[0]));
+                    x1 = min(x1, cell_of(qhi[0] + rx, b[0], inv_h, g[0]));
+                }
+                if (x0 <= x1) {
+                    const int rowbase = (iz * g[1] + iy) * g[0];
+                    sA = cst[rowbase + x0];
+                    lA = cst[rowbase + x1 + 1] - sA;
+                }
+            }
+        }
+        if (__ballot(lA > 0) == 0) continue;  // nothing but empty buckets in these rows
+        // flatten the <= 64 runs into one index space so that every lane gets a point (grid_knn's scheme, one run per item)
+        const int incl = wave_incl_scan_i32(lA);
+        const int total = __builtin_amdgcn_readlane(incl, 63);
+        const int mypre = incl - lA, mylen = lA;
+        ws->item[lane] = make_int4(mypre, lA, sA, 0);
+        auto fetch = [&](int w0, double &d, double &tc, int &ic, int &ip) {
+            ++win;
+            const int rel = mypre - w0;
+            // every lane stores (the silent ones into the spare slot) and the wave is fenced before it reads: see grid_knn
+            ws->mark[(mylen > 0 && rel >= 0 && rel < 64) ? rel : 64] = (win << 6) | lane;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            const unsigned long long before = __ballot(mylen > 0 && mypre <= w0);
+            const int carry = 63 - __clzll((long long)before);   // (w0 < total: some non-empty item holds w0)
+            const int mk = ws->mark[lane];
+            const int o = max(wave_incl_scan_max_i32((mk >> 6) == win ? (mk & 63) + 1 : 0) - 1, carry);
+            const int t = w0 + lane;
+            d = __builtin_nan("");
+            tc = 0.0;
+            ic = kNoIndex;
+            ip = 0;
+            if (t < total) {
+                const int4 it = ws->item[o];
+                const int pos = it.z + (t - it.x);
+                const float4 p4 = gs.pt[pos];
+                d = seg_dist(leg, p4.x, p4.y, p4.z, tc);
+                ic = __float_as_int(p4.w);
+                ip = pos;
+            }
+        };
+        double d, dn, tc, tcn;
+        int ic, icn, ip, ipn;
+        fetch(0, d, tc, ic, ip);
+        for (int t0 = 0; t0 < total; t0 += 64) {
+            if (t0 + 64 < total) fetch(t0 + 64, dn, tcn, icn, ipn);  // next window in flight while this one is counted and merged
+            const bool in = d < r2;   // strict; false for NaN (no candidate) -- and d < r2 <= DBL_MAX: usable
+            count += __popcll(__ballot(in));
+            if (k > 0) {
+                // the list: grid_knn's lane-held sorted insertion with t as a further payload
+                bool live = in && d <= tau;
+                for (;;) {
+                    const unsigned long long m = __ballot(live);
+                    if (!m) break;
+                    int src = __ffsll((long long)m) - 1;
+                    if (m & (m - 1)) {   // several: (one of) the nearest by the high word of the distance (any order gives the same list)
+                        const int hk = live ? __double2hiint(d) : 0x7FFFFFFF;
+                        const int hmin = grid_wave_min_i32(hk);
+                        src = __ffsll((long long)__ballot(hk == hmin)) - 1;
+                    }
+                    const double dc = readlane_f64(d, src), tcc = readlane_f64(tc, src);
+                    const int icc = __builtin_amdgcn_readlane(ic, src);
+                    const int ipc = __builtin_amdgcn_readlane(ip, src);
+                    // rank of the candidate in (distance, index) order among the kept entries
+                    const bool lt_c = (lane < k) & ((ld < dc) | ((ld == dc) & (li < icc)));
+                    const int pos = __popcll(__ballot(lt_c));
+                    if (pos < k) {
+                        const double up_d = wave_shr1_f64(ld), up_t = wave_shr1_f64(lt);
+                        const int up_i = wave_shr1_i32(li), up_p = wave_shr1_i32(lpos);
+                        const bool above = lane > pos, here = lane == pos;   // selects, not branches
+                        ld = here ? dc : (above ? up_d : ld);
+                        lt = here ? tcc : (above ? up_t : lt);
+                        li = here ? icc : (above ? up_i : li);
+                        lpos = here ? ipc : (above ? up_p : lpos);
+                        tau = readlane_f64(ld, k - 1);
+                    }
+                    live = live && lane != src && d <= tau;
+                }
+            }
+            d = dn;
+            tc = tcn;
+            ic = icn;
+            ip = ipn;
+        }
+    }
+    return count;
+}
+
 // 1-NN squared distance of q, one THREAD per query (the n-queries-on-n-points keyframe sweep,
 // AM/src/FrameKDMap.cpp:466-476): same ring walk and stopping rule as grid_knn with k = 1, scalar per lane.
 // Returns DBL_MAX when the index holds no point with a finite distance to q.

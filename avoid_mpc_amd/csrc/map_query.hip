@@ -55,9 +55,11 @@ __device__ __forceinline__ void frame_list(const GridScene &gs, const ExactPtrs 
 // Folds one frame's sorted list (frame_list's nd / rec, frame number f) into the running list held one entry per lane < k: the
 // frame's entries are offered best first, an entry ranks behind every kept one at the same or a smaller distance (kept entries came
 // from an earlier frame or are earlier neighbours of this one: the tie rule), and the fold ends at the first entry that ranks
-// behind the k-th kept one.
+// behind the k-th kept one.  WITH_T (the segment search): every entry carries a further payload, its t (nt in the frame's list, rt
+// in the running one); without it the two are never touched and the code is what it was.
+template <bool WITH_T = false>
 __device__ __forceinline__ void fold_frame_list(double nd, const float4 &rec, int f, int k, int lane, double &rd, float &rx, float &ry,
-                                                float &rz, int &rf) {
+                                                float &rz, int &rf, double nt = 0.0, double *rt = nullptr) {
     for (int e = 0; e < k; ++e) {     // this frame's entries, best first
         const double dc = readlane_f64(nd, e);
         if (!(dc < DBL_MAX)) break;
@@ -76,6 +78,10 @@ __device__ __forceinline__ void fold_frame_list(double nd, const float4 &rec, in
         ry = here ? cy : (above ? up_y : ry);
         rz = here ? cz : (above ? up_z : rz);
         rf = here ? f : (above ? up_f : rf);
+        if constexpr (WITH_T) {
+            const double ct = readlane_f64(nt, e), up_t = wave_shr1_f64(*rt);
+            *rt = here ? ct : (above ? up_t : *rt);
+        }
     }
 }
 
@@ -283,6 +289,66 @@ int launch_radius(const QueryFrames &qf, int S, const double *d_queries, int que
     return AMK_OK;
 }
 
+// Segment search over the frames (amk_kfmap_segment_search / amk_kd_segment_search_frames): one wavefront per (scene, leg) walks
+// every frame its scene holds with grid_segment, as map_radius_kernel does with grid_radius -- the counts add up, each frame's list
+// is folded into the running list with its t (equal distances keep the earlier frame, then the lower index within a frame).
+template <bool MAP>
+__global__ __launch_bounds__(256) void map_segment_kernel(QueryFrames qf, int n_scenes, const double *__restrict__ path,
+                                                          int point_stride, int n_points, double r2, int k,
+                                                          float *__restrict__ out_pts, double *__restrict__ out_d2,
+                                                          double *__restrict__ out_t, int *__restrict__ out_frame,
+                                                          int *__restrict__ out_cnt) {
+    __shared__ GridWaveLds wl[4];
+    const int n_legs = n_points - 1;
+    const WaveSlot ws = wave_slot(n_legs);
+    const int s = ws.s, w = ws.w, lane = ws.lane, q = ws.unit;
+    if (s >= n_scenes || q >= n_legs) return;
+    const double *pa = path + ((size_t)s * n_points + q) * point_stride;
+    const SegLeg leg = seg_leg(pa, pa + point_stride);
+    const size_t row = (size_t)s * n_legs + q;
+    const int F = MAP ? qf.map.held(s, lane) : qf.map.n;
+    const GridPtrs pool = qf.g[0];   // (map mode: one set of pool pointers stays live over the loop)
+    double rd = DBL_MAX, rt = 0.0;   // the running list: lane i < k holds the i-th best (distance, t, point, frame) so far
+    float rx = 0.f, ry = 0.f, rz = 0.f;
+    int rf = -1, cnt = 0;
+    for (int f = 0; f < F; ++f) {
+        const int m = MAP ? qf.map.pool_scene(f, s) : s;
+        if (m < 0) continue;         // (map mode: this scene's map has no frame f)
+        const GridScene gs = (MAP ? pool : qf.g[f]).scene(m);
+        double ld, lt;
+        int li, lpos;
+        cnt += grid_segment(gs, leg, r2, k, ld, li, lpos, lt, &wl[w]);
+        if (k > 0) {
+            const float4 rec = gs.pt[lpos];   // (lpos = 0 for empty slots: a valid address)
+            fold_frame_list<true>((lane < k && li != kNoIndex) ? ld : DBL_MAX, rec, f, k, lane, rd, rx, ry, rz, rf, lt, &rt);
+        }
+    }
+    if (lane == 0 && out_cnt) out_cnt[row] = cnt;
+    if (lane < k) {
+        const bool ok = rd < DBL_MAX;
+        const size_t o = row * k + lane;
+        if (out_d2) out_d2[o] = ok ? rd : DBL_MAX;
+        if (out_t) out_t[o] = ok ? rt : 0.0;
+        if (out_frame) out_frame[o] = ok ? rf : -1;
+        if (out_pts) {
+            out_pts[o * 3 + 0] = ok ? rx : 0.f;
+            out_pts[o * 3 + 1] = ok ? ry : 0.f;
+            out_pts[o * 3 + 2] = ok ? rz : 0.f;
+        }
+    }
+}
+
+int launch_segment(const QueryFrames &qf, int S, const double *d_path, int point_stride, int n_points, double radius_sq, int max_results,
+                   float *d_pts, double *d_sqdist, double *d_t, int *d_frame, int *d_counts, hipStream_t stream) {
+    const long long blocks = search_blocks(S, n_points - 1);
+    if (blocks > 0x7fffffffll) return AMK_ERR_UNSUPPORTED;
+    auto kernel = qf.map.fmap ? map_segment_kernel<true> : map_segment_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, stream, qf, S, d_path, point_stride, n_points,
+                       radius_clamped(radius_sq), max_results, d_pts, d_sqdist, d_t, d_frame, d_counts);
+    AMK_HIP(hipGetLastError());
+    return AMK_OK;
+}
+
 }  // namespace
 
 namespace amk {
@@ -317,6 +383,17 @@ int map_radius_search(amk_kd *pool, int n_frames, const int *d_fmap, int S, cons
         return st;
     return launch_radius(frames_of_pool(pool, n_frames, d_fmap, S), S, d_queries, query_stride, n_queries, radius_sq, max_results, d_pts,
                          d_sqdist, d_frame, d_counts, stream);
+}
+int map_segment_search(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_path, int point_stride, int n_points,
+                       double radius_sq, int max_results, float *d_pts, double *d_sqdist, double *d_t, int *d_frame, int *d_counts,
+                       hipStream_t stream) {
+    if (!pool || !d_fmap || n_frames < 1 || S < 1) return AMK_ERR_INVALID_ARG;
+    if (const int st = segment_args_status(d_path, point_stride, n_points, radius_sq, max_results, d_pts || d_sqdist || d_t || d_frame,
+                                           d_pts || d_sqdist || d_t || d_frame || d_counts);
+        st != AMK_OK)
+        return st;
+    return launch_segment(frames_of_pool(pool, n_frames, d_fmap, S), S, d_path, point_stride, n_points, radius_sq, max_results, d_pts,
+                          d_sqdist, d_t, d_frame, d_counts, stream);
 }
 }  // namespace amk
 
@@ -386,6 +463,35 @@ int amk_kd_radius_search_frames_host(amk_kd *const *frames, int n_frames, const 
                                                                        max_results, d[amk::MQ_PTS], d[amk::MQ_SQDIST], d[amk::MQ_FRAME],
                                                                        d[amk::MQ_COUNTS], nullptr);
                                 });
+}
+
+int amk_kd_segment_search_frames(amk_kd *const *frames, int n_frames, const double *d_path, int point_stride, int n_points,
+                                 double radius_sq, int max_results, float *d_pts, double *d_sqdist, double *d_t, int *d_frame,
+                                 int *d_counts, void *stream) {
+    if (const int st = segment_args_status(d_path, point_stride, n_points, radius_sq, max_results, d_pts || d_sqdist || d_t || d_frame,
+                                           d_pts || d_sqdist || d_t || d_frame || d_counts);
+        st != AMK_OK)
+        return st;
+    QueryFrames qf;
+    int S = 0;
+    if (const int st = frames_of_handles(frames, n_frames, qf, S, false); st != AMK_OK) return st;
+    return launch_segment(qf, S, d_path, point_stride, n_points, radius_sq, max_results, d_pts, d_sqdist, d_t, d_frame, d_counts,
+                          (hipStream_t)stream);
+}
+
+int amk_kd_segment_search_frames_host(amk_kd *const *frames, int n_frames, const double *h_path, int point_stride, int n_points,
+                                      double radius_sq, int max_results, float *h_pts, double *h_sqdist, double *h_t, int *h_frame,
+                                      int *h_counts) {
+    QueryFrames qf;
+    int S = 0;
+    if (const int st = frames_of_handles(frames, n_frames, qf, S, false); st != AMK_OK) return st;
+    amk::HostStage stage;   // frees at return: these frames belong to no one handle
+    return amk::map_segment_host(stage, S, h_path, point_stride, n_points, radius_sq, max_results, h_pts, h_sqdist, h_t, h_frame, h_counts,
+                                 [&](const amk::HostStage::Dev *d) {
+                                     return amk_kd_segment_search_frames(frames, n_frames, d[amk::MQ_QUERIES], point_stride, n_points,
+                                                                         radius_sq, max_results, d[amk::MQ_PTS], d[amk::MQ_SQDIST],
+                                                                         d[amk::MQ_DIST], d[amk::MQ_FRAME], d[amk::MQ_COUNTS], nullptr);
+                                 });
 }
 
 }  // extern "C"

@@ -150,6 +150,39 @@ class KdBatch:
                                                       vp(cnt)), "amk_kd_radius_search_host")
         return dict(indices=idx, sqdist=d2, pts=pts, counts=cnt)
 
+    def segment_search(self, path, radius_sq, max_results, want_pts=True, stream=None, out=None):
+        """amk_kd_segment_search: the points within a radius of every leg of a path, float64 [S, n_points >= 2, >= 3] (the first
+        three of every row are read; leg j runs from point j to point j + 1).  radius_sq: a SQUARED distance, the test is strict;
+        counts [S, n_legs] is the full number whatever max_results; the lists hold the nearest max_results, ascending, ties by cloud
+        index, t = where along the leg (0 .. 1) each comes closest, empty slots -1 / DBL_MAX / 0.  max_results = 0: the pure count
+        (no lists).  -> dict(indices, sqdist, t, pts, counts)"""
+        P, stride = _check_path(path, self.S)
+        k, dev, L = int(max_results), path.device, P - 1
+        if out is None:
+            lists = k > 0
+            out = dict(indices=torch.empty((self.S, L, k), dtype=torch.int32, device=dev) if lists else None,
+                       sqdist=torch.empty((self.S, L, k), dtype=torch.float64, device=dev) if lists else None,
+                       t=torch.empty((self.S, L, k), dtype=torch.float64, device=dev) if lists else None,
+                       pts=torch.empty((self.S, L, k, 3), dtype=torch.float32, device=dev) if lists and want_pts else None,
+                       counts=torch.empty((self.S, L), dtype=torch.int32, device=dev))
+        capi.check(self.lib.amk_kd_segment_search(self.h, capi.dptr(path), stride, P, float(radius_sq), k, capi.dptr(out["indices"]),
+                                                  capi.dptr(out["sqdist"]), capi.dptr(out["t"]), capi.dptr(out["pts"]),
+                                                  capi.dptr(out["counts"]), _stream_arg(stream)), "amk_kd_segment_search")
+        return out
+
+    def segment_search_host(self, path, radius_sq, max_results):
+        """amk_kd_segment_search_host: segment_search with numpy buffers (path [S, n_points, >= 3]); synchronises."""
+        p = np.ascontiguousarray(path, np.float64)
+        assert p.ndim == 3 and p.shape[0] == self.S and p.shape[2] >= 3
+        L, k = p.shape[1] - 1, int(max_results)
+        idx = np.zeros((self.S, L, k), np.int32); d2 = np.zeros((self.S, L, k), np.float64); t = np.zeros((self.S, L, k), np.float64)
+        pts = np.zeros((self.S, L, k, 3), np.float32); cnt = np.zeros((self.S, L), np.int32)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        lst = (lambda a: vp(a)) if k > 0 else (lambda a: None)   # max_results = 0 is the pure count: no list pointers
+        capi.check(self.lib.amk_kd_segment_search_host(self.h, vp(p), int(p.shape[2]), int(p.shape[1]), float(radius_sq), k, lst(idx),
+                                                       lst(d2), lst(t), lst(pts), vp(cnt)), "amk_kd_segment_search_host")
+        return dict(indices=idx, sqdist=d2, t=t, pts=pts, counts=cnt)
+
 
 def kd_build_pair(kd_obstacle, xyz, kd_edge, edge_xyz, counts=None, edge_counts=None, stream=None):
     """amk_kd_build_pair: FrameKDMap::AddVertex's two InitializeNew calls as one launch (clouds packed [S, max_points, 3|4])."""
@@ -355,6 +388,33 @@ def radius_search_frames(handles, queries, radius_sq, max_results, stream=None, 
     return out
 
 
+def _check_path(path, S):
+    assert path.dtype == torch.float64 and path.dim() == 3 and path.shape[0] == S and path.shape[2] >= 3 and path.shape[1] >= 1
+    return int(path.shape[1]), int(path.shape[2])
+
+
+def _segment_out(S, L, k, dev):
+    """outputs of the multi-frame segment searches, a row per leg; max_results = 0 is the pure count: no lists"""
+    out = _radius_out(S, L, k, dev)
+    out["t"] = torch.empty((S, L, k), dtype=torch.float64, device=dev) if k > 0 else None
+    return out
+
+
+def segment_search_frames(handles, path, radius_sq, max_results, stream=None, out=None):
+    """amk_kd_segment_search_frames: the segment search over a list of KdBatch handles (obstacle OR edge, index 0 = current frame);
+    counts sum over the frames, the lists merge by (squared distance, frame, cloud index).  -> dict(pts, sqdist, t, frame, counts)"""
+    F, S = len(handles), handles[0].S
+    P, stride = _check_path(path, S)
+    if out is None:
+        out = _segment_out(S, P - 1, int(max_results), path.device)
+    ha = (C.c_void_p * F)(*[h.h for h in handles])
+    capi.check(capi.load().amk_kd_segment_search_frames(ha, F, capi.dptr(path), stride, P, float(radius_sq), int(max_results),
+                                                        capi.dptr(out["pts"]), capi.dptr(out["sqdist"]), capi.dptr(out["t"]),
+                                                        capi.dptr(out["frame"]), capi.dptr(out["counts"]), _stream_arg(stream)),
+               "amk_kd_segment_search_frames")
+    return out
+
+
 class KfMap:
     """amk_kfmap: FrameKDMap's keyframe list for S scenes on the device (FrameKDMap.cpp:29-74,233-252,428-488)."""
 
@@ -430,6 +490,22 @@ class KfMap:
         capi.check(self.lib.amk_kfmap_radius_search(self.h, capi.dptr(queries), stride, Q, float(radius_sq), int(max_results), int(bool(edge)),
                                                     capi.dptr(out["pts"]), capi.dptr(out["sqdist"]), capi.dptr(out["frame"]),
                                                     capi.dptr(out["counts"]), _stream_arg(stream)), "amk_kfmap_radius_search")
+        return out
+
+    def segment_search(self, path, radius_sq, max_results, edge=False, stream=None, out=None):
+        """amk_kfmap_segment_search: the points within a radius of every leg of a path float64 [S, n_points >= 2, >= 3], over every
+        frame each scene's query vector holds (no fast path, no frustum test, no size rule).  radius_sq is a squared distance, the test
+        is strict; counts is the full number over the frames; the lists hold the nearest max_results by (squared distance, frame,
+        cloud index) with t, the position of the closest approach along the leg.
+        -> dict(pts [S,L,k,3] f32, sqdist, t [S,L,k] f64, frame [S,L,k] i32, counts [S,L] i32), L = n_points - 1; max_results = 0:
+        counts only"""
+        P, stride = _check_path(path, self.S)
+        if out is None:
+            out = _segment_out(self.S, P - 1, int(max_results), path.device)
+        capi.check(self.lib.amk_kfmap_segment_search(self.h, capi.dptr(path), stride, P, float(radius_sq), int(max_results), int(bool(edge)),
+                                                     capi.dptr(out["pts"]), capi.dptr(out["sqdist"]), capi.dptr(out["t"]),
+                                                     capi.dptr(out["frame"]), capi.dptr(out["counts"]), _stream_arg(stream)),
+                   "amk_kfmap_segment_search")
         return out
 
     def nearest_distance(self, queries, stream=None, out=None):

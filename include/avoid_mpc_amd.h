@@ -240,6 +240,50 @@ int amk_kd_radius_search(amk_kd *kd, const double *d_queries, int query_stride, 
 int amk_kd_radius_search_host(amk_kd *kd, const double *h_queries, int query_stride, int n_queries, double radius_sq,
                               int max_results, int *h_indices, double *h_sqdist, float *h_pts, int *h_counts);
 
+/* Segment search: which points lie within a radius of the LINE between two successive positions of a path, how many, and where
+ * along the leg each comes closest.  The MPC sees obstacles at its N sampled states only; at the reference's settings two samples
+ * are 0.33 m apart and the scenes hold cylinders of radius 0.1 m, so a thin obstacle can stand between two samples while every
+ * sampled clearance looks fine.  Not on the reference's surface either (PlanWapionts checks reference point 0 only): the
+ * radius search's walk around a segment instead of a point.
+ * Layout.  A path is n_points >= 2 positions per scene: point j of scene s is read at
+ * d_path[(s*n_points + j)*point_stride + {0,1,2}], point_stride >= 3 (3 = packed points, 10 = the rows of mRefPath, 14 = the
+ * rows of x0array).  Leg j, 0 <= j < n_points - 1, runs from point j (a) to point j + 1 (b); n_points = 2 is a lone segment.
+ * Every output is [S][n_legs = n_points - 1]...
+ * Per leg, in fp64 with contraction off, summing left to right as the squared distance of amk_kd_search does:
+ *     ab = b - a;  L2 = (ab0*ab0 + ab1*ab1) + ab2*ab2;  inv = 1.0 / L2
+ * Per stored point p (float32, widened first), by the same rules:
+ *     ap  = p - a;  dot = (ap0*ab0 + ap1*ab1) + ap2*ab2
+ *     t   = dot > 0 ? dot*inv : 0;  t = t < 1 ? t : 1            (comparisons, so a NaN dot gives 0)
+ *     c   = t < 1 ? a + t*ab (per component: one product, one sum) : b exactly
+ *     e   = c - p;  d2 = (e0*e0 + e1*e1) + e2*e2
+ * There is one reciprocal per leg, not a division per candidate.  A degenerate leg (a == b) has dot == 0, so t = 0, c = a, inv
+ * is never used, and the leg answers exactly what amk_kd_radius_search answers at a, bit for bit.
+ *   radius_sq   a SQUARED distance under the radius search's rules: >= 0 and not NaN (else AMK_ERR_INVALID_ARG); +inf and
+ *               anything >= DBL_MAX mean every usable point.  The test is strict: a result has d2 < radius_sq.  A point is
+ *               usable when d2 < DBL_MAX (false for NaN, inf and overflow).
+ *   d_counts    [S][n_legs] int: the full number of results of the leg, never capped by max_results.  A leg with a non-finite
+ *               coordinate in either endpoint, or whose L2 is not finite, gets count 0 and empty slots; a non-finite path
+ *               point spoils only the one or two legs that touch it.  An empty or never-built scene answers 0.
+ *   lists       d_indices [S][n_legs][max_results] int, d_sqdist and d_t [..][max_results] double, d_pts [..][max_results][3]
+ *               float: the min(count, max_results) NEAREST results, ascending by d2, equal d2 by cloud index; d_t is the t
+ *               above, the position of the closest approach along the leg (0 at a, 1 at b).  The tie-order modes do not
+ *               apply, as for radius results.  Empty slots hold -1 / DBL_MAX / 0.0 / (0,0,0).  Each list output may be NULL,
+ *               and so may d_counts, but not all of them.
+ *   max_results 0 <= max_results <= AMK_MAX_K.  max_results == 0 requires every list pointer NULL (else AMK_ERR_INVALID_ARG):
+ *               the pure count, "is the tube free".  > AMK_MAX_K: AMK_ERR_UNSUPPORTED; < 0, or n_points < 2:
+ *               AMK_ERR_INVALID_ARG.
+ * No size rule, no fast path, no PtIsInFrame.  A handle in scan mode (internal, tests) returns AMK_ERR_UNSUPPORTED.  Every error
+ * is returned before anything is launched, the outputs untouched.  The call is stream-ordered and allocates nothing.
+ * Not offered: per-leg radii, uncapped result lists, an unbounded "nearest point to the segment" query, segment queries inside
+ * amk_step_batch or the pipeline.                                                                                          */
+int amk_kd_segment_search(amk_kd *kd, const double *d_path, int point_stride, int n_points, double radius_sq,
+                          int max_results, int *d_indices, double *d_sqdist, double *d_t, float *d_pts, int *d_counts,
+                          void *stream);
+/* Same with host buffers: stages through the handle's own block (as amk_kd_search_host) and synchronises.  h_path holds at
+ * least (S * n_points - 1) * point_stride + 3 doubles.                                                                      */
+int amk_kd_segment_search_host(amk_kd *kd, const double *h_path, int point_stride, int n_points, double radius_sq,
+                               int max_results, int *h_indices, double *h_sqdist, double *h_t, float *h_pts, int *h_counts);
+
 /* ------------------------------------------------------------------------------------------ */
 /* MPC: batch of ObstacleAvoidanceMPC                          HighLvlMpc.h:4-33, .cpp:5-137    */
 /* ------------------------------------------------------------------------------------------ */
@@ -761,6 +805,31 @@ int amk_kd_radius_search_frames(amk_kd *const *frames, int n_frames, const doubl
 int amk_kd_radius_search_frames_host(amk_kd *const *frames, int n_frames, const double *h_queries, int query_stride, int n_queries,
                                      double radius_sq, int max_results, float *h_pts, double *h_sqdist, int *h_frame,
                                      int *h_counts);
+/* Segment search over the frames: amk_kd_segment_search (see there: the path's layout, the per-leg and per-point values, radius_sq,
+ * the strict test, the uncapped count, max_results, the errors) over every frame a scene holds -- a keyframe map's query vector,
+ * or a caller's list of frame handles; no fast path, no PtIsInFrame, no size rule, as for the radius search over the frames.
+ *   d_counts [S][n_legs]                  the SUM over the frames of the leg's results (never capped)
+ *   d_pts / d_sqdist / d_t / d_frame [S][n_legs][max_results]   the min(count, max_results) nearest of all frames, ascending by
+ *               d2; equal d2: the earlier frame first, then the lower cloud index within a frame; d_frame is the position in the
+ *               query vector (0 = current frame).  Empty slots hold (0,0,0) / DBL_MAX / 0.0 / -1.  Each output may be NULL,
+ *               not all; max_results == 0 (the pure count) requires the four lists NULL.
+ *   query_edge  != 0: the frames' edge clouds, else their obstacle clouds
+ * A scene with no frame yet answers 0.  Tie orders do not apply; scan-mode handles and n_frames > AMK_MAX_FRAMES return
+ * AMK_ERR_UNSUPPORTED before anything is launched.  Stream-ordered, nothing allocated, no map state changed; ordering against
+ * the map's updates as stated for its own queries above.  The *_host variants stage through device memory and synchronise the
+ * device.                                                                                                                    */
+int amk_kfmap_segment_search(amk_kfmap *map, const double *d_path, int point_stride, int n_points, double radius_sq,
+                             int max_results, int query_edge, float *d_pts, double *d_sqdist, double *d_t, int *d_frame,
+                             int *d_counts, void *stream);
+int amk_kfmap_segment_search_host(amk_kfmap *map, const double *h_path, int point_stride, int n_points, double radius_sq,
+                                  int max_results, int query_edge, float *h_pts, double *h_sqdist, double *h_t, int *h_frame,
+                                  int *h_counts);
+int amk_kd_segment_search_frames(amk_kd *const *frames, int n_frames, const double *d_path, int point_stride, int n_points,
+                                 double radius_sq, int max_results, float *d_pts, double *d_sqdist, double *d_t, int *d_frame,
+                                 int *d_counts, void *stream);
+int amk_kd_segment_search_frames_host(amk_kd *const *frames, int n_frames, const double *h_path, int point_stride, int n_points,
+                                      double radius_sq, int max_results, float *h_pts, double *h_sqdist, double *h_t,
+                                      int *h_frame, int *h_counts);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Scenes sharded over the GPUs of a node (one process per GPU), RCCL over xGMI                 */

@@ -236,6 +236,36 @@ public:
         return count;
     }
 
+    // Not in the reference either: every point of the map within a radius of the SEGMENT from -> to (KDTreeTwo::SegmentSearch over
+    // the frames of the query vector, every frame contributing as in QueryRadius).  Returns the full number and fills the nearest
+    // min(count, max_results), ascending, with `params` = t of each (0 at `from`, 1 at `to`); equal distances keep the earlier
+    // frame, then the lower index within a frame.
+    size_t QuerySegment(const Vector3d &from, const Vector3d &to, double radius_sq, int max_results, std::vector<Vector3d> &nearestPoints,
+                        std::vector<double> &distances, std::vector<double> &params, bool queryEdge = false) {
+        struct PtDists { Vector3d pt; double dist, t; };
+        std::vector<PtDists> pointsDist;
+        size_t count = 0;
+        std::lock_guard<std::mutex> lock(mMtxKdTree);
+        for (auto &fr : mVecQueryVector) {
+            PtCloudKdPtr pc = queryEdge ? fr.edgeCloud : fr.pointCloud;
+            if (!pc) continue;
+            count += pc->SegmentSearch(vx(from), vy(from), vz(from), vx(to), vy(to), vz(to), radius_sq, max_results);
+            for (size_t j = 0; j < pc->squared_distances.size(); ++j)
+                pointsDist.push_back({Vector3d(pc->closest_pts[j].x, pc->closest_pts[j].y, pc->closest_pts[j].z),
+                                      pc->squared_distances[j], pc->segment_t[j]});
+        }
+        nearestPoints.clear();
+        distances.clear();
+        params.clear();
+        std::stable_sort(pointsDist.begin(), pointsDist.end(), [](const PtDists &a, const PtDists &b) { return a.dist < b.dist; });
+        for (int i = 0; i < max_results && i < (int)pointsDist.size(); ++i) {
+            nearestPoints.push_back(pointsDist[i].pt);
+            distances.push_back(pointsDist[i].dist);
+            params.push_back(pointsDist[i].t);
+        }
+        return count;
+    }
+
     // One pass of KeyframeThreadWorker's body (:443-486) -- the caller owns the 30 ms cadence and the
     // "new frame arrived" flag.  dronePos / bodyX: translation of Twb = Twc * Tbc^-1 and the world
     // direction of the body x axis (first column of Rwb), what DroneBehindPts (:233-252) derives.

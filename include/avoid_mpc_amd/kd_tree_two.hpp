@@ -42,6 +42,7 @@ public:
     std::vector<num_t> squared_distances;
     std::vector<int> indices;
     std::vector<int> colors;
+    std::vector<double> segment_t;  // not in the reference: filled by SegmentSearch, beside squared_distances
 
     KDTreeTwo() {
         for (int i = 0; i < 3; i++) colors.push_back(rand() % 256);  // kd_tree_two.h:69-72
@@ -155,6 +156,33 @@ public:
             closest_pts.push_back(cloud.pts[idx[i]]);
             squared_distances.push_back((num_t)d2[i]);
             indices.push_back(idx[i]);
+        }
+        return (size_t)count;
+    }
+    // Not in the reference either: the points of this tree within a radius of the SEGMENT a -> b (amk_kd_segment_search, see the C
+    // header: the closest approach c = a + t (b - a), t clamped to [0, 1]).  radius_sq is a SQUARED distance and the test is strict.
+    // Returns the full number, whatever max_results, and fills closest_pts / squared_distances / indices / segment_t (t of each
+    // result) with the nearest min(count, max_results), ascending, equal distances by index.  max_results = 0: the pure count.
+    size_t SegmentSearch(num_t ax, num_t ay, num_t az, num_t bx, num_t by, num_t bz, double radius_sq, int max_results) {
+        closest_pts.clear();
+        squared_distances.clear();
+        indices.clear();
+        segment_t.clear();
+        if (cloud.pts.size() == 0) return 0;
+        if (max_results < 0 || max_results > AMK_MAX_K) throw std::runtime_error("KDTreeTwo::SegmentSearch: max_results outside [0, AMK_MAX_K]");
+        const double path[6] = {(double)ax, (double)ay, (double)az, (double)bx, (double)by, (double)bz};
+        const int n = max_results;
+        std::vector<int> idx(n);
+        std::vector<double> d2(n), t(n);
+        int count = 0;
+        amk_throw(amk_kd_segment_search_host(kd_, path, 3, 2, radius_sq, n, n ? idx.data() : nullptr, n ? d2.data() : nullptr,
+                                             n ? t.data() : nullptr, nullptr, &count),
+                  "amk_kd_segment_search_host");
+        for (int i = 0; i < n && i < count; i++) {
+            closest_pts.push_back(cloud.pts[idx[i]]);
+            squared_distances.push_back((num_t)d2[i]);
+            indices.push_back(idx[i]);
+            segment_t.push_back(t[i]);
         }
         return (size_t)count;
     }
