@@ -249,6 +249,26 @@ int map_segment_host(HostStage &stage, int S, const double *h_path, int point_st
                       },
                       hipDeviceSynchronize);
 }
+// kd_segment_nearest.hip / map_query.hip / kfmap.hip: the argument rules all six segment-nearest entries share
+// (include/avoid_mpc_amd.h, "Segment nearest"), checked before anything is staged or launched.  any_out: an output at all
+inline int segment_nearest_args_status(const double *path, int point_stride, int n_points, int k, bool any_out) {
+    if (n_points < 2 || !query_args_ok(path, point_stride, n_points) || k < 1 || !any_out) return AMK_ERR_INVALID_ARG;
+    if (k > AMK_MAX_K) return AMK_ERR_UNSUPPORTED;
+    return AMK_OK;
+}
+// map_query.hip, for kfmap.hip: segment nearest over a pool
+int map_segment_nearest(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_path, int point_stride, int n_points, int k,
+                        float *d_pts, double *d_sqdist, double *d_t, int *d_frame, int *d_counts, hipStream_t stream);
+// The *_host variants of the map's segment-nearest queries: map_segment_host as it is, k in place of max_results and every
+// usable point in place of the radius, under the rules above
+template <class Launch>
+int map_segment_nearest_host(HostStage &stage, int S, const double *h_path, int point_stride, int n_points, int k, float *h_pts,
+                             double *h_sqdist, double *h_t, int *h_frame, int *h_counts, Launch &&launch) {
+    if (const int st = segment_nearest_args_status(h_path, point_stride, n_points, k, h_pts || h_sqdist || h_t || h_frame || h_counts);
+        st != AMK_OK)
+        return st;
+    return map_segment_host(stage, S, h_path, point_stride, n_points, DBL_MAX, k, h_pts, h_sqdist, h_t, h_frame, h_counts, launch);
+}
 // kfmap.hip, for pipeline.hip: AddVertex for the frames of a gang (see there)
 int kfmap_add_vertex_gang(amk_kfmap *m, int n_frames, int frame_scenes, const float *const *d_xyz, const int *const *d_counts,
                           const float *const *d_edge_xyz, const int *const *d_edge_counts, int point_stride, const double *const *d_Twc,

@@ -1066,6 +1066,205 @@ __device__ __forceinline__ int grid_segment(const GridScene &gs, const SegLeg &l
     return count;
 }
 
+// Segment nearest on the bucketed index, one wavefront per leg (include/avoid_mpc_amd.h, "Segment nearest"): the k usable points
+// with the smallest seg_dist to the leg, no radius.  Same return convention as grid_segment: lane i < k holds the i-th best
+// (ld, li, lpos, lt), ties by index, empty slots (DBL_MAX, kNoIndex, 0, 0.0); returns (in every lane) the number of kept entries,
+// min(k, usable points of the scene).  The lists are, bit for bit, grid_segment's at r2 = DBL_MAX: the same seg_dist, the same
+// (distance, index) order; only the cells that are read differ.
+//
+// grid_knn's branch and bound around grid_segment's box.  With [clo, chi] the cells the leg's bounding box [qlo, qhi] spans,
+// shell r is the set of cells within Chebyshev distance r of that box (shell 0: the box itself).  For r > 0 a row (iy, iz)
+// outside the box already seen, [clo - rp, chi + rp], contributes its whole run [clo_x - r, chi_x + r], a row inside it the two
+// end runs left and right of that box, all clipped to the grid.  Once k candidates are known (tau = the k-th kept distance is
+// finite) a row is skipped, and its run clipped in x, exactly as grid_segment does it with tau in place of r2: slab distances to
+// the leg's y and z INTERVALS through interior faces only (a boundary cell holds the points the sampled box missed), the same
+// slack, the same (1 +- 1e-12) factors, inf - inf leaves the row unclipped.  The clip is not strict -- a point at exactly tau
+// with a lower index displaces a kept one -- and like grid_segment's it is against the leg's bounding box, not the leg.
+//
+// The stop rule, after shell r.  Every cell not yet seen lies outside the box [clo - r, chi + r], so beyond one of its faces on
+// some axis a: below face(clo_a - r) or above face(chi_a + r + 1), both interior faces whenever cells lie behind them.  A record
+// of such a cell has floor((p_a - bbmin_a) * inv_h) on the far side of that face (clamping only moves a point further out), so
+// p_a is at least D_a = qlo_a - face, or face - qhi_a, from the interval [qlo_a, qhi_a].  The closest approach c lies within
+// delta_a = 4u (|a_a| + |b_a|) of that interval whatever t is (the derivation above grid_segment: three roundings, each relative
+// to at most |a_a| + |b_a|), so |c_a - p_a| >= D_a - delta_a, and the computed d2 >= (1 - 4u) (D_a - delta_a)^2, the sum's
+// other terms being non-negative.  The face itself is formed as bbmin + i * h: off by less than 4e-13 h + 4u |bbmin|, and the
+// difference adds u (|a| + |b| + |bbmin| + 1024 h).  With dmin the smallest D over the axes and sides that still have cells,
+// floored at 0 and shrunk by slack = 1e-9 h + 1e-12 (sum |a_i| + sum |b_i| + sum |bbmin_i|) -- more than 1000 times the sum of
+// those errors and of the 2u D that the factor (1 - 4u) costs -- every unseen point has d2 >= fl(dmin * dmin).  The walk stops
+// when tau < dmin * dmin, STRICTLY: equal distances order by index, so an unseen point at exactly tau could still displace a
+// kept one.  It also stops when no side has cells left, or at r = rmax = max over the axes of max(clo, g - 1 - chi).
+__device__ __forceinline__ int grid_segment_knn(const GridScene &gs, const SegLeg &leg, int k, double &ld, int &li, int &lpos,
+                                                double &lt, GridWaveLds *ws) {
+    const int lane = threadIdx.x & 63;
+    const double b[3] = {gs.gp[0], gs.gp[1], gs.gp[2]};
+    const double h = gs.gp[3], inv_h = gs.gp[4];
+    const int g[3] = {(int)gs.gp[5], (int)gs.gp[6], (int)gs.gp[7]};
+    ld = DBL_MAX;
+    li = kNoIndex;
+    lpos = 0;
+    lt = 0.0;
+    if (!leg.ok || g[0] * g[1] * g[2] <= 0) return 0;   // (wave-uniform)
+    const double slack = 1e-9 * h + 1e-12 * (fabs(leg.a[0]) + fabs(leg.a[1]) + fabs(leg.a[2]) + fabs(leg.b[0]) + fabs(leg.b[1]) +
+                                             fabs(leg.b[2]) + fabs(b[0]) + fabs(b[1]) + fabs(b[2]));
+    double qlo[3], qhi[3];
+    int clo[3], chi[3], rmax = 0;   // the cells the leg spans
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        qlo[a] = fmin(leg.a[a], leg.b[a]);
+        qhi[a] = fmax(leg.a[a], leg.b[a]);
+        clo[a] = cell_of(qlo[a], b[a], inv_h, g[a]);
+        chi[a] = cell_of(qhi[a], b[a], inv_h, g[a]);
+        rmax = max(rmax, max(clo[a], g[a] - 1 - chi[a]));
+    }
+    double tau = DBL_MAX;  // the k-th kept distance
+    int win = 0;           // number of the candidate window being fetched (tags ws->mark)
+    ws->mark[lane] = 0;
+    int rp = -1;           // every cell of [clo - rp, chi + rp] has been seen
+    for (int r = 0;;) {
+        // the (iy, iz) rows of the shell that lie inside the grid
+        const int ylo = max(clo[1] - r, 0), ny = min(chi[1] + r, g[1] - 1) - ylo + 1;
+        const int zlo = max(clo[2] - r, 0), nz = min(chi[2] + r, g[2] - 1) - zlo + 1;
+        const int nitems = ny * nz * gs.nt;
+        // item -> (row, tile) and row -> (iy, iz) through float reciprocals, exact while nitems < 4e6 (grid_knn)
+        const float inv_nt = 1.0f / (float)gs.nt, inv_ny = 1.0f / (float)ny;
+        for (int row0 = 0; row0 < nitems; row0 += 64) {
+            const int item = row0 + lane;
+            int sA = 0, lA = 0, sB = 0, lB = 0;
+            if (item < nitems) {
+                const int j = (int)(((float)item + 0.5f) * inv_nt);
+                const int *cst = gs.cs + (size_t)(item - j * gs.nt) * (kGridMaxCells + 2);
+                const int jz = (int)(((float)j + 0.5f) * inv_ny);
+                const int iy = ylo + (j - jz * ny), iz = zlo + jz;
+                int x0 = max(clo[0] - r, 0), x1 = min(chi[0] + r, g[0] - 1);
+                if (tau < DBL_MAX) {  // clip to the current k-th distance: grid_segment's row test and x clip with tau in place of r2
+                    const double taus = tau * (1.0 + 1e-12);
+                    // iy < clo: the row's upper face iy + 1 <= clo <= g - 1 is an interior face, and so is iy > chi's lower face iy >= 1
+                    const double ey = iy < clo[1] ? qlo[1] - (b[1] + (double)(iy + 1) * h) : (iy > chi[1] ? (b[1] + (double)iy * h) - qhi[1] : 0.0);
+                    const double ez = iz < clo[2] ? qlo[2] - (b[2] + (double)(iz + 1) * h) : (iz > chi[2] ? (b[2] + (double)iz * h) - qhi[2] : 0.0);
+                    const double fy = fmax(0.0, ey - slack) * (1.0 - 1e-12), fz = fmax(0.0, ez - slack) * (1.0 - 1e-12);
+                    const double far2 = fy * fy + fz * fz;
+                    if (far2 > taus) {
+                        x1 = x0 - 1;  // the whole row is out of reach
+                    } else {
+                        const double rem = taus - far2;   // NaN = inf - inf: no clip
+                        if (rem == rem) {
+                            const double rx = sqrt(rem) * (1.0 + 1e-12) + slack;
+                            x0 = max(x0, cell_of(qlo[0] - rx, b[0], inv_h, g[0]));
+                            x1 = min(x1, cell_of(qhi[0] + rx, b[0], inv_h, g[0]));
+                        }
+                    }
+                }
+                const int rowbase = (iz * g[1] + iy) * g[0];
+                if (rp < 0 || iy < clo[1] - rp || iy > chi[1] + rp || iz < clo[2] - rp || iz > chi[2] + rp) {
+                    if (x0 <= x1) {
+                        sA = cst[rowbase + x0];
+                        lA = cst[rowbase + x1 + 1] - sA;
+                    }
+                } else {
+                    const int a1 = min(clo[0] - rp - 1, x1), b0 = max(chi[0] + rp + 1, x0);
+                    if (x0 <= a1) {
+                        sA = cst[rowbase + x0];
+                        lA = cst[rowbase + a1 + 1] - sA;
+                    }
+                    if (b0 <= x1) {
+                        sB = cst[rowbase + b0];
+                        lB = cst[rowbase + x1 + 1] - sB;
+                    }
+                }
+            }
+            if (__ballot(lA + lB > 0) == 0) continue;  // nothing but empty buckets in these rows
+            // flatten the <= 128 runs into one index space so that every lane gets a point (grid_knn's announce / running-max scheme)
+            const int incl = wave_incl_scan_i32(lA + lB);
+            const int total = __builtin_amdgcn_readlane(incl, 63);
+            const int mypre = incl - (lA + lB), mylen = lA + lB;
+            ws->item[lane] = make_int4(mypre, lA, sA, sB);
+            auto fetch = [&](int w0, double &d, double &tc, int &ic, int &ip) {
+                ++win;
+                const int rel = mypre - w0;
+                // every lane stores (the silent ones into the spare slot) and the wave is fenced before it reads: see grid_knn
+                ws->mark[(mylen > 0 && rel >= 0 && rel < 64) ? rel : 64] = (win << 6) | lane;
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                const unsigned long long before = __ballot(mylen > 0 && mypre <= w0);
+                const int carry = 63 - __clzll((long long)before);   // (w0 < total: some non-empty item holds w0)
+                const int mk = ws->mark[lane];
+                const int o = max(wave_incl_scan_max_i32((mk >> 6) == win ? (mk & 63) + 1 : 0) - 1, carry);
+                const int t = w0 + lane;
+                d = __builtin_nan("");
+                tc = 0.0;
+                ic = kNoIndex;
+                ip = 0;
+                if (t < total) {
+                    const int4 it = ws->item[o];
+                    const int u = t - it.x;
+                    const int pos = u < it.y ? it.z + u : it.w + (u - it.y);
+                    const float4 p4 = gs.pt[pos];
+                    d = seg_dist(leg, p4.x, p4.y, p4.z, tc);
+                    ic = __float_as_int(p4.w);
+                    ip = pos;
+                }
+            };
+            double d, dn, tc, tcn;
+            int ic, icn, ip, ipn;
+            fetch(0, d, tc, ic, ip);
+            for (int t0 = 0; t0 < total; t0 += 64) {
+                if (t0 + 64 < total) fetch(t0 + 64, dn, tcn, icn, ipn);  // next window in flight while this one is merged
+                // grid_segment's lane-held sorted insertion with t as a further payload, candidates best first as in grid_knn
+                bool live = d <= tau && d < DBL_MAX;   // (NaN: no candidate; inf and overflow: not usable)
+                for (;;) {
+                    const unsigned long long m = __ballot(live);
+                    if (!m) break;
+                    int src = __ffsll((long long)m) - 1;
+                    if (m & (m - 1)) {   // several: (one of) the nearest by the high word of the distance (any order gives the same list)
+                        const int hk = live ? __double2hiint(d) : 0x7FFFFFFF;
+                        const int hmin = grid_wave_min_i32(hk);
+                        src = __ffsll((long long)__ballot(hk == hmin)) - 1;
+                    }
+                    const double dc = readlane_f64(d, src), tcc = readlane_f64(tc, src);
+                    const int icc = __builtin_amdgcn_readlane(ic, src);
+                    const int ipc = __builtin_amdgcn_readlane(ip, src);
+                    // rank of the candidate in (distance, index) order among the kept entries
+                    const bool lt_c = (lane < k) & ((ld < dc) | ((ld == dc) & (li < icc)));
+                    const int pos = __popcll(__ballot(lt_c));
+                    if (pos < k) {
+                        const double up_d = wave_shr1_f64(ld), up_t = wave_shr1_f64(lt);
+                        const int up_i = wave_shr1_i32(li), up_p = wave_shr1_i32(lpos);
+                        const bool above = lane > pos, here = lane == pos;   // selects, not branches
+                        ld = here ? dc : (above ? up_d : ld);
+                        lt = here ? tcc : (above ? up_t : lt);
+                        li = here ? icc : (above ? up_i : li);
+                        lpos = here ? ipc : (above ? up_p : lpos);
+                        tau = readlane_f64(ld, k - 1);
+                    }
+                    live = live && lane != src && d <= tau;
+                }
+                d = dn;
+                tc = tcn;
+                ic = icn;
+                ip = ipn;
+            }
+        }
+        // every cell of the box [clo - r, chi + r] has been seen: stop when the k-th best is closer than the nearest face of that
+        // box that still has cells behind it (the bound is derived above)
+        if (tau < DBL_MAX) {
+            double dmin = DBL_MAX;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                if (clo[a] - r > 0) dmin = fmin(dmin, fmax(0.0, qlo[a] - (b[a] + (double)(clo[a] - r) * h)));
+                if (chi[a] + r < g[a] - 1) dmin = fmin(dmin, fmax(0.0, (b[a] + (double)(chi[a] + r + 1) * h) - qhi[a]));
+            }
+            if (dmin == DBL_MAX) break;  // the box covers the whole grid
+            dmin = fmax(0.0, dmin - slack);
+            if (tau < dmin * dmin) break;
+        }
+        if (r >= rmax) break;
+        rp = r;
+        r = r + 1;
+    }
+    return __popcll(__ballot(lane < k && li != kNoIndex));
+}
+
 // 1-NN squared distance of q, one THREAD per query (the n-queries-on-n-points keyframe sweep,
 // AM/src/FrameKDMap.cpp:466-476): same ring walk and stopping rule as grid_knn with k = 1, scalar per lane.
 // Returns DBL_MAX when the index holds no point with a finite distance to q.

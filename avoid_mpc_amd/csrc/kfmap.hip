@@ -550,6 +550,25 @@ int amk_kfmap_segment_search_host(amk_kfmap *m, const double *h_path, int point_
                                  });
 }
 
+// Segment nearest over the map as it stands (map_query.hip): every frame a scene holds, stream-ordered, no map state changes
+int amk_kfmap_segment_nearest(amk_kfmap *m, const double *d_path, int point_stride, int n_points, int k, int query_edge, float *d_pts,
+                              double *d_sqdist, double *d_t, int *d_frame, int *d_counts, void *stream) {
+    if (!m) return AMK_ERR_INVALID_ARG;
+    return amk::map_segment_nearest(query_edge ? m->edge : m->obs, m->F, m->fmap.p, m->S, d_path, point_stride, n_points, k, d_pts,
+                                    d_sqdist, d_t, d_frame, d_counts, (hipStream_t)stream);
+}
+
+int amk_kfmap_segment_nearest_host(amk_kfmap *m, const double *h_path, int point_stride, int n_points, int k, int query_edge,
+                                   float *h_pts, double *h_sqdist, double *h_t, int *h_frame, int *h_counts) {
+    if (!m) return AMK_ERR_INVALID_ARG;
+    return amk::map_segment_nearest_host(m->stage, m->S, h_path, point_stride, n_points, k, h_pts, h_sqdist, h_t, h_frame, h_counts,
+                                         [&](const HostStage::Dev *d) {
+                                             return amk_kfmap_segment_nearest(m, d[MQ_QUERIES], point_stride, n_points, k, query_edge,
+                                                                              d[MQ_PTS], d[MQ_SQDIST], d[MQ_DIST], d[MQ_FRAME],
+                                                                              d[MQ_COUNTS], nullptr);
+                                         });
+}
+
 // FrameKDMap::GetPtCloud (:490-515) for one scene: the obstacle points of its query frames, in query-vector order, from the
 // pool's index-ordered planes (kd_sweep.hip: pool_planes -- written by every build, compacted by every sweep).  Synchronises.
 int amk_kfmap_points_host(amk_kfmap *m, int scene, float *h_xyz, long long capacity_points, int *h_frame_sizes, long long *n_points_out) {

@@ -56,8 +56,11 @@ __device__ __forceinline__ void frame_list(const GridScene &gs, const ExactPtrs 
 // frame's entries are offered best first, an entry ranks behind every kept one at the same or a smaller distance (kept entries came
 // from an earlier frame or are earlier neighbours of this one: the tie rule), and the fold ends at the first entry that ranks
 // behind the k-th kept one.  WITH_T (the segment search): every entry carries a further payload, its t (nt in the frame's list, rt
-// in the running one); without it the two are never touched and the code is what it was.
-template <bool WITH_T = false>
+// in the running one); without it the two are never touched and the code is what it was.  USER tells apart instantiations that are
+// otherwise the same function: map_segment_nearest_kernel folds through <true, 1>, because a second caller of <true> changed the
+// scalar registers the compiler gives map_segment_kernel (97 / 103 -> 95 / 101 SGPRs), and a new query leaves the old kernels'
+// code as it was.
+template <bool WITH_T = false, int USER = 0>
 __device__ __forceinline__ void fold_frame_list(double nd, const float4 &rec, int f, int k, int lane, double &rd, float &rx, float &ry,
                                                 float &rz, int &rf, double nt = 0.0, double *rt = nullptr) {
     for (int e = 0; e < k; ++e) {     // this frame's entries, best first
@@ -349,6 +352,65 @@ int launch_segment(const QueryFrames &qf, int S, const double *d_path, int point
     return AMK_OK;
 }
 
+// Segment nearest over the frames (amk_kfmap_segment_nearest / amk_kd_segment_nearest_frames): one wavefront per (scene, leg) walks
+// every frame its scene holds with grid_segment_knn and folds each frame's k nearest into the running list with their t, as
+// map_segment_kernel does (equal distances keep the earlier frame, then the lower index within a frame).  Every frame's walk
+// starts unbounded: the k nearest of all frames are among the frames' own k nearest, whatever the other frames hold.  The count is
+// min(k, sum of the frames' kept entries) = min(k, sum of their usable points).
+template <bool MAP>
+__global__ __launch_bounds__(256) void map_segment_nearest_kernel(QueryFrames qf, int n_scenes, const double *__restrict__ path,
+                                                                  int point_stride, int n_points, int k, float *__restrict__ out_pts,
+                                                                  double *__restrict__ out_d2, double *__restrict__ out_t,
+                                                                  int *__restrict__ out_frame, int *__restrict__ out_cnt) {
+    __shared__ GridWaveLds wl[4];
+    const int n_legs = n_points - 1;
+    const WaveSlot ws = wave_slot(n_legs);
+    const int s = ws.s, w = ws.w, lane = ws.lane, q = ws.unit;
+    if (s >= n_scenes || q >= n_legs) return;
+    const double *pa = path + ((size_t)s * n_points + q) * point_stride;
+    const SegLeg leg = seg_leg(pa, pa + point_stride);
+    const size_t row = (size_t)s * n_legs + q;
+    const int F = MAP ? qf.map.held(s, lane) : qf.map.n;
+    const GridPtrs pool = qf.g[0];   // (map mode: one set of pool pointers stays live over the loop)
+    double rd = DBL_MAX, rt = 0.0;   // the running list: lane i < k holds the i-th best (distance, t, point, frame) so far
+    float rx = 0.f, ry = 0.f, rz = 0.f;
+    int rf = -1, cnt = 0;
+    for (int f = 0; f < F; ++f) {
+        const int m = MAP ? qf.map.pool_scene(f, s) : s;
+        if (m < 0) continue;         // (map mode: this scene's map has no frame f)
+        const GridScene gs = (MAP ? pool : qf.g[f]).scene(m);
+        double ld, lt;
+        int li, lpos;
+        cnt += grid_segment_knn(gs, leg, k, ld, li, lpos, lt, &wl[w]);
+        const float4 rec = gs.pt[lpos];   // (lpos = 0 for empty slots: a valid address)
+        fold_frame_list<true, 1>((lane < k && li != kNoIndex) ? ld : DBL_MAX, rec, f, k, lane, rd, rx, ry, rz, rf, lt, &rt);
+    }
+    if (lane == 0 && out_cnt) out_cnt[row] = min(cnt, k);
+    if (lane < k) {
+        const bool ok = rd < DBL_MAX;
+        const size_t o = row * k + lane;
+        if (out_d2) out_d2[o] = ok ? rd : DBL_MAX;
+        if (out_t) out_t[o] = ok ? rt : 0.0;
+        if (out_frame) out_frame[o] = ok ? rf : -1;
+        if (out_pts) {
+            out_pts[o * 3 + 0] = ok ? rx : 0.f;
+            out_pts[o * 3 + 1] = ok ? ry : 0.f;
+            out_pts[o * 3 + 2] = ok ? rz : 0.f;
+        }
+    }
+}
+
+int launch_segment_nearest(const QueryFrames &qf, int S, const double *d_path, int point_stride, int n_points, int k, float *d_pts,
+                           double *d_sqdist, double *d_t, int *d_frame, int *d_counts, hipStream_t stream) {
+    const long long blocks = search_blocks(S, n_points - 1);
+    if (blocks > 0x7fffffffll) return AMK_ERR_UNSUPPORTED;
+    auto kernel = qf.map.fmap ? map_segment_nearest_kernel<true> : map_segment_nearest_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, stream, qf, S, d_path, point_stride, n_points, k, d_pts, d_sqdist,
+                       d_t, d_frame, d_counts);
+    AMK_HIP(hipGetLastError());
+    return AMK_OK;
+}
+
 }  // namespace
 
 namespace amk {
@@ -394,6 +456,15 @@ int map_segment_search(amk_kd *pool, int n_frames, const int *d_fmap, int S, con
         return st;
     return launch_segment(frames_of_pool(pool, n_frames, d_fmap, S), S, d_path, point_stride, n_points, radius_sq, max_results, d_pts,
                           d_sqdist, d_t, d_frame, d_counts, stream);
+}
+int map_segment_nearest(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_path, int point_stride, int n_points, int k,
+                        float *d_pts, double *d_sqdist, double *d_t, int *d_frame, int *d_counts, hipStream_t stream) {
+    if (!pool || !d_fmap || n_frames < 1 || S < 1) return AMK_ERR_INVALID_ARG;
+    if (const int st = segment_nearest_args_status(d_path, point_stride, n_points, k, d_pts || d_sqdist || d_t || d_frame || d_counts);
+        st != AMK_OK)
+        return st;
+    return launch_segment_nearest(frames_of_pool(pool, n_frames, d_fmap, S), S, d_path, point_stride, n_points, k, d_pts, d_sqdist, d_t,
+                                  d_frame, d_counts, stream);
 }
 }  // namespace amk
 
@@ -492,6 +563,32 @@ int amk_kd_segment_search_frames_host(amk_kd *const *frames, int n_frames, const
                                                                          radius_sq, max_results, d[amk::MQ_PTS], d[amk::MQ_SQDIST],
                                                                          d[amk::MQ_DIST], d[amk::MQ_FRAME], d[amk::MQ_COUNTS], nullptr);
                                  });
+}
+
+int amk_kd_segment_nearest_frames(amk_kd *const *frames, int n_frames, const double *d_path, int point_stride, int n_points, int k,
+                                  float *d_pts, double *d_sqdist, double *d_t, int *d_frame, int *d_counts, void *stream) {
+    if (const int st = segment_nearest_args_status(d_path, point_stride, n_points, k, d_pts || d_sqdist || d_t || d_frame || d_counts);
+        st != AMK_OK)
+        return st;
+    QueryFrames qf;
+    int S = 0;
+    if (const int st = frames_of_handles(frames, n_frames, qf, S, false); st != AMK_OK) return st;
+    return launch_segment_nearest(qf, S, d_path, point_stride, n_points, k, d_pts, d_sqdist, d_t, d_frame, d_counts, (hipStream_t)stream);
+}
+
+int amk_kd_segment_nearest_frames_host(amk_kd *const *frames, int n_frames, const double *h_path, int point_stride, int n_points, int k,
+                                       float *h_pts, double *h_sqdist, double *h_t, int *h_frame, int *h_counts) {
+    QueryFrames qf;
+    int S = 0;
+    if (const int st = frames_of_handles(frames, n_frames, qf, S, false); st != AMK_OK) return st;
+    amk::HostStage stage;   // frees at return: these frames belong to no one handle
+    return amk::map_segment_nearest_host(stage, S, h_path, point_stride, n_points, k, h_pts, h_sqdist, h_t, h_frame, h_counts,
+                                         [&](const amk::HostStage::Dev *d) {
+                                             return amk_kd_segment_nearest_frames(frames, n_frames, d[amk::MQ_QUERIES], point_stride,
+                                                                                  n_points, k, d[amk::MQ_PTS], d[amk::MQ_SQDIST],
+                                                                                  d[amk::MQ_DIST], d[amk::MQ_FRAME], d[amk::MQ_COUNTS],
+                                                                                  nullptr);
+                                         });
 }
 
 }  // extern "C"

@@ -183,6 +183,36 @@ class KdBatch:
                                                        lst(d2), lst(t), lst(pts), vp(cnt)), "amk_kd_segment_search_host")
         return dict(indices=idx, sqdist=d2, t=t, pts=pts, counts=cnt)
 
+    def segment_nearest(self, path, k, want_pts=True, stream=None, out=None):
+        """amk_kd_segment_nearest: the k usable points closest to every leg of a path, float64 [S, n_points >= 2, >= 3], no radius:
+        ascending, ties by cloud index, t = where along the leg (0 .. 1) each comes closest; counts [S, n_legs] = min(k, usable
+        points of the scene), empty slots -1 / DBL_MAX / 0.  The lists are those of segment_search(path, inf, k), bit for bit.
+        -> dict(indices, sqdist, t, pts, counts)"""
+        P, stride = _check_path(path, self.S)
+        k, dev, L = int(k), path.device, P - 1
+        if out is None:
+            out = dict(indices=torch.empty((self.S, L, k), dtype=torch.int32, device=dev),
+                       sqdist=torch.empty((self.S, L, k), dtype=torch.float64, device=dev),
+                       t=torch.empty((self.S, L, k), dtype=torch.float64, device=dev),
+                       pts=torch.empty((self.S, L, k, 3), dtype=torch.float32, device=dev) if want_pts else None,
+                       counts=torch.empty((self.S, L), dtype=torch.int32, device=dev))
+        capi.check(self.lib.amk_kd_segment_nearest(self.h, capi.dptr(path), stride, P, k, capi.dptr(out["indices"]),
+                                                   capi.dptr(out["sqdist"]), capi.dptr(out["t"]), capi.dptr(out["pts"]),
+                                                   capi.dptr(out["counts"]), _stream_arg(stream)), "amk_kd_segment_nearest")
+        return out
+
+    def segment_nearest_host(self, path, k):
+        """amk_kd_segment_nearest_host: segment_nearest with numpy buffers (path [S, n_points, >= 3]); synchronises."""
+        p = np.ascontiguousarray(path, np.float64)
+        assert p.ndim == 3 and p.shape[0] == self.S and p.shape[2] >= 3
+        L, k = p.shape[1] - 1, int(k)
+        idx = np.zeros((self.S, L, k), np.int32); d2 = np.zeros((self.S, L, k), np.float64); t = np.zeros((self.S, L, k), np.float64)
+        pts = np.zeros((self.S, L, k, 3), np.float32); cnt = np.zeros((self.S, L), np.int32)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        capi.check(self.lib.amk_kd_segment_nearest_host(self.h, vp(p), int(p.shape[2]), int(p.shape[1]), k, vp(idx), vp(d2), vp(t),
+                                                        vp(pts), vp(cnt)), "amk_kd_segment_nearest_host")
+        return dict(indices=idx, sqdist=d2, t=t, pts=pts, counts=cnt)
+
 
 def kd_build_pair(kd_obstacle, xyz, kd_edge, edge_xyz, counts=None, edge_counts=None, stream=None):
     """amk_kd_build_pair: FrameKDMap::AddVertex's two InitializeNew calls as one launch (clouds packed [S, max_points, 3|4])."""
@@ -415,6 +445,22 @@ def segment_search_frames(handles, path, radius_sq, max_results, stream=None, ou
     return out
 
 
+def segment_nearest_frames(handles, path, k, stream=None, out=None):
+    """amk_kd_segment_nearest_frames: segment nearest over a list of KdBatch handles (obstacle OR edge, index 0 = current frame):
+    per leg the k nearest of all frames by (squared distance, frame, cloud index), counts = min(k, usable points over the frames).
+    -> dict(pts, sqdist, t, frame, counts)"""
+    F, S = len(handles), handles[0].S
+    P, stride = _check_path(path, S)
+    if out is None:
+        out = _segment_out(S, P - 1, int(k), path.device)
+    ha = (C.c_void_p * F)(*[h.h for h in handles])
+    capi.check(capi.load().amk_kd_segment_nearest_frames(ha, F, capi.dptr(path), stride, P, int(k), capi.dptr(out["pts"]),
+                                                         capi.dptr(out["sqdist"]), capi.dptr(out["t"]), capi.dptr(out["frame"]),
+                                                         capi.dptr(out["counts"]), _stream_arg(stream)),
+               "amk_kd_segment_nearest_frames")
+    return out
+
+
 class KfMap:
     """amk_kfmap: FrameKDMap's keyframe list for S scenes on the device (FrameKDMap.cpp:29-74,233-252,428-488)."""
 
@@ -506,6 +552,19 @@ class KfMap:
                                                      capi.dptr(out["pts"]), capi.dptr(out["sqdist"]), capi.dptr(out["t"]),
                                                      capi.dptr(out["frame"]), capi.dptr(out["counts"]), _stream_arg(stream)),
                    "amk_kfmap_segment_search")
+        return out
+
+    def segment_nearest(self, path, k, edge=False, stream=None, out=None):
+        """amk_kfmap_segment_nearest: the k points closest to every leg of a path float64 [S, n_points >= 2, >= 3], over every frame
+        each scene's query vector holds (no radius, no fast path, no frustum test, no size rule): the nearest k by (squared distance,
+        frame, cloud index) with t, the position of the closest approach along the leg; counts = min(k, usable points over the frames).
+        -> dict(pts [S,L,k,3] f32, sqdist, t [S,L,k] f64, frame [S,L,k] i32, counts [S,L] i32), L = n_points - 1"""
+        P, stride = _check_path(path, self.S)
+        if out is None:
+            out = _segment_out(self.S, P - 1, int(k), path.device)
+        capi.check(self.lib.amk_kfmap_segment_nearest(self.h, capi.dptr(path), stride, P, int(k), int(bool(edge)), capi.dptr(out["pts"]),
+                                                      capi.dptr(out["sqdist"]), capi.dptr(out["t"]), capi.dptr(out["frame"]),
+                                                      capi.dptr(out["counts"]), _stream_arg(stream)), "amk_kfmap_segment_nearest")
         return out
 
     def nearest_distance(self, queries, stream=None, out=None):

@@ -284,6 +284,36 @@ int amk_kd_segment_search(amk_kd *kd, const double *d_path, int point_stride, in
 int amk_kd_segment_search_host(amk_kd *kd, const double *h_path, int point_stride, int n_points, double radius_sq,
                                int max_results, int *h_indices, double *h_sqdist, double *h_t, float *h_pts, int *h_counts);
 
+/* Segment nearest: the k map points closest to each leg of a path, with no radius to choose.  The segment search answers "what
+ * lies within r of the leg", so a caller that wants the clearance of a leg has to guess r: too small and every count is 0, too
+ * large and the walk reads every record of a wide box to find one point.  This is the unbounded query the segment search does
+ * not offer: per leg the smallest distances to the cloud, as numbers, and where along the leg they occur.
+ * The path's layout, the legs (n_legs = n_points - 1), ab, L2, the one inv per leg, t clamped by comparisons, c = a + t*ab below
+ * 1 and b exactly at 1, and d2 summed left to right in fp64 with contraction off are exactly those of "Segment search" above.
+ * Per leg the result is the k usable points (d2 < DBL_MAX) with the smallest d2, ascending; equal d2 order by cloud index.
+ *   d_indices [S][n_legs][k] int, d_sqdist and d_t [..][k] double, d_pts [..][k][3] float; d_t is the position of the closest
+ *               approach along the leg (0 at a, 1 at b).
+ *   d_counts    [S][n_legs] int: min(k, usable points of the scene).  Slots beyond the count hold -1 / DBL_MAX / 0.0 / (0,0,0).
+ * A leg with a non-finite coordinate in either endpoint, or with a non-finite L2, gets count 0 and empty slots; a non-finite
+ * path point spoils only the legs that touch it.  An empty or never-built scene answers 0.  A degenerate leg (a == b) has t = 0.
+ * There is no radius, no size rule, no fast path and no PtIsInFrame.  The tie-order modes do not apply, as for radius and segment
+ * results: the exact tree is never consulted, and a handle in AMK_TIES_NANOFLANN / AMK_TIES_AUTO answers like the default.
+ *   k           1 <= k <= AMK_MAX_K.  k < 1, n_points < 2, point_stride < 3, a NULL handle, a NULL path, or every output NULL:
+ *               AMK_ERR_INVALID_ARG.  k > AMK_MAX_K, a scan-mode handle, or a launch grid beyond 2^31 - 1 blocks:
+ *               AMK_ERR_UNSUPPORTED.  Each output may be NULL, but not all of them.
+ * Every error is returned before anything is staged or launched, the outputs untouched.  The call is stream-ordered and
+ * allocates nothing.
+ * Two identities.  (1) The lists equal, bit for bit, those of amk_kd_segment_search called with radius_sq = +inf and
+ * max_results = k; the count is min(k, that search's count).  (2) A degenerate leg at a answers with the distances, indices and
+ * points of amk_kd_search(k) at a, in the default tie order, for a scene holding more than k points; the size rule of
+ * SearchForNearest belongs to amk_kd_search and is absent here (a scene of exactly k points answers all k).
+ * Not offered: per-leg k, a radius cap on the nearest query, segment queries inside amk_step_batch or the pipeline.          */
+int amk_kd_segment_nearest(amk_kd *kd, const double *d_path, int point_stride, int n_points, int k, int *d_indices,
+                           double *d_sqdist, double *d_t, float *d_pts, int *d_counts, void *stream);
+/* Same with host buffers: stages and synchronises exactly as amk_kd_segment_search_host does.                               */
+int amk_kd_segment_nearest_host(amk_kd *kd, const double *h_path, int point_stride, int n_points, int k, int *h_indices,
+                                double *h_sqdist, double *h_t, float *h_pts, int *h_counts);
+
 /* ------------------------------------------------------------------------------------------ */
 /* MPC: batch of ObstacleAvoidanceMPC                          HighLvlMpc.h:4-33, .cpp:5-137    */
 /* ------------------------------------------------------------------------------------------ */
@@ -830,6 +860,27 @@ int amk_kd_segment_search_frames(amk_kd *const *frames, int n_frames, const doub
 int amk_kd_segment_search_frames_host(amk_kd *const *frames, int n_frames, const double *h_path, int point_stride, int n_points,
                                       double radius_sq, int max_results, float *h_pts, double *h_sqdist, double *h_t,
                                       int *h_frame, int *h_counts);
+/* Segment nearest over the frames: amk_kd_segment_nearest (see there: the path, the per-leg result, k, the errors, the two
+ * identities) over every frame a scene holds -- a keyframe map's query vector, or a caller's list of frame handles; no fast path,
+ * no PtIsInFrame, no size rule.  The answer is the k nearest of all frames a scene holds.
+ *   d_pts / d_sqdist / d_t / d_frame [S][n_legs][k]   ascending by d2; equal d2 keep the earlier frame, then the lower index
+ *               within a frame; d_frame is the position in the query vector (0 = current frame), -1 in empty slots, which hold
+ *               (0,0,0) / DBL_MAX / 0.0 otherwise.  Each output may be NULL, not all.
+ *   d_counts [S][n_legs]                  min(k, sum of the frames' usable points)
+ *   query_edge  != 0: the frames' edge clouds, else their obstacle clouds
+ * A map scene with no frame answers 0.  A map in AMK_TIES_NANOFLANN answers like the default.  Scan-mode handles and
+ * n_frames > AMK_MAX_FRAMES return AMK_ERR_UNSUPPORTED before anything is staged or launched.  Stream-ordered, nothing
+ * allocated, no map state changed; ordering against the map's updates as stated for its own queries above.  The *_host variants
+ * stage and synchronise exactly as their segment-search counterparts do.                                                     */
+int amk_kfmap_segment_nearest(amk_kfmap *map, const double *d_path, int point_stride, int n_points, int k, int query_edge,
+                              float *d_pts, double *d_sqdist, double *d_t, int *d_frame, int *d_counts, void *stream);
+int amk_kfmap_segment_nearest_host(amk_kfmap *map, const double *h_path, int point_stride, int n_points, int k, int query_edge,
+                                   float *h_pts, double *h_sqdist, double *h_t, int *h_frame, int *h_counts);
+int amk_kd_segment_nearest_frames(amk_kd *const *frames, int n_frames, const double *d_path, int point_stride, int n_points,
+                                  int k, float *d_pts, double *d_sqdist, double *d_t, int *d_frame, int *d_counts, void *stream);
+int amk_kd_segment_nearest_frames_host(amk_kd *const *frames, int n_frames, const double *h_path, int point_stride,
+                                       int n_points, int k, float *h_pts, double *h_sqdist, double *h_t, int *h_frame,
+                                       int *h_counts);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Scenes sharded over the GPUs of a node (one process per GPU), RCCL over xGMI                 */

@@ -266,6 +266,34 @@ public:
         return count;
     }
 
+    // Not in the reference either: the k points of the map closest to the SEGMENT from -> to, no radius (KDTreeTwo::SegmentNearest
+    // over the frames of the query vector).  Outputs as QuerySegment's: the nearest min(k, points of the map), ascending, with
+    // `params` = t of each; equal distances keep the earlier frame, then the lower index within a frame.  Returns their number.
+    size_t QuerySegmentNearest(const Vector3d &from, const Vector3d &to, int k, std::vector<Vector3d> &nearestPoints,
+                               std::vector<double> &distances, std::vector<double> &params, bool queryEdge = false) {
+        struct PtDists { Vector3d pt; double dist, t; };
+        std::vector<PtDists> pointsDist;
+        std::lock_guard<std::mutex> lock(mMtxKdTree);
+        for (auto &fr : mVecQueryVector) {
+            PtCloudKdPtr pc = queryEdge ? fr.edgeCloud : fr.pointCloud;
+            if (!pc) continue;
+            pc->SegmentNearest(vx(from), vy(from), vz(from), vx(to), vy(to), vz(to), k);
+            for (size_t j = 0; j < pc->squared_distances.size(); ++j)
+                pointsDist.push_back({Vector3d(pc->closest_pts[j].x, pc->closest_pts[j].y, pc->closest_pts[j].z),
+                                      pc->squared_distances[j], pc->segment_t[j]});
+        }
+        nearestPoints.clear();
+        distances.clear();
+        params.clear();
+        std::stable_sort(pointsDist.begin(), pointsDist.end(), [](const PtDists &a, const PtDists &b) { return a.dist < b.dist; });
+        for (int i = 0; i < k && i < (int)pointsDist.size(); ++i) {
+            nearestPoints.push_back(pointsDist[i].pt);
+            distances.push_back(pointsDist[i].dist);
+            params.push_back(pointsDist[i].t);
+        }
+        return distances.size();
+    }
+
     // One pass of KeyframeThreadWorker's body (:443-486) -- the caller owns the 30 ms cadence and the
     // "new frame arrived" flag.  dronePos / bodyX: translation of Twb = Twc * Tbc^-1 and the world
     // direction of the body x axis (first column of Rwb), what DroneBehindPts (:233-252) derives.

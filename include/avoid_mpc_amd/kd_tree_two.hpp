@@ -186,6 +186,30 @@ public:
         }
         return (size_t)count;
     }
+    // Not in the reference either: the n points of this tree closest to the SEGMENT a -> b, no radius (amk_kd_segment_nearest, see
+    // the C header).  Returns how many were found, min(n, usable points) -- no size rule: a tree of exactly n points answers all n --
+    // and fills closest_pts / squared_distances / indices / segment_t with them, ascending, equal distances by index.
+    size_t SegmentNearest(num_t ax, num_t ay, num_t az, num_t bx, num_t by, num_t bz, int n) {
+        closest_pts.clear();
+        squared_distances.clear();
+        indices.clear();
+        segment_t.clear();
+        if (cloud.pts.size() == 0) return 0;
+        if (n < 1 || n > AMK_MAX_K) throw std::runtime_error("KDTreeTwo::SegmentNearest: n outside [1, AMK_MAX_K]");
+        const double path[6] = {(double)ax, (double)ay, (double)az, (double)bx, (double)by, (double)bz};
+        std::vector<int> idx(n);
+        std::vector<double> d2(n), t(n);
+        int count = 0;
+        amk_throw(amk_kd_segment_nearest_host(kd_, path, 3, 2, n, idx.data(), d2.data(), t.data(), nullptr, &count),
+                  "amk_kd_segment_nearest_host");
+        for (int i = 0; i < n && i < count; i++) {
+            closest_pts.push_back(cloud.pts[idx[i]]);
+            squared_distances.push_back((num_t)d2[i]);
+            indices.push_back(idx[i]);
+            segment_t.push_back(t[i]);
+        }
+        return (size_t)count;
+    }
     PointCloudTwo<num_t> const &GetPointCloud() { return cloud; }
     std::vector<int> const &GetColors() { return colors; }
     amk_kd *handle() { return kd_; }  // for batched / fused use through the C ABI
