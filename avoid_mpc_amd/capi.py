@@ -45,6 +45,8 @@ SYMBOLS = [
     "amk_kd_segment_search_frames", "amk_kd_segment_search_frames_host",
     "amk_kd_segment_nearest", "amk_kd_segment_nearest_host", "amk_kfmap_segment_nearest", "amk_kfmap_segment_nearest_host",
     "amk_kd_segment_nearest_frames", "amk_kd_segment_nearest_frames_host",
+    "amk_kd_segment_cast", "amk_kd_segment_cast_host", "amk_kfmap_segment_cast", "amk_kfmap_segment_cast_host",
+    "amk_kd_segment_cast_frames", "amk_kd_segment_cast_frames_host",
     "amk_mpc_set_drone_accel_limits", "amk_mpc_set_solver_options", "amk_mpc_set_solve_budget", "amk_mpc_set_precision", "amk_mpc_solve",
     "amk_mpc_get_warm_start", "amk_mpc_set_warm_start", "amk_mpc_reset_warm_start",
     "amk_mpc_solve_host", "amk_mpc_ng", "amk_mpc_jac_nnz", "amk_mpc_hess_nnz", "amk_mpc_jac_sparsity",
@@ -252,6 +254,12 @@ def load():
         "amk_kfmap_segment_nearest_host": (i, [vp, vp, i, i, i, i, vp, vp, vp, vp, vp]),
         "amk_kd_segment_nearest_frames": (i, [vp, i, vp, i, i, i, vp, vp, vp, vp, vp, vp]),
         "amk_kd_segment_nearest_frames_host": (i, [vp, i, vp, i, i, i, vp, vp, vp, vp, vp]),
+        "amk_kd_segment_cast": (i, [vp, vp, i, i, d, vp, vp, vp, vp, vp]),
+        "amk_kd_segment_cast_host": (i, [vp, vp, i, i, d, vp, vp, vp, vp]),
+        "amk_kfmap_segment_cast": (i, [vp, vp, i, i, d, i, vp, vp, vp, vp, vp]),
+        "amk_kfmap_segment_cast_host": (i, [vp, vp, i, i, d, i, vp, vp, vp, vp]),
+        "amk_kd_segment_cast_frames": (i, [vp, i, vp, i, i, d, vp, vp, vp, vp, vp]),
+        "amk_kd_segment_cast_frames_host": (i, [vp, i, vp, i, i, d, vp, vp, vp, vp]),
         "amk_shard_scene_range": (i, [i, i, i, C.POINTER(i), C.POINTER(i)]),
         "amk_shard_unique_id": (i, [C.c_char_p]),
         "amk_shard_create": (i, [C.c_char_p, i, i, C.POINTER(vp)]),

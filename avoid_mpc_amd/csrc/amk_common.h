@@ -269,6 +269,26 @@ int map_segment_nearest_host(HostStage &stage, int S, const double *h_path, int 
         return st;
     return map_segment_host(stage, S, h_path, point_stride, n_points, DBL_MAX, k, h_pts, h_sqdist, h_t, h_frame, h_counts, launch);
 }
+// kd_segment_cast.hip / map_query.hip / kfmap.hip: the argument rules all six segment-cast entries share
+// (include/avoid_mpc_amd.h, "Segment cast"), checked before anything is staged or launched: the segment search's path and radius
+// rules, no max_results.  any_out: an output at all
+inline int segment_cast_args_status(const double *path, int point_stride, int n_points, double radius_sq, bool any_out) {
+    if (n_points < 2 || !query_args_ok(path, point_stride, n_points) || !(radius_sq >= 0.0) || !any_out) return AMK_ERR_INVALID_ARG;
+    return AMK_OK;
+}
+// map_query.hip, for kfmap.hip: the segment cast over a pool
+int map_segment_cast(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_path, int point_stride, int n_points,
+                     double radius_sq, int *d_hit, double *d_t, float *d_pts, int *d_frame, hipStream_t stream);
+// The *_host variants of the map's segment casts: map_segment_host as it is with one result per leg -- hit in MQ_COUNTS, t in
+// MQ_DIST, no squared distance -- under the rules above
+template <class Launch>
+int map_segment_cast_host(HostStage &stage, int S, const double *h_path, int point_stride, int n_points, double radius_sq, int *h_hit,
+                          double *h_t, float *h_pts, int *h_frame, Launch &&launch) {
+    if (const int st = segment_cast_args_status(h_path, point_stride, n_points, radius_sq, h_hit || h_t || h_pts || h_frame);
+        st != AMK_OK)
+        return st;
+    return map_segment_host(stage, S, h_path, point_stride, n_points, radius_sq, 1, h_pts, nullptr, h_t, h_frame, h_hit, launch);
+}
 // kfmap.hip, for pipeline.hip: AddVertex for the frames of a gang (see there)
 int kfmap_add_vertex_gang(amk_kfmap *m, int n_frames, int frame_scenes, const float *const *d_xyz, const int *const *d_counts,
                           const float *const *d_edge_xyz, const int *const *d_edge_counts, int point_stride, const double *const *d_Twc,

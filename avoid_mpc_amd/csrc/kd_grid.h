@@ -1265,6 +1265,192 @@ __device__ __forceinline__ int grid_segment_knn(const GridScene &gs, const SegLe
     return __popcll(__ballot(lane < k && li != kNoIndex));
 }
 
+// Segment cast (include/avoid_mpc_amd.h, "Segment cast"): where along the leg a sphere of squared radius r2, its centre moving
+// a -> b, first touches the stored point p.  fp64 with contraction off, sums left to right; q is sq_dist(a, p) bit for bit, L2 the
+// squared length seg_leg formed (the same expression, the same bits), inv the leg's one reciprocal.  True when p is usable
+// (q < DBL_MAX) and the contact counts; t = 0 for a point inside the sphere at the start, else the smaller root of
+// |a + t ab - p|^2 = r2.  Every test is strict: a grazing pass (disc == 0), a contact that would begin at b (t == 1), NaN and
+// inf - inf give none.  A degenerate leg has dot == 0 and never uses inv.
+__device__ __forceinline__ double seg_leg_l2(const SegLeg &g) {
+#pragma clang fp contract(off)
+    return (g.ab[0] * g.ab[0] + g.ab[1] * g.ab[1]) + g.ab[2] * g.ab[2];
+}
+__device__ __forceinline__ bool seg_contact(const SegLeg &g, double L2, double r2, float px, float py, float pz, double &t) {
+#pragma clang fp contract(off)
+    const double ap0 = (double)px - g.a[0], ap1 = (double)py - g.a[1], ap2 = (double)pz - g.a[2];
+    const double q = (ap0 * ap0 + ap1 * ap1) + ap2 * ap2;
+    const double dot = (ap0 * g.ab[0] + ap1 * g.ab[1]) + ap2 * g.ab[2];
+    const double c = q - r2;
+    const double disc = dot * dot - L2 * c;
+    const double tt = (dot - sqrt(disc)) * g.inv;   // (NaN where disc < 0 or the leg is degenerate: never selected)
+    const bool inside = q < r2;
+    t = inside ? 0.0 : tt;
+    return (q < DBL_MAX) & (inside | ((dot > 0.0) & (disc > 0.0) & (tt < 1.0)));
+}
+
+// Segment cast on the bucketed index, one wavefront per leg: of the usable points whose seg_contact begins at t < tcap (strictly;
+// tcap <= 1, and tcap = 1 is the contract's own t < 1) the one with the smallest (t, cloud index).  Returns (in every lane)
+// whether there is one and leaves, wave-uniform, its t in bt, its index in bi and the position of its record in bpos; without
+// one (tcap, kNoIndex, 0).  r2 in [0, DBL_MAX].  A caller that folds frames passes the best t so far as tcap: an equal t in a later
+// frame does not displace it, and the walk of that frame ends where nothing can begin earlier.
+//
+// The walk follows the leg instead of filling its bounding box, and it ends at the first contact.  The leg is cut at
+// t_0 = 0 < t_1 < ... < t_n = 1, t_i = fl(i * fl(1 / n)), into n sub-legs, n = the leg's extent on its dominant axis in cell edges,
+// rounded up -- but no more than 1 + the cells it crosses on the three axes together (a leg beyond the sampled bounding box crosses
+// none: it sits in the clamped boundary cells) and at most 1024.  Slab i is the cell box [cell_of(lo_i - rho), cell_of(hi_i + rho)]
+// per axis, [lo_i, hi_i] the bounding box of P_i = fl(a + t_i ab) and P_{i+1} (P_n = b).  Its (row, tile) items go one per lane, 64
+// at a time, through grid_knn's announce / running-max windows; every record is evaluated against the WHOLE leg, every lane keeps
+// its own least (t, index), and the lanes are reduced once per slab.  A row of slab i leaves out the cells slab i - 1 held: those
+// were evaluated (by induction every cell of every earlier slab was), and because the boxes move one way along every axis what
+// remains is one run at the row's leading end; were the previous box ever to lie strictly inside the run, the run is read whole.
+// A point seen twice changes nothing: the result is a minimum.
+//
+// Who sees a point (u = 2^-53).  Let T be the COMPUTED t of a point that counts, 0 <= T < 1 (s = sqrt(disc) <= dot, since
+// sqrt(fl(x * x)) = x and L2 c >= 0).  T = 0 by q < r2: |p_i - a_i| < sqrt(r2) (1 + 4u) on every axis, and a = P_0.  Otherwise
+// T L2 = (dot - s)(1 + 3u'), and |a + T ab - p|^2 = q - (dot^2 - (dot - T L2)^2) / L2 with (dot - T L2)^2 = disc + 8u' dot^2 and
+// disc = dot^2 - L2 c + 2u' dot^2 + 3u' L2 c, c = (q - r2)(1 + u'): together |a + T ab - p|^2 = r2 + 15u' q, as dot^2 <= L2 q
+// (1 + 4u).  So p lies within sqrt(r2) + 4.2e-8 |p - a| of the centre at T, and |p - a| <= (1 + 1e-7)(sqrt(r2) + |ab|): within
+// sqrt(r2) + 5e-8 (sqrt(r2) + sum |ab_i|) on every axis.  The centre a + T ab lies between the real a + t_j ab and a + t_{j+1} ab
+// for the j with t_j <= T <= t_{j+1} (the t_i are monotone and cover [0, 1]), and the computed P differ from those by at most
+// 2u (|a_i| + |ab_i|), b from a + ab by u |b_i|.  With
+//   rho = sqrt(r2) (1 + 1e-12) + slack + 1e-7 (sqrt(r2) + sum |ab_i|),  slack = 1e-9 h + 1e-12 (sum |a_i| + sum |b_i| + sum |bbmin_i|)
+// -- the siblings' slack, here more than 1000 times those roundings, and twice the 5e-8 -- p lies in [lo_j - rho, hi_j + rho] on
+// every axis.  No cell face enters: a record of cell i has cell_of(p) = i, the box is found through the same cell_of, and cell_of
+// is monotone in p, every rounding step and the clamp included, so lo <= p <= hi gives cell_of(lo) <= cell_of(p) <= cell_of(hi).
+// A point the sampled bounding box missed sits clamped in a boundary cell and is found like any other; no boundary face bounds
+// the walk or ends it.
+//
+// The stop bound.  After slab i every point with T <= t_{i+1} has been seen: T lies in some [t_j, t_{j+1}] with j <= i.  An
+// unseen point therefore has T > t_{i+1}, as computed numbers, and all the slack above went into rho: the walk ends as soon as
+// best <= t_{i+1}, best being the least t found so far, tcap to begin with.  Not strictly: an unseen point is strictly later, so it
+// can neither win nor tie.  A contact at t = 0 ends the walk after slab 0; a leg without contact walks all n slabs.
+__device__ __forceinline__ bool grid_cast(const GridScene &gs, const SegLeg &leg, double r2, double tcap, double &bt, int &bi,
+                                          int &bpos, GridWaveLds *ws) {
+    const int lane = threadIdx.x & 63;
+    const double b[3] = {gs.gp[0], gs.gp[1], gs.gp[2]};
+    const double h = gs.gp[3], inv_h = gs.gp[4];
+    const int g[3] = {(int)gs.gp[5], (int)gs.gp[6], (int)gs.gp[7]};
+    bt = tcap;
+    bi = kNoIndex;
+    bpos = 0;
+    if (!leg.ok || g[0] * g[1] * g[2] <= 0 || !(tcap > 0.0)) return false;   // (wave-uniform; no t is below 0)
+    const double L2 = seg_leg_l2(leg);
+    const double slack = 1e-9 * h + 1e-12 * (fabs(leg.a[0]) + fabs(leg.a[1]) + fabs(leg.a[2]) + fabs(leg.b[0]) + fabs(leg.b[1]) +
+                                             fabs(leg.b[2]) + fabs(b[0]) + fabs(b[1]) + fabs(b[2]));
+    const double rad = sqrt(r2);
+    const double rho = rad * (1.0 + 1e-12) + slack + 1e-7 * (rad + fabs(leg.ab[0]) + fabs(leg.ab[1]) + fabs(leg.ab[2]));
+    int span = 0;
+    double amax = 0.0;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        span += abs(cell_of(leg.b[a], b[a], inv_h, g[a]) - cell_of(leg.a[a], b[a], inv_h, g[a]));
+        amax = fmax(amax, fabs(leg.ab[a]));
+    }
+    const int n = max(1, min((int)fmin(ceil(amax * inv_h), 1024.0), span + 1));
+    const double inv_n = 1.0 / (double)n;
+    double lt = tcap;      // this lane's least (t, index, record) so far
+    int li = kNoIndex, lpos = 0;
+    double best = tcap;    // the least t of all lanes after the last slab
+    int win = 0;           // number of the candidate window being fetched (tags ws->mark)
+    ws->mark[lane] = 0;
+    double p0[3] = {leg.a[0], leg.a[1], leg.a[2]};
+    int plo[3] = {0, 0, 0}, phi[3] = {-1, -1, -1};   // the cell box of the previous slab (none yet)
+    for (int i = 0; i < n; ++i) {
+        const double t1 = i + 1 < n ? (double)(i + 1) * inv_n : 1.0;
+        double p1[3];
+        int lo[3], hi[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            p1[a] = i + 1 < n ? leg.a[a] + t1 * leg.ab[a] : leg.b[a];
+            lo[a] = cell_of(fmin(p0[a], p1[a]) - rho, b[a], inv_h, g[a]);
+            hi[a] = cell_of(fmax(p0[a], p1[a]) + rho, b[a], inv_h, g[a]);
+        }
+        const int ny = hi[1] - lo[1] + 1, nz = hi[2] - lo[2] + 1;
+        const int nitems = ny * nz * gs.nt;
+        // item -> (row, tile) and row -> (iy, iz) through float reciprocals, exact while nitems < 4e6 (grid_knn)
+        const float inv_nt = 1.0f / (float)gs.nt, inv_ny = 1.0f / (float)ny;
+        for (int row0 = 0; row0 < nitems; row0 += 64) {
+            const int item = row0 + lane;
+            int sA = 0, lA = 0;
+            if (item < nitems) {
+                const int j = (int)(((float)item + 0.5f) * inv_nt);
+                const int *cst = gs.cs + (size_t)(item - j * gs.nt) * (kGridMaxCells + 2);
+                const int jz = (int)(((float)j + 0.5f) * inv_ny);
+                const int iy = lo[1] + (j - jz * ny), iz = lo[2] + jz;
+                int x0 = lo[0], x1 = hi[0];
+                if (iy >= plo[1] && iy <= phi[1] && iz >= plo[2] && iz <= phi[2]) {   // the previous slab read [plo, phi] of this row
+                    if (plo[0] <= x0) x0 = max(x0, phi[0] + 1);
+                    else if (phi[0] >= x1) x1 = min(x1, plo[0] - 1);
+                }
+                if (x0 <= x1) {
+                    const int rowbase = (iz * g[1] + iy) * g[0];
+                    sA = cst[rowbase + x0];
+                    lA = cst[rowbase + x1 + 1] - sA;
+                }
+            }
+            if (__ballot(lA > 0) == 0) continue;  // nothing but empty buckets, or cells already read, in these rows
+            // flatten the <= 64 runs into one index space so that every lane gets a point (grid_knn's scheme, one run per item)
+            const int incl = wave_incl_scan_i32(lA);
+            const int total = __builtin_amdgcn_readlane(incl, 63);
+            const int mypre = incl - lA, mylen = lA;
+            ws->item[lane] = make_int4(mypre, lA, sA, 0);
+            auto fetch = [&](int w0, float4 &p4, int &ip) {
+                ++win;
+                const int rel = mypre - w0;
+                // every lane stores (the silent ones into the spare slot) and the wave is fenced before it reads: see grid_knn
+                ws->mark[(mylen > 0 && rel >= 0 && rel < 64) ? rel : 64] = (win << 6) | lane;
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                const unsigned long long before = __ballot(mylen > 0 && mypre <= w0);
+                const int carry = 63 - __clzll((long long)before);   // (w0 < total: some non-empty item holds w0)
+                const int mk = ws->mark[lane];
+                const int o = max(wave_incl_scan_max_i32((mk >> 6) == win ? (mk & 63) + 1 : 0) - 1, carry);
+                const int t = w0 + lane;
+                ip = -1;   // no candidate
+                if (t < total) {
+                    const int4 it = ws->item[o];
+                    ip = it.z + (t - it.x);
+                    p4 = gs.pt[ip];
+                }
+            };
+            float4 p4 = make_float4(0.f, 0.f, 0.f, 0.f), p4n = p4;
+            int ip, ipn = -1;
+            fetch(0, p4, ip);
+            for (int t0 = 0; t0 < total; t0 += 64) {
+                if (t0 + 64 < total) fetch(t0 + 64, p4n, ipn);  // next window in flight while this one is evaluated
+                double tc;
+                const bool hit = seg_contact(leg, L2, r2, p4.x, p4.y, p4.z, tc);
+                const int ic = __float_as_int(p4.w);
+                // strictly below tcap; then the least (t, index) of this lane (lt == tcap until the first one)
+                if (ip >= 0 && hit && tc < tcap && (tc < lt || (tc == lt && ic < li))) {
+                    lt = tc;
+                    li = ic;
+                    lpos = ip;
+                }
+                p4 = p4n;
+                ip = ipn;
+            }
+        }
+        best = grid_wave_min_f64(lt);
+        if (best <= t1) break;   // every unseen point begins after t1 (the bound is derived above)
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            p0[a] = p1[a];
+            plo[a] = lo[a];
+            phi[a] = hi[a];
+        }
+    }
+    if (!(best < tcap)) return false;
+    // the lowest index among the lanes that hold the least t, and the record that goes with it
+    const int imin = grid_wave_min_i32(lt == best ? li : kNoIndex);
+    const int src = __ffsll((long long)__ballot(lt == best && li == imin)) - 1;
+    bt = best;
+    bi = imin;
+    bpos = __builtin_amdgcn_readlane(lpos, src);
+    return true;
+}
+
 // 1-NN squared distance of q, one THREAD per query (the n-queries-on-n-points keyframe sweep,
 // AM/src/FrameKDMap.cpp:466-476): same ring walk and stopping rule as grid_knn with k = 1, scalar per lane.
 // Returns DBL_MAX when the index holds no point with a finite distance to q.

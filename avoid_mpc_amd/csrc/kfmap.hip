@@ -569,6 +569,24 @@ int amk_kfmap_segment_nearest_host(amk_kfmap *m, const double *h_path, int point
                                          });
 }
 
+// Segment cast over the map as it stands (map_query.hip): every frame a scene holds, stream-ordered, no map state changes
+int amk_kfmap_segment_cast(amk_kfmap *m, const double *d_path, int point_stride, int n_points, double radius_sq, int query_edge,
+                           int *d_hit, double *d_t, float *d_pts, int *d_frame, void *stream) {
+    if (!m) return AMK_ERR_INVALID_ARG;
+    return amk::map_segment_cast(query_edge ? m->edge : m->obs, m->F, m->fmap.p, m->S, d_path, point_stride, n_points, radius_sq, d_hit,
+                                 d_t, d_pts, d_frame, (hipStream_t)stream);
+}
+
+int amk_kfmap_segment_cast_host(amk_kfmap *m, const double *h_path, int point_stride, int n_points, double radius_sq, int query_edge,
+                                int *h_hit, double *h_t, float *h_pts, int *h_frame) {
+    if (!m) return AMK_ERR_INVALID_ARG;
+    return amk::map_segment_cast_host(m->stage, m->S, h_path, point_stride, n_points, radius_sq, h_hit, h_t, h_pts, h_frame,
+                                      [&](const HostStage::Dev *d) {
+                                          return amk_kfmap_segment_cast(m, d[MQ_QUERIES], point_stride, n_points, radius_sq, query_edge,
+                                                                        d[MQ_COUNTS], d[MQ_DIST], d[MQ_PTS], d[MQ_FRAME], nullptr);
+                                      });
+}
+
 // FrameKDMap::GetPtCloud (:490-515) for one scene: the obstacle points of its query frames, in query-vector order, from the
 // pool's index-ordered planes (kd_sweep.hip: pool_planes -- written by every build, compacted by every sweep).  Synchronises.
 int amk_kfmap_points_host(amk_kfmap *m, int scene, float *h_xyz, long long capacity_points, int *h_frame_sizes, long long *n_points_out) {

@@ -411,6 +411,63 @@ int launch_segment_nearest(const QueryFrames &qf, int S, const double *d_path, i
     return AMK_OK;
 }
 
+// Segment cast over the frames (amk_kfmap_segment_cast / amk_kd_segment_cast_frames): one wavefront per (scene, leg) walks the
+// frames its scene holds with grid_cast and keeps the least (t, frame, index) -- a plain minimum, no list to fold.  Unlike
+// segment nearest the running best bounds the next frame's walk: grid_cast takes it as tcap, counts only contacts strictly
+// below it (an equal t keeps the earlier frame) and ends that frame's walk where nothing can begin earlier; after a contact at
+// t = 0 the remaining frames are not walked at all.
+template <bool MAP>
+__global__ __launch_bounds__(256) void map_segment_cast_kernel(QueryFrames qf, int n_scenes, const double *__restrict__ path,
+                                                               int point_stride, int n_points, double r2, int *__restrict__ out_hit,
+                                                               double *__restrict__ out_t, float *__restrict__ out_pts,
+                                                               int *__restrict__ out_frame) {
+    __shared__ GridWaveLds wl[4];
+    const int n_legs = n_points - 1;
+    const WaveSlot ws = wave_slot(n_legs);
+    const int s = ws.s, w = ws.w, lane = ws.lane, q = ws.unit;
+    if (s >= n_scenes || q >= n_legs) return;
+    const double *pa = path + ((size_t)s * n_points + q) * point_stride;
+    const SegLeg leg = seg_leg(pa, pa + point_stride);
+    const size_t row = (size_t)s * n_legs + q;
+    const int F = MAP ? qf.map.held(s, lane) : qf.map.n;
+    const GridPtrs pool = qf.g[0];   // (map mode: one set of pool pointers stays live over the loop)
+    double rt = 1.0;                 // the first contact so far (wave-uniform); 1.0: none
+    float rx = 0.f, ry = 0.f, rz = 0.f;
+    int rf = -1;
+    for (int f = 0; f < F && rt > 0.0; ++f) {
+        const int m = MAP ? qf.map.pool_scene(f, s) : s;
+        if (m < 0) continue;         // (map mode: this scene's map has no frame f)
+        const GridScene gs = (MAP ? pool : qf.g[f]).scene(m);
+        double bt;
+        int bi, bpos;
+        if (grid_cast(gs, leg, r2, rt, bt, bi, bpos, &wl[w])) {   // (wave-uniform)
+            const float4 rec = gs.pt[bpos];
+            rt = bt; rx = rec.x; ry = rec.y; rz = rec.z; rf = f;
+        }
+    }
+    if (lane == 0) {
+        if (out_hit) out_hit[row] = rf >= 0 ? 1 : 0;
+        if (out_t) out_t[row] = rt;   // 1.0 without a contact: free all the way
+        if (out_frame) out_frame[row] = rf;
+        if (out_pts) {
+            out_pts[row * 3 + 0] = rx;
+            out_pts[row * 3 + 1] = ry;
+            out_pts[row * 3 + 2] = rz;
+        }
+    }
+}
+
+int launch_segment_cast(const QueryFrames &qf, int S, const double *d_path, int point_stride, int n_points, double radius_sq, int *d_hit,
+                        double *d_t, float *d_pts, int *d_frame, hipStream_t stream) {
+    const long long blocks = search_blocks(S, n_points - 1);
+    if (blocks > 0x7fffffffll) return AMK_ERR_UNSUPPORTED;
+    auto kernel = qf.map.fmap ? map_segment_cast_kernel<true> : map_segment_cast_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, stream, qf, S, d_path, point_stride, n_points,
+                       radius_clamped(radius_sq), d_hit, d_t, d_pts, d_frame);
+    AMK_HIP(hipGetLastError());
+    return AMK_OK;
+}
+
 }  // namespace
 
 namespace amk {
@@ -465,6 +522,14 @@ int map_segment_nearest(amk_kd *pool, int n_frames, const int *d_fmap, int S, co
         return st;
     return launch_segment_nearest(frames_of_pool(pool, n_frames, d_fmap, S), S, d_path, point_stride, n_points, k, d_pts, d_sqdist, d_t,
                                   d_frame, d_counts, stream);
+}
+int map_segment_cast(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_path, int point_stride, int n_points,
+                     double radius_sq, int *d_hit, double *d_t, float *d_pts, int *d_frame, hipStream_t stream) {
+    if (!pool || !d_fmap || n_frames < 1 || S < 1) return AMK_ERR_INVALID_ARG;
+    if (const int st = segment_cast_args_status(d_path, point_stride, n_points, radius_sq, d_hit || d_t || d_pts || d_frame); st != AMK_OK)
+        return st;
+    return launch_segment_cast(frames_of_pool(pool, n_frames, d_fmap, S), S, d_path, point_stride, n_points, radius_sq, d_hit, d_t, d_pts,
+                               d_frame, stream);
 }
 }  // namespace amk
 
@@ -589,6 +654,30 @@ int amk_kd_segment_nearest_frames_host(amk_kd *const *frames, int n_frames, cons
                                                                                   d[amk::MQ_DIST], d[amk::MQ_FRAME], d[amk::MQ_COUNTS],
                                                                                   nullptr);
                                          });
+}
+
+int amk_kd_segment_cast_frames(amk_kd *const *frames, int n_frames, const double *d_path, int point_stride, int n_points,
+                               double radius_sq, int *d_hit, double *d_t, float *d_pts, int *d_frame, void *stream) {
+    if (const int st = segment_cast_args_status(d_path, point_stride, n_points, radius_sq, d_hit || d_t || d_pts || d_frame); st != AMK_OK)
+        return st;
+    QueryFrames qf;
+    int S = 0;
+    if (const int st = frames_of_handles(frames, n_frames, qf, S); st != AMK_OK) return st;
+    return launch_segment_cast(qf, S, d_path, point_stride, n_points, radius_sq, d_hit, d_t, d_pts, d_frame, (hipStream_t)stream);
+}
+
+int amk_kd_segment_cast_frames_host(amk_kd *const *frames, int n_frames, const double *h_path, int point_stride, int n_points,
+                                    double radius_sq, int *h_hit, double *h_t, float *h_pts, int *h_frame) {
+    QueryFrames qf;
+    int S = 0;
+    if (const int st = frames_of_handles(frames, n_frames, qf, S); st != AMK_OK) return st;
+    amk::HostStage stage;   // frees at return: these frames belong to no one handle
+    return amk::map_segment_cast_host(stage, S, h_path, point_stride, n_points, radius_sq, h_hit, h_t, h_pts, h_frame,
+                                      [&](const amk::HostStage::Dev *d) {
+                                          return amk_kd_segment_cast_frames(frames, n_frames, d[amk::MQ_QUERIES], point_stride, n_points,
+                                                                            radius_sq, d[amk::MQ_COUNTS], d[amk::MQ_DIST], d[amk::MQ_PTS],
+                                                                            d[amk::MQ_FRAME], nullptr);
+                                      });
 }
 
 }  // extern "C"

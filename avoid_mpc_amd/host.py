@@ -213,6 +213,39 @@ class KdBatch:
                                                         vp(pts), vp(cnt)), "amk_kd_segment_nearest_host")
         return dict(indices=idx, sqdist=d2, t=t, pts=pts, counts=cnt)
 
+    def segment_cast(self, path, radius_sq, want_pts=True, stream=None, out=None):
+        """amk_kd_segment_cast: the first contact of a sphere of SQUARED radius radius_sq whose centre moves along every leg of a
+        path, float64 [S, n_points >= 2, >= 3]: hit [S, n_legs] 1 / 0, t where along the leg the contact begins (1.0 without one, so
+        t * |ab| is the free distance), the point touched and its cloud index (-1 / (0,0,0) without one); the least t, ties by
+        cloud index.  -> dict(hit, t, pts, indices)"""
+        P, stride = _check_path(path, self.S)
+        dev, L = path.device, P - 1
+        if out is None:
+            out = _cast_out(self.S, L, dev, "indices", want_pts)
+        capi.check(self.lib.amk_kd_segment_cast(self.h, capi.dptr(path), stride, P, float(radius_sq), capi.dptr(out["hit"]),
+                                                capi.dptr(out["t"]), capi.dptr(out["pts"]), capi.dptr(out["indices"]),
+                                                _stream_arg(stream)), "amk_kd_segment_cast")
+        return out
+
+    def segment_cast_host(self, path, radius_sq):
+        """amk_kd_segment_cast_host: segment_cast with numpy buffers (path [S, n_points, >= 3]); synchronises."""
+        p = np.ascontiguousarray(path, np.float64)
+        assert p.ndim == 3 and p.shape[0] == self.S and p.shape[2] >= 3
+        L = p.shape[1] - 1
+        hit = np.zeros((self.S, L), np.int32); t = np.zeros((self.S, L), np.float64)
+        pts = np.zeros((self.S, L, 3), np.float32); idx = np.zeros((self.S, L), np.int32)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        capi.check(self.lib.amk_kd_segment_cast_host(self.h, vp(p), int(p.shape[2]), int(p.shape[1]), float(radius_sq), vp(hit), vp(t),
+                                                     vp(pts), vp(idx)), "amk_kd_segment_cast_host")
+        return dict(hit=hit, t=t, pts=pts, indices=idx)
+
+
+def _cast_out(S, L, dev, which, want_pts=True):
+    """outputs of the segment casts, one result per leg; which: "indices" (one handle) or "frame" (a map, a list of handles)"""
+    return {"hit": torch.empty((S, L), dtype=torch.int32, device=dev), "t": torch.empty((S, L), dtype=torch.float64, device=dev),
+            "pts": torch.empty((S, L, 3), dtype=torch.float32, device=dev) if want_pts else None,
+            which: torch.empty((S, L), dtype=torch.int32, device=dev)}
+
 
 def kd_build_pair(kd_obstacle, xyz, kd_edge, edge_xyz, counts=None, edge_counts=None, stream=None):
     """amk_kd_build_pair: FrameKDMap::AddVertex's two InitializeNew calls as one launch (clouds packed [S, max_points, 3|4])."""
@@ -461,6 +494,20 @@ def segment_nearest_frames(handles, path, k, stream=None, out=None):
     return out
 
 
+def segment_cast_frames(handles, path, radius_sq, stream=None, out=None):
+    """amk_kd_segment_cast_frames: the segment cast over a list of KdBatch handles (obstacle OR edge, index 0 = current frame): per
+    leg the first contact over all frames by (t, frame, cloud index).  -> dict(hit, t, pts, frame)"""
+    F, S = len(handles), handles[0].S
+    P, stride = _check_path(path, S)
+    if out is None:
+        out = _cast_out(S, P - 1, path.device, "frame")
+    ha = (C.c_void_p * F)(*[h.h for h in handles])
+    capi.check(capi.load().amk_kd_segment_cast_frames(ha, F, capi.dptr(path), stride, P, float(radius_sq), capi.dptr(out["hit"]),
+                                                      capi.dptr(out["t"]), capi.dptr(out["pts"]), capi.dptr(out["frame"]),
+                                                      _stream_arg(stream)), "amk_kd_segment_cast_frames")
+    return out
+
+
 class KfMap:
     """amk_kfmap: FrameKDMap's keyframe list for S scenes on the device (FrameKDMap.cpp:29-74,233-252,428-488)."""
 
@@ -565,6 +612,18 @@ class KfMap:
         capi.check(self.lib.amk_kfmap_segment_nearest(self.h, capi.dptr(path), stride, P, int(k), int(bool(edge)), capi.dptr(out["pts"]),
                                                       capi.dptr(out["sqdist"]), capi.dptr(out["t"]), capi.dptr(out["frame"]),
                                                       capi.dptr(out["counts"]), _stream_arg(stream)), "amk_kfmap_segment_nearest")
+        return out
+
+    def segment_cast(self, path, radius_sq, edge=False, stream=None, out=None):
+        """amk_kfmap_segment_cast: the first contact of a sphere of SQUARED radius radius_sq moving along every leg of a path float64
+        [S, n_points >= 2, >= 3], over every frame each scene's query vector holds: the least (t, frame, cloud index); t = 1.0 and
+        frame -1 without a contact.  -> dict(hit [S,L] i32, t [S,L] f64, pts [S,L,3] f32, frame [S,L] i32), L = n_points - 1"""
+        P, stride = _check_path(path, self.S)
+        if out is None:
+            out = _cast_out(self.S, P - 1, path.device, "frame")
+        capi.check(self.lib.amk_kfmap_segment_cast(self.h, capi.dptr(path), stride, P, float(radius_sq), int(bool(edge)),
+                                                   capi.dptr(out["hit"]), capi.dptr(out["t"]), capi.dptr(out["pts"]),
+                                                   capi.dptr(out["frame"]), _stream_arg(stream)), "amk_kfmap_segment_cast")
         return out
 
     def nearest_distance(self, queries, stream=None, out=None):

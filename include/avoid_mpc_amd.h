@@ -314,6 +314,46 @@ int amk_kd_segment_nearest(amk_kd *kd, const double *d_path, int point_stride, i
 int amk_kd_segment_nearest_host(amk_kd *kd, const double *h_path, int point_stride, int n_points, int k, int *h_indices,
                                 double *h_sqdist, double *h_t, float *h_pts, int *h_counts);
 
+/* Segment cast: the first contact of a moving sphere along each leg of a path.  The three queries above order by distance to the
+ * leg; none says how far the vehicle can travel along a line before it loses its clearance, or which obstacle it meets first:
+ * the point closest to the line can stand behind others that are reached earlier.  A sphere of squared radius radius_sq has its
+ * centre at a + t*ab; the answer of a leg is the point it touches first, and the t at which that contact begins.
+ * The path's layout, point_stride, n_points, the legs (n_legs = n_points - 1) and radius_sq (>= 0, not NaN; +inf and anything
+ * >= DBL_MAX are clamped to DBL_MAX) are exactly those of "Segment search" above.  There is no max_results: one contact per leg.
+ * All arithmetic is fp64 with contraction off and sums left to right, as in "Segment search".  Per leg ab, L2 and inv = 1.0 / L2
+ * are exactly those of the segment search.  Per stored point p (float32, widened first), with r2 the clamped radius_sq:
+ *     ap  = p - a;  q = (ap0*ap0 + ap1*ap1) + ap2*ap2           (the squared distance of amk_kd_search at a; usable iff q < DBL_MAX)
+ *     q < r2:  contact at t = 0                                   (already inside at the start)
+ *     else:    dot = (ap0*ab0 + ap1*ab1) + ap2*ab2;  c = q - r2;  disc = dot*dot - L2*c
+ *              contact iff dot > 0 and disc > 0 and t < 1, with t = (dot - sqrt(disc)) * inv
+ * Every test is a strict comparison, so NaN and inf - inf give no contact.  A grazing pass (disc == 0) and a contact that would
+ * begin exactly at b (t == 1) do not count.  This matches the segment search's strict d2 < r2: in exact arithmetic, a cast hits
+ * if and only if the segment search's count is above 0.
+ * The answer of a leg is the usable point with the smallest t; equal t keeps the lower cloud index.
+ *   d_hit       [S][n_legs] int: 1 when the leg has a contact, else 0.
+ *   d_t         [S][n_legs] double: where along the leg the contact begins (0 at a).  A leg without contact holds 1.0 -- free all
+ *               the way -- so t * |ab| is the free distance in both cases.
+ *   d_pts       [S][n_legs][3] float: the point touched, (0,0,0) if none.
+ *   d_indices   [S][n_legs] int: its cloud index (in the NaN-x-filtered cloud, as every index here), -1 if none.
+ * Each output may be NULL, but not all of them.
+ * A degenerate leg (a == b) has dot == 0 and never uses inv.  It hits iff some usable point has q < r2, at t = 0, and returns the
+ * lowest such index, not the nearest such point.  radius_sq >= DBL_MAX (after clamping) puts every usable point inside at the
+ * start.  radius_sq == 0 is allowed and answers by the formula.  A leg with a non-finite coordinate in either endpoint, or with a
+ * non-finite L2, has no contact; a non-finite path point spoils only the one or two legs that touch it.  An empty or never-built
+ * scene answers no contact.  The fp64 sqrt and the one division are correctly rounded on the device, as amk_kd_query_frames
+ * already relies on; there is one reciprocal per leg and no division per candidate.
+ * Errors: a NULL handle, a NULL path, point_stride < 3, n_points < 2, radius_sq < 0 or NaN, or every output NULL:
+ * AMK_ERR_INVALID_ARG.  A scan-mode handle, or a launch grid beyond 2^31 - 1 blocks: AMK_ERR_UNSUPPORTED.  Every error is
+ * returned before anything is staged or launched, the outputs untouched.  The call is stream-ordered and allocates nothing.  No
+ * size rule, no fast path, no PtIsInFrame; the tie-order modes do not apply, as for the three queries above.
+ * Not offered: several contacts per leg, per-leg radii, the first contact over a whole path as one number, casts inside
+ * amk_step_batch or the pipeline; an independent ray is a path of n_points = 2.                                            */
+int amk_kd_segment_cast(amk_kd *kd, const double *d_path, int point_stride, int n_points, double radius_sq, int *d_hit,
+                        double *d_t, float *d_pts, int *d_indices, void *stream);
+/* Same with host buffers: stages and synchronises exactly as amk_kd_segment_search_host does.                               */
+int amk_kd_segment_cast_host(amk_kd *kd, const double *h_path, int point_stride, int n_points, double radius_sq, int *h_hit,
+                             double *h_t, float *h_pts, int *h_indices);
+
 /* ------------------------------------------------------------------------------------------ */
 /* MPC: batch of ObstacleAvoidanceMPC                          HighLvlMpc.h:4-33, .cpp:5-137    */
 /* ------------------------------------------------------------------------------------------ */
@@ -881,6 +921,28 @@ int amk_kd_segment_nearest_frames(amk_kd *const *frames, int n_frames, const dou
 int amk_kd_segment_nearest_frames_host(amk_kd *const *frames, int n_frames, const double *h_path, int point_stride,
                                        int n_points, int k, float *h_pts, double *h_sqdist, double *h_t, int *h_frame,
                                        int *h_counts);
+
+/* Segment cast over the frames: amk_kd_segment_cast (see there: the path, radius_sq, the per-point arithmetic, the strict tests,
+ * the errors) over every frame a scene holds -- a keyframe map's query vector, or a caller's list of frame handles; no fast path,
+ * no PtIsInFrame, no size rule.  The answer of a leg is the usable point of all frames with the smallest t; equal t keeps the
+ * earlier frame, then the lower cloud index within a frame.
+ *   d_hit / d_t [S][n_legs], d_pts [S][n_legs][3]   as for one handle: 1 or 0; where the contact begins, 1.0 without one; the point
+ *               touched, (0,0,0) if none
+ *   d_frame [S][n_legs]                   the frame touched, its position in the query vector (0 = current frame), -1 if none
+ *   query_edge  != 0: the frames' edge clouds, else their obstacle clouds
+ * Each output may be NULL, not all.  A map scene with no frame answers no contact.  A map in AMK_TIES_NANOFLANN answers like the
+ * default.  Scan-mode handles, tie-order handles in the frame list and n_frames > AMK_MAX_FRAMES return AMK_ERR_UNSUPPORTED
+ * before anything is staged or launched.  Stream-ordered, nothing allocated, no map state changed; ordering against the map's
+ * updates as stated for its own queries above.  The *_host variants stage and synchronise exactly as their segment-search
+ * counterparts do.                                                                                                           */
+int amk_kfmap_segment_cast(amk_kfmap *map, const double *d_path, int point_stride, int n_points, double radius_sq, int query_edge,
+                           int *d_hit, double *d_t, float *d_pts, int *d_frame, void *stream);
+int amk_kfmap_segment_cast_host(amk_kfmap *map, const double *h_path, int point_stride, int n_points, double radius_sq,
+                                int query_edge, int *h_hit, double *h_t, float *h_pts, int *h_frame);
+int amk_kd_segment_cast_frames(amk_kd *const *frames, int n_frames, const double *d_path, int point_stride, int n_points,
+                               double radius_sq, int *d_hit, double *d_t, float *d_pts, int *d_frame, void *stream);
+int amk_kd_segment_cast_frames_host(amk_kd *const *frames, int n_frames, const double *h_path, int point_stride, int n_points,
+                                    double radius_sq, int *h_hit, double *h_t, float *h_pts, int *h_frame);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Scenes sharded over the GPUs of a node (one process per GPU), RCCL over xGMI                 */

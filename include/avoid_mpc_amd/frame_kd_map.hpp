@@ -294,6 +294,27 @@ public:
         return distances.size();
     }
 
+    // Not in the reference either: the first point of the map that a sphere of SQUARED radius radius_sq touches while its centre
+    // moves from -> to (KDTreeTwo::SegmentCast over the frames of the query vector).  Returns whether there is a contact; t is
+    // where along the segment it begins (1.0 without one: free all the way) and `point` the point touched; an equal t keeps the
+    // earlier frame, then the lower index within a frame.
+    bool QuerySegmentCast(const Vector3d &from, const Vector3d &to, double radius_sq, Vector3d &point, double &t, bool queryEdge = false) {
+        bool hit = false;
+        t = 1.0;
+        std::lock_guard<std::mutex> lock(mMtxKdTree);
+        for (auto &fr : mVecQueryVector) {
+            PtCloudKdPtr pc = queryEdge ? fr.edgeCloud : fr.pointCloud;
+            if (!pc) continue;
+            double tf = 1.0;
+            if (pc->SegmentCast(vx(from), vy(from), vz(from), vx(to), vy(to), vz(to), radius_sq, tf) && tf < t) {
+                hit = true;
+                t = tf;
+                point = Vector3d(pc->closest_pts[0].x, pc->closest_pts[0].y, pc->closest_pts[0].z);
+            }
+        }
+        return hit;
+    }
+
     // One pass of KeyframeThreadWorker's body (:443-486) -- the caller owns the 30 ms cadence and the
     // "new frame arrived" flag.  dronePos / bodyX: translation of Twb = Twc * Tbc^-1 and the world
     // direction of the body x axis (first column of Rwb), what DroneBehindPts (:233-252) derives.

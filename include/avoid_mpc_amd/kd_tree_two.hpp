@@ -210,6 +210,27 @@ public:
         }
         return (size_t)count;
     }
+    // Not in the reference either: the first point of this tree that a sphere of SQUARED radius radius_sq touches while its centre
+    // moves a -> b (amk_kd_segment_cast, see the C header: every test strict, the least t, equal t by index).  Returns whether
+    // there is a contact; t is where along the segment it begins, 1.0 without one, so t * |b - a| is the free distance either
+    // way.  With a contact closest_pts / indices / segment_t hold that one point; squared_distances stays empty.
+    bool SegmentCast(num_t ax, num_t ay, num_t az, num_t bx, num_t by, num_t bz, double radius_sq, double &t) {
+        closest_pts.clear();
+        squared_distances.clear();
+        indices.clear();
+        segment_t.clear();
+        t = 1.0;
+        if (cloud.pts.size() == 0) return false;
+        const double path[6] = {(double)ax, (double)ay, (double)az, (double)bx, (double)by, (double)bz};
+        int hit = 0, idx = -1;
+        amk_throw(amk_kd_segment_cast_host(kd_, path, 3, 2, radius_sq, &hit, &t, nullptr, &idx), "amk_kd_segment_cast_host");
+        if (hit) {
+            closest_pts.push_back(cloud.pts[idx]);
+            indices.push_back(idx);
+            segment_t.push_back(t);
+        }
+        return hit != 0;
+    }
     PointCloudTwo<num_t> const &GetPointCloud() { return cloud; }
     std::vector<int> const &GetColors() { return colors; }
     amk_kd *handle() { return kd_; }  // for batched / fused use through the C ABI
