@@ -47,6 +47,8 @@ SYMBOLS = [
     "amk_kd_segment_nearest_frames", "amk_kd_segment_nearest_frames_host",
     "amk_kd_segment_cast", "amk_kd_segment_cast_host", "amk_kfmap_segment_cast", "amk_kfmap_segment_cast_host",
     "amk_kd_segment_cast_frames", "amk_kd_segment_cast_frames_host",
+    "amk_kd_path_cast", "amk_kd_path_cast_host", "amk_kfmap_path_cast", "amk_kfmap_path_cast_host",
+    "amk_kd_path_cast_frames", "amk_kd_path_cast_frames_host", "amk_pipeline_set_path_audit", "amk_pipeline_audit_outputs",
     "amk_mpc_set_drone_accel_limits", "amk_mpc_set_solver_options", "amk_mpc_set_solve_budget", "amk_mpc_set_precision", "amk_mpc_solve",
     "amk_mpc_get_warm_start", "amk_mpc_set_warm_start", "amk_mpc_reset_warm_start",
     "amk_mpc_solve_host", "amk_mpc_ng", "amk_mpc_jac_nnz", "amk_mpc_hess_nnz", "amk_mpc_jac_sparsity",
@@ -120,6 +122,7 @@ class FrameCamera(C.Structure):
 
 AMK_DEPTH_U16, AMK_DEPTH_F32 = 0, 1
 AMK_QUEUES_POOLED, AMK_QUEUES_PRIORITY = 0, 1   # amk_pipeline_queue_mode
+AMK_AUDIT_OFF, AMK_AUDIT_REPORT, AMK_AUDIT_SLOW_DOWN = 0, 1, 2   # amk_pipeline_set_path_audit
 AMK_PIPELINE_MAX_OWN_QUEUES = 24
 
 _lib = None
@@ -260,6 +263,14 @@ def load():
         "amk_kfmap_segment_cast_host": (i, [vp, vp, i, i, d, i, vp, vp, vp, vp]),
         "amk_kd_segment_cast_frames": (i, [vp, i, vp, i, i, d, vp, vp, vp, vp, vp]),
         "amk_kd_segment_cast_frames_host": (i, [vp, i, vp, i, i, d, vp, vp, vp, vp]),
+        "amk_kd_path_cast": (i, [vp, vp, i, i, d, vp, vp, vp, vp, vp, vp, vp]),
+        "amk_kd_path_cast_host": (i, [vp, vp, i, i, d, vp, vp, vp, vp, vp, vp]),
+        "amk_kfmap_path_cast": (i, [vp, vp, i, i, d, i, vp, vp, vp, vp, vp, vp, vp]),
+        "amk_kfmap_path_cast_host": (i, [vp, vp, i, i, d, i, vp, vp, vp, vp, vp, vp]),
+        "amk_kd_path_cast_frames": (i, [vp, i, vp, i, i, d, vp, vp, vp, vp, vp, vp, vp]),
+        "amk_kd_path_cast_frames_host": (i, [vp, i, vp, i, i, d, vp, vp, vp, vp, vp, vp]),
+        "amk_pipeline_set_path_audit": (i, [vp, i, d, i]),
+        "amk_pipeline_audit_outputs": (i, [vp, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]),
         "amk_shard_scene_range": (i, [i, i, i, C.POINTER(i), C.POINTER(i)]),
         "amk_shard_unique_id": (i, [C.c_char_p]),
         "amk_shard_create": (i, [C.c_char_p, i, i, C.POINTER(vp)]),

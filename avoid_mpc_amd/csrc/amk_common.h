@@ -289,6 +289,44 @@ int map_segment_cast_host(HostStage &stage, int S, const double *h_path, int poi
         return st;
     return map_segment_host(stage, S, h_path, point_stride, n_points, radius_sq, 1, h_pts, nullptr, h_t, h_frame, h_hit, launch);
 }
+// Path cast (include/avoid_mpc_amd.h, "Path cast"; kd_path_cast.hip / map_query.hip / kfmap.hip): the outputs, a row per SCENE,
+// each null where it is not wanted
+struct PathCastOut {
+    int *stop, *leg;
+    double *t, *free;
+    float *pts;
+    int *id;   // cloud index (one handle) or frame (a map, a list of handles)
+    bool any() const { return stop || leg || t || free || pts || id; }
+};
+// The entries behind the six calls, which the pipeline's audit stage uses as well: the leading n_scenes scenes of the handle (the
+// map), scene s's path at path + s * scene_stride doubles.  The public calls pass every scene and n_points * point_stride.
+int kd_path_cast_scenes(amk_kd *kd, int n_scenes, const double *d_path, int point_stride, long long scene_stride, int n_points,
+                        double radius_sq, const PathCastOut &out, hipStream_t stream);
+int map_path_cast(amk_kd *pool, int n_frames, const int *d_fmap, int S, int n_scenes, const double *d_path, int point_stride,
+                  long long scene_stride, int n_points, double radius_sq, const PathCastOut &out, hipStream_t stream);
+int kfmap_path_cast_scenes(amk_kfmap *m, int n_scenes, const double *d_path, int point_stride, long long scene_stride, int n_points,
+                           double radius_sq, int query_edge, const PathCastOut &out, hipStream_t stream);
+// The *_host variants of the map's path casts: the segment cast's staging (device-wide waits around a launch on the null stream)
+// with one result per scene
+enum PathCastSlot { PC_PATH, PC_STOP, PC_LEG, PC_T, PC_FREE, PC_PTS, PC_ID };
+template <class Launch>
+int map_path_cast_host(HostStage &stage, int S, const double *h_path, int point_stride, int n_points, double radius_sq, int *h_stop,
+                       int *h_leg, double *h_t, double *h_free, float *h_pts, int *h_frame, Launch &&launch) {
+    if (S < 1) return AMK_ERR_INVALID_ARG;
+    if (const int st = segment_cast_args_status(h_path, point_stride, n_points, radius_sq, h_stop || h_leg || h_t || h_free || h_pts || h_frame);
+        st != AMK_OK)
+        return st;
+    const size_t np = ((size_t)S * n_points - 1) * point_stride + 3, rows = (size_t)S;
+    return stage.call({to_device(h_path, sizeof(double) * np), if_given(to_host(h_stop, sizeof(int) * rows)),
+                       if_given(to_host(h_leg, sizeof(int) * rows)), if_given(to_host(h_t, sizeof(double) * rows)),
+                       if_given(to_host(h_free, sizeof(double) * rows)), if_given(to_host(h_pts, sizeof(float) * rows * 3)),
+                       if_given(to_host(h_frame, sizeof(int) * rows))},
+                      [&](const HostStage::Dev *d) {
+                          AMK_HIP(hipDeviceSynchronize());
+                          return launch(d);
+                      },
+                      hipDeviceSynchronize);
+}
 // kfmap.hip, for pipeline.hip: AddVertex for the frames of a gang (see there)
 int kfmap_add_vertex_gang(amk_kfmap *m, int n_frames, int frame_scenes, const float *const *d_xyz, const int *const *d_counts,
                           const float *const *d_edge_xyz, const int *const *d_edge_counts, int point_stride, const double *const *d_Twc,

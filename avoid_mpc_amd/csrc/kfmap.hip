@@ -447,6 +447,14 @@ int kfmap_add_vertex_gang(amk_kfmap *m, int n_frames, int frame_scenes, const fl
     if (st != AMK_OK || m->tie_order != AMK_TIES_NANOFLANN) return st;
     return kd_pool_exact_build(m->obs, m->edge, n, m->out_scene.p, nullptr, stream);   // one launch pair for all G frames
 }
+// amk_kfmap_path_cast over the leading n_scenes scenes of the map, a scene's path every scene_stride doubles (the pipeline's audit
+// of a partly filled gang on the step's x0array)
+int kfmap_path_cast_scenes(amk_kfmap *m, int n_scenes, const double *d_path, int point_stride, long long scene_stride, int n_points,
+                           double radius_sq, int query_edge, const PathCastOut &out, hipStream_t stream) {
+    if (!m) return AMK_ERR_INVALID_ARG;
+    return map_path_cast(query_edge ? m->edge : m->obs, m->F, m->fmap.p, m->S, n_scenes, d_path, point_stride, scene_stride, n_points,
+                         radius_sq, out, stream);
+}
 }  // namespace amk
 extern "C" {
 
@@ -585,6 +593,25 @@ int amk_kfmap_segment_cast_host(amk_kfmap *m, const double *h_path, int point_st
                                           return amk_kfmap_segment_cast(m, d[MQ_QUERIES], point_stride, n_points, radius_sq, query_edge,
                                                                         d[MQ_COUNTS], d[MQ_DIST], d[MQ_PTS], d[MQ_FRAME], nullptr);
                                       });
+}
+
+// Path cast over the map as it stands (map_query.hip): every frame a scene holds, stream-ordered, no map state changes
+int amk_kfmap_path_cast(amk_kfmap *m, const double *d_path, int point_stride, int n_points, double radius_sq, int query_edge,
+                        int *d_stop, int *d_leg, double *d_t, double *d_free, float *d_pts, int *d_frame, void *stream) {
+    if (!m) return AMK_ERR_INVALID_ARG;
+    return amk::kfmap_path_cast_scenes(m, m->S, d_path, point_stride, (long long)n_points * point_stride, n_points, radius_sq, query_edge,
+                                       amk::PathCastOut{d_stop, d_leg, d_t, d_free, d_pts, d_frame}, (hipStream_t)stream);
+}
+
+int amk_kfmap_path_cast_host(amk_kfmap *m, const double *h_path, int point_stride, int n_points, double radius_sq, int query_edge,
+                             int *h_stop, int *h_leg, double *h_t, double *h_free, float *h_pts, int *h_frame) {
+    if (!m) return AMK_ERR_INVALID_ARG;
+    return amk::map_path_cast_host(m->stage, m->S, h_path, point_stride, n_points, radius_sq, h_stop, h_leg, h_t, h_free, h_pts, h_frame,
+                                   [&](const HostStage::Dev *d) {
+                                       return amk_kfmap_path_cast(m, d[amk::PC_PATH], point_stride, n_points, radius_sq, query_edge,
+                                                                  d[amk::PC_STOP], d[amk::PC_LEG], d[amk::PC_T], d[amk::PC_FREE],
+                                                                  d[amk::PC_PTS], d[amk::PC_ID], nullptr);
+                                   });
 }
 
 // FrameKDMap::GetPtCloud (:490-515) for one scene: the obstacle points of its query frames, in query-vector order, from the

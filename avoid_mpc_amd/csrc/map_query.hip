@@ -13,6 +13,7 @@
 // fold of a frame ends at its first entry that ranks behind the k-th kept one -- every later one is no nearer.  On a map whose
 // running list is full of near points a frame that holds nothing nearer costs ONE rank (a ballot and a population count).
 #include "step_common.h"
+#include "kd_path_cast.h"
 
 using namespace amk;
 
@@ -468,9 +469,59 @@ int launch_segment_cast(const QueryFrames &qf, int S, const double *d_path, int 
     return AMK_OK;
 }
 
+// Path cast over the frames (amk_kfmap_path_cast / amk_kd_path_cast_frames): kd_path_cast_kernel's block per scene and rounds
+// (path_cast_scene, kd_path_cast.h, with the barrier rules; the only return before it is the whole-block one), a leg's wave
+// folding the frames exactly as map_segment_cast_kernel does -- the running best t is the next frame's tcap, an equal t keeps the
+// earlier frame, and after a contact at t = 0 the remaining frames are not walked.
+template <bool MAP, int W>
+__global__ __launch_bounds__(64 * W) void map_path_cast_kernel(QueryFrames qf, int n_scenes, const double *__restrict__ path,
+                                                               int point_stride, long long scene_stride, int n_points, double r2,
+                                                               PathCastOut out) {
+    __shared__ PathCastLds<W> lds;
+    const int s = blockIdx.x;
+    if (s >= n_scenes) return;   // (the whole block)
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int F = MAP ? qf.map.held(s, lane) : qf.map.n;
+    const GridPtrs pool = qf.g[0];   // (map mode: one set of pool pointers stays live over the loop)
+    path_cast_scene<W>(s, path + (size_t)s * scene_stride, point_stride, n_points - 1, lds, out,
+                       [&](const SegLeg &leg, double &rt, int &rf, float &rx, float &ry, float &rz) {
+                           rt = 1.0;   // the first contact so far (wave-uniform); 1.0: none
+                           rf = -1;
+                           for (int f = 0; f < F && rt > 0.0; ++f) {
+                               const int m = MAP ? qf.map.pool_scene(f, s) : s;
+                               if (m < 0) continue;   // (map mode: this scene's map has no frame f)
+                               const GridScene gs = (MAP ? pool : qf.g[f]).scene(m);
+                               double bt;
+                               int bi, bpos;
+                               if (grid_cast(gs, leg, r2, rt, bt, bi, bpos, &lds.wl[w])) {   // (wave-uniform)
+                                   const float4 rec = gs.pt[bpos];
+                                   rt = bt; rx = rec.x; ry = rec.y; rz = rec.z; rf = f;
+                               }
+                           }
+                           return rf >= 0;
+                       });
+}
+
+int launch_path_cast(const QueryFrames &qf, int n_scenes, const double *d_path, int point_stride, long long scene_stride, int n_points,
+                     double radius_sq, const PathCastOut &out, hipStream_t stream) {
+    auto kernel = qf.map.fmap ? map_path_cast_kernel<true, kPathCastWaves> : map_path_cast_kernel<false, kPathCastWaves>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n_scenes), dim3(64 * kPathCastWaves), 0, stream, qf, n_scenes, d_path, point_stride,
+                       scene_stride, n_points, radius_clamped(radius_sq), out);
+    AMK_HIP(hipGetLastError());
+    return AMK_OK;
+}
+
 }  // namespace
 
 namespace amk {
+// The path cast over a pool (kfmap.hip, pipeline.hip): the leading n_scenes scenes of a map of S
+int map_path_cast(amk_kd *pool, int n_frames, const int *d_fmap, int S, int n_scenes, const double *d_path, int point_stride,
+                  long long scene_stride, int n_points, double radius_sq, const PathCastOut &out, hipStream_t stream) {
+    if (!pool || !d_fmap || n_frames < 1 || S < 1 || n_scenes < 1 || n_scenes > S || scene_stride < 0) return AMK_ERR_INVALID_ARG;
+    if (const int st = segment_cast_args_status(d_path, point_stride, n_points, radius_sq, out.any()); st != AMK_OK) return st;
+    return launch_path_cast(frames_of_pool(pool, n_frames, d_fmap, S), n_scenes, d_path, point_stride, scene_stride, n_points, radius_sq,
+                            out, stream);
+}
 // The two queries over a keyframe map's pool (kfmap.hip): frame f of scene s = pool scene d_fmap[f * S + s] (< 0: absent).
 int map_query_nearest(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_Twc, const amk_frame_camera *cam,
                       const double *d_queries, int query_stride, int n_queries, int k, float *d_pts, double *d_sqdist, int *d_frame,
@@ -678,6 +729,30 @@ int amk_kd_segment_cast_frames_host(amk_kd *const *frames, int n_frames, const d
                                                                             radius_sq, d[amk::MQ_COUNTS], d[amk::MQ_DIST], d[amk::MQ_PTS],
                                                                             d[amk::MQ_FRAME], nullptr);
                                       });
+}
+
+int amk_kd_path_cast_frames(amk_kd *const *frames, int n_frames, const double *d_path, int point_stride, int n_points, double radius_sq,
+                            int *d_stop, int *d_leg, double *d_t, double *d_free, float *d_pts, int *d_frame, void *stream) {
+    const PathCastOut out{d_stop, d_leg, d_t, d_free, d_pts, d_frame};
+    if (const int st = segment_cast_args_status(d_path, point_stride, n_points, radius_sq, out.any()); st != AMK_OK) return st;
+    QueryFrames qf;
+    int S = 0;
+    if (const int st = frames_of_handles(frames, n_frames, qf, S); st != AMK_OK) return st;
+    return launch_path_cast(qf, S, d_path, point_stride, (long long)n_points * point_stride, n_points, radius_sq, out, (hipStream_t)stream);
+}
+
+int amk_kd_path_cast_frames_host(amk_kd *const *frames, int n_frames, const double *h_path, int point_stride, int n_points,
+                                 double radius_sq, int *h_stop, int *h_leg, double *h_t, double *h_free, float *h_pts, int *h_frame) {
+    QueryFrames qf;
+    int S = 0;
+    if (const int st = frames_of_handles(frames, n_frames, qf, S); st != AMK_OK) return st;
+    amk::HostStage stage;   // frees at return: these frames belong to no one handle
+    return amk::map_path_cast_host(stage, S, h_path, point_stride, n_points, radius_sq, h_stop, h_leg, h_t, h_free, h_pts, h_frame,
+                                   [&](const amk::HostStage::Dev *d) {
+                                       return amk_kd_path_cast_frames(frames, n_frames, d[amk::PC_PATH], point_stride, n_points, radius_sq,
+                                                                      d[amk::PC_STOP], d[amk::PC_LEG], d[amk::PC_T], d[amk::PC_FREE],
+                                                                      d[amk::PC_PTS], d[amk::PC_ID], nullptr);
+                                   });
 }
 
 }  // extern "C"

@@ -53,12 +53,19 @@ struct amk_pipeline {
         amk_kfmap *map = nullptr;       // amk_pipeline_config.keyframes.max_frame_count > 0: the slot's keyframe map (gang x n_scenes scenes)
         int fail_status = AMK_OK;       // the slot's newest launch failed half-way with this status: its frames were dropped, their
                                         // results are undefined; reported by that submit() and by wait() / drain() until the next launch
+        // the trajectory audit's answers, [G S] each (amk_pipeline_set_path_audit allocates them; never freed before destroy)
+        amk::DevBuf<int> audit_stop, audit_leg, audit_src;
+        amk::DevBuf<double> audit_t, audit_free;
+        amk::DevBuf<float> audit_pts;   // [G S][3]
     };
     int depth = 1, gang = 1;
     std::vector<Slot> slots;
     int next = 0;
     long long submitted = 0;
     int inject_failure = 0;             // tests only (amk__pipeline_inject_failure): the next launch fails at this stage
+    int audit_mode = AMK_AUDIT_OFF;     // amk_pipeline_set_path_audit: the stage between the step and the command
+    double audit_radius_sq = 0.0;
+    int audit_points = 0;               // path points audited: n_legs + 1 <= N
 };
 extern "C" int amk__pipeline_queue_policy(int pool, int n_slots, int n_classes, int forced, int *mode_out, int *class_out);
 
@@ -114,6 +121,30 @@ __global__ __launch_bounds__(256) void pipeline_scatter_kernel(const ScatterArgs
             }
             a.cmd[g][i] = v;
         }
+    }
+}
+// AMK_AUDIT_SLOW_DOWN, behind pipeline_scatter_kernel and only then: a scene that the step called safe (flags[0] == 1) but whose
+// audited trajectory stops gets PubSlowDownCmd after all -- the else-branch above, the same expression.  Nothing else is written.
+struct VetoArgs {
+    double *cmd[AMK_PIPELINE_MAX_GANG];   // NULL: not a TASK frame, or no command wanted
+    const double *odom[AMK_PIPELINE_MAX_GANG];
+    const int *flags, *stop;
+    int S;
+    double kp, kd, a_max_xy, a_max_z;
+};
+__global__ __launch_bounds__(256) void pipeline_audit_veto_kernel(const VetoArgs a) {
+#pragma clang fp contract(off)   // the command is compared bit for bit with the host twin (avoid_mpc_amd/flight.py: command)
+    const int g = blockIdx.y;
+    if (!a.cmd[g]) return;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < a.S * 3; i += gridDim.x * 256) {
+        const int s = i / 3, c = i - 3 * s;
+        const size_t gs = (size_t)g * a.S + s;
+        if (!a.flags[gs * 4 + 0] || !a.stop[gs]) continue;   // (not safe: the slow-down command is there already; safe and free: u stays)
+        const double *o = a.odom[g] + (size_t)s * 10;
+        double v = -o[4 + c] * a.kp - o[7 + c] * a.kd + (c == 2 ? 9.8 : 0.0);
+        const double lim = c == 2 ? a.a_max_z : a.a_max_xy;
+        v = fmax(-lim, fmin(lim, v));
+        a.cmd[g][i] = v;
     }
 }
 
@@ -256,7 +287,7 @@ struct Launch {
     bool any_task, any_depth, own_inputs;   // own_inputs: the step reads the slot's contiguous copies (gang 1 without TASK mode: the caller's)
     const amk_pipeline_frame &frame(int g) const { return s.open[g].frame; }
     int wait_for_inputs(), restart_robots(), gather_inputs(), depth_stage();   // the stages, in launch_gang's order
-    int build_indices(Stopwatch &watch), control_step(), finish();
+    int build_indices(Stopwatch &watch), control_step(), path_audit(), finish();
     int ensure_depth_buffers(long long work_bytes), depth_camera(amk_frame_camera *cam);   // (parts of depth_stage and control_step)
 };
 int Launch::wait_for_inputs() {   // inputs produced on the caller's streams: ordered on the device, not by the host
@@ -408,6 +439,15 @@ int Launch::control_step() {
     return amk_step_batch_frames(kd_ob.data(), kd_ed.data(), (int)kd_ob.size(), twc_cur, o.has_camera ? &o.camera : nullptr, s.mpc, &c.step, sq, px,
                                  s.ref_path.p, u, s.x0array.p, s.flags.p, st);
 }
+// The trajectory audit (amk_pipeline_set_path_audit; launch_gang calls it only when the mode is not OFF): the path cast on the
+// step's own x0array -- a scene's path is its first audit_points rows of 14, row 0 = X0 -- over the filled * S leading scenes,
+// against the slot's map as it stands after this period's AddVertex and update, else against its obstacle index
+int Launch::path_audit() {
+    const amk::PathCastOut out{s.audit_stop.p, s.audit_leg.p, s.audit_t.p, s.audit_free.p, s.audit_pts.p, s.audit_src.p};
+    if (s.map)
+        return amk::kfmap_path_cast_scenes(s.map, filled * S, s.x0array.p, 14, (long long)N * 14, p->audit_points, p->audit_radius_sq, 0, out, st);
+    return amk::kd_path_cast_scenes(s.obstacle, filled * S, s.x0array.p, 14, (long long)N * 14, p->audit_points, p->audit_radius_sq, out, st);
+}
 // The controls to where the callers want them (pipeline_scatter_kernel), the completion event, the slot's books
 int Launch::finish() {
     if (own_inputs) {
@@ -423,6 +463,20 @@ int Launch::finish() {
         if (any) {
             hipLaunchKernelGGL(pipeline_scatter_kernel, dim3((sa.n_u + 255) / 256 > 16 ? 16 : (sa.n_u + 255) / 256, filled), dim3(256), 0, st, sa);
             AMK_HIP(hipGetLastError());
+        }
+        if (p->audit_mode == AMK_AUDIT_SLOW_DOWN) {   // the veto, behind the command it overrides
+            VetoArgs va{};
+            bool any_cmd = false;
+            for (int g = 0; g < filled; ++g) {
+                va.cmd[g] = sa.cmd[g]; va.odom[g] = sa.odom[g];
+                any_cmd = any_cmd || va.cmd[g];
+            }
+            va.flags = s.flags.p; va.stop = s.audit_stop.p; va.S = S;
+            va.kp = sa.kp; va.kd = sa.kd; va.a_max_xy = sa.a_max_xy; va.a_max_z = sa.a_max_z;
+            if (any_cmd) {
+                hipLaunchKernelGGL(pipeline_audit_veto_kernel, dim3((S * 3 + 255) / 256 > 16 ? 16 : (S * 3 + 255) / 256, filled), dim3(256), 0, st, va);
+                AMK_HIP(hipGetLastError());
+            }
         }
     }
     AMK_HIP(hipEventRecord(s.done[s.count % p->depth], st));
@@ -454,7 +508,9 @@ int launch_gang(amk_pipeline *p, Slot &s) {
     if (Stopwatch::on())
         fprintf(stderr, "amk_pipeline launch: add_vertex %.0f us, map update %.0f us, step %.0f us (host enqueue time)\n", watch.us[0],
                 watch.us[1], watch.lap(2));
-    return rc != AMK_OK ? rc : L.finish();
+    if (rc != AMK_OK) return rc;
+    if (p->audit_mode != AMK_AUDIT_OFF && (rc = L.path_audit()) != AMK_OK) return rc;
+    return L.finish();
 }
 // launch_gang, if a gang is open, with the slot left consistent whatever happens: on a failure half-way (a build or a step that
 // could not be launched) the staged frames are DROPPED -- a later submit() starts a new gang instead of re-launching a
@@ -671,6 +727,7 @@ int amk_pipeline_submit(amk_pipeline *p, const amk_pipeline_frame *f, int *ticke
         if (!f->d_depth && std::memcmp(&o.camera, f->camera, sizeof(amk_frame_camera)) != 0) return AMK_ERR_INVALID_ARG;
     }
     if (f->n_keyframes > 0) {
+        if (p->audit_mode != AMK_AUDIT_OFF) return AMK_ERR_UNSUPPORTED;   // the audit runs against the slot's own index or map only
         if (p->gang != 1) return AMK_ERR_UNSUPPORTED;   // keyframe handles hold n_scenes scenes, a gang's handles gang x n_scenes
         if (!f->kf_obstacle || !f->kf_edge) return AMK_ERR_INVALID_ARG;
         for (int i = 0; i < f->n_keyframes; ++i)
@@ -750,6 +807,56 @@ int amk__pipeline_inject_failure(amk_pipeline *p, int stage) {
     if (!p && stage == 3) { g_fail_queue_creation = 1; return AMK_OK; }   // (no pipeline yet: the next amk_pipeline_create's)
     if (!p || stage < 0 || stage > 2) return AMK_ERR_INVALID_ARG;
     p->inject_failure = stage;
+    return AMK_OK;
+}
+
+// The audit's switch.  Valid only while nothing is staged or in flight: a launch reads the mode, the radius and the buffers.
+int amk_pipeline_set_path_audit(amk_pipeline *p, int mode, double radius, int n_legs) {
+    if (!p || p->slots.empty() || (mode != AMK_AUDIT_OFF && mode != AMK_AUDIT_REPORT && mode != AMK_AUDIT_SLOW_DOWN) || !(radius >= 0.0))
+        return AMK_ERR_INVALID_ARG;
+    const int N = amk_mpc_horizon(p->slots[0].mpc);
+    if (n_legs < 0 || n_legs > N - 1 || N < 2) return AMK_ERR_INVALID_ARG;
+    for (auto &s : p->slots) {
+        if (!s.open.empty()) return AMK_ERR_UNSUPPORTED;
+        if (s.waited < s.count) {   // finished without the host having asked yet?
+            const hipError_t e = hipEventQuery(s.done[(s.count - 1) % p->depth]);
+            if (e == hipErrorNotReady) {
+                (void)hipGetLastError();   // (not a failure: nothing for the next launch's check to find)
+                return AMK_ERR_UNSUPPORTED;
+            }
+            if (e != hipSuccess) return amk::hip_fail(e);
+            s.waited = s.count;
+        }
+    }
+    if (mode != AMK_AUDIT_OFF) {
+        const size_t GS = (size_t)p->gang * p->cfg.n_scenes;
+        for (auto &s : p->slots) {
+            if (s.audit_stop.p) continue;   // (all six or none: a failed attempt released them)
+            const hipError_t e = alloc_all(s.audit_stop, GS, s.audit_leg, GS, s.audit_src, GS, s.audit_t, GS, s.audit_free, GS, s.audit_pts, GS * 3);
+            if (e != hipSuccess) {
+                s.audit_stop.release(); s.audit_leg.release(); s.audit_src.release(); s.audit_t.release(); s.audit_free.release(); s.audit_pts.release();
+                return amk::hip_fail(e);
+            }
+        }
+    }
+    p->audit_mode = mode;
+    p->audit_radius_sq = radius * radius;
+    p->audit_points = (n_legs > 0 ? n_legs : N - 1) + 1;
+    return AMK_OK;
+}
+
+int amk_pipeline_audit_outputs(amk_pipeline *p, int ticket, int **d_stop, int **d_leg, double **d_t, double **d_free, float **d_pts,
+                               int **d_src) {
+    Slot *s = slot_of(p, ticket);
+    if (!s) return AMK_ERR_INVALID_ARG;
+    if (!s->audit_stop.p) return AMK_ERR_UNSUPPORTED;   // (no amk_pipeline_set_path_audit yet)
+    const size_t o = (size_t)(ticket / (int)p->slots.size()) * p->cfg.n_scenes;
+    if (d_stop) *d_stop = s->audit_stop.p + o;
+    if (d_leg) *d_leg = s->audit_leg.p + o;
+    if (d_t) *d_t = s->audit_t.p + o;
+    if (d_free) *d_free = s->audit_free.p + o;
+    if (d_pts) *d_pts = s->audit_pts.p + o * 3;
+    if (d_src) *d_src = s->audit_src.p + o;
     return AMK_OK;
 }
 

@@ -239,6 +239,38 @@ class KdBatch:
                                                      vp(pts), vp(idx)), "amk_kd_segment_cast_host")
         return dict(hit=hit, t=t, pts=pts, indices=idx)
 
+    def path_cast(self, path, radius_sq, want_pts=True, stream=None, out=None):
+        """amk_kd_path_cast: ONE answer per scene for a whole path float64 [S, n_points >= 2, >= 3] -- the first leg that cannot be
+        passed: stop [S] 0 free / 1 contact / 2 unjudgeable (non-finite) leg, leg (-1 when free), t on that leg, free = the free
+        distance along the path, the point touched and its cloud index.  The reduction of segment_cast's per-leg answers, bit for
+        bit; legs behind the stop leg are not walked.  -> dict(stop, leg, t, free, pts, indices)"""
+        P, stride = _check_path(path, self.S)
+        if out is None:
+            out = _path_cast_out(self.S, path.device, "indices", want_pts)
+        capi.check(self.lib.amk_kd_path_cast(self.h, capi.dptr(path), stride, P, float(radius_sq), capi.dptr(out["stop"]),
+                                             capi.dptr(out["leg"]), capi.dptr(out["t"]), capi.dptr(out["free"]), capi.dptr(out["pts"]),
+                                             capi.dptr(out["indices"]), _stream_arg(stream)), "amk_kd_path_cast")
+        return out
+
+    def path_cast_host(self, path, radius_sq):
+        """amk_kd_path_cast_host: path_cast with numpy buffers (path [S, n_points, >= 3]); synchronises."""
+        p = np.ascontiguousarray(path, np.float64)
+        assert p.ndim == 3 and p.shape[0] == self.S and p.shape[2] >= 3
+        stop = np.zeros(self.S, np.int32); leg = np.zeros(self.S, np.int32); idx = np.zeros(self.S, np.int32)
+        t = np.zeros(self.S, np.float64); free = np.zeros(self.S, np.float64); pts = np.zeros((self.S, 3), np.float32)
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        capi.check(self.lib.amk_kd_path_cast_host(self.h, vp(p), int(p.shape[2]), int(p.shape[1]), float(radius_sq), vp(stop), vp(leg),
+                                                  vp(t), vp(free), vp(pts), vp(idx)), "amk_kd_path_cast_host")
+        return dict(stop=stop, leg=leg, t=t, free=free, pts=pts, indices=idx)
+
+
+def _path_cast_out(S, dev, which, want_pts=True):
+    """outputs of the path casts, one result per scene; which: "indices" (one handle) or "frame" (a map, a list of handles)"""
+    i32 = lambda: torch.empty((S,), dtype=torch.int32, device=dev)
+    f64 = lambda: torch.empty((S,), dtype=torch.float64, device=dev)
+    return {"stop": i32(), "leg": i32(), "t": f64(), "free": f64(),
+            "pts": torch.empty((S, 3), dtype=torch.float32, device=dev) if want_pts else None, which: i32()}
+
 
 def _cast_out(S, L, dev, which, want_pts=True):
     """outputs of the segment casts, one result per leg; which: "indices" (one handle) or "frame" (a map, a list of handles)"""
@@ -508,6 +540,21 @@ def segment_cast_frames(handles, path, radius_sq, stream=None, out=None):
     return out
 
 
+def path_cast_frames(handles, path, radius_sq, stream=None, out=None):
+    """amk_kd_path_cast_frames: the path cast over a list of KdBatch handles (obstacle OR edge, index 0 = current frame): per scene
+    the first leg that cannot be passed, a leg's contact the least (t, frame, cloud index).  -> dict(stop, leg, t, free, pts, frame)"""
+    F, S = len(handles), handles[0].S
+    P, stride = _check_path(path, S)
+    if out is None:
+        out = _path_cast_out(S, path.device, "frame")
+    ha = (C.c_void_p * F)(*[h.h for h in handles])
+    capi.check(capi.load().amk_kd_path_cast_frames(ha, F, capi.dptr(path), stride, P, float(radius_sq), capi.dptr(out["stop"]),
+                                                   capi.dptr(out["leg"]), capi.dptr(out["t"]), capi.dptr(out["free"]),
+                                                   capi.dptr(out["pts"]), capi.dptr(out["frame"]), _stream_arg(stream)),
+               "amk_kd_path_cast_frames")
+    return out
+
+
 class KfMap:
     """amk_kfmap: FrameKDMap's keyframe list for S scenes on the device (FrameKDMap.cpp:29-74,233-252,428-488)."""
 
@@ -624,6 +671,18 @@ class KfMap:
         capi.check(self.lib.amk_kfmap_segment_cast(self.h, capi.dptr(path), stride, P, float(radius_sq), int(bool(edge)),
                                                    capi.dptr(out["hit"]), capi.dptr(out["t"]), capi.dptr(out["pts"]),
                                                    capi.dptr(out["frame"]), _stream_arg(stream)), "amk_kfmap_segment_cast")
+        return out
+
+    def path_cast(self, path, radius_sq, edge=False, stream=None, out=None):
+        """amk_kfmap_path_cast: per scene the first leg of a path float64 [S, n_points >= 2, >= 3] that cannot be passed, over every
+        frame the scene's query vector holds; a leg's contact is the least (t, frame, cloud index).
+        -> dict(stop [S] i32, leg [S] i32, t [S] f64, free [S] f64, pts [S,3] f32, frame [S] i32)"""
+        P, stride = _check_path(path, self.S)
+        if out is None:
+            out = _path_cast_out(self.S, path.device, "frame")
+        capi.check(self.lib.amk_kfmap_path_cast(self.h, capi.dptr(path), stride, P, float(radius_sq), int(bool(edge)),
+                                                capi.dptr(out["stop"]), capi.dptr(out["leg"]), capi.dptr(out["t"]), capi.dptr(out["free"]),
+                                                capi.dptr(out["pts"]), capi.dptr(out["frame"]), _stream_arg(stream)), "amk_kfmap_path_cast")
         return out
 
     def nearest_distance(self, queries, stream=None, out=None):
@@ -839,6 +898,27 @@ class Pipeline:
         S, N = self.S, self.N
         return dict(u=capi.tensor_from_ptr(ptr[0].value, (S, 4), torch.float64), x0array=capi.tensor_from_ptr(ptr[1].value, (S, N, 14), torch.float64),
                     flags=capi.tensor_from_ptr(ptr[2].value, (S, 4), torch.int32), ref_path=capi.tensor_from_ptr(ptr[3].value, (S, N, 10), torch.float64))
+
+    def set_path_audit(self, mode, radius, n_legs=0):
+        """amk_pipeline_set_path_audit: the trajectory audit between the step and the command -- mode capi.AMK_AUDIT_OFF / _REPORT /
+        _SLOW_DOWN, radius in metres, n_legs 0 = all N - 1.  Only while nothing is staged or in flight (before the first submit,
+        after drain)."""
+        capi.check(self.lib.amk_pipeline_set_path_audit(self.h, int(mode), float(radius), int(n_legs)), "amk_pipeline_set_path_audit")
+
+    def audit_outputs(self, ticket):
+        """Host copies of the frame's audit answers (after wait): dict(stop [S], leg [S], t [S], free [S], pts [S,3], src [S]);
+        src is the cloud index of the point touched, the frame for a slot with a keyframe map."""
+        ptr = [C.c_void_p() for _ in range(6)]
+        capi.check(self.lib.amk_pipeline_audit_outputs(self.h, int(ticket), *[C.byref(p) for p in ptr]), "amk_pipeline_audit_outputs")
+        S = self.S
+        shapes = [("stop", (S,), np.int32), ("leg", (S,), np.int32), ("t", (S,), np.float64), ("free", (S,), np.float64),
+                  ("pts", (S, 3), np.float32), ("src", (S,), np.int32)]
+        out = {}
+        for p, (name, shp, dt) in zip(ptr, shapes):
+            a = np.empty(shp, dt)
+            capi.check_hip(capi.hip_memcpy_dtoh(a, p.value), name)
+            out[name] = a
+        return out
 
     def wait(self, ticket):
         capi.check(self.lib.amk_pipeline_wait(self.h, int(ticket)), "amk_pipeline_wait")

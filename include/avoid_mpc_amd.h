@@ -354,6 +354,40 @@ int amk_kd_segment_cast(amk_kd *kd, const double *d_path, int point_stride, int 
 int amk_kd_segment_cast_host(amk_kd *kd, const double *h_path, int point_stride, int n_points, double radius_sq, int *h_hit,
                              double *h_t, float *h_pts, int *h_indices);
 
+/* Path cast: one answer per scene for a whole path -- the first leg that cannot be passed.  The segment cast answers every leg
+ * on its own; a monitor that wants one verdict per robot would copy back four [S][n_legs] arrays and reduce them, and every leg
+ * behind the first contact would still be walked.  Here the reduction happens on the device and the walk stops at the stop leg.
+ * The path's layout, point_stride, n_points, the legs, radius_sq with its clamping and the error rules are exactly those of
+ * "Segment cast" above, and so is every per-point formula.
+ * The stop leg of a scene is the first leg j, in leg order, for which one of these holds:
+ *   (a) the leg has a contact by the segment cast's rule.  It carries that contact's t, point and cloud index: the least
+ *       (t, index).
+ *   (b) the leg is unjudgeable: it has a non-finite endpoint coordinate or a non-finite L2.
+ * A segment cast reads a non-finite leg as "no contact"; an audit must not read a NaN trajectory as free, hence (b).
+ *   d_stop      [S] int: 0 = free to the end, 1 = contact, 2 = unjudgeable leg.
+ *   d_leg       [S] int: the stop leg, -1 when free.
+ *   d_t         [S] double: t of the contact on the stop leg; 0.0 when d_stop is 2, 1.0 when free.
+ *   d_free      [S] double: the free distance along the path, ((len_0 + len_1) + ... + len_{leg-1}) + t * len_leg with
+ *               len_j = sqrt(L2_j), L2_j exactly the segment search's.  fp64 with contraction off, summed left to right; the
+ *               t * len_leg term is left out when d_stop is 2.  A free path gives its whole length.
+ *   d_pts       [S][3] float: the point touched, (0,0,0) unless d_stop is 1.
+ *   d_indices   [S] int: its cloud index, -1 unless d_stop is 1.
+ * Each output may be NULL, but not all of them.  A degenerate leg has length 0 and stops the path iff a usable point lies inside
+ * at its start, as the cast says.  An empty or never-built scene is free to the end unless a leg is unjudgeable.
+ * Identity: the answer equals this reduction applied to amk_kd_segment_cast's per-leg outputs on the same path, bit for bit;
+ * d_free is rebuilt from the path by the formula.  The legs behind the stop leg are never walked.
+ * Errors as for the segment cast: a NULL handle, a NULL path, point_stride < 3, n_points < 2, radius_sq < 0 or NaN, or every
+ * output NULL: AMK_ERR_INVALID_ARG; a scan-mode handle: AMK_ERR_UNSUPPORTED.  Every error is returned before anything is staged or
+ * launched, the outputs untouched.  The call is stream-ordered and allocates nothing; the tie-order modes do not apply.
+ * Not offered: several stops per path, per-scene radii, tie-order modes and scan-mode handles, the path cast inside
+ * amk_step_batch, amk_step_batch_frames or amk_kfmap_step (their callers own the stream and enqueue it behind the step
+ * themselves; the pipeline has amk_pipeline_set_path_audit).                                                                */
+int amk_kd_path_cast(amk_kd *kd, const double *d_path, int point_stride, int n_points, double radius_sq, int *d_stop, int *d_leg,
+                     double *d_t, double *d_free, float *d_pts, int *d_indices, void *stream);
+/* Same with host buffers: stages and synchronises exactly as amk_kd_segment_cast_host does.                                  */
+int amk_kd_path_cast_host(amk_kd *kd, const double *h_path, int point_stride, int n_points, double radius_sq, int *h_stop,
+                          int *h_leg, double *h_t, double *h_free, float *h_pts, int *h_indices);
+
 /* ------------------------------------------------------------------------------------------ */
 /* MPC: batch of ObstacleAvoidanceMPC                          HighLvlMpc.h:4-33, .cpp:5-137    */
 /* ------------------------------------------------------------------------------------------ */
@@ -716,6 +750,35 @@ int amk_pipeline_query(amk_pipeline *p, int ticket);  /* 1 finished / idle, 0 ru
 int amk_pipeline_drain(amk_pipeline *p);              /* wait for every slot                                              */
 /* Device pointers of the frame's results (valid after wait): u [S][4], x0array [S][N][14], flags [S][4], ref_path [S][N][10] */
 int amk_pipeline_outputs(amk_pipeline *p, int ticket, double **d_u, double **d_x0array, int **d_flags, double **d_ref_path);
+/* The trajectory audit, off by default.  The MPC's collision terms sit at the N sampled states; a predicted trajectory can keep
+ * every sampled clearance and still pass through a thin obstacle between two samples.  With the audit on, every launch runs the
+ * path cast ("Path cast" below the KD index) on the step's own x0array -- row 0 is X0, the state the step planned from -- against
+ * the map the step planned on, on the slot's stream, after the step and before the command is written.  By definition the stage
+ * is amk_kd_path_cast(the slot's obstacle index, x0array, 14, n_legs + 1, radius * radius, ...) with a scene's path every N rows,
+ * or, for a slot with a keyframe map, amk_kfmap_path_cast(the slot's map, ..., query_edge 0, ...) on the map as it stands after
+ * the period's AddVertex and update; it covers the scenes of the frames a launch really holds.
+ *   AMK_AUDIT_REPORT     keeps the answers (amk_pipeline_audit_outputs); nothing else changes.
+ *   AMK_AUDIT_SLOW_DOWN  also, for a TASK-mode frame with d_cmd_out, publishes PubSlowDownCmd instead of u for a scene with
+ *                        flags[0] == 1 whose audit stops (d_stop != 0) -- the arithmetic of the flags[0] == 0 case, bit for bit.
+ *                        d_flags, d_u, x0array, mRefPath and the warm start are what they are without the audit: the verdict lives
+ *                        only in the audit outputs and the command, and the next period re-plans from the same persistent state.
+ * amk_pipeline_set_path_audit is valid only while no frame is staged or in flight on any slot (before the first submit or after
+ * amk_pipeline_drain), else AMK_ERR_UNSUPPORTED.  radius is in metres (used as radius * radius); n_legs = 0 means all N - 1.  A
+ * negative or NaN radius, an unknown mode or n_legs outside [0, N - 1]: AMK_ERR_INVALID_ARG.  It allocates the slots' result
+ * buffers ([gang * n_scenes] each); submit and launch allocate nothing more.  AMK_AUDIT_OFF frees nothing and stops the stage;
+ * with the audit off a launch enqueues exactly what it enqueued before.  While the audit is on, a frame that brings its own keyframe
+ * list (n_keyframes > 0) is refused at submit with AMK_ERR_UNSUPPORTED.  A stage that fails ends the launch like any other stage.
+ * amk_pipeline_audit_outputs: device pointers of the frame's audit answers (valid after wait, until the slot's next launch):
+ * d_stop / d_leg / d_src [S] int, d_t / d_free [S] double, d_pts [S][3] float; d_src is the cloud index of the point touched, the
+ * frame for a slot with a keyframe map.  AMK_ERR_UNSUPPORTED before the first amk_pipeline_set_path_audit.
+ * Not offered: the audit inside amk_step_batch, amk_step_batch_frames or amk_kfmap_step; an audit that changes flags, the re-plan
+ * loop or the persistent path; per-scene radii; several stops per path; the edge cloud in the audit.                         */
+#define AMK_AUDIT_OFF 0
+#define AMK_AUDIT_REPORT 1       /* run the path cast on every step's x0array, keep the answers                  */
+#define AMK_AUDIT_SLOW_DOWN 2    /* ... and in TASK mode publish PubSlowDownCmd for a scene whose audit stops   */
+int amk_pipeline_set_path_audit(amk_pipeline *p, int mode, double radius, int n_legs /* 0 = all N - 1 */);
+int amk_pipeline_audit_outputs(amk_pipeline *p, int ticket, int **d_stop, int **d_leg, double **d_t, double **d_free,
+                               float **d_pts, int **d_src /* cloud index; frame for a map slot */);
 
 /* ------------------------------------------------------------------------------------------ */
 /* The multi-frame map with keyframes, batched: FrameKDMap's keyframe list on the device       */
@@ -943,6 +1006,23 @@ int amk_kd_segment_cast_frames(amk_kd *const *frames, int n_frames, const double
                                double radius_sq, int *d_hit, double *d_t, float *d_pts, int *d_frame, void *stream);
 int amk_kd_segment_cast_frames_host(amk_kd *const *frames, int n_frames, const double *h_path, int point_stride, int n_points,
                                     double radius_sq, int *h_hit, double *h_t, float *h_pts, int *h_frame);
+
+/* Path cast over the frames: amk_kd_path_cast (see there: the stop leg, d_stop / d_leg / d_t / d_free, the identity, the errors)
+ * with every leg answered as "Segment cast over the frames" answers it: the contact of a leg is the least (t, frame, index) over
+ * the frames its scene holds.  d_frame [S] takes the place of d_indices: the frame touched, -1 unless d_stop is 1.  The answer
+ * equals the reduction applied to amk_kfmap_segment_cast's (amk_kd_segment_cast_frames') per-leg outputs, bit for bit.  A map
+ * scene with no frame is free to the end unless a leg is unjudgeable.  Scan-mode handles, tie-order handles in the frame list and
+ * n_frames > AMK_MAX_FRAMES return AMK_ERR_UNSUPPORTED before anything is staged or launched.  Stream-ordered, nothing allocated,
+ * no map state changed.  The *_host variants stage and synchronise exactly as their segment-cast counterparts do.              */
+int amk_kfmap_path_cast(amk_kfmap *map, const double *d_path, int point_stride, int n_points, double radius_sq, int query_edge,
+                        int *d_stop, int *d_leg, double *d_t, double *d_free, float *d_pts, int *d_frame, void *stream);
+int amk_kfmap_path_cast_host(amk_kfmap *map, const double *h_path, int point_stride, int n_points, double radius_sq, int query_edge,
+                             int *h_stop, int *h_leg, double *h_t, double *h_free, float *h_pts, int *h_frame);
+int amk_kd_path_cast_frames(amk_kd *const *frames, int n_frames, const double *d_path, int point_stride, int n_points,
+                            double radius_sq, int *d_stop, int *d_leg, double *d_t, double *d_free, float *d_pts, int *d_frame,
+                            void *stream);
+int amk_kd_path_cast_frames_host(amk_kd *const *frames, int n_frames, const double *h_path, int point_stride, int n_points,
+                                 double radius_sq, int *h_stop, int *h_leg, double *h_t, double *h_free, float *h_pts, int *h_frame);
 
 /* ------------------------------------------------------------------------------------------ */
 /* Scenes sharded over the GPUs of a node (one process per GPU), RCCL over xGMI                 */

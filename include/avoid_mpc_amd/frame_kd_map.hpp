@@ -315,6 +315,41 @@ public:
         return hit;
     }
 
+    // Not in the reference either: ONE answer for a whole path (KDTreeTwo::PathCast over the frames of the query vector): the first
+    // leg that cannot be passed in any frame.  Returns 0 = free to the end, 1 = contact, 2 = a leg with a non-finite coordinate or
+    // length; leg, t and freeDist as KDTreeTwo::PathCast gives them, `point` the point touched.  Over the frames the earliest leg
+    // wins, then the least t on it; an equal (leg, t) keeps the earlier frame, then the lower index within a frame.
+    int QueryPathCast(const std::vector<Vector3d> &path, double radius_sq, int &leg, double &t, double &freeDist, Vector3d &point,
+                      bool queryEdge = false) {
+        std::vector<double> xyz;
+        for (const Vector3d &p : path) { xyz.push_back(vx(p)); xyz.push_back(vy(p)); xyz.push_back(vz(p)); }
+        int stop = 0;
+        bool judged = false;
+        leg = -1;
+        t = 1.0;
+        freeDist = 0.0;
+        std::lock_guard<std::mutex> lock(mMtxKdTree);
+        for (auto &fr : mVecQueryVector) {
+            PtCloudKdPtr pc = queryEdge ? fr.edgeCloud : fr.pointCloud;
+            if (!pc) continue;
+            int lf = -1;
+            double tf = 1.0, ff = 0.0;
+            const int sf = pc->PathCast(xyz.data(), (int)path.size(), radius_sq, lf, tf, ff);
+            // a free frame gives the whole length; a stop replaces it when it comes earlier than what is held
+            const bool better = sf != 0 && (stop == 0 || lf < leg || (lf == leg && tf < t));
+            if (better || !judged) {
+                stop = sf; leg = lf; t = tf; freeDist = ff;
+                if (sf == 1) point = Vector3d(pc->closest_pts[0].x, pc->closest_pts[0].y, pc->closest_pts[0].z);
+            }
+            judged = true;
+        }
+        if (!judged) {   // a map without a frame: free to the end unless a leg is non-finite (an empty tree judges on the host)
+            KDTreeTwo<double> none;
+            stop = none.PathCast(xyz.data(), (int)path.size(), radius_sq, leg, t, freeDist);
+        }
+        return stop;
+    }
+
     // One pass of KeyframeThreadWorker's body (:443-486) -- the caller owns the 30 ms cadence and the
     // "new frame arrived" flag.  dronePos / bodyX: translation of Twb = Twc * Tbc^-1 and the world
     // direction of the body x axis (first column of Rwb), what DroneBehindPts (:233-252) derives.

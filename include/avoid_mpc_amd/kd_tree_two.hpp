@@ -3,6 +3,8 @@
 // cloud pointer whose pointee has a `points` container of {x,y,z} floats works, which
 // pcl::PointCloud<pcl::PointXYZ>::Ptr satisfies.
 #pragma once
+#include <cfloat>
+#include <cmath>
 #include <cstdlib>
 #include <memory>
 #include <stdexcept>
@@ -230,6 +232,45 @@ public:
             segment_t.push_back(t);
         }
         return hit != 0;
+    }
+    // Not in the reference either: ONE answer for a whole path of n_points positions, path_xyz[3*i + {0,1,2}] (amk_kd_path_cast,
+    // see the C header): the first leg that cannot be passed.  Returns 0 = free to the end, 1 = contact, 2 = a leg with a non-finite
+    // coordinate or length; leg is that leg (-1 when free), t where on it the contact begins (0.0 for code 2, 1.0 when free) and
+    // free_dist the free distance along the path.  With a contact closest_pts / indices / segment_t hold that one point.  An empty
+    // tree has no device index: its path is judged on the host by the same rules (free unless a leg is non-finite).
+    int PathCast(const double *path_xyz, int n_points, double radius_sq, int &leg, double &t, double &free_dist) {
+        closest_pts.clear();
+        squared_distances.clear();
+        indices.clear();
+        segment_t.clear();
+        if (n_points < 2 || !path_xyz) throw std::runtime_error("KDTreeTwo::PathCast: a path needs two points");
+        leg = -1;
+        t = 1.0;
+        free_dist = 0.0;
+        if (cloud.pts.size() == 0) {
+            for (int j = 0; j + 1 < n_points; ++j) {
+                const double *a = path_xyz + 3 * j, *b = a + 3;
+                const double d0 = b[0] - a[0], d1 = b[1] - a[1], d2 = b[2] - a[2];
+                const double L2 = (d0 * d0 + d1 * d1) + d2 * d2;
+                bool ok = L2 <= DBL_MAX;   // (false for NaN and inf)
+                for (int c = 0; c < 3; ++c) ok = ok && std::fabs(a[c]) <= DBL_MAX && std::fabs(b[c]) <= DBL_MAX;
+                if (!ok) {
+                    leg = j;
+                    t = 0.0;
+                    return 2;
+                }
+                free_dist = free_dist + std::sqrt(L2);
+            }
+            return 0;
+        }
+        int stop = 0, idx = -1;
+        amk_throw(amk_kd_path_cast_host(kd_, path_xyz, 3, n_points, radius_sq, &stop, &leg, &t, &free_dist, nullptr, &idx), "amk_kd_path_cast_host");
+        if (stop == 1) {
+            closest_pts.push_back(cloud.pts[idx]);
+            indices.push_back(idx);
+            segment_t.push_back(t);
+        }
+        return stop;
     }
     PointCloudTwo<num_t> const &GetPointCloud() { return cloud; }
     std::vector<int> const &GetColors() { return colors; }
