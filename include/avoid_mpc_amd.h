@@ -534,7 +534,10 @@ typedef struct amk_step_params {
  *                                           overflow; -1 no solve ran), total interior-point
  *                                           iterations}.  The reference ignores IPOPT's status
  *                                           (HighLvlMpc.cpp:116-122); a host that wants to fall back to
- *                                           PubSlowDownCmd on an unconverged solve tests flags[2] > 0.  */
+ *                                           PubSlowDownCmd on an unconverged solve tests flags[2] > 0.
+ * The step needs neighbours to plan with: a handle created with nearest_point_num = 0 (which amk_mpc_solve and amk_mpc_eval
+ * serve) is refused here and by the multi-frame steps with AMK_ERR_INVALID_ARG, as is mpc_max_iter outside 1 .. AMK_MAX_OUTER_ITER,
+ * before anything is launched: no output and no reference path is written.                                                  */
 int amk_step_batch(amk_kd *obstacle, amk_kd *edge, amk_mpc *mpc, const amk_step_params *params,
                    const double *d_state_quad, const double *d_pos_x, double *d_ref_path,
                    double *d_u, double *d_x0array, int *d_flags, void *stream);

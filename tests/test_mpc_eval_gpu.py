@@ -110,7 +110,9 @@ def test_eval_matches_oracle(cfg):
 
 # Horizons without an instantiation of their own (the generic one, NT = 0: LDS offsets at run-time N): 2 is the smallest
 # amk_mpc_create accepts -- one path stage, one 25-entry Hessian block; 7 is odd, so every take() of LdsMap rounds; 32 is AMK_MAX_HORIZON
-GENERIC = [(2, 1), (7, 3), (32, 2)]
+# K across its range (the collision terms' lane map, per = 64 / (N - 1) slots per round: tests/_mpc_kn_cases.py): (2, 64) one round of
+# 64 lanes on one stage's cells, (17, 64) no idle lane and 16 rounds, (32, 64) both maxima, (7, 0) no collision term at all
+GENERIC = [(2, 1), (7, 3), (32, 2), (2, 64), (17, 64), (32, 64), (7, 0)]
 
 
 def _generic_prm(N, K):
