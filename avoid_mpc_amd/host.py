@@ -364,8 +364,7 @@ class MpcBatch:
         self.SetupWeights(prm.weights); self.SetupTau(prm.tau); self.SetupGains(prm.gain)
         self.SetDroneAccelLimits(prm.a_min_z, prm.a_max_z, prm.a_max_xy, prm.a_max_yaw_dot)
         self.SetDroneRadius(prm.radius)
-        if any(getattr(prm, "drag", (0.0, 0.0, 0.0))):
-            self.SetDragCoefficient(*prm.drag)
+        self.SetDragCoefficient(*getattr(prm, "drag", (0.0, 0.0, 0.0)))   # always: a handle configured before may carry another drag
 
     def Solve(self, ref_states, faster=False, stream=None, want_traj=True):
         assert ref_states.dtype == torch.float64 and tuple(ref_states.shape) == (self.S, self.ref_len)

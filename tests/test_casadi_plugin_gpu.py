@@ -163,6 +163,27 @@ res["grad_gamma_p"] = float((np.abs(gp - fd) / scale).max())
 res["grad_gamma_p_blocks"] = {"x_init": float(np.abs(gp[:10] - fd[:10]).max()), "tau": float(np.abs(gp[-30:-26] - fd[-30:-26]).max()),
                               "weights": float((np.abs(gp[-26:-1] - fd[-26:-1]) / np.maximum(1.0, np.abs(fd[-26:-1]))).max()),
                               "radius": float(abs(gp[-1] - fd[-1]) / max(1.0, abs(fd[-1])))}
+# ---- grad_gamma_p against the forward-mode reference, row by row (tests/_gamma_ref.py; the rule of tests/test_mpc_eval_gamma_gpu.py)
+from tests import _gamma_ref as GR
+from tests.test_mpc_eval_gpu import RTOL
+def rows(gp_, pp):
+    _, ref_, tabs_ = GR.gamma_ref(x, pp, N, K, prm.dt, 1.7, lam_g, (0.0, 0.0, 0.0))
+    worst_, bad_ = GR.compare_rows(gp_, ref_, tabs_, N, K, RTOL)
+    return dict(worst_, x_init=0.0 if np.array_equal(gp_[:10], -lam_g[:10]) else float("inf"), failing=len(bad_))
+res["gamma_rows"] = rows(gp, p)
+# a changed tau and radius in the tail of p are picked up on the next call, and the first p again returns the first call's bits
+p3 = p.copy(); p3[-30:-26] = [3.0, 9.0, 20.0, 0.0]; p3[-1] = 0.3
+(g3,) = call("nlp_g", [x, p3], [ng])
+f3_, g3b, gx3, gp3 = call("nlp_grad", [x, p3, lam_f, lam_g], [1, ng, nx, npar])
+assert np.array_equal(g3b, g3)
+res["g_tail"] = float(np.abs(g3 - M.nlp_g(x, p3, N, K, prm.dt)).max())
+res["g_tail_moved"] = float(np.abs(g3 - g).max())
+res["gamma_rows_tail"] = rows(gp3, p3)
+f4, g4, gx4, gp4 = call("nlp_grad", [x, p, lam_f, lam_g], [1, ng, nx, npar])
+bits = lambda a: a.view(np.int64)
+res["first_bits_again"] = bool(np.array_equal(bits(f4), bits(fg_)) and np.array_equal(bits(g4), bits(gg_))
+                               and np.array_equal(bits(gx4), bits(gx)) and np.array_equal(bits(gp4), bits(gp)))
+res["tau_entries_moved"] = bool(np.all(gp3[-30:-27] != gp[-30:-27]))
 # ---- another horizon in the same process: amk_plugin_configure
 lib.amk_plugin_configure.restype = C.c_int; lib.amk_plugin_configure.argtypes = [C.c_double, C.c_double, C.c_int]
 assert lib.amk_plugin_configure(0.33, 0.033, 3) == 0
@@ -185,3 +206,8 @@ def test_plugin_symbols(cfg, T, K):
     assert res["g"] <= 1e-11 and res["jac"] <= 1e-14
     assert res["grad_gamma_x"] <= 1e-12
     assert res["grad_gamma_p"] <= 1e-5, res      # against central differences of the numpy twin over the whole of p
+    from tests.test_mpc_eval_gpu import RTOL
+    for which in ("gamma_rows", "gamma_rows_tail"):   # against the forward-mode reference: worst |gpu - ref| / row scale per block
+        assert res[which]["failing"] == 0 and res[which]["x_init"] == 0.0, res[which]
+        assert all(res[which][b] <= RTOL for b in ("ref", "obstacles", "target", "tail", "tau")), res[which]
+    assert res["g_tail"] <= 1e-11 and res["g_tail_moved"] > 1e-4 and res["tau_entries_moved"] and res["first_bits_again"], res

@@ -87,3 +87,44 @@ def test_solve_and_control_step_with_drag_match_the_oracle():
                 assert r["flags"][0] == outs["drag"]["flags"][s][0] and np.abs(r["u"] - outs["drag"]["u"][s]).max() <= 1e-4
     print(f"control step with drag {K_REF}: |gpu - oracle| <= {worst:.2e}, flipped {flipped}/{S}")
     assert worst <= 1e-6 and flipped <= 1
+
+
+def test_configure_with_the_defaults_clears_an_earlier_drag():
+    """configure(B) then configure(default) on one handle: the drag of set B (tests/_pose.py) must not stay in A.  The bits of a fresh
+    default handle in eval (g, jac_g), in amk_mpc_eval_gamma and in one Solve on 4 scenes."""
+    import torch
+    from avoid_mpc_amd import capi
+    from avoid_mpc_amd.host import MpcBatch
+    from tests import _pose
+    from tests.test_mpc_eval_gpu import _points
+    S = 4
+    prm, W, R = _points("C2", S, 31)
+    prm_b = _pose.params("C2", _pose.B)
+    assert any(prm_b.drag) and not any(prm.drag)
+    ng, npar = 10 + 10 * prm.N, R.shape[1] + 34
+    rng = np.random.default_rng(32)
+    Wd, Rd = torch.from_numpy(W).cuda(), torch.from_numpy(R).cuda()
+    lam_f, lam_g = torch.from_numpy(np.linspace(0.5, 2.0, S)).cuda(), torch.from_numpy(rng.normal(size=(S, ng))).cuda()
+    ref = torch.from_numpy(_pose.first_ref_states(5000, [800 + s for s in range(S)], prm)).cuda()
+
+    def run(m):
+        out = {k: v.cpu().numpy() for k, v in m.eval(Wd, Rd, want=("g", "jac_g")).items()}
+        gx = torch.empty((S, m.nx), dtype=torch.float64, device="cuda"); gp = torch.empty((S, npar), dtype=torch.float64, device="cuda")
+        capi.check(m.lib.amk_mpc_eval_gamma(m.h, capi.dptr(Wd), capi.dptr(Rd), capi.dptr(lam_f), capi.dptr(lam_g), capi.dptr(gx),
+                                            capi.dptr(gp), capi.stream_ptr(None)), "amk_mpc_eval_gamma")
+        m.reset_warm_start()                                          # the solve starts where a fresh handle's does
+        u, x0, info = m.Solve(ref)
+        torch.cuda.synchronize()
+        out.update(grad_x=gx.cpu().numpy(), grad_p=gp.cpu().numpy(), u=u.cpu().numpy(), x0=x0.cpu().numpy(), info=info.cpu().numpy())
+        return out
+
+    fresh = MpcBatch(prm.T, prm.dt, prm.K, S); fresh.configure(prm)
+    want = run(fresh)
+    with_b = MpcBatch(prm.T, prm.dt, prm.K, S); with_b.configure(prm_b)
+    under_b = run(with_b)
+    assert np.abs(under_b["g"] - want["g"]).max() > 1e-4              # set B is another problem ...
+    with_b.configure(prm)
+    got = run(with_b)
+    for k in want:                                                    # ... and nothing of it is left
+        assert np.array_equal(got[k].view(np.int64 if got[k].dtype == np.float64 else got[k].dtype),
+                              want[k].view(np.int64 if want[k].dtype == np.float64 else want[k].dtype)), k
