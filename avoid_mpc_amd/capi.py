@@ -64,6 +64,7 @@ SYMBOLS = [
     "amk_depth_out_size", "amk_depth_to_cloud", "amk_depth_to_cloud_host",
     "amk_depth_to_edge_cloud", "amk_depth_to_edge_cloud_host",
     "amk_depth_clouds_work_bytes", "amk_depth_to_clouds", "amk_depth_to_clouds_host",
+    "amk_sim_render_depth", "amk_sim_render_depth_host", "amk_sim_vehicle_step", "amk_sim_vehicle_step_host",
 ]
 
 
@@ -294,6 +295,10 @@ def load():
                                     i, vp, C.c_longlong, vp]),
         "amk_depth_to_clouds_host": (i, [vp, i, i, i, C.c_longlong, i, C.POINTER(DepthParams), vp, vp, vp, C.c_longlong, vp, vp, C.c_longlong,
                                          vp, i]),
+        "amk_sim_render_depth": (i, [vp, vp, i, i, d, d, C.POINTER(DepthParams), i, i, vp, vp, i, vp]),
+        "amk_sim_render_depth_host": (i, [vp, vp, i, i, d, d, C.POINTER(DepthParams), i, i, vp, vp, i]),
+        "amk_sim_vehicle_step": (i, [vp, vp, vp, vp, i, d, vp]),
+        "amk_sim_vehicle_step_host": (i, [vp, vp, vp, vp, i, d]),
     }
     sig["amk__kd_set_mode"] = (i, [vp, i])  # internal: 0 bucketed index, 1 streaming scan
     sig["amk__sweep_set_target"] = (None, [i])  # internal (tests, A/B): the pool's sweep against 1 a fine hashed grid of the current frame (default), 0 the frame's own index
@@ -303,6 +308,8 @@ def load():
     sig["amk__kfmap_slots_host"] = (i, [vp, vp, vp, vp, vp, vp])  # internal (tests): cur_slot [S], kf_n [S], kf_slots [S][P], fmap [F][S], need [S] of a keyframe map
     sig["amk__mpc_dynamics"] = (i, [vp, vp, d, vp, vp, vp, vp])  # internal (tests), host only, no device: tau[4], drag[3], dt -> A [10][10], B [10][4], c [10], dtau [3][150] or NULL
     sig["amk__depth_set_band_rows"] = (i, [i])  # internal (tests, measurements): amk_depth_to_clouds tiled with bands of this many rows at any image size; 0 automatic
+    sig["amk__sim_render_t"] = (i, [vp, vp, i, i, d, d, C.POINTER(DepthParams), i, i, vp, vp, vp])  # internal (tests): amk_sim_render_depth's fp64 ray parameter t [S][rows][cols], 0 = no return
+    sig["amk__sim_chunk"] = (i, [])  # internal (tests): cylinders per LDS round of the render kernel
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)
         if fn is None:

@@ -15,6 +15,8 @@ GPU driver (tests/_flight.py, bench.py --workload flight) and the CPU-oracle dri
   FlightWorld                 a static corridor of vertical cylinders; frame(t) = what a forward-looking sensor
                               returns in period t: surface points RESAMPLED every period (fresh frame, fresh indices)
   period_inputs / apply_command   GetInitPath + the clock model on one side of the step, PubCmd / PubSlowDownCmd on the other
+  render_depth / render_depth_ordered / quantise_depth / vehicle_step_ordered   the depth sensor and the affine vehicle in numpy;
+                              the *_ordered ones restate csrc/sim.hip (amk_sim_render_depth, amk_sim_vehicle_step) operation for operation
 
 Nothing here computes neighbours or solves anything: that is the step's job (amk_step_batch / the oracle's stepo_run).
 """
@@ -259,3 +261,72 @@ def render_depth(cyl, Twb, Tbc, rows, cols, fx, fy, cx, cy, z_top=4.0, max_range
             ok = (disc >= 0) & (t > 0) & (z >= 0) & (z <= z_top)
             best = np.where(ok & (t < best), t, best)
     return np.where(best <= max_range, best, 0.0).astype(np.float32)
+
+
+def render_depth_ordered(cyl, Twb, Tbc, rows, cols, fx, fy, cx, cy, z_top=4.0, max_range=60.0):
+    """The ray parameter t = planar depth of every pixel's first hit (float64 [rows, cols] in metres; 0 = no return), the scene of
+    render_depth in the OPERATION ORDER of amk_sim_render_depth (include/avoid_mpc_amd.h, "Closed-loop simulation"): every product
+    and sum written out, left to right in index order, no matrix product -- numpy's element-wise float64 operations, its division
+    and its square root are the IEEE operations the kernel performs, so the two agree bit for bit.  quantise_depth turns t into
+    the pixels of either depth type."""
+    ccx, ccy, cr = (np.asarray(v, np.float64).reshape(-1) for v in cyl)
+    A, B = np.asarray(Twb, np.float64).reshape(4, 4), np.asarray(Tbc, np.float64).reshape(4, 4)
+    M = np.empty((3, 4))
+    for i in range(3):
+        for j in range(4):
+            M[i, j] = ((A[i, 0] * B[0, j] + A[i, 1] * B[1, j]) + A[i, 2] * B[2, j]) + A[i, 3] * B[3, j]
+    o = M[:, 3]
+    v, u = np.meshgrid(np.arange(rows, dtype=np.float64), np.arange(cols, dtype=np.float64), indexing="ij")
+    dc0, dc1 = (u - cx) / fx, (v - cy) / fy
+    dx, dy, dz = ((M[i, 0] * dc0 + M[i, 1] * dc1) + M[i, 2] * 1.0 for i in range(3))
+    best = np.full((rows, cols), np.inf)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        tg = -o[2] / dz                                                              # ground plane
+        best = np.where((dz < 0) & (tg > 0), tg, best)
+        a = dx * dx + dy * dy
+        for k in range(ccx.size):
+            ox, oy = o[0] - ccx[k], o[1] - ccy[k]
+            b = ox * dx + oy * dy
+            c = (ox * ox + oy * oy) - cr[k] * cr[k]
+            disc = b * b - a * c
+            t = (-b - np.sqrt(np.where(disc >= 0, disc, np.nan))) / a
+            z = o[2] + t * dz
+            ok = (disc >= 0) & (t > 0) & (z >= 0) & (z <= z_top)
+            best = np.where(ok & (t < best), t, best)                                # strict <: the earlier hit keeps an equal t
+    return np.where(best <= max_range, best, 0.0)
+
+
+def quantise_depth(t, pixel2meter, dtype=np.uint16):
+    """The pixels amk_sim_render_depth writes for ray parameters t: float32(t) / float32(pixel2meter) in float32 (AMK_DEPTH_F32),
+    and that value rounded to the nearest integer, ties to even, clamped to [0, 65535] (AMK_DEPTH_U16) -- the rule of the depth
+    flights' frames (np.clip(np.round(float32 image / pixel2meter), 0, 65535))."""
+    q = np.asarray(t, np.float64).astype(np.float32) / np.float32(pixel2meter)
+    if np.dtype(dtype) == np.float32:
+        return q
+    assert np.dtype(dtype) == np.uint16
+    return np.clip(np.rint(q), 0, 65535).astype(np.uint16)
+
+
+def vehicle_step_ordered(ABc, x, cmd, pose_quantum=0.0):
+    """amk_sim_vehicle_step in numpy, operation for operation: x [S, 10], cmd [S, 3] -> (x+ [S, 10], Twb [S, 4, 4]) with
+    x+_i = ((sum_j A_ij x_j) + (sum_j B_ij u_j)) + c_i, u = (cmd, 0), the sums left to right from j = 0, and
+    Twb = [Rz(yaw) | rint(p q) / q] (exactly the identity rotation at yaw == 0; numpy's cos / sin otherwise)."""
+    ABc = np.asarray(ABc, np.float64).reshape(-1)
+    A, B, c = ABc[:100].reshape(10, 10), ABc[100:140].reshape(10, 4), ABc[140:150]
+    x, cmd = np.asarray(x, np.float64), np.asarray(cmd, np.float64)
+    u = np.concatenate([cmd, np.zeros((cmd.shape[0], 1))], axis=1)
+    xn = np.empty_like(x)
+    for i in range(10):
+        ax = A[i, 0] * x[:, 0]
+        for j in range(1, 10):
+            ax = ax + A[i, j] * x[:, j]
+        bu = B[i, 0] * u[:, 0]
+        for j in range(1, 4):
+            bu = bu + B[i, j] * u[:, j]
+        xn[:, i] = (ax + bu) + c[i]
+    T = np.tile(np.eye(4), (x.shape[0], 1, 1))
+    yaw = xn[:, 3]
+    cs, sn = np.where(yaw != 0, np.cos(yaw), 1.0), np.where(yaw != 0, np.sin(yaw), 0.0)
+    T[:, 0, 0] = cs; T[:, 0, 1] = 0.0 - sn; T[:, 1, 0] = sn; T[:, 1, 1] = cs
+    T[:, :3, 3] = np.rint(xn[:, 0:3] * pose_quantum) / pose_quantum if pose_quantum > 0 else xn[:, 0:3]
+    return xn, T

@@ -1082,3 +1082,54 @@ def depth_to_clouds(depth, params, Twb, Twc, point_stride=3, stream=None):
                                        capi.dptr(edge_counts), int(point_stride), capi.dptr(work), work.numel() * 8,
                                        capi.stream_ptr(stream)), "amk_depth_to_clouds")
     return cloud, counts, edge, edge_counts
+
+
+def sim_render_depth(cyl, Twb, params, rows, cols, counts=None, z_top=4.0, max_range=60.0, dtype=torch.uint16, out=None, stream=None):
+    """amk_sim_render_depth: the depth frames a camera at Twb * params.Tbc sees in worlds of vertical cylinders on the ground plane.
+    cyl float64 [S, max_cyl, 3] = (cx, cy, r), counts int32 [S] or None (max_cyl in every scene), Twb float64 [S, 4, 4]
+    -> depth [S, rows, cols] of `dtype` (torch.uint16 / int16: AMK_DEPTH_U16, torch.float32: AMK_DEPTH_F32), 0 = no return; it feeds
+    depth_to_clouds and Pipeline.submit(depth=...).  dtype torch.float64 is the test-only fp64 ray parameter (amk__sim_render_t).
+    Stream-ordered on torch's current stream (or `stream`); `out` re-uses a buffer."""
+    assert cyl.dtype == torch.float64 and cyl.dim() == 3 and cyl.shape[2] == 3 and cyl.is_contiguous()
+    S, max_cyl = int(cyl.shape[0]), int(cyl.shape[1])
+    assert Twb.dtype == torch.float64 and tuple(Twb.shape) == (S, 4, 4) and Twb.is_contiguous()
+    assert counts is None or (counts.dtype == torch.int32 and tuple(counts.shape) == (S,) and counts.is_contiguous())
+    if out is None:
+        out = torch.empty((S, int(rows), int(cols)), dtype=dtype, device=Twb.device)
+    assert tuple(out.shape) == (S, int(rows), int(cols)) and out.is_contiguous()
+    lib = capi.load()
+    head = (capi.dptr(cyl) if max_cyl else None, capi.dptr(counts), max_cyl, S, float(z_top), float(max_range), C.byref(params), int(rows),
+            int(cols), capi.dptr(Twb), capi.dptr(out))
+    if out.dtype == torch.float64:
+        capi.check(lib.amk__sim_render_t(*head, capi.stream_ptr(stream)), "amk__sim_render_t")
+    else:
+        kind = capi.AMK_DEPTH_F32 if out.dtype == torch.float32 else capi.AMK_DEPTH_U16
+        assert kind == capi.AMK_DEPTH_F32 or out.dtype in (torch.uint16, torch.int16)
+        capi.check(lib.amk_sim_render_depth(*head, kind, capi.stream_ptr(stream)), "amk_sim_render_depth")
+    return out
+
+
+def sim_vehicle_step(ABc, cmd, x, Twb=None, pose_quantum=0.0, stream=None):
+    """amk_sim_vehicle_step: x <- A x + B (cmd, 0) + c in place for every scene, and Twb = [Rz(yaw) | rint(p q) / q] of the new state.
+    ABc: numpy float64 [150] on the HOST (A [10][10], B [10][4], c [10]; plant_model() makes it), cmd float64 [S, 3], x float64 [S, 10]
+    (the layout of Pipeline.submit's odom), Twb float64 [S, 4, 4] or None; pose_quantum 1e6 rounds the pose to a micrometre."""
+    ABc = np.ascontiguousarray(ABc, np.float64).reshape(-1)
+    assert ABc.size == 150
+    S = int(x.shape[0])
+    assert x.dtype == torch.float64 and tuple(x.shape) == (S, 10) and cmd.dtype == torch.float64 and tuple(cmd.shape) == (S, 3)
+    assert Twb is None or (Twb.dtype == torch.float64 and tuple(Twb.shape) == (S, 4, 4))
+    capi.check(capi.load().amk_sim_vehicle_step(ABc.ctypes.data_as(C.c_void_p), capi.dptr(cmd), capi.dptr(x), capi.dptr(Twb), S,
+                                                float(pose_quantum), capi.stream_ptr(stream)), "amk_sim_vehicle_step")
+    return x
+
+
+def plant_model(tau, con_dt, drag=(0.0, 0.0, 0.0)):
+    """h_ABc of sim_vehicle_step: the MPC's own model at the control period con_dt (the library's host-side amk__mpc_dynamics; no
+    device) -> numpy float64 [150] = A [10][10], B [10][4], c [10]."""
+    tau4 = np.zeros(4); tau4[:min(4, len(tau))] = np.asarray(tau, np.float64)[:4]   # (tau_yaw, when given, is not in the model)
+    tau, drag = tau4, np.ascontiguousarray(drag, np.float64)
+    ABc = np.zeros(150)
+    vp = lambda a: C.c_void_p(a.ctypes.data)
+    capi.check(capi.load().amk__mpc_dynamics(vp(tau), vp(drag), float(con_dt), vp(ABc[:100]), vp(ABc[100:140]), vp(ABc[140:]), None),
+               "amk__mpc_dynamics")
+    return ABc

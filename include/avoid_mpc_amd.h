@@ -1145,6 +1145,69 @@ int amk_depth_to_clouds_host(const void *h_depth, int depth_type, int rows, int 
                              float *h_cloud, long long cloud_scene_stride, int *h_counts, float *h_edge,
                              long long edge_scene_stride, int *h_edge_counts, int point_stride);
 
+/* ------------------------------------------------------------------------------------------ */
+/* Closed-loop simulation: the depth sensor and the vehicle on the device                      */
+/* (the two ends of a flight around amk_pipeline_submit; DESIGN.md "Closed loop on the device") */
+/* ------------------------------------------------------------------------------------------ */
+/* The reference flies AirSim (DepthPlanar frames, AM/src/AvoidanceStateMachine.cpp:153-164) and bfctrl; neither is here.  These two
+ * calls stand in for them so that a fleet flies from a world description to commands with no host round trip:
+ *   amk_pipeline_submit(d_depth, d_Twb, d_odom = x, d_cmd_out = cmd) -> amk_pipeline_wait_stream -> amk_sim_vehicle_step(cmd, x, Twb)
+ *   -> amk_sim_render_depth(Twb, depth) -> the next submit, ordered by amk_pipeline_frame.input_ready.
+ *
+ * amk_sim_render_depth: the depth image a pinhole camera sees in a world of vertical cylinders on a ground plane.
+ *   d_cyl         [S][max_cyl][3] double = (cx, cy, r): scene s holds counts[s] vertical cylinders, each standing on the ground
+ *                 plane z = 0 and cut at z_top (the world of the bench's synthetic clouds).  May be NULL when max_cyl == 0.
+ *   d_cyl_counts  [S] or NULL = max_cyl in every scene; a count outside [0, max_cyl] is clamped into it.
+ *   params        the sensor: FULL-resolution fx, fy, cx, cy, Tbc and pixel2meter (> 0); depth_min / depth_max / resize_scale are
+ *                 not read (they belong to the consumer, amk_depth_to_clouds).
+ *   d_Twb         [S][16] world <- body, row-major; the camera sits at Twc = Twb * Tbc.
+ *   d_depth       [S][rows][cols] out, AMK_DEPTH_U16 or AMK_DEPTH_F32.  0 means no return within max_range; a return holds the
+ *                 PLANAR depth t (the hit's z in the camera frame), which is what UV2Camera back-projects, in the units
+ *                 amk_depth_to_cloud reads: F32 = float32(t) / float32(pixel2meter), the correctly rounded float32 quotient;
+ *                 U16 = that value rounded to the nearest integer, ties to even, clamped to [0, 65535]
+ *                 (rint(t / pixel2meter) on the float32 image, as numpy's round does it).
+ * Arithmetic: fp64, no contraction, every sum left to right in index order, so that a restatement in any IEEE language matches it
+ * operation for operation (avoid_mpc_amd/flight.py render_depth_ordered is one):
+ *   Twc_ij = ((Twb_i0 Tbc_0j + Twb_i1 Tbc_1j) + Twb_i2 Tbc_2j) + Twb_i3 Tbc_3j;  R, o = its rotation and translation
+ *   pixel (u, v) = (column, row):  dc = ((u - cx) / fx, (v - cy) / fy, 1),  d_i = (R_i0 dc_0 + R_i1 dc_1) + R_i2 dc_2
+ *   ground:      t = -o_z / d_z                                  a hit when d_z < 0 and t > 0
+ *   cylinder k:  ox = o_x - cx_k, oy = o_y - cy_k, a = d_x d_x + d_y d_y, b = ox d_x + oy d_y, c = (ox ox + oy oy) - r r,
+ *                disc = b b - a c;  for disc >= 0: t = (-b - sqrt(disc)) / a, z = o_z + t d_z
+ *                                                                a hit when t > 0 && 0 <= z <= z_top
+ *   The pixel takes the least t.  The comparison is a strict <, so on equal t the ground and then the lower cylinder index keep it.
+ *   The pixel's t is kept when t <= max_range, else it is 0.
+ * A vertical ray (a == 0) and a camera inside a cylinder behave as the formulas say: a NaN or negative t is no hit.
+ * AMK_ERR_INVALID_ARG: a NULL pointer (d_cyl_counts excepted), rows or cols < 1, max_cyl < 0, n_scenes < 1, a negative or NaN z_top
+ * or max_range, pixel2meter not > 0, an unknown depth_type.  AMK_ERR_UNSUPPORTED: a launch grid beyond 2^31 - 1 blocks (256 pixels
+ * per block) or more than 65 535 scenes (the scenes are the grid's second dimension).  Every error is returned before anything is
+ * launched.  The call is stream-ordered and allocates nothing.  amk_sim_render_depth_host takes host pointers, stages them and
+ * synchronises.                                                                                                             */
+int amk_sim_render_depth(const double *d_cyl, const int *d_cyl_counts, int max_cyl, int n_scenes, double z_top, double max_range,
+                         const amk_depth_params *params, int rows, int cols, const double *d_Twb, void *d_depth, int depth_type,
+                         void *stream);
+int amk_sim_render_depth_host(const double *h_cyl, const int *h_cyl_counts, int max_cyl, int n_scenes, double z_top,
+                              double max_range, const amk_depth_params *params, int rows, int cols, const double *h_Twb,
+                              void *h_depth, int depth_type);
+
+/* amk_sim_vehicle_step: the vehicle over one control period.  Its model is the MPC's own (mpc_obstacle_casadi.py:106-122 integrated by
+ * :338-357), which is exactly affine for fixed time constants: x+ = A x + B u + c.
+ *   h_ABc   HOST pointer to 150 doubles, A [10][10], B [10][4], c [10], handed to the kernel by value: the model at the CALLER's
+ *           control period (the node's con_dt, which need not be the MPC's dt), from wherever the caller has it.
+ *   d_cmd   [S][3] the published acceleration command (amk_pipeline_frame.d_cmd_out); u = (cmd, yaw_dot = 0): Command.yaw = 0 holds
+ *           the heading (AvoidanceStateMachine.cpp:376).
+ *   d_x     [S][10] in/out, the layout of amk_pipeline_frame.d_odom: [p(3), yaw, v(3), a(3)].  One buffer is the plant, the
+ *           odometry of the next submit and the clock model's input.
+ *   d_Twb   [S][16] out or NULL: [Rz(yaw) | p'] of the NEW state, row-major, p' = rint(p q) / q for pose_quantum q > 0 (q = 1e6: the
+ *           pose rounded to a micrometre, numpy's round(p, 6)); q = 0: p' = p.  At yaw == 0 the rotation is exactly the identity;
+ *           otherwise its entries are the device's cos / sin of the yaw.
+ * Arithmetic: x+_i = ((sum_j A_ij x_j) + (sum_j B_ij u_j)) + c_i, fp64, no contraction, each sum left to right from j = 0 (the
+ * u_3 = 0 term included).  AMK_ERR_INVALID_ARG: a NULL pointer (d_Twb excepted), n_scenes < 1, a negative or NaN pose_quantum --
+ * returned before anything is launched.  Stream-ordered; allocates nothing.  amk_sim_vehicle_step_host takes host pointers.    */
+int amk_sim_vehicle_step(const double *h_ABc, const double *d_cmd, double *d_x, double *d_Twb, int n_scenes, double pose_quantum,
+                         void *stream);
+int amk_sim_vehicle_step_host(const double *h_ABc, const double *h_cmd, double *h_x, double *h_Twb, int n_scenes,
+                              double pose_quantum);
+
 #ifdef __cplusplus
 }
 #endif
