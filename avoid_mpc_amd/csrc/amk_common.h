@@ -180,23 +180,26 @@ int map_radius_search(amk_kd *pool, int n_frames, const int *d_fmap, int S, cons
 // Their *_host variants and amk_kd_query_frames_host: queries (and poses) staged through `stage`, launch(d) -- the entry's device
 // call, d[i] = MapQuerySlot i, null where the host pointer is -- enqueued on the null stream between two device-wide waits (a
 // build or an update enqueued on any stream is seen), results copied back.  A convenience for single-robot hosts and tests,
-// not a hot path.  Any output may be NULL.
+// not a hot path.  Any output may be NULL.  map_stage_call is that staging, the tail of every one of them.
+template <class Launch>
+int map_stage_call(HostStage &stage, std::initializer_list<HostCopy> slots, Launch &&launch) {
+    return stage.call(slots, [&](const HostStage::Dev *d) { AMK_HIP(hipDeviceSynchronize()); return launch(d); }, hipDeviceSynchronize);
+}
+// the doubles a batch of queries or path points spans in host memory: n_points of `stride` doubles per scene, the last one 3 long
+inline size_t points_extent(size_t S, int n_points, int stride) { return (S * n_points - 1) * stride + 3; }
 enum MapQuerySlot { MQ_QUERIES, MQ_TWC, MQ_PTS, MQ_SQDIST, MQ_FRAME, MQ_COUNTS, MQ_DIST };
 template <class Launch>
 int map_query_host(HostStage &stage, int S, const double *h_queries, int query_stride, int n_queries, int k, const double *h_Twc,
                    float *h_pts, double *h_sqdist, int *h_frame, int *h_counts, double *h_dist, Launch &&launch) {
     if (S < 1 || !query_args_ok(h_queries, query_stride, n_queries) || k < 1) return AMK_ERR_INVALID_ARG;
     if (k > AMK_MAX_K) return AMK_ERR_UNSUPPORTED;
-    const size_t rows = (size_t)S * n_queries, nq = (rows - 1) * query_stride + 3;
-    return stage.call({to_device(h_queries, sizeof(double) * nq), if_given(to_device(h_Twc, sizeof(double) * S * 16)),
-                       if_given(to_host(h_pts, sizeof(float) * rows * k * 3)), if_given(to_host(h_sqdist, sizeof(double) * rows * k)),
-                       if_given(to_host(h_frame, sizeof(int) * rows * k)), if_given(to_host(h_counts, sizeof(int) * rows)),
-                       if_given(to_host(h_dist, sizeof(double) * rows))},
-                      [&](const HostStage::Dev *d) {
-                          AMK_HIP(hipDeviceSynchronize());
-                          return launch(d);
-                      },
-                      hipDeviceSynchronize);
+    const size_t rows = (size_t)S * n_queries;
+    return map_stage_call(stage,
+                          {to_device(h_queries, sizeof(double) * points_extent(S, n_queries, query_stride)),
+                           if_given(to_device(h_Twc, sizeof(double) * S * 16)), if_given(to_host(h_pts, sizeof(float) * rows * k * 3)),
+                           if_given(to_host(h_sqdist, sizeof(double) * rows * k)), if_given(to_host(h_frame, sizeof(int) * rows * k)),
+                           if_given(to_host(h_counts, sizeof(int) * rows)), if_given(to_host(h_dist, sizeof(double) * rows))},
+                          launch);
 }
 // The *_host variants of the map's radius searches: the same staging (slots MQ_QUERIES, MQ_PTS ... MQ_COUNTS) under the radius
 // search's argument rules
@@ -208,15 +211,12 @@ int map_radius_host(HostStage &stage, int S, const double *h_queries, int query_
                                           h_pts || h_sqdist || h_frame || h_counts);
         st != AMK_OK)
         return st;
-    const size_t rows = (size_t)S * n_queries, nq = (rows - 1) * query_stride + 3, k = (size_t)max_results;
-    return stage.call({to_device(h_queries, sizeof(double) * nq), scratch(0), if_given(to_host(h_pts, sizeof(float) * rows * k * 3)),
-                       if_given(to_host(h_sqdist, sizeof(double) * rows * k)), if_given(to_host(h_frame, sizeof(int) * rows * k)),
-                       if_given(to_host(h_counts, sizeof(int) * rows))},
-                      [&](const HostStage::Dev *d) {
-                          AMK_HIP(hipDeviceSynchronize());
-                          return launch(d);
-                      },
-                      hipDeviceSynchronize);
+    const size_t rows = (size_t)S * n_queries, k = (size_t)max_results;
+    return map_stage_call(stage,
+                          {to_device(h_queries, sizeof(double) * points_extent(S, n_queries, query_stride)), scratch(0),
+                           if_given(to_host(h_pts, sizeof(float) * rows * k * 3)), if_given(to_host(h_sqdist, sizeof(double) * rows * k)),
+                           if_given(to_host(h_frame, sizeof(int) * rows * k)), if_given(to_host(h_counts, sizeof(int) * rows))},
+                          launch);
 }
 // kd_segment.hip / map_query.hip: the argument rules every segment search shares (include/avoid_mpc_amd.h, "Segment search"),
 // checked before anything is staged or launched: a path is n_points >= 2 positions, the rest as for the radius searches
@@ -239,15 +239,13 @@ int map_segment_host(HostStage &stage, int S, const double *h_path, int point_st
                                            h_pts || h_sqdist || h_t || h_frame || h_counts);
         st != AMK_OK)
         return st;
-    const size_t np = ((size_t)S * n_points - 1) * point_stride + 3, rows = (size_t)S * (n_points - 1), k = (size_t)max_results;
-    return stage.call({to_device(h_path, sizeof(double) * np), scratch(0), if_given(to_host(h_pts, sizeof(float) * rows * k * 3)),
-                       if_given(to_host(h_sqdist, sizeof(double) * rows * k)), if_given(to_host(h_frame, sizeof(int) * rows * k)),
-                       if_given(to_host(h_counts, sizeof(int) * rows)), if_given(to_host(h_t, sizeof(double) * rows * k))},
-                      [&](const HostStage::Dev *d) {
-                          AMK_HIP(hipDeviceSynchronize());
-                          return launch(d);
-                      },
-                      hipDeviceSynchronize);
+    const size_t rows = (size_t)S * (n_points - 1), k = (size_t)max_results;
+    return map_stage_call(stage,
+                          {to_device(h_path, sizeof(double) * points_extent(S, n_points, point_stride)), scratch(0),
+                           if_given(to_host(h_pts, sizeof(float) * rows * k * 3)), if_given(to_host(h_sqdist, sizeof(double) * rows * k)),
+                           if_given(to_host(h_frame, sizeof(int) * rows * k)), if_given(to_host(h_counts, sizeof(int) * rows)),
+                           if_given(to_host(h_t, sizeof(double) * rows * k))},
+                          launch);
 }
 // kd_segment_nearest.hip / map_query.hip / kfmap.hip: the argument rules all six segment-nearest entries share
 // (include/avoid_mpc_amd.h, "Segment nearest"), checked before anything is staged or launched.  any_out: an output at all
@@ -316,16 +314,13 @@ int map_path_cast_host(HostStage &stage, int S, const double *h_path, int point_
     if (const int st = segment_cast_args_status(h_path, point_stride, n_points, radius_sq, h_stop || h_leg || h_t || h_free || h_pts || h_frame);
         st != AMK_OK)
         return st;
-    const size_t np = ((size_t)S * n_points - 1) * point_stride + 3, rows = (size_t)S;
-    return stage.call({to_device(h_path, sizeof(double) * np), if_given(to_host(h_stop, sizeof(int) * rows)),
-                       if_given(to_host(h_leg, sizeof(int) * rows)), if_given(to_host(h_t, sizeof(double) * rows)),
-                       if_given(to_host(h_free, sizeof(double) * rows)), if_given(to_host(h_pts, sizeof(float) * rows * 3)),
-                       if_given(to_host(h_frame, sizeof(int) * rows))},
-                      [&](const HostStage::Dev *d) {
-                          AMK_HIP(hipDeviceSynchronize());
-                          return launch(d);
-                      },
-                      hipDeviceSynchronize);
+    const size_t rows = (size_t)S;
+    return map_stage_call(stage,
+                          {to_device(h_path, sizeof(double) * points_extent(S, n_points, point_stride)),
+                           if_given(to_host(h_stop, sizeof(int) * rows)), if_given(to_host(h_leg, sizeof(int) * rows)),
+                           if_given(to_host(h_t, sizeof(double) * rows)), if_given(to_host(h_free, sizeof(double) * rows)),
+                           if_given(to_host(h_pts, sizeof(float) * rows * 3)), if_given(to_host(h_frame, sizeof(int) * rows))},
+                          launch);
 }
 // kfmap.hip, for pipeline.hip: AddVertex for the frames of a gang (see there)
 int kfmap_add_vertex_gang(amk_kfmap *m, int n_frames, int frame_scenes, const float *const *d_xyz, const int *const *d_counts,

@@ -65,6 +65,82 @@ __device__ __forceinline__ WaveSlot wave_slot(int units, int wpb = 4) {
     return m;
 }
 
+// ---- what the queries around the index walks share (kd_radius.hip ... kd_path_cast.hip, map_query.hip) ----
+// The wavefront of a kernel with one result row per (scene, unit): its slot, its row, and where its unit's input begins -- point
+// `unit` of the scene's n_points points of `stride` doubles (a query: units = n_points; the first end of a path's leg: units =
+// n_points - 1).  Address arithmetic only: the kernel returns where !in(n_scenes) before it reads anything.
+struct RowSlot {
+    WaveSlot ws;
+    int units;
+    size_t row;
+    const double *p;
+    __device__ __forceinline__ bool in(int n_scenes) const { return ws.s < n_scenes && ws.unit < units; }
+};
+__device__ __forceinline__ RowSlot row_slot(const double *pts, int stride, int n_points, int units) {
+    RowSlot r;
+    r.ws = wave_slot(units);
+    r.units = units;
+    r.row = (size_t)r.ws.s * units + r.ws.unit;
+    r.p = pts + ((size_t)r.ws.s * n_points + r.ws.unit) * stride;
+    return r;
+}
+
+// One row of a list query (radius search, segment search, segment nearest; every output may be null): its count, and in lane < k
+// slot `lane` -- the entry when `ok`, else DBL_MAX, t 0, id -1 and zeros.  id: the cloud index (one handle) or the frame (a map, a
+// list of handles).  point(): the entry's float4 record, a callable so that only the lanes that store a slot read one (the lanes
+// behind k hold positions the walk pushed out of its list: so many more cache lines).  WITH_T: the row has a t.  (No __restrict__,
+// as for store_search_row below.)
+template <bool WITH_T, class Point>
+__device__ __forceinline__ void write_list_row(size_t row, int k, int lane, int cnt, bool ok, double d2, double t, Point point, int id,
+                                               int *out_cnt, double *out_d2, double *out_t, int *out_id, float *out_pts) {
+    if (lane == 0 && out_cnt) out_cnt[row] = cnt;
+    if (lane < k) {
+        const float4 rec = point();
+        const size_t o = row * k + lane;
+        if (out_d2) out_d2[o] = ok ? d2 : DBL_MAX;
+        if (WITH_T && out_t) out_t[o] = ok ? t : 0.0;
+        if (out_id) out_id[o] = ok ? id : -1;
+        if (out_pts) {
+            out_pts[o * 3 + 0] = ok ? rec.x : 0.f;
+            out_pts[o * 3 + 1] = ok ? rec.y : 0.f;
+            out_pts[o * 3 + 2] = ok ? rec.z : 0.f;
+        }
+    }
+}
+// One row of a segment cast, written by lane 0 (every output may be null): whether there is a contact, and the contact.  The
+// caller passes the row's values as they are stored: without a contact t = 1.0 (free all the way), id -1 and zeros.
+__device__ __forceinline__ void write_cast_row(size_t row, int lane, bool hit, double t, float x, float y, float z, int id, int *out_hit,
+                                               double *out_t, int *out_id, float *out_pts) {
+    if (lane == 0) {
+        if (out_hit) out_hit[row] = hit ? 1 : 0;
+        if (out_t) out_t[row] = t;
+        if (out_id) out_id[row] = id;
+        if (out_pts) {
+            out_pts[row * 3 + 0] = x;
+            out_pts[row * 3 + 1] = y;
+            out_pts[row * 3 + 2] = z;
+        }
+    }
+}
+
+// The rules of a query on ONE handle's bucketed index, behind the query's own argument rules (args_status, which does not look
+// at the handle): the streaming scan (mode 1) has none of these walks, and the grid of `units` wavefronts per scene must fit
+inline int kd_query_handle_status(const amk_kd *kd, int units, int args_status) {
+    if (!kd) return AMK_ERR_INVALID_ARG;
+    if (args_status != AMK_OK) return args_status;
+    if (kd->mode != 0) return AMK_ERR_UNSUPPORTED;
+    if (search_blocks(kd->n_scenes, units) > 0x7fffffffll) return AMK_ERR_UNSUPPORTED;
+    return AMK_OK;
+}
+// A *_host entry of a handle: a build / sweep enqueued on some other stream since the last wait -- order behind it once
+inline int kd_order_behind_pending(amk_kd *kd) {
+    if (kd->async_pending) {
+        AMK_HIP(hipDeviceSynchronize());
+        kd->async_pending = 0;
+    }
+    return AMK_OK;
+}
+
 // Tie visibility on the cnt + 1 nearest of a query (lane i: the i-th best (distance, index), kNoIndex: empty): true, in every
 // lane, when two of them are at the same squared distance -- two kept neighbours, or the last kept and the best rejected one.
 // Only then can the index list (and, at the last slot, the neighbour SET) differ from nanoflann's, which keeps the first VISITED

@@ -596,10 +596,7 @@ int amk_kd_search_host(amk_kd *kd, const double *h_queries, int n_queries, int k
     if (!kd || !h_queries || n_queries <= 0 || k <= 0) return AMK_ERR_INVALID_ARG;
     if (k > AMK_MAX_K || n_queries > AMK_MAX_QUERIES) return AMK_ERR_UNSUPPORTED;
     if (kd->mode == 0 && kd->tie_order == AMK_TIES_AUTO && k + 1 > AMK_MAX_K) return AMK_ERR_UNSUPPORTED;   // (before anything is staged)
-    if (kd->async_pending) {  // a build / sweep enqueued on some other stream: order behind it once
-        AMK_HIP(hipDeviceSynchronize());
-        kd->async_pending = 0;
-    }
+    if (const int st = amk::kd_order_behind_pending(kd); st != AMK_OK) return st;
     const size_t rows = (size_t)kd->n_scenes * n_queries;
     enum { QUERIES, SQDIST, INDICES, COUNTS, PTS };
     return kd->stage.call_pinned({amk::to_device(h_queries, rows * 3 * sizeof(double)), amk::to_host(h_sqdist, rows * k * sizeof(double)),

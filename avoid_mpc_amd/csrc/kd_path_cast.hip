@@ -30,10 +30,8 @@ __global__ __launch_bounds__(64 * W) void kd_path_cast_kernel(amk::GridPtrs gpt,
 
 // the header's rules for one handle, before anything is staged or launched
 static int path_cast_handle_status(const amk_kd *kd, const double *path, int point_stride, int n_points, double radius_sq, bool any_out) {
-    if (!kd) return AMK_ERR_INVALID_ARG;
-    if (const int st = amk::segment_cast_args_status(path, point_stride, n_points, radius_sq, any_out); st != AMK_OK) return st;
-    if (kd->mode != 0) return AMK_ERR_UNSUPPORTED;   // the streaming scan has no segment walk
-    return AMK_OK;
+    // (mode 1, the streaming scan, has no segment walk; a block per scene: no grid of per-leg wavefronts to bound)
+    return amk::kd_query_handle_status(kd, 0, amk::segment_cast_args_status(path, point_stride, n_points, radius_sq, any_out));
 }
 
 namespace amk {
@@ -64,11 +62,8 @@ int amk_kd_path_cast_host(amk_kd *kd, const double *h_path, int point_stride, in
                                                h_stop || h_leg || h_t || h_free || h_pts || h_indices);
         st != AMK_OK)
         return st;
-    if (kd->async_pending) {  // a build / sweep enqueued on some other stream: order behind it once
-        AMK_HIP(hipDeviceSynchronize());
-        kd->async_pending = 0;
-    }
-    const size_t np = ((size_t)kd->n_scenes * n_points - 1) * point_stride + 3, rows = (size_t)kd->n_scenes;
+    if (const int st = amk::kd_order_behind_pending(kd); st != AMK_OK) return st;
+    const size_t np = amk::points_extent(kd->n_scenes, n_points, point_stride), rows = (size_t)kd->n_scenes;
     enum { PATH, T, FREE, STOP, LEG, INDICES, PTS };
     return kd->stage.call_pinned(
         {amk::to_device(h_path, np * sizeof(double)), amk::if_given(amk::to_host(h_t, rows * sizeof(double))),

@@ -10,40 +10,23 @@ __global__ __launch_bounds__(256) void kd_radius_search_kernel(amk::GridPtrs gpt
     int query_stride, int n_queries, double r2, int k, int *__restrict__ out_idx, double *__restrict__ out_d2,
     float *__restrict__ out_pts, int *__restrict__ out_cnt) {
     __shared__ amk::GridWaveLds wl[4];
-    const amk::WaveSlot m = amk::wave_slot(n_queries);
-    if (m.s >= n_scenes || m.unit >= n_queries) return;
-    const size_t row = (size_t)m.s * n_queries + m.unit;
-    const double *qp = queries + row * query_stride;
+    const amk::RowSlot r = amk::row_slot(queries, query_stride, n_queries, n_queries);
+    const amk::WaveSlot &m = r.ws;
+    if (!r.in(n_scenes)) return;
     double ld;
     int li, lpos;
     const amk::GridScene gs = gpt.scene(m.s);
-    const int cnt = amk::grid_radius(gs, qp[0], qp[1], qp[2], r2, k, ld, li, lpos, &wl[m.w]);
-    if (m.lane == 0 && out_cnt) out_cnt[row] = cnt;   // the full number, whatever k
-    if (m.lane < k) {
-        const bool ok = li != amk::kNoIndex;
-        const float4 rec = gs.pt[lpos];  // lpos = 0 for empty slots: a valid address
-        const size_t o = row * k + m.lane;
-        if (out_idx) out_idx[o] = ok ? li : -1;
-        if (out_d2) out_d2[o] = ok ? ld : DBL_MAX;
-        if (out_pts) {
-            out_pts[o * 3 + 0] = ok ? rec.x : 0.f;
-            out_pts[o * 3 + 1] = ok ? rec.y : 0.f;
-            out_pts[o * 3 + 2] = ok ? rec.z : 0.f;
-        }
-    }
+    const int cnt = amk::grid_radius(gs, r.p[0], r.p[1], r.p[2], r2, k, ld, li, lpos, &wl[m.w]);   // the full number, whatever k
+    amk::write_list_row<false>(r.row, k, m.lane, cnt, li != amk::kNoIndex, ld, 0.0, [&] { return gs.pt[lpos]; }, li, out_cnt, out_d2, nullptr, out_idx,
+                               out_pts);
 }
 
 // the header's rules for one handle, before anything is staged or launched
 static int radius_handle_status(const amk_kd *kd, const double *queries, int query_stride, int n_queries, double radius_sq,
                                 int max_results, const void *indices, const void *sqdist, const void *pts, const void *counts) {
-    if (!kd) return AMK_ERR_INVALID_ARG;
-    if (const int st = amk::radius_args_status(queries, query_stride, n_queries, radius_sq, max_results, indices || sqdist || pts,
-                                               indices || sqdist || pts || counts);
-        st != AMK_OK)
-        return st;
-    if (kd->mode != 0) return AMK_ERR_UNSUPPORTED;   // the streaming scan has no radius walk
-    if (amk::search_blocks(kd->n_scenes, n_queries) > 0x7fffffffll) return AMK_ERR_UNSUPPORTED;
-    return AMK_OK;
+    return amk::kd_query_handle_status(kd, n_queries,   // (mode 1, the streaming scan, has no radius walk)
+                                       amk::radius_args_status(queries, query_stride, n_queries, radius_sq, max_results,
+                                                               indices || sqdist || pts, indices || sqdist || pts || counts));
 }
 
 extern "C" {
@@ -66,15 +49,13 @@ int amk_kd_radius_search_host(amk_kd *kd, const double *h_queries, int query_str
     if (const int st = radius_handle_status(kd, h_queries, query_stride, n_queries, radius_sq, max_results, h_indices, h_sqdist, h_pts, h_counts);
         st != AMK_OK)
         return st;
-    if (kd->async_pending) {  // a build / sweep enqueued on some other stream: order behind it once
-        AMK_HIP(hipDeviceSynchronize());
-        kd->async_pending = 0;
-    }
+    if (const int st = amk::kd_order_behind_pending(kd); st != AMK_OK) return st;
     const size_t rows = (size_t)kd->n_scenes * n_queries, k = (size_t)max_results;
     enum { QUERIES, SQDIST, INDICES, COUNTS, PTS };
     return kd->stage.call_pinned(
-        {amk::to_device(h_queries, ((rows - 1) * query_stride + 3) * sizeof(double)), amk::if_given(amk::to_host(h_sqdist, rows * k * sizeof(double))),
-         amk::if_given(amk::to_host(h_indices, rows * k * sizeof(int))), amk::if_given(amk::to_host(h_counts, rows * sizeof(int))),
+        {amk::to_device(h_queries, amk::points_extent(kd->n_scenes, n_queries, query_stride) * sizeof(double)),
+         amk::if_given(amk::to_host(h_sqdist, rows * k * sizeof(double))), amk::if_given(amk::to_host(h_indices, rows * k * sizeof(int))),
+         amk::if_given(amk::to_host(h_counts, rows * sizeof(int))),
          amk::if_given(amk::to_host(h_pts, rows * k * 3 * sizeof(float)))},
         [&](const amk::HostStage::Dev *d, hipStream_t stream) {
             return amk_kd_radius_search(kd, d[QUERIES], query_stride, n_queries, radius_sq, max_results, d[INDICES], d[SQDIST], d[PTS],

@@ -11,38 +11,24 @@ __global__ __launch_bounds__(256) void kd_segment_cast_kernel(amk::GridPtrs gpt,
     int point_stride, int n_points, double r2, int *__restrict__ out_hit, double *__restrict__ out_t, float *__restrict__ out_pts,
     int *__restrict__ out_idx) {
     __shared__ amk::GridWaveLds wl[4];
-    const int n_legs = n_points - 1;
-    const amk::WaveSlot m = amk::wave_slot(n_legs);
-    if (m.s >= n_scenes || m.unit >= n_legs) return;
-    const double *pa = path + ((size_t)m.s * n_points + m.unit) * point_stride;
-    const amk::SegLeg leg = amk::seg_leg(pa, pa + point_stride);
-    const size_t row = (size_t)m.s * n_legs + m.unit;
+    const amk::RowSlot r = amk::row_slot(path, point_stride, n_points, n_points - 1);
+    const amk::WaveSlot &m = r.ws;
+    if (!r.in(n_scenes)) return;
+    const amk::SegLeg leg = amk::seg_leg(r.p, r.p + point_stride);
     double bt;
     int bi, bpos;
     const amk::GridScene gs = gpt.scene(m.s);
     const bool hit = amk::grid_cast(gs, leg, r2, 1.0, bt, bi, bpos, &wl[m.w]);
-    if (m.lane == 0) {
-        const float4 rec = gs.pt[bpos];  // bpos = 0 without a contact: a valid address
-        if (out_hit) out_hit[row] = hit ? 1 : 0;
-        if (out_t) out_t[row] = hit ? bt : 1.0;   // free all the way
-        if (out_idx) out_idx[row] = hit ? bi : -1;
-        if (out_pts) {
-            out_pts[row * 3 + 0] = hit ? rec.x : 0.f;
-            out_pts[row * 3 + 1] = hit ? rec.y : 0.f;
-            out_pts[row * 3 + 2] = hit ? rec.z : 0.f;
-        }
-    }
+    const float4 rec = gs.pt[bpos];  // bpos = 0 without a contact: a valid address
+    amk::write_cast_row(r.row, m.lane, hit, hit ? bt : 1.0, hit ? rec.x : 0.f, hit ? rec.y : 0.f, hit ? rec.z : 0.f, hit ? bi : -1, out_hit,
+                        out_t, out_idx, out_pts);
 }
 
 // the header's rules for one handle, before anything is staged or launched
 static int cast_handle_status(const amk_kd *kd, const double *path, int point_stride, int n_points, double radius_sq, const void *hit,
                               const void *t, const void *pts, const void *indices) {
-    if (!kd) return AMK_ERR_INVALID_ARG;
-    if (const int st = amk::segment_cast_args_status(path, point_stride, n_points, radius_sq, hit || t || pts || indices); st != AMK_OK)
-        return st;
-    if (kd->mode != 0) return AMK_ERR_UNSUPPORTED;   // the streaming scan has no segment walk
-    if (amk::search_blocks(kd->n_scenes, n_points - 1) > 0x7fffffffll) return AMK_ERR_UNSUPPORTED;
-    return AMK_OK;
+    return amk::kd_query_handle_status(kd, n_points - 1,   // (mode 1, the streaming scan, has no segment walk)
+                                       amk::segment_cast_args_status(path, point_stride, n_points, radius_sq, hit || t || pts || indices));
 }
 
 extern "C" {
@@ -62,11 +48,8 @@ int amk_kd_segment_cast_host(amk_kd *kd, const double *h_path, int point_stride,
                              double *h_t, float *h_pts, int *h_indices) {
     if (const int st = cast_handle_status(kd, h_path, point_stride, n_points, radius_sq, h_hit, h_t, h_pts, h_indices); st != AMK_OK)
         return st;
-    if (kd->async_pending) {  // a build / sweep enqueued on some other stream: order behind it once
-        AMK_HIP(hipDeviceSynchronize());
-        kd->async_pending = 0;
-    }
-    const size_t np = ((size_t)kd->n_scenes * n_points - 1) * point_stride + 3, rows = (size_t)kd->n_scenes * (n_points - 1);
+    if (const int st = amk::kd_order_behind_pending(kd); st != AMK_OK) return st;
+    const size_t np = amk::points_extent(kd->n_scenes, n_points, point_stride), rows = (size_t)kd->n_scenes * (n_points - 1);
     enum { PATH, T, HIT, INDICES, PTS };
     return kd->stage.call_pinned(
         {amk::to_device(h_path, np * sizeof(double)), amk::if_given(amk::to_host(h_t, rows * sizeof(double))),

@@ -10,42 +10,24 @@ __global__ __launch_bounds__(256) void kd_segment_nearest_kernel(amk::GridPtrs g
     int point_stride, int n_points, int k, int *__restrict__ out_idx, double *__restrict__ out_d2, double *__restrict__ out_t,
     float *__restrict__ out_pts, int *__restrict__ out_cnt) {
     __shared__ amk::GridWaveLds wl[4];
-    const int n_legs = n_points - 1;
-    const amk::WaveSlot m = amk::wave_slot(n_legs);
-    if (m.s >= n_scenes || m.unit >= n_legs) return;
-    const double *pa = path + ((size_t)m.s * n_points + m.unit) * point_stride;
-    const amk::SegLeg leg = amk::seg_leg(pa, pa + point_stride);
-    const size_t row = (size_t)m.s * n_legs + m.unit;
+    const amk::RowSlot r = amk::row_slot(path, point_stride, n_points, n_points - 1);
+    const amk::WaveSlot &m = r.ws;
+    if (!r.in(n_scenes)) return;
+    const amk::SegLeg leg = amk::seg_leg(r.p, r.p + point_stride);
     double ld, lt;
     int li, lpos;
     const amk::GridScene gs = gpt.scene(m.s);
-    const int cnt = amk::grid_segment_knn(gs, leg, k, ld, li, lpos, lt, &wl[m.w]);
-    if (m.lane == 0 && out_cnt) out_cnt[row] = cnt;   // min(k, usable points of the scene)
-    if (m.lane < k) {
-        const bool ok = li != amk::kNoIndex;
-        const float4 rec = gs.pt[lpos];  // lpos = 0 for empty slots: a valid address
-        const size_t o = row * k + m.lane;
-        if (out_idx) out_idx[o] = ok ? li : -1;
-        if (out_d2) out_d2[o] = ok ? ld : DBL_MAX;
-        if (out_t) out_t[o] = ok ? lt : 0.0;
-        if (out_pts) {
-            out_pts[o * 3 + 0] = ok ? rec.x : 0.f;
-            out_pts[o * 3 + 1] = ok ? rec.y : 0.f;
-            out_pts[o * 3 + 2] = ok ? rec.z : 0.f;
-        }
-    }
+    const int cnt = amk::grid_segment_knn(gs, leg, k, ld, li, lpos, lt, &wl[m.w]);   // min(k, usable points of the scene)
+    amk::write_list_row<true>(r.row, k, m.lane, cnt, li != amk::kNoIndex, ld, lt, [&] { return gs.pt[lpos]; }, li, out_cnt, out_d2, out_t, out_idx,
+                              out_pts);
 }
 
 // the header's rules for one handle, before anything is staged or launched
 static int segment_nearest_handle_status(const amk_kd *kd, const double *path, int point_stride, int n_points, int k, const void *indices,
                                          const void *sqdist, const void *t, const void *pts, const void *counts) {
-    if (!kd) return AMK_ERR_INVALID_ARG;
-    if (const int st = amk::segment_nearest_args_status(path, point_stride, n_points, k, indices || sqdist || t || pts || counts);
-        st != AMK_OK)
-        return st;
-    if (kd->mode != 0) return AMK_ERR_UNSUPPORTED;   // the streaming scan has no segment walk
-    if (amk::search_blocks(kd->n_scenes, n_points - 1) > 0x7fffffffll) return AMK_ERR_UNSUPPORTED;
-    return AMK_OK;
+    return amk::kd_query_handle_status(kd, n_points - 1,   // (mode 1, the streaming scan, has no segment walk)
+                                       amk::segment_nearest_args_status(path, point_stride, n_points, k,
+                                                                        indices || sqdist || t || pts || counts));
 }
 
 extern "C" {
@@ -67,11 +49,8 @@ int amk_kd_segment_nearest_host(amk_kd *kd, const double *h_path, int point_stri
     if (const int st = segment_nearest_handle_status(kd, h_path, point_stride, n_points, k, h_indices, h_sqdist, h_t, h_pts, h_counts);
         st != AMK_OK)
         return st;
-    if (kd->async_pending) {  // a build / sweep enqueued on some other stream: order behind it once
-        AMK_HIP(hipDeviceSynchronize());
-        kd->async_pending = 0;
-    }
-    const size_t np = ((size_t)kd->n_scenes * n_points - 1) * point_stride + 3, rows = (size_t)kd->n_scenes * (n_points - 1),
+    if (const int st = amk::kd_order_behind_pending(kd); st != AMK_OK) return st;
+    const size_t np = amk::points_extent(kd->n_scenes, n_points, point_stride), rows = (size_t)kd->n_scenes * (n_points - 1),
                  kk = (size_t)k;
     enum { PATH, SQDIST, T, INDICES, COUNTS, PTS };
     return kd->stage.call_pinned(

@@ -57,11 +57,8 @@ __device__ __forceinline__ void frame_list(const GridScene &gs, const ExactPtrs 
 // frame's entries are offered best first, an entry ranks behind every kept one at the same or a smaller distance (kept entries came
 // from an earlier frame or are earlier neighbours of this one: the tie rule), and the fold ends at the first entry that ranks
 // behind the k-th kept one.  WITH_T (the segment search): every entry carries a further payload, its t (nt in the frame's list, rt
-// in the running one); without it the two are never touched and the code is what it was.  USER tells apart instantiations that are
-// otherwise the same function: map_segment_nearest_kernel folds through <true, 1>, because a second caller of <true> changed the
-// scalar registers the compiler gives map_segment_kernel (97 / 103 -> 95 / 101 SGPRs), and a new query leaves the old kernels'
-// code as it was.
-template <bool WITH_T = false, int USER = 0>
+// in the running one); without it the two are never touched.
+template <bool WITH_T = false>
 __device__ __forceinline__ void fold_frame_list(double nd, const float4 &rec, int f, int k, int lane, double &rd, float &rx, float &ry,
                                                 float &rz, int &rf, double nt = 0.0, double *rt = nullptr) {
     for (int e = 0; e < k; ++e) {     // this frame's entries, best first
@@ -89,6 +86,26 @@ __device__ __forceinline__ void fold_frame_list(double nd, const float4 &rec, in
     }
 }
 
+// The frame walk every kernel below shares.  frames_held: one past the last frame scene s holds -- asked ONCE per wavefront, by all
+// of its lanes, ahead of any lane-dependent branch and of the walk (the path cast walks once per leg and asks once per block).
+// for_each_frame: the frames below F that the scene holds, in order: visit(f, m, gs) -- frame f, which scene m of its handle it is
+// (MAP, a keyframe map: of the pool; a frame the scene's map does not hold is passed over) and that scene's index -- for as long
+// as more() holds, asked ahead of every frame (the casts: nothing can begin earlier than a contact at t = 0).
+template <bool MAP>
+__device__ __forceinline__ int frame_scene(const QueryFrames &qf, int f, int s) { return MAP ? qf.map.pool_scene(f, s) : s; }   // (< 0: absent)
+template <bool MAP>
+__device__ __forceinline__ int frames_held(const QueryFrames &qf, int s, int lane) { return MAP ? qf.map.held(s, lane) : qf.map.n; }
+struct EveryFrame { __device__ bool operator()() const { return true; } };
+template <bool MAP, class Visit, class More = EveryFrame>
+__device__ __forceinline__ void for_each_frame(const QueryFrames &qf, int s, int F, Visit &&visit, More &&more = More{}) {
+    const GridPtrs pool = qf.g[0];   // (map mode: one set of pool pointers stays live over the loop)
+    for (int f = 0; f < F && more(); ++f) {
+        const int m = frame_scene<MAP>(qf, f, s);
+        if (m < 0) continue;         // (map mode: this scene's map has no frame f)
+        visit(f, m, (MAP ? pool : qf.g[f]).scene(m));
+    }
+}
+
 // DIST: GetNearestDistance -- the same walk with k = 1 and no fast path; out_dist = sqrt of the best squared distance
 template <bool MAP, bool DIST, bool EXACT>
 __device__ __forceinline__ void map_query_row(const QueryFrames &qf, const ExactPtrs &ex, int n_scenes, const double *__restrict__ queries,
@@ -98,28 +115,24 @@ __device__ __forceinline__ void map_query_row(const QueryFrames &qf, const Exact
                                               int *__restrict__ out_frame, int *__restrict__ out_cnt,
                                               double *__restrict__ out_dist) {
     __shared__ GridWaveLds wl[4];
-    const WaveSlot ws = wave_slot(n_queries);
-    const int s = ws.s, w = ws.w, lane = ws.lane, q = ws.unit;
-    if (s >= n_scenes || q >= n_queries) return;
+    const RowSlot r = row_slot(queries, query_stride, n_queries, n_queries);
+    const int s = r.ws.s, w = r.ws.w, lane = r.ws.lane;
+    if (!r.in(n_scenes)) return;
     const int k = DIST ? 1 : k_in;
-    const size_t row = (size_t)s * n_queries + q;
-    const double *qp = queries + row * query_stride;
-    const double qx = qp[0], qy = qp[1], qz = qp[2];
-    const int F = MAP ? qf.map.held(s, lane) : qf.map.n;   // the walk ends at the last frame this scene's map holds
-    auto scene_of = [&](int f) { return MAP ? qf.map.pool_scene(f, s) : s; };
-    const GridPtrs pool = qf.g[0];   // (map mode: one set of pool pointers stays live over the loop)
-    const int *pool_size = qf.size[0];
+    const double qx = r.p[0], qy = r.p[1], qz = r.p[2];
+    const int F = frames_held<MAP>(qf, s, lane);
+    auto size_of = [&](int f, int m) { return (MAP ? qf.size[0] : qf.size[f])[m]; };
 
     double rd = DBL_MAX;             // the running list: lane i < k holds the i-th best (distance, point, frame) so far
     float rx = 0.f, ry = 0.f, rz = 0.f;
     int rf = -1, cnt = 0;
     bool fast = false;
     if (!DIST && F > 0) {            // QueryNearestWithCurFrame (:254-275, 339-345)
-        const int m0 = scene_of(0);
-        const int n0 = m0 < 0 ? 0 : (MAP ? pool_size : qf.size[0])[m0];
+        const int m0 = frame_scene<MAP>(qf, 0, s);
+        const int n0 = m0 < 0 ? 0 : size_of(0, m0);
         fast = n0 >= k && (!Twc || pt_in_frame(Twc + (size_t)s * 16, cam, qx, qy, qz));
         if (fast) {
-            const GridScene gs = (MAP ? pool : qf.g[0]).scene(m0);
+            const GridScene gs = qf.g[0].scene(m0);
             cnt = adaptor_count(n0, k);   // (n0 >= k here: k, or nothing from a cloud of exactly k points)
             if constexpr (EXACT) {
                 double nd;
@@ -138,35 +151,21 @@ __device__ __forceinline__ void map_query_row(const QueryFrames &qf, const Exact
         }
     }
     if (!fast) {                     // QueryNearestThreadWorker over mVecQueryVector (:276-321) + sort by distance (:371-375)
-        for (int f = 0; f < F; ++f) {
-            const int m = scene_of(f);
-            if (m < 0) continue;     // (map mode: this scene's map has no frame f)
-            const int n = (MAP ? pool_size : qf.size[f])[m];
-            if (n <= k) continue;    // k' = min(k, size_f) results exist iff size_f > k'
-            const GridScene gs = (MAP ? pool : qf.g[f]).scene(m);
+        for_each_frame<MAP>(qf, s, F, [&](int f, int m, const GridScene &gs) {
+            if (size_of(f, m) <= k) return;   // k' = min(k, size_f) results exist iff size_f > k'
             double nd;
             float4 rec;
             frame_list<EXACT>(gs, ex, m, qx, qy, qz, k, lane, &wl[w], nd, rec);
             fold_frame_list(nd, rec, f, k, lane, rd, rx, ry, rz, rf);
-        }
+        });
         cnt = __popcll(__ballot((lane < k) & (rd < DBL_MAX)));
     }
     if (DIST) {
-        if (lane == 0) out_dist[row] = sqrt(rd);   // (no frame answered: sqrt(DBL_MAX), :381,426)
+        if (lane == 0) out_dist[r.row] = sqrt(rd);   // (no frame answered: sqrt(DBL_MAX), :381,426)
         return;
     }
-    if (lane == 0 && out_cnt) out_cnt[row] = cnt;
-    if (lane < k) {
-        const bool ok = rd < DBL_MAX;
-        const size_t o = row * k + lane;
-        if (out_d2) out_d2[o] = ok ? rd : DBL_MAX;
-        if (out_frame) out_frame[o] = ok ? rf : -1;
-        if (out_pts) {
-            out_pts[o * 3 + 0] = ok ? rx : 0.f;
-            out_pts[o * 3 + 1] = ok ? ry : 0.f;
-            out_pts[o * 3 + 2] = ok ? rz : 0.f;
-        }
-    }
+    write_list_row<false>(r.row, k, lane, cnt, rd < DBL_MAX, rd, 0.0, [&] { return make_float4(rx, ry, rz, 0.f); }, rf, out_cnt, out_d2,
+                          nullptr, out_frame, out_pts);
 }
 template <bool MAP, bool DIST>
 __global__ __launch_bounds__(256) void map_query_kernel(QueryFrames qf, int n_scenes, const double *__restrict__ queries,
@@ -209,30 +208,57 @@ int launch_query(const QueryFrames &qf, int S, const double *d_queries, int quer
     return AMK_OK;
 }
 
-// a caller's list of frame handles -> the kernel's argument (status: the header's rules, before anything is launched).
-// default_ties_only: the multi-frame kNN queries answer in the default tie order only; radius results have no tie-order modes
-int frames_of_handles(amk_kd *const *frames, int n_frames, QueryFrames &qf, int &S, bool default_ties_only = true) {
-    if (!frames || n_frames < 1) return AMK_ERR_INVALID_ARG;
-    if (n_frames > AMK_MAX_FRAMES) return AMK_ERR_UNSUPPORTED;
+// a caller's list of frame handles -> the kernel's argument and the scenes, or a status (the header's rules, before anything is
+// launched).  default_ties_only: the multi-frame kNN queries and casts answer in the default tie order only; the list queries'
+// results have no tie-order modes
+struct HandleFrames {
+    int status;
+    QueryFrames qf;
+    int S;
+};
+HandleFrames frames_of_handles(amk_kd *const *frames, int n_frames, bool default_ties_only = true) {
+    HandleFrames h{AMK_OK, QueryFrames{}, 0};
+    auto refused = [&](int status) { h.status = status; return h; };
+    if (!frames || n_frames < 1) return refused(AMK_ERR_INVALID_ARG);
+    if (n_frames > AMK_MAX_FRAMES) return refused(AMK_ERR_UNSUPPORTED);
     for (int f = 0; f < n_frames; ++f)
-        if (!frames[f] || frames[f]->n_scenes != frames[0]->n_scenes) return AMK_ERR_INVALID_ARG;
-    qf = QueryFrames{};
-    S = frames[0]->n_scenes;
-    qf.map = FrameMap{n_frames, nullptr, S};
+        if (!frames[f] || frames[f]->n_scenes != frames[0]->n_scenes) return refused(AMK_ERR_INVALID_ARG);
+    h.S = frames[0]->n_scenes;
+    h.qf.map = FrameMap{n_frames, nullptr, h.S};
     for (int f = 0; f < n_frames; ++f) {
-        if (frames[f]->mode != 0 || (default_ties_only && frames[f]->tie_order != AMK_TIES_LOWEST_INDEX)) return AMK_ERR_UNSUPPORTED;
-        qf.g[f] = grid_ptrs(frames[f]);
-        qf.size[f] = frames[f]->size.p;
+        if (frames[f]->mode != 0 || (default_ties_only && frames[f]->tie_order != AMK_TIES_LOWEST_INDEX)) return refused(AMK_ERR_UNSUPPORTED);
+        h.qf.g[f] = grid_ptrs(frames[f]);
+        h.qf.size[f] = frames[f]->size.p;
     }
-    return AMK_OK;
+    return h;
+}
+// The *_frames_host entries: host(stage, S) stages through a block of its own, freed at return -- these frames belong to no one handle
+template <class Host>
+int frames_host(amk_kd *const *frames, int n_frames, bool default_ties_only, Host &&host) {
+    const HandleFrames h = frames_of_handles(frames, n_frames, default_ties_only);
+    if (h.status != AMK_OK) return h.status;
+    amk::HostStage stage;
+    return host(stage, h.S);
 }
 
+bool pool_args_ok(const amk_kd *pool, const int *d_fmap, int n_frames, int S) { return pool && d_fmap && n_frames >= 1 && S >= 1; }
 QueryFrames frames_of_pool(amk_kd *pool, int n_frames, const int *d_fmap, int S) {
     QueryFrames qf{};
     qf.map = FrameMap{n_frames, d_fmap, S};
     qf.g[0] = grid_ptrs(pool);
     qf.size[0] = pool->size.p;
     return qf;
+}
+
+// The launch of a kernel with one wavefront per (scene, unit) (wave_slot): its keyframe-map or its list-of-handles instantiation,
+// whichever qf describes, with (qf, S, args...)
+template <class Kernel, class... Args>
+int launch_rows(Kernel map_kernel, Kernel handles_kernel, const QueryFrames &qf, int S, int units, hipStream_t stream, Args... args) {
+    const long long blocks = search_blocks(S, units);
+    if (blocks > 0x7fffffffll) return AMK_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(qf.map.fmap ? map_kernel : handles_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, qf, S, args...);
+    AMK_HIP(hipGetLastError());
+    return AMK_OK;
 }
 
 // Radius search over the frames (amk_kfmap_radius_search / amk_kd_radius_search_frames): one wavefront per (scene, query) walks
@@ -245,21 +271,15 @@ __global__ __launch_bounds__(256) void map_radius_kernel(QueryFrames qf, int n_s
                                                          float *__restrict__ out_pts, double *__restrict__ out_d2,
                                                          int *__restrict__ out_frame, int *__restrict__ out_cnt) {
     __shared__ GridWaveLds wl[4];
-    const WaveSlot ws = wave_slot(n_queries);
-    const int s = ws.s, w = ws.w, lane = ws.lane, q = ws.unit;
-    if (s >= n_scenes || q >= n_queries) return;
-    const size_t row = (size_t)s * n_queries + q;
-    const double *qp = queries + row * query_stride;
-    const double qx = qp[0], qy = qp[1], qz = qp[2];
-    const int F = MAP ? qf.map.held(s, lane) : qf.map.n;
-    const GridPtrs pool = qf.g[0];   // (map mode: one set of pool pointers stays live over the loop)
+    const RowSlot r = row_slot(queries, query_stride, n_queries, n_queries);
+    const int s = r.ws.s, w = r.ws.w, lane = r.ws.lane;
+    if (!r.in(n_scenes)) return;
+    const double qx = r.p[0], qy = r.p[1], qz = r.p[2];
+    const int F = frames_held<MAP>(qf, s, lane);
     double rd = DBL_MAX;             // the running list: lane i < k holds the i-th best (distance, point, frame) so far
     float rx = 0.f, ry = 0.f, rz = 0.f;
     int rf = -1, cnt = 0;
-    for (int f = 0; f < F; ++f) {
-        const int m = MAP ? qf.map.pool_scene(f, s) : s;
-        if (m < 0) continue;         // (map mode: this scene's map has no frame f)
-        const GridScene gs = (MAP ? pool : qf.g[f]).scene(m);
+    for_each_frame<MAP>(qf, s, F, [&](int f, int, const GridScene &gs) {
         double ld;
         int li, lpos;
         cnt += grid_radius(gs, qx, qy, qz, r2, k, ld, li, lpos, &wl[w]);
@@ -267,30 +287,9 @@ __global__ __launch_bounds__(256) void map_radius_kernel(QueryFrames qf, int n_s
             const float4 rec = gs.pt[lpos];   // (lpos = 0 for empty slots: a valid address)
             fold_frame_list((lane < k && li != kNoIndex) ? ld : DBL_MAX, rec, f, k, lane, rd, rx, ry, rz, rf);
         }
-    }
-    if (lane == 0 && out_cnt) out_cnt[row] = cnt;
-    if (lane < k) {
-        const bool ok = rd < DBL_MAX;
-        const size_t o = row * k + lane;
-        if (out_d2) out_d2[o] = ok ? rd : DBL_MAX;
-        if (out_frame) out_frame[o] = ok ? rf : -1;
-        if (out_pts) {
-            out_pts[o * 3 + 0] = ok ? rx : 0.f;
-            out_pts[o * 3 + 1] = ok ? ry : 0.f;
-            out_pts[o * 3 + 2] = ok ? rz : 0.f;
-        }
-    }
-}
-
-int launch_radius(const QueryFrames &qf, int S, const double *d_queries, int query_stride, int n_queries, double radius_sq, int max_results,
-                  float *d_pts, double *d_sqdist, int *d_frame, int *d_counts, hipStream_t stream) {
-    const long long blocks = search_blocks(S, n_queries);
-    if (blocks > 0x7fffffffll) return AMK_ERR_UNSUPPORTED;
-    auto kernel = qf.map.fmap ? map_radius_kernel<true> : map_radius_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, stream, qf, S, d_queries, query_stride, n_queries,
-                       radius_clamped(radius_sq), max_results, d_pts, d_sqdist, d_frame, d_counts);
-    AMK_HIP(hipGetLastError());
-    return AMK_OK;
+    });
+    write_list_row<false>(r.row, k, lane, cnt, rd < DBL_MAX, rd, 0.0, [&] { return make_float4(rx, ry, rz, 0.f); }, rf, out_cnt, out_d2,
+                          nullptr, out_frame, out_pts);
 }
 
 // Segment search over the frames (amk_kfmap_segment_search / amk_kd_segment_search_frames): one wavefront per (scene, leg) walks
@@ -303,22 +302,15 @@ __global__ __launch_bounds__(256) void map_segment_kernel(QueryFrames qf, int n_
                                                           double *__restrict__ out_t, int *__restrict__ out_frame,
                                                           int *__restrict__ out_cnt) {
     __shared__ GridWaveLds wl[4];
-    const int n_legs = n_points - 1;
-    const WaveSlot ws = wave_slot(n_legs);
-    const int s = ws.s, w = ws.w, lane = ws.lane, q = ws.unit;
-    if (s >= n_scenes || q >= n_legs) return;
-    const double *pa = path + ((size_t)s * n_points + q) * point_stride;
-    const SegLeg leg = seg_leg(pa, pa + point_stride);
-    const size_t row = (size_t)s * n_legs + q;
-    const int F = MAP ? qf.map.held(s, lane) : qf.map.n;
-    const GridPtrs pool = qf.g[0];   // (map mode: one set of pool pointers stays live over the loop)
+    const RowSlot r = row_slot(path, point_stride, n_points, n_points - 1);
+    const int s = r.ws.s, w = r.ws.w, lane = r.ws.lane;
+    if (!r.in(n_scenes)) return;
+    const SegLeg leg = seg_leg(r.p, r.p + point_stride);
+    const int F = frames_held<MAP>(qf, s, lane);
     double rd = DBL_MAX, rt = 0.0;   // the running list: lane i < k holds the i-th best (distance, t, point, frame) so far
     float rx = 0.f, ry = 0.f, rz = 0.f;
     int rf = -1, cnt = 0;
-    for (int f = 0; f < F; ++f) {
-        const int m = MAP ? qf.map.pool_scene(f, s) : s;
-        if (m < 0) continue;         // (map mode: this scene's map has no frame f)
-        const GridScene gs = (MAP ? pool : qf.g[f]).scene(m);
+    for_each_frame<MAP>(qf, s, F, [&](int f, int, const GridScene &gs) {
         double ld, lt;
         int li, lpos;
         cnt += grid_segment(gs, leg, r2, k, ld, li, lpos, lt, &wl[w]);
@@ -326,31 +318,9 @@ __global__ __launch_bounds__(256) void map_segment_kernel(QueryFrames qf, int n_
             const float4 rec = gs.pt[lpos];   // (lpos = 0 for empty slots: a valid address)
             fold_frame_list<true>((lane < k && li != kNoIndex) ? ld : DBL_MAX, rec, f, k, lane, rd, rx, ry, rz, rf, lt, &rt);
         }
-    }
-    if (lane == 0 && out_cnt) out_cnt[row] = cnt;
-    if (lane < k) {
-        const bool ok = rd < DBL_MAX;
-        const size_t o = row * k + lane;
-        if (out_d2) out_d2[o] = ok ? rd : DBL_MAX;
-        if (out_t) out_t[o] = ok ? rt : 0.0;
-        if (out_frame) out_frame[o] = ok ? rf : -1;
-        if (out_pts) {
-            out_pts[o * 3 + 0] = ok ? rx : 0.f;
-            out_pts[o * 3 + 1] = ok ? ry : 0.f;
-            out_pts[o * 3 + 2] = ok ? rz : 0.f;
-        }
-    }
-}
-
-int launch_segment(const QueryFrames &qf, int S, const double *d_path, int point_stride, int n_points, double radius_sq, int max_results,
-                   float *d_pts, double *d_sqdist, double *d_t, int *d_frame, int *d_counts, hipStream_t stream) {
-    const long long blocks = search_blocks(S, n_points - 1);
-    if (blocks > 0x7fffffffll) return AMK_ERR_UNSUPPORTED;
-    auto kernel = qf.map.fmap ? map_segment_kernel<true> : map_segment_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, stream, qf, S, d_path, point_stride, n_points,
-                       radius_clamped(radius_sq), max_results, d_pts, d_sqdist, d_t, d_frame, d_counts);
-    AMK_HIP(hipGetLastError());
-    return AMK_OK;
+    });
+    write_list_row<true>(r.row, k, lane, cnt, rd < DBL_MAX, rd, rt, [&] { return make_float4(rx, ry, rz, 0.f); }, rf, out_cnt, out_d2,
+                         out_t, out_frame, out_pts);
 }
 
 // Segment nearest over the frames (amk_kfmap_segment_nearest / amk_kd_segment_nearest_frames): one wavefront per (scene, leg) walks
@@ -364,115 +334,66 @@ __global__ __launch_bounds__(256) void map_segment_nearest_kernel(QueryFrames qf
                                                                   double *__restrict__ out_d2, double *__restrict__ out_t,
                                                                   int *__restrict__ out_frame, int *__restrict__ out_cnt) {
     __shared__ GridWaveLds wl[4];
-    const int n_legs = n_points - 1;
-    const WaveSlot ws = wave_slot(n_legs);
-    const int s = ws.s, w = ws.w, lane = ws.lane, q = ws.unit;
-    if (s >= n_scenes || q >= n_legs) return;
-    const double *pa = path + ((size_t)s * n_points + q) * point_stride;
-    const SegLeg leg = seg_leg(pa, pa + point_stride);
-    const size_t row = (size_t)s * n_legs + q;
-    const int F = MAP ? qf.map.held(s, lane) : qf.map.n;
-    const GridPtrs pool = qf.g[0];   // (map mode: one set of pool pointers stays live over the loop)
+    const RowSlot r = row_slot(path, point_stride, n_points, n_points - 1);
+    const int s = r.ws.s, w = r.ws.w, lane = r.ws.lane;
+    if (!r.in(n_scenes)) return;
+    const SegLeg leg = seg_leg(r.p, r.p + point_stride);
+    const int F = frames_held<MAP>(qf, s, lane);
     double rd = DBL_MAX, rt = 0.0;   // the running list: lane i < k holds the i-th best (distance, t, point, frame) so far
     float rx = 0.f, ry = 0.f, rz = 0.f;
     int rf = -1, cnt = 0;
-    for (int f = 0; f < F; ++f) {
-        const int m = MAP ? qf.map.pool_scene(f, s) : s;
-        if (m < 0) continue;         // (map mode: this scene's map has no frame f)
-        const GridScene gs = (MAP ? pool : qf.g[f]).scene(m);
+    for_each_frame<MAP>(qf, s, F, [&](int f, int, const GridScene &gs) {
         double ld, lt;
         int li, lpos;
         cnt += grid_segment_knn(gs, leg, k, ld, li, lpos, lt, &wl[w]);
         const float4 rec = gs.pt[lpos];   // (lpos = 0 for empty slots: a valid address)
-        fold_frame_list<true, 1>((lane < k && li != kNoIndex) ? ld : DBL_MAX, rec, f, k, lane, rd, rx, ry, rz, rf, lt, &rt);
-    }
-    if (lane == 0 && out_cnt) out_cnt[row] = min(cnt, k);
-    if (lane < k) {
-        const bool ok = rd < DBL_MAX;
-        const size_t o = row * k + lane;
-        if (out_d2) out_d2[o] = ok ? rd : DBL_MAX;
-        if (out_t) out_t[o] = ok ? rt : 0.0;
-        if (out_frame) out_frame[o] = ok ? rf : -1;
-        if (out_pts) {
-            out_pts[o * 3 + 0] = ok ? rx : 0.f;
-            out_pts[o * 3 + 1] = ok ? ry : 0.f;
-            out_pts[o * 3 + 2] = ok ? rz : 0.f;
+        fold_frame_list<true>((lane < k && li != kNoIndex) ? ld : DBL_MAX, rec, f, k, lane, rd, rx, ry, rz, rf, lt, &rt);
+    });
+    write_list_row<true>(r.row, k, lane, min(cnt, k), rd < DBL_MAX, rd, rt, [&] { return make_float4(rx, ry, rz, 0.f); }, rf, out_cnt, out_d2,
+                         out_t, out_frame, out_pts);
+}
+
+// One leg's cast over the frames scene s holds, for map_segment_cast_kernel and map_path_cast_kernel: the least (t, frame, index)
+// -- a plain minimum, no list to fold.  Unlike segment nearest the running best bounds the next frame's walk: grid_cast takes it
+// as tcap, counts only contacts strictly below it (an equal t keeps the earlier frame) and ends that frame's walk where nothing
+// can begin earlier; after a contact at t = 0 the remaining frames are not walked at all.  True: a contact, in rt (wave-uniform;
+// 1.0 without one), its frame rf (-1) and the point touched (left as the caller set it: zeros).
+template <bool MAP>
+__device__ __forceinline__ bool cast_frames(const QueryFrames &qf, int s, int F, const SegLeg &leg, double r2, GridWaveLds *wl,
+                                            double &rt, int &rf, float &rx, float &ry, float &rz) {
+    rt = 1.0;   // the first contact so far
+    rf = -1;
+    for_each_frame<MAP>(qf, s, F, [&](int f, int, const GridScene &gs) {
+        double bt;
+        int bi, bpos;
+        if (grid_cast(gs, leg, r2, rt, bt, bi, bpos, wl)) {   // (wave-uniform)
+            const float4 rec = gs.pt[bpos];
+            rt = bt; rx = rec.x; ry = rec.y; rz = rec.z; rf = f;
         }
-    }
+    }, [&] { return rt > 0.0; });
+    return rf >= 0;
 }
 
-int launch_segment_nearest(const QueryFrames &qf, int S, const double *d_path, int point_stride, int n_points, int k, float *d_pts,
-                           double *d_sqdist, double *d_t, int *d_frame, int *d_counts, hipStream_t stream) {
-    const long long blocks = search_blocks(S, n_points - 1);
-    if (blocks > 0x7fffffffll) return AMK_ERR_UNSUPPORTED;
-    auto kernel = qf.map.fmap ? map_segment_nearest_kernel<true> : map_segment_nearest_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, stream, qf, S, d_path, point_stride, n_points, k, d_pts, d_sqdist,
-                       d_t, d_frame, d_counts);
-    AMK_HIP(hipGetLastError());
-    return AMK_OK;
-}
-
-// Segment cast over the frames (amk_kfmap_segment_cast / amk_kd_segment_cast_frames): one wavefront per (scene, leg) walks the
-// frames its scene holds with grid_cast and keeps the least (t, frame, index) -- a plain minimum, no list to fold.  Unlike
-// segment nearest the running best bounds the next frame's walk: grid_cast takes it as tcap, counts only contacts strictly
-// below it (an equal t keeps the earlier frame) and ends that frame's walk where nothing can begin earlier; after a contact at
-// t = 0 the remaining frames are not walked at all.
+// Segment cast over the frames (amk_kfmap_segment_cast / amk_kd_segment_cast_frames): one wavefront per (scene, leg), cast_frames
 template <bool MAP>
 __global__ __launch_bounds__(256) void map_segment_cast_kernel(QueryFrames qf, int n_scenes, const double *__restrict__ path,
                                                                int point_stride, int n_points, double r2, int *__restrict__ out_hit,
                                                                double *__restrict__ out_t, float *__restrict__ out_pts,
                                                                int *__restrict__ out_frame) {
     __shared__ GridWaveLds wl[4];
-    const int n_legs = n_points - 1;
-    const WaveSlot ws = wave_slot(n_legs);
-    const int s = ws.s, w = ws.w, lane = ws.lane, q = ws.unit;
-    if (s >= n_scenes || q >= n_legs) return;
-    const double *pa = path + ((size_t)s * n_points + q) * point_stride;
-    const SegLeg leg = seg_leg(pa, pa + point_stride);
-    const size_t row = (size_t)s * n_legs + q;
-    const int F = MAP ? qf.map.held(s, lane) : qf.map.n;
-    const GridPtrs pool = qf.g[0];   // (map mode: one set of pool pointers stays live over the loop)
-    double rt = 1.0;                 // the first contact so far (wave-uniform); 1.0: none
+    const RowSlot r = row_slot(path, point_stride, n_points, n_points - 1);
+    if (!r.in(n_scenes)) return;
+    const SegLeg leg = seg_leg(r.p, r.p + point_stride);
+    double rt;
     float rx = 0.f, ry = 0.f, rz = 0.f;
-    int rf = -1;
-    for (int f = 0; f < F && rt > 0.0; ++f) {
-        const int m = MAP ? qf.map.pool_scene(f, s) : s;
-        if (m < 0) continue;         // (map mode: this scene's map has no frame f)
-        const GridScene gs = (MAP ? pool : qf.g[f]).scene(m);
-        double bt;
-        int bi, bpos;
-        if (grid_cast(gs, leg, r2, rt, bt, bi, bpos, &wl[w])) {   // (wave-uniform)
-            const float4 rec = gs.pt[bpos];
-            rt = bt; rx = rec.x; ry = rec.y; rz = rec.z; rf = f;
-        }
-    }
-    if (lane == 0) {
-        if (out_hit) out_hit[row] = rf >= 0 ? 1 : 0;
-        if (out_t) out_t[row] = rt;   // 1.0 without a contact: free all the way
-        if (out_frame) out_frame[row] = rf;
-        if (out_pts) {
-            out_pts[row * 3 + 0] = rx;
-            out_pts[row * 3 + 1] = ry;
-            out_pts[row * 3 + 2] = rz;
-        }
-    }
-}
-
-int launch_segment_cast(const QueryFrames &qf, int S, const double *d_path, int point_stride, int n_points, double radius_sq, int *d_hit,
-                        double *d_t, float *d_pts, int *d_frame, hipStream_t stream) {
-    const long long blocks = search_blocks(S, n_points - 1);
-    if (blocks > 0x7fffffffll) return AMK_ERR_UNSUPPORTED;
-    auto kernel = qf.map.fmap ? map_segment_cast_kernel<true> : map_segment_cast_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, stream, qf, S, d_path, point_stride, n_points,
-                       radius_clamped(radius_sq), d_hit, d_t, d_pts, d_frame);
-    AMK_HIP(hipGetLastError());
-    return AMK_OK;
+    int rf;
+    const bool hit = cast_frames<MAP>(qf, r.ws.s, frames_held<MAP>(qf, r.ws.s, r.ws.lane), leg, r2, &wl[r.ws.w], rt, rf, rx, ry, rz);
+    write_cast_row(r.row, r.ws.lane, hit, rt, rx, ry, rz, rf, out_hit, out_t, out_frame, out_pts);
 }
 
 // Path cast over the frames (amk_kfmap_path_cast / amk_kd_path_cast_frames): kd_path_cast_kernel's block per scene and rounds
 // (path_cast_scene, kd_path_cast.h, with the barrier rules; the only return before it is the whole-block one), a leg's wave
-// folding the frames exactly as map_segment_cast_kernel does -- the running best t is the next frame's tcap, an equal t keeps the
-// earlier frame, and after a contact at t = 0 the remaining frames are not walked.
+// folding the frames exactly as map_segment_cast_kernel does, inside the per-leg call.
 template <bool MAP, int W>
 __global__ __launch_bounds__(64 * W) void map_path_cast_kernel(QueryFrames qf, int n_scenes, const double *__restrict__ path,
                                                                int point_stride, long long scene_stride, int n_points, double r2,
@@ -481,24 +402,10 @@ __global__ __launch_bounds__(64 * W) void map_path_cast_kernel(QueryFrames qf, i
     const int s = blockIdx.x;
     if (s >= n_scenes) return;   // (the whole block)
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int F = MAP ? qf.map.held(s, lane) : qf.map.n;
-    const GridPtrs pool = qf.g[0];   // (map mode: one set of pool pointers stays live over the loop)
+    const int F = frames_held<MAP>(qf, s, lane);   // (once, ahead of the rounds)
     path_cast_scene<W>(s, path + (size_t)s * scene_stride, point_stride, n_points - 1, lds, out,
                        [&](const SegLeg &leg, double &rt, int &rf, float &rx, float &ry, float &rz) {
-                           rt = 1.0;   // the first contact so far (wave-uniform); 1.0: none
-                           rf = -1;
-                           for (int f = 0; f < F && rt > 0.0; ++f) {
-                               const int m = MAP ? qf.map.pool_scene(f, s) : s;
-                               if (m < 0) continue;   // (map mode: this scene's map has no frame f)
-                               const GridScene gs = (MAP ? pool : qf.g[f]).scene(m);
-                               double bt;
-                               int bi, bpos;
-                               if (grid_cast(gs, leg, r2, rt, bt, bi, bpos, &lds.wl[w])) {   // (wave-uniform)
-                                   const float4 rec = gs.pt[bpos];
-                                   rt = bt; rx = rec.x; ry = rec.y; rz = rec.z; rf = f;
-                               }
-                           }
-                           return rf >= 0;
+                           return cast_frames<MAP>(qf, s, F, leg, r2, &lds.wl[w], rt, rf, rx, ry, rz);
                        });
 }
 
@@ -517,7 +424,7 @@ namespace amk {
 // The path cast over a pool (kfmap.hip, pipeline.hip): the leading n_scenes scenes of a map of S
 int map_path_cast(amk_kd *pool, int n_frames, const int *d_fmap, int S, int n_scenes, const double *d_path, int point_stride,
                   long long scene_stride, int n_points, double radius_sq, const PathCastOut &out, hipStream_t stream) {
-    if (!pool || !d_fmap || n_frames < 1 || S < 1 || n_scenes < 1 || n_scenes > S || scene_stride < 0) return AMK_ERR_INVALID_ARG;
+    if (!pool_args_ok(pool, d_fmap, n_frames, S) || n_scenes < 1 || n_scenes > S || scene_stride < 0) return AMK_ERR_INVALID_ARG;
     if (const int st = segment_cast_args_status(d_path, point_stride, n_points, radius_sq, out.any()); st != AMK_OK) return st;
     return launch_path_cast(frames_of_pool(pool, n_frames, d_fmap, S), n_scenes, d_path, point_stride, scene_stride, n_points, radius_sq,
                             out, stream);
@@ -526,7 +433,7 @@ int map_path_cast(amk_kd *pool, int n_frames, const int *d_fmap, int S, int n_sc
 int map_query_nearest(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_Twc, const amk_frame_camera *cam,
                       const double *d_queries, int query_stride, int n_queries, int k, float *d_pts, double *d_sqdist, int *d_frame,
                       int *d_counts, hipStream_t stream, bool exact) {
-    if (!pool || !d_fmap || n_frames < 1 || S < 1 || !query_args_ok(d_queries, query_stride, n_queries) || k < 1) return AMK_ERR_INVALID_ARG;
+    if (!pool_args_ok(pool, d_fmap, n_frames, S) || !query_args_ok(d_queries, query_stride, n_queries) || k < 1) return AMK_ERR_INVALID_ARG;
     if (d_Twc && !cam) return AMK_ERR_INVALID_ARG;
     if (k > AMK_MAX_K) return AMK_ERR_UNSUPPORTED;
     ExactPtrs ex;
@@ -540,47 +447,48 @@ int map_query_nearest(amk_kd *pool, int n_frames, const int *d_fmap, int S, cons
 
 int map_nearest_distance(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_queries, int query_stride,
                          int n_queries, double *d_dist, hipStream_t stream) {
-    if (!pool || !d_fmap || n_frames < 1 || S < 1 || !query_args_ok(d_queries, query_stride, n_queries) || !d_dist) return AMK_ERR_INVALID_ARG;
+    if (!pool_args_ok(pool, d_fmap, n_frames, S) || !query_args_ok(d_queries, query_stride, n_queries) || !d_dist) return AMK_ERR_INVALID_ARG;
     return launch_query<true>(frames_of_pool(pool, n_frames, d_fmap, S), S, d_queries, query_stride, n_queries, 1, nullptr, nullptr,
                               nullptr, nullptr, nullptr, nullptr, d_dist, stream);
 }
 int map_radius_search(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_queries, int query_stride, int n_queries,
                       double radius_sq, int max_results, float *d_pts, double *d_sqdist, int *d_frame, int *d_counts, hipStream_t stream) {
-    if (!pool || !d_fmap || n_frames < 1 || S < 1) return AMK_ERR_INVALID_ARG;
+    if (!pool_args_ok(pool, d_fmap, n_frames, S)) return AMK_ERR_INVALID_ARG;
     if (const int st = radius_args_status(d_queries, query_stride, n_queries, radius_sq, max_results, d_pts || d_sqdist || d_frame,
                                           d_pts || d_sqdist || d_frame || d_counts);
         st != AMK_OK)
         return st;
-    return launch_radius(frames_of_pool(pool, n_frames, d_fmap, S), S, d_queries, query_stride, n_queries, radius_sq, max_results, d_pts,
-                         d_sqdist, d_frame, d_counts, stream);
+    return launch_rows(map_radius_kernel<true>, map_radius_kernel<false>, frames_of_pool(pool, n_frames, d_fmap, S), S, n_queries, stream,
+                       d_queries, query_stride, n_queries, radius_clamped(radius_sq), max_results, d_pts, d_sqdist, d_frame, d_counts);
 }
 int map_segment_search(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_path, int point_stride, int n_points,
                        double radius_sq, int max_results, float *d_pts, double *d_sqdist, double *d_t, int *d_frame, int *d_counts,
                        hipStream_t stream) {
-    if (!pool || !d_fmap || n_frames < 1 || S < 1) return AMK_ERR_INVALID_ARG;
+    if (!pool_args_ok(pool, d_fmap, n_frames, S)) return AMK_ERR_INVALID_ARG;
     if (const int st = segment_args_status(d_path, point_stride, n_points, radius_sq, max_results, d_pts || d_sqdist || d_t || d_frame,
                                            d_pts || d_sqdist || d_t || d_frame || d_counts);
         st != AMK_OK)
         return st;
-    return launch_segment(frames_of_pool(pool, n_frames, d_fmap, S), S, d_path, point_stride, n_points, radius_sq, max_results, d_pts,
-                          d_sqdist, d_t, d_frame, d_counts, stream);
+    return launch_rows(map_segment_kernel<true>, map_segment_kernel<false>, frames_of_pool(pool, n_frames, d_fmap, S), S, n_points - 1,
+                       stream, d_path, point_stride, n_points, radius_clamped(radius_sq), max_results, d_pts, d_sqdist, d_t, d_frame,
+                       d_counts);
 }
 int map_segment_nearest(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_path, int point_stride, int n_points, int k,
                         float *d_pts, double *d_sqdist, double *d_t, int *d_frame, int *d_counts, hipStream_t stream) {
-    if (!pool || !d_fmap || n_frames < 1 || S < 1) return AMK_ERR_INVALID_ARG;
+    if (!pool_args_ok(pool, d_fmap, n_frames, S)) return AMK_ERR_INVALID_ARG;
     if (const int st = segment_nearest_args_status(d_path, point_stride, n_points, k, d_pts || d_sqdist || d_t || d_frame || d_counts);
         st != AMK_OK)
         return st;
-    return launch_segment_nearest(frames_of_pool(pool, n_frames, d_fmap, S), S, d_path, point_stride, n_points, k, d_pts, d_sqdist, d_t,
-                                  d_frame, d_counts, stream);
+    return launch_rows(map_segment_nearest_kernel<true>, map_segment_nearest_kernel<false>, frames_of_pool(pool, n_frames, d_fmap, S), S,
+                       n_points - 1, stream, d_path, point_stride, n_points, k, d_pts, d_sqdist, d_t, d_frame, d_counts);
 }
 int map_segment_cast(amk_kd *pool, int n_frames, const int *d_fmap, int S, const double *d_path, int point_stride, int n_points,
                      double radius_sq, int *d_hit, double *d_t, float *d_pts, int *d_frame, hipStream_t stream) {
-    if (!pool || !d_fmap || n_frames < 1 || S < 1) return AMK_ERR_INVALID_ARG;
+    if (!pool_args_ok(pool, d_fmap, n_frames, S)) return AMK_ERR_INVALID_ARG;
     if (const int st = segment_cast_args_status(d_path, point_stride, n_points, radius_sq, d_hit || d_t || d_pts || d_frame); st != AMK_OK)
         return st;
-    return launch_segment_cast(frames_of_pool(pool, n_frames, d_fmap, S), S, d_path, point_stride, n_points, radius_sq, d_hit, d_t, d_pts,
-                               d_frame, stream);
+    return launch_rows(map_segment_cast_kernel<true>, map_segment_cast_kernel<false>, frames_of_pool(pool, n_frames, d_fmap, S), S,
+                       n_points - 1, stream, d_path, point_stride, n_points, radius_clamped(radius_sq), d_hit, d_t, d_pts, d_frame);
 }
 }  // namespace amk
 
@@ -592,36 +500,33 @@ int amk_kd_query_frames(amk_kd *const *frames, int n_frames, const double *d_Twc
     if (!query_args_ok(d_queries, query_stride, n_queries) || k < 1) return AMK_ERR_INVALID_ARG;
     if (d_Twc && !cam) return AMK_ERR_INVALID_ARG;
     if (k > AMK_MAX_K) return AMK_ERR_UNSUPPORTED;
-    QueryFrames qf;
-    int S = 0;
-    if (const int st = frames_of_handles(frames, n_frames, qf, S); st != AMK_OK) return st;
-    return launch_query<false>(qf, S, d_queries, query_stride, n_queries, k, d_Twc, cam, d_pts, d_sqdist, d_frame, d_counts, nullptr,
+    const HandleFrames h = frames_of_handles(frames, n_frames);
+    if (h.status != AMK_OK) return h.status;
+    return launch_query<false>(h.qf, h.S, d_queries, query_stride, n_queries, k, d_Twc, cam, d_pts, d_sqdist, d_frame, d_counts, nullptr,
                                (hipStream_t)stream);
 }
 
 int amk_kd_nearest_distance_frames(amk_kd *const *frames, int n_frames, const double *d_queries, int query_stride, int n_queries,
                                    double *d_dist, void *stream) {
     if (!query_args_ok(d_queries, query_stride, n_queries) || !d_dist) return AMK_ERR_INVALID_ARG;
-    QueryFrames qf;
-    int S = 0;
-    if (const int st = frames_of_handles(frames, n_frames, qf, S); st != AMK_OK) return st;
-    return launch_query<true>(qf, S, d_queries, query_stride, n_queries, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, d_dist,
-                              (hipStream_t)stream);
+    const HandleFrames h = frames_of_handles(frames, n_frames);
+    if (h.status != AMK_OK) return h.status;
+    return launch_query<true>(h.qf, h.S, d_queries, query_stride, n_queries, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                              d_dist, (hipStream_t)stream);
 }
 
 int amk_kd_query_frames_host(amk_kd *const *frames, int n_frames, const double *h_Twc, const amk_frame_camera *cam,
                              const double *h_queries, int query_stride, int n_queries, int k, float *h_pts, double *h_sqdist,
                              int *h_frame, int *h_counts) {
     if (h_Twc && !cam) return AMK_ERR_INVALID_ARG;
-    QueryFrames qf;
-    int S = 0;
-    if (const int st = frames_of_handles(frames, n_frames, qf, S); st != AMK_OK) return st;
-    amk::HostStage stage;   // frees at return: these frames belong to no one handle
-    return amk::map_query_host(stage, S, h_queries, query_stride, n_queries, k, h_Twc, h_pts, h_sqdist, h_frame, h_counts, nullptr,
-                               [&](const amk::HostStage::Dev *d) {
-                                   return amk_kd_query_frames(frames, n_frames, d[amk::MQ_TWC], cam, d[amk::MQ_QUERIES], query_stride, n_queries, k,
-                                                              d[amk::MQ_PTS], d[amk::MQ_SQDIST], d[amk::MQ_FRAME], d[amk::MQ_COUNTS], nullptr);
-                               });
+    return frames_host(frames, n_frames, true, [&](amk::HostStage &stage, int S) {
+        return amk::map_query_host(stage, S, h_queries, query_stride, n_queries, k, h_Twc, h_pts, h_sqdist, h_frame, h_counts, nullptr,
+                                   [&](const amk::HostStage::Dev *d) {
+                                       return amk_kd_query_frames(frames, n_frames, d[amk::MQ_TWC], cam, d[amk::MQ_QUERIES], query_stride,
+                                                                  n_queries, k, d[amk::MQ_PTS], d[amk::MQ_SQDIST], d[amk::MQ_FRAME],
+                                                                  d[amk::MQ_COUNTS], nullptr);
+                                   });
+    });
 }
 
 int amk_kd_radius_search_frames(amk_kd *const *frames, int n_frames, const double *d_queries, int query_stride, int n_queries,
@@ -631,25 +536,22 @@ int amk_kd_radius_search_frames(amk_kd *const *frames, int n_frames, const doubl
                                           d_pts || d_sqdist || d_frame || d_counts);
         st != AMK_OK)
         return st;
-    QueryFrames qf;
-    int S = 0;
-    if (const int st = frames_of_handles(frames, n_frames, qf, S, false); st != AMK_OK) return st;
-    return launch_radius(qf, S, d_queries, query_stride, n_queries, radius_sq, max_results, d_pts, d_sqdist, d_frame, d_counts,
-                         (hipStream_t)stream);
+    const HandleFrames h = frames_of_handles(frames, n_frames, false);
+    if (h.status != AMK_OK) return h.status;
+    return launch_rows(map_radius_kernel<true>, map_radius_kernel<false>, h.qf, h.S, n_queries, (hipStream_t)stream, d_queries,
+                       query_stride, n_queries, radius_clamped(radius_sq), max_results, d_pts, d_sqdist, d_frame, d_counts);
 }
 
 int amk_kd_radius_search_frames_host(amk_kd *const *frames, int n_frames, const double *h_queries, int query_stride, int n_queries,
                                      double radius_sq, int max_results, float *h_pts, double *h_sqdist, int *h_frame, int *h_counts) {
-    QueryFrames qf;
-    int S = 0;
-    if (const int st = frames_of_handles(frames, n_frames, qf, S, false); st != AMK_OK) return st;
-    amk::HostStage stage;   // frees at return: these frames belong to no one handle
-    return amk::map_radius_host(stage, S, h_queries, query_stride, n_queries, radius_sq, max_results, h_pts, h_sqdist, h_frame, h_counts,
-                                [&](const amk::HostStage::Dev *d) {
-                                    return amk_kd_radius_search_frames(frames, n_frames, d[amk::MQ_QUERIES], query_stride, n_queries, radius_sq,
-                                                                       max_results, d[amk::MQ_PTS], d[amk::MQ_SQDIST], d[amk::MQ_FRAME],
-                                                                       d[amk::MQ_COUNTS], nullptr);
-                                });
+    return frames_host(frames, n_frames, false, [&](amk::HostStage &stage, int S) {
+        return amk::map_radius_host(stage, S, h_queries, query_stride, n_queries, radius_sq, max_results, h_pts, h_sqdist, h_frame, h_counts,
+                                    [&](const amk::HostStage::Dev *d) {
+                                        return amk_kd_radius_search_frames(frames, n_frames, d[amk::MQ_QUERIES], query_stride, n_queries,
+                                                                           radius_sq, max_results, d[amk::MQ_PTS], d[amk::MQ_SQDIST],
+                                                                           d[amk::MQ_FRAME], d[amk::MQ_COUNTS], nullptr);
+                                    });
+    });
 }
 
 int amk_kd_segment_search_frames(amk_kd *const *frames, int n_frames, const double *d_path, int point_stride, int n_points,
@@ -659,26 +561,23 @@ int amk_kd_segment_search_frames(amk_kd *const *frames, int n_frames, const doub
                                            d_pts || d_sqdist || d_t || d_frame || d_counts);
         st != AMK_OK)
         return st;
-    QueryFrames qf;
-    int S = 0;
-    if (const int st = frames_of_handles(frames, n_frames, qf, S, false); st != AMK_OK) return st;
-    return launch_segment(qf, S, d_path, point_stride, n_points, radius_sq, max_results, d_pts, d_sqdist, d_t, d_frame, d_counts,
-                          (hipStream_t)stream);
+    const HandleFrames h = frames_of_handles(frames, n_frames, false);
+    if (h.status != AMK_OK) return h.status;
+    return launch_rows(map_segment_kernel<true>, map_segment_kernel<false>, h.qf, h.S, n_points - 1, (hipStream_t)stream, d_path,
+                       point_stride, n_points, radius_clamped(radius_sq), max_results, d_pts, d_sqdist, d_t, d_frame, d_counts);
 }
 
 int amk_kd_segment_search_frames_host(amk_kd *const *frames, int n_frames, const double *h_path, int point_stride, int n_points,
                                       double radius_sq, int max_results, float *h_pts, double *h_sqdist, double *h_t, int *h_frame,
                                       int *h_counts) {
-    QueryFrames qf;
-    int S = 0;
-    if (const int st = frames_of_handles(frames, n_frames, qf, S, false); st != AMK_OK) return st;
-    amk::HostStage stage;   // frees at return: these frames belong to no one handle
-    return amk::map_segment_host(stage, S, h_path, point_stride, n_points, radius_sq, max_results, h_pts, h_sqdist, h_t, h_frame, h_counts,
-                                 [&](const amk::HostStage::Dev *d) {
-                                     return amk_kd_segment_search_frames(frames, n_frames, d[amk::MQ_QUERIES], point_stride, n_points,
-                                                                         radius_sq, max_results, d[amk::MQ_PTS], d[amk::MQ_SQDIST],
-                                                                         d[amk::MQ_DIST], d[amk::MQ_FRAME], d[amk::MQ_COUNTS], nullptr);
-                                 });
+    return frames_host(frames, n_frames, false, [&](amk::HostStage &stage, int S) {
+        return amk::map_segment_host(stage, S, h_path, point_stride, n_points, radius_sq, max_results, h_pts, h_sqdist, h_t, h_frame, h_counts,
+                                     [&](const amk::HostStage::Dev *d) {
+                                         return amk_kd_segment_search_frames(frames, n_frames, d[amk::MQ_QUERIES], point_stride, n_points,
+                                                                             radius_sq, max_results, d[amk::MQ_PTS], d[amk::MQ_SQDIST],
+                                                                             d[amk::MQ_DIST], d[amk::MQ_FRAME], d[amk::MQ_COUNTS], nullptr);
+                                     });
+    });
 }
 
 int amk_kd_segment_nearest_frames(amk_kd *const *frames, int n_frames, const double *d_path, int point_stride, int n_points, int k,
@@ -686,73 +585,67 @@ int amk_kd_segment_nearest_frames(amk_kd *const *frames, int n_frames, const dou
     if (const int st = segment_nearest_args_status(d_path, point_stride, n_points, k, d_pts || d_sqdist || d_t || d_frame || d_counts);
         st != AMK_OK)
         return st;
-    QueryFrames qf;
-    int S = 0;
-    if (const int st = frames_of_handles(frames, n_frames, qf, S, false); st != AMK_OK) return st;
-    return launch_segment_nearest(qf, S, d_path, point_stride, n_points, k, d_pts, d_sqdist, d_t, d_frame, d_counts, (hipStream_t)stream);
+    const HandleFrames h = frames_of_handles(frames, n_frames, false);
+    if (h.status != AMK_OK) return h.status;
+    return launch_rows(map_segment_nearest_kernel<true>, map_segment_nearest_kernel<false>, h.qf, h.S, n_points - 1, (hipStream_t)stream,
+                       d_path, point_stride, n_points, k, d_pts, d_sqdist, d_t, d_frame, d_counts);
 }
 
 int amk_kd_segment_nearest_frames_host(amk_kd *const *frames, int n_frames, const double *h_path, int point_stride, int n_points, int k,
                                        float *h_pts, double *h_sqdist, double *h_t, int *h_frame, int *h_counts) {
-    QueryFrames qf;
-    int S = 0;
-    if (const int st = frames_of_handles(frames, n_frames, qf, S, false); st != AMK_OK) return st;
-    amk::HostStage stage;   // frees at return: these frames belong to no one handle
-    return amk::map_segment_nearest_host(stage, S, h_path, point_stride, n_points, k, h_pts, h_sqdist, h_t, h_frame, h_counts,
-                                         [&](const amk::HostStage::Dev *d) {
-                                             return amk_kd_segment_nearest_frames(frames, n_frames, d[amk::MQ_QUERIES], point_stride,
-                                                                                  n_points, k, d[amk::MQ_PTS], d[amk::MQ_SQDIST],
-                                                                                  d[amk::MQ_DIST], d[amk::MQ_FRAME], d[amk::MQ_COUNTS],
-                                                                                  nullptr);
-                                         });
+    return frames_host(frames, n_frames, false, [&](amk::HostStage &stage, int S) {
+        return amk::map_segment_nearest_host(stage, S, h_path, point_stride, n_points, k, h_pts, h_sqdist, h_t, h_frame, h_counts,
+                                             [&](const amk::HostStage::Dev *d) {
+                                                 return amk_kd_segment_nearest_frames(frames, n_frames, d[amk::MQ_QUERIES], point_stride,
+                                                                                      n_points, k, d[amk::MQ_PTS], d[amk::MQ_SQDIST],
+                                                                                      d[amk::MQ_DIST], d[amk::MQ_FRAME], d[amk::MQ_COUNTS],
+                                                                                      nullptr);
+                                             });
+    });
 }
 
 int amk_kd_segment_cast_frames(amk_kd *const *frames, int n_frames, const double *d_path, int point_stride, int n_points,
                                double radius_sq, int *d_hit, double *d_t, float *d_pts, int *d_frame, void *stream) {
     if (const int st = segment_cast_args_status(d_path, point_stride, n_points, radius_sq, d_hit || d_t || d_pts || d_frame); st != AMK_OK)
         return st;
-    QueryFrames qf;
-    int S = 0;
-    if (const int st = frames_of_handles(frames, n_frames, qf, S); st != AMK_OK) return st;
-    return launch_segment_cast(qf, S, d_path, point_stride, n_points, radius_sq, d_hit, d_t, d_pts, d_frame, (hipStream_t)stream);
+    const HandleFrames h = frames_of_handles(frames, n_frames);
+    if (h.status != AMK_OK) return h.status;
+    return launch_rows(map_segment_cast_kernel<true>, map_segment_cast_kernel<false>, h.qf, h.S, n_points - 1, (hipStream_t)stream, d_path,
+                       point_stride, n_points, radius_clamped(radius_sq), d_hit, d_t, d_pts, d_frame);
 }
 
 int amk_kd_segment_cast_frames_host(amk_kd *const *frames, int n_frames, const double *h_path, int point_stride, int n_points,
                                     double radius_sq, int *h_hit, double *h_t, float *h_pts, int *h_frame) {
-    QueryFrames qf;
-    int S = 0;
-    if (const int st = frames_of_handles(frames, n_frames, qf, S); st != AMK_OK) return st;
-    amk::HostStage stage;   // frees at return: these frames belong to no one handle
-    return amk::map_segment_cast_host(stage, S, h_path, point_stride, n_points, radius_sq, h_hit, h_t, h_pts, h_frame,
-                                      [&](const amk::HostStage::Dev *d) {
-                                          return amk_kd_segment_cast_frames(frames, n_frames, d[amk::MQ_QUERIES], point_stride, n_points,
-                                                                            radius_sq, d[amk::MQ_COUNTS], d[amk::MQ_DIST], d[amk::MQ_PTS],
-                                                                            d[amk::MQ_FRAME], nullptr);
-                                      });
+    return frames_host(frames, n_frames, true, [&](amk::HostStage &stage, int S) {
+        return amk::map_segment_cast_host(stage, S, h_path, point_stride, n_points, radius_sq, h_hit, h_t, h_pts, h_frame,
+                                          [&](const amk::HostStage::Dev *d) {
+                                              return amk_kd_segment_cast_frames(frames, n_frames, d[amk::MQ_QUERIES], point_stride, n_points,
+                                                                                radius_sq, d[amk::MQ_COUNTS], d[amk::MQ_DIST],
+                                                                                d[amk::MQ_PTS], d[amk::MQ_FRAME], nullptr);
+                                          });
+    });
 }
 
 int amk_kd_path_cast_frames(amk_kd *const *frames, int n_frames, const double *d_path, int point_stride, int n_points, double radius_sq,
                             int *d_stop, int *d_leg, double *d_t, double *d_free, float *d_pts, int *d_frame, void *stream) {
     const PathCastOut out{d_stop, d_leg, d_t, d_free, d_pts, d_frame};
     if (const int st = segment_cast_args_status(d_path, point_stride, n_points, radius_sq, out.any()); st != AMK_OK) return st;
-    QueryFrames qf;
-    int S = 0;
-    if (const int st = frames_of_handles(frames, n_frames, qf, S); st != AMK_OK) return st;
-    return launch_path_cast(qf, S, d_path, point_stride, (long long)n_points * point_stride, n_points, radius_sq, out, (hipStream_t)stream);
+    const HandleFrames h = frames_of_handles(frames, n_frames);
+    if (h.status != AMK_OK) return h.status;
+    return launch_path_cast(h.qf, h.S, d_path, point_stride, (long long)n_points * point_stride, n_points, radius_sq, out,
+                            (hipStream_t)stream);
 }
 
 int amk_kd_path_cast_frames_host(amk_kd *const *frames, int n_frames, const double *h_path, int point_stride, int n_points,
                                  double radius_sq, int *h_stop, int *h_leg, double *h_t, double *h_free, float *h_pts, int *h_frame) {
-    QueryFrames qf;
-    int S = 0;
-    if (const int st = frames_of_handles(frames, n_frames, qf, S); st != AMK_OK) return st;
-    amk::HostStage stage;   // frees at return: these frames belong to no one handle
-    return amk::map_path_cast_host(stage, S, h_path, point_stride, n_points, radius_sq, h_stop, h_leg, h_t, h_free, h_pts, h_frame,
-                                   [&](const amk::HostStage::Dev *d) {
-                                       return amk_kd_path_cast_frames(frames, n_frames, d[amk::PC_PATH], point_stride, n_points, radius_sq,
-                                                                      d[amk::PC_STOP], d[amk::PC_LEG], d[amk::PC_T], d[amk::PC_FREE],
-                                                                      d[amk::PC_PTS], d[amk::PC_ID], nullptr);
-                                   });
+    return frames_host(frames, n_frames, true, [&](amk::HostStage &stage, int S) {
+        return amk::map_path_cast_host(stage, S, h_path, point_stride, n_points, radius_sq, h_stop, h_leg, h_t, h_free, h_pts, h_frame,
+                                       [&](const amk::HostStage::Dev *d) {
+                                           return amk_kd_path_cast_frames(frames, n_frames, d[amk::PC_PATH], point_stride, n_points,
+                                                                          radius_sq, d[amk::PC_STOP], d[amk::PC_LEG], d[amk::PC_T],
+                                                                          d[amk::PC_FREE], d[amk::PC_PTS], d[amk::PC_ID], nullptr);
+                                       });
+    });
 }
 
 }  // extern "C"
