@@ -65,6 +65,7 @@ SYMBOLS = [
     "amk_depth_to_edge_cloud", "amk_depth_to_edge_cloud_host",
     "amk_depth_clouds_work_bytes", "amk_depth_to_clouds", "amk_depth_to_clouds_host",
     "amk_sim_render_depth", "amk_sim_render_depth_host", "amk_sim_vehicle_step", "amk_sim_vehicle_step_host",
+    "amk_sim_render_world", "amk_sim_render_world_host", "amk_sim_vehicle_step_att", "amk_sim_vehicle_step_att_host",
 ]
 
 
@@ -122,6 +123,7 @@ class FrameCamera(C.Structure):
 
 
 AMK_DEPTH_U16, AMK_DEPTH_F32 = 0, 1
+AMK_SIM_ATT_YAW, AMK_SIM_ATT_ACCEL = 0, 1
 AMK_QUEUES_POOLED, AMK_QUEUES_PRIORITY = 0, 1   # amk_pipeline_queue_mode
 AMK_AUDIT_OFF, AMK_AUDIT_REPORT, AMK_AUDIT_SLOW_DOWN = 0, 1, 2   # amk_pipeline_set_path_audit
 AMK_PIPELINE_MAX_OWN_QUEUES = 24
@@ -299,6 +301,10 @@ def load():
         "amk_sim_render_depth_host": (i, [vp, vp, i, i, d, d, C.POINTER(DepthParams), i, i, vp, vp, i]),
         "amk_sim_vehicle_step": (i, [vp, vp, vp, vp, i, d, vp]),
         "amk_sim_vehicle_step_host": (i, [vp, vp, vp, vp, i, d]),
+        "amk_sim_render_world": (i, [vp, vp, i, vp, vp, i, i, d, d, C.POINTER(DepthParams), i, i, vp, vp, i, vp]),
+        "amk_sim_render_world_host": (i, [vp, vp, i, vp, vp, i, i, d, d, C.POINTER(DepthParams), i, i, vp, vp, i]),
+        "amk_sim_vehicle_step_att": (i, [vp, vp, vp, vp, i, d, i, d, vp]),
+        "amk_sim_vehicle_step_att_host": (i, [vp, vp, vp, vp, i, d, i, d]),
     }
     sig["amk__kd_set_mode"] = (i, [vp, i])  # internal: 0 bucketed index, 1 streaming scan
     sig["amk__sweep_set_target"] = (None, [i])  # internal (tests, A/B): the pool's sweep against 1 a fine hashed grid of the current frame (default), 0 the frame's own index
@@ -310,6 +316,8 @@ def load():
     sig["amk__depth_set_band_rows"] = (i, [i])  # internal (tests, measurements): amk_depth_to_clouds tiled with bands of this many rows at any image size; 0 automatic
     sig["amk__sim_render_t"] = (i, [vp, vp, i, i, d, d, C.POINTER(DepthParams), i, i, vp, vp, vp])  # internal (tests): amk_sim_render_depth's fp64 ray parameter t [S][rows][cols], 0 = no return
     sig["amk__sim_chunk"] = (i, [])  # internal (tests): cylinders per LDS round of the render kernel
+    sig["amk__sim_render_world_t"] = (i, [vp, vp, i, vp, vp, i, i, d, d, C.POINTER(DepthParams), i, i, vp, vp, vp])  # internal (tests): amk_sim_render_world's fp64 ray parameter t
+    sig["amk__sim_world_chunk"] = (i, [])  # internal (tests): boxes per LDS round of the world kernel
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)
         if fn is None:

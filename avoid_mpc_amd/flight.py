@@ -17,6 +17,8 @@ GPU driver (tests/_flight.py, bench.py --workload flight) and the CPU-oracle dri
   period_inputs / apply_command   GetInitPath + the clock model on one side of the step, PubCmd / PubSlowDownCmd on the other
   render_depth / render_depth_ordered / quantise_depth / vehicle_step_ordered   the depth sensor and the affine vehicle in numpy;
                               the *_ordered ones restate csrc/sim.hip (amk_sim_render_depth, amk_sim_vehicle_step) operation for operation
+  render_world_ordered / vehicle_attitude_ordered / box_clearance / WallWorld   the same for amk_sim_render_world (cylinders and
+                              boxes) and amk_sim_vehicle_step_att (the vehicle tilts into its thrust); a corridor with walls and gates
 
 Nothing here computes neighbours or solves anything: that is the step's job (amk_step_batch / the oracle's stepo_run).
 """
@@ -330,3 +332,132 @@ def vehicle_step_ordered(ABc, x, cmd, pose_quantum=0.0):
     T[:, 0, 0] = cs; T[:, 0, 1] = 0.0 - sn; T[:, 1, 0] = sn; T[:, 1, 1] = cs
     T[:, :3, 3] = np.rint(xn[:, 0:3] * pose_quantum) / pose_quantum if pose_quantum > 0 else xn[:, 0:3]
     return xn, T
+
+
+# ---- boxes and attitude: amk_sim_render_world, amk_sim_vehicle_step_att --------------------------------------------------------------
+ATT_YAW, ATT_ACCEL = 0, 1   # AMK_SIM_ATT_YAW, AMK_SIM_ATT_ACCEL
+
+
+def _box_slab(lo_o, hi_o, d, inv, inside):
+    """One slab of amk_sim_render_world: lo_o = lo - o, hi_o = hi - o, inv = 1.0 / d -> (near, far); a parallel ray (d == 0) gets
+    (-inf, +inf) when the origin lies in the slab and (+inf, -inf), a miss, when it does not."""
+    t1, t2 = lo_o * inv, hi_o * inv
+    lt = t1 < t2
+    near, far = np.where(lt, t1, t2), np.where(lt, t2, t1)
+    par = d == 0
+    return np.where(par, -np.inf if inside else np.inf, near), np.where(par, np.inf if inside else -np.inf, far)
+
+
+def render_world_ordered(cyl, box, Twb, Tbc, rows, cols, fx, fy, cx, cy, z_top=4.0, max_range=60.0):
+    """render_depth_ordered in a world that also holds boxes, in the OPERATION ORDER of amk_sim_render_world (include/avoid_mpc_amd.h,
+    "Closed-loop simulation"): box float64 [n, 8] = (cx, cy, hx, hy, c, s, z0, z1).  The ground and the cylinders are
+    render_depth_ordered's lines; then every box in index order by three slabs, one reciprocal each, a strict < throughout.
+    -> t float64 [rows, cols], 0 = no return."""
+    ccx, ccy, cr = (np.asarray(v, np.float64).reshape(-1) for v in cyl)
+    box = np.asarray(box, np.float64).reshape(-1, 8)
+    A, B = np.asarray(Twb, np.float64).reshape(4, 4), np.asarray(Tbc, np.float64).reshape(4, 4)
+    M = np.empty((3, 4))
+    for i in range(3):
+        for j in range(4):
+            M[i, j] = ((A[i, 0] * B[0, j] + A[i, 1] * B[1, j]) + A[i, 2] * B[2, j]) + A[i, 3] * B[3, j]
+    o = M[:, 3]
+    v, u = np.meshgrid(np.arange(rows, dtype=np.float64), np.arange(cols, dtype=np.float64), indexing="ij")
+    dc0, dc1 = (u - cx) / fx, (v - cy) / fy
+    dx, dy, dz = ((M[i, 0] * dc0 + M[i, 1] * dc1) + M[i, 2] * 1.0 for i in range(3))
+    best = np.full((rows, cols), np.inf)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        tg = -o[2] / dz                                                              # ground plane
+        best = np.where((dz < 0) & (tg > 0), tg, best)
+        a = dx * dx + dy * dy
+        for k in range(ccx.size):
+            ox, oy = o[0] - ccx[k], o[1] - ccy[k]
+            b = ox * dx + oy * dy
+            c = (ox * ox + oy * oy) - cr[k] * cr[k]
+            disc = b * b - a * c
+            t = (-b - np.sqrt(np.where(disc >= 0, disc, np.nan))) / a
+            z = o[2] + t * dz
+            ok = (disc >= 0) & (t > 0) & (z >= 0) & (z <= z_top)
+            best = np.where(ok & (t < best), t, best)
+        inv_z = 1.0 / dz
+        for bx, by, hx, hy, c, s, z0, z1 in box:
+            ox, oy = o[0] - bx, o[1] - by
+            olx, oly = c * ox + s * oy, c * oy - s * ox
+            dlx, dly = c * dx + s * dy, c * dy - s * dx
+            n0, f0 = _box_slab(-hx - olx, hx - olx, dlx, 1.0 / dlx, bool(-hx <= olx and olx <= hx))
+            n1, f1 = _box_slab(-hy - oly, hy - oly, dly, 1.0 / dly, bool(-hy <= oly and oly <= hy))
+            n2, f2 = _box_slab(z0 - o[2], z1 - o[2], dz, inv_z, bool(z0 <= o[2] and o[2] <= z1))
+            tn, tf = np.where(n0 > n1, n0, n1), np.where(f0 < f1, f0, f1)
+            tn, tf = np.where(n2 > tn, n2, tn), np.where(f2 < tf, f2, tf)
+            ok = (n0 <= f0) & (n1 <= f1) & (n2 <= f2) & (tn > 0) & (tn <= tf)
+            best = np.where(ok & (tn < best), tn, best)                              # strict <: the earlier hit keeps an equal t
+    return np.where(best <= max_range, best, 0.0)
+
+
+def vehicle_attitude_ordered(ABc, x, cmd, pose_quantum=0.0, attitude=ATT_ACCEL, gz=GZ, cs_sn=None):
+    """amk_sim_vehicle_step_att in numpy, operation for operation: vehicle_step_ordered's x+ and pose, and for ATT_ACCEL the rotation
+    [xb yb zb] of acc2rotmat (mpc_obstacle_casadi.py:253-264) on the NEW acceleration plus (0, 0, gz), with the yaw mode's cs, sn;
+    Rz(yaw) stays unless n > 0 and m > 0.  cs_sn = (cs [S], sn [S]) replaces numpy's cos / sin of the yaw by the caller's (the device's
+    own, read from a yaw-mode pose: the two libraries differ by an ulp at some yaws).  -> (x+ [S, 10], Twb [S, 4, 4])"""
+    xn, T = vehicle_step_ordered(ABc, x, cmd, pose_quantum)
+    if cs_sn is not None:
+        T[:, 0, 0] = T[:, 1, 1] = cs_sn[0]; T[:, 1, 0] = cs_sn[1]; T[:, 0, 1] = 0.0 - np.asarray(cs_sn[1])
+    if attitude == ATT_YAW:
+        return xn, T
+    assert attitude == ATT_ACCEL
+    cs, sn = T[:, 0, 0].copy(), T[:, 1, 0].copy()
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        t0, t1, t2 = xn[:, 7], xn[:, 8], xn[:, 9] + gz
+        n = np.sqrt((t0 * t0 + t1 * t1) + t2 * t2)
+        zb0, zb1, zb2 = t0 / n, t1 / n, t2 / n
+        y0, y1, y2 = 0.0 - zb2 * sn, zb2 * cs, zb0 * sn - zb1 * cs
+        m = np.sqrt((y0 * y0 + y1 * y1) + y2 * y2)
+        yb0, yb1, yb2 = y0 / m, y1 / m, y2 / m
+        R = np.empty((len(xn), 3, 3))
+        R[:, 0, 0] = yb1 * zb2 - yb2 * zb1; R[:, 0, 1] = yb0; R[:, 0, 2] = zb0
+        R[:, 1, 0] = yb2 * zb0 - yb0 * zb2; R[:, 1, 1] = yb1; R[:, 1, 2] = zb1
+        R[:, 2, 0] = yb0 * zb1 - yb1 * zb0; R[:, 2, 1] = yb2; R[:, 2, 2] = zb2
+    ok = (n > 0) & (m > 0)
+    T[ok, :3, :3] = R[ok]
+    return xn, T
+
+
+def box_clearance(p, box):
+    """Horizontal distance from position(s) p [..., 3] to the nearest FACE of the boxes box [n, 8] whose vertical extent [z0, z1] holds
+    p's height (negative: inside a box; +inf where no box is at that height).  For reports, not for the contract."""
+    p, box = np.asarray(p, np.float64), np.asarray(box, np.float64).reshape(-1, 8)
+    ox, oy = p[..., 0:1] - box[:, 0], p[..., 1:2] - box[:, 1]
+    qx = np.abs(box[:, 4] * ox + box[:, 5] * oy) - np.abs(box[:, 2])
+    qy = np.abs(box[:, 4] * oy - box[:, 5] * ox) - np.abs(box[:, 3])
+    out = np.sqrt(np.maximum(qx, 0.0) ** 2 + np.maximum(qy, 0.0) ** 2) + np.minimum(np.maximum(qx, qy), 0.0)
+    level = (p[..., 2:3] >= box[:, 6]) & (p[..., 2:3] <= box[:, 7])
+    return np.where(level, out, np.inf).min(axis=-1, initial=np.inf)
+
+
+class WallWorld(FlightWorld):
+    """FlightWorld's corridor of cylinders with flat things in it: every `wall_every` metres from `wall_first` on a wall stands across
+    the corridor (|y| <= 8 m, `thick` m deep, 4 m high) with one gap `gap` m wide at a seeded y.  A wall is two boxes, the piers left
+    and right of the gap; every second wall has a lintel over the gap (z0 = `lintel` > 0: a gate), and every third is yawed a few
+    degrees about its own middle, gap and lintel with it.  Cylinders that would stand in a wall are left out, so the worlds of a
+    fleet hold different cylinder counts.  Seeded and pure, like FlightWorld: `box` float64 [n_box, 8] =
+    (cx, cy, hx, hy, c, s, z0, z1), the layout of amk_sim_render_world."""
+
+    def __init__(self, seed, prm, n_points, length=80.0, wall_first=9.0, wall_every=12.0, gap=3.0, thick=0.1, lintel=2.5, **kw):
+        super().__init__(seed, prm, n_points, length=length, **kw)
+        rng = np.random.default_rng([self.seed, 0xB0C5])
+        rows = []
+        for i, wx in enumerate(np.arange(wall_first, float(length), wall_every)):
+            gy = rng.uniform(-4.0, 4.0)
+            yaw = rng.uniform(-0.15, 0.15) if i % 3 == 2 else 0.0
+            c, s = (np.cos(yaw), np.sin(yaw)) if yaw != 0.0 else (1.0, 0.0)
+            for lo, hi in ((-8.0, gy - gap / 2), (gy + gap / 2, 8.0)):             # the two piers, along the wall's own y axis
+                mid, half = (lo + hi) / 2, (hi - lo) / 2
+                rows.append([wx - s * mid, c * mid, thick / 2, half, c, s, 0.0, 4.0])
+            if i % 2 == 1:
+                rows.append([wx - s * gy, c * gy, thick / 2, gap / 2, c, s, lintel, 4.0])
+        self.box = np.array(rows, np.float64).reshape(-1, 8)
+        footprint = self.box.copy(); footprint[:, 6] = 0.0                          # (a cylinder under a lintel would pierce it)
+        keep = np.abs(box_clearance(np.stack([self.cx, self.cy, np.ones_like(self.cx)], axis=1), footprint)) > self.cr + 0.05
+        self.cx, self.cy, self.cr = self.cx[keep], self.cy[keep], self.cr[keep]   # no cylinder stands in a wall
+
+    def box_clearance(self, p):
+        return box_clearance(p, self.box)

@@ -1123,6 +1123,47 @@ def sim_vehicle_step(ABc, cmd, x, Twb=None, pose_quantum=0.0, stream=None):
     return x
 
 
+def sim_render_world(cyl, box, Twb, params, rows, cols, cyl_counts=None, box_counts=None, z_top=4.0, max_range=60.0, dtype=torch.uint16,
+                     out=None, stream=None):
+    """amk_sim_render_world: sim_render_depth in worlds that also hold boxes.  cyl float64 [S, max_cyl, 3], box float64 [S, max_box, 8]
+    = (cx, cy, hx, hy, c, s, z0, z1), cyl_counts / box_counts int32 [S] or None (the maximum in every scene), Twb float64 [S, 4, 4]
+    -> depth [S, rows, cols] of `dtype`, as sim_render_depth; dtype torch.float64 is the test-only fp64 ray parameter
+    (amk__sim_render_world_t).  Stream-ordered on torch's current stream (or `stream`); `out` re-uses a buffer."""
+    assert cyl.dtype == torch.float64 and cyl.dim() == 3 and cyl.shape[2] == 3 and cyl.is_contiguous()
+    S, max_cyl, max_box = int(cyl.shape[0]), int(cyl.shape[1]), int(box.shape[1])
+    assert box.dtype == torch.float64 and tuple(box.shape) == (S, max_box, 8) and box.is_contiguous()
+    assert Twb.dtype == torch.float64 and tuple(Twb.shape) == (S, 4, 4) and Twb.is_contiguous()
+    for counts in (cyl_counts, box_counts):
+        assert counts is None or (counts.dtype == torch.int32 and tuple(counts.shape) == (S,) and counts.is_contiguous())
+    if out is None:
+        out = torch.empty((S, int(rows), int(cols)), dtype=dtype, device=Twb.device)
+    assert tuple(out.shape) == (S, int(rows), int(cols)) and out.is_contiguous()
+    lib = capi.load()
+    head = (capi.dptr(cyl) if max_cyl else None, capi.dptr(cyl_counts), max_cyl, capi.dptr(box) if max_box else None, capi.dptr(box_counts),
+            max_box, S, float(z_top), float(max_range), C.byref(params), int(rows), int(cols), capi.dptr(Twb), capi.dptr(out))
+    if out.dtype == torch.float64:
+        capi.check(lib.amk__sim_render_world_t(*head, capi.stream_ptr(stream)), "amk__sim_render_world_t")
+    else:
+        kind = capi.AMK_DEPTH_F32 if out.dtype == torch.float32 else capi.AMK_DEPTH_U16
+        assert kind == capi.AMK_DEPTH_F32 or out.dtype in (torch.uint16, torch.int16)
+        capi.check(lib.amk_sim_render_world(*head, kind, capi.stream_ptr(stream)), "amk_sim_render_world")
+    return out
+
+
+def sim_vehicle_step_att(ABc, cmd, x, Twb=None, pose_quantum=0.0, attitude=capi.AMK_SIM_ATT_ACCEL, gz=9.81, stream=None):
+    """amk_sim_vehicle_step_att: sim_vehicle_step, with Twb's rotation chosen by `attitude`: capi.AMK_SIM_ATT_YAW is sim_vehicle_step
+    bit for bit, capi.AMK_SIM_ATT_ACCEL tilts the vehicle into its thrust a + (0, 0, gz) (acc2rotmat on the new state)."""
+    ABc = np.ascontiguousarray(ABc, np.float64).reshape(-1)
+    assert ABc.size == 150
+    S = int(x.shape[0])
+    assert x.dtype == torch.float64 and tuple(x.shape) == (S, 10) and cmd.dtype == torch.float64 and tuple(cmd.shape) == (S, 3)
+    assert Twb is None or (Twb.dtype == torch.float64 and tuple(Twb.shape) == (S, 4, 4))
+    capi.check(capi.load().amk_sim_vehicle_step_att(ABc.ctypes.data_as(C.c_void_p), capi.dptr(cmd), capi.dptr(x), capi.dptr(Twb), S,
+                                                    float(pose_quantum), int(attitude), float(gz), capi.stream_ptr(stream)),
+               "amk_sim_vehicle_step_att")
+    return x
+
+
 def plant_model(tau, con_dt, drag=(0.0, 0.0, 0.0)):
     """h_ABc of sim_vehicle_step: the MPC's own model at the control period con_dt (the library's host-side amk__mpc_dynamics; no
     device) -> numpy float64 [150] = A [10][10], B [10][4], c [10]."""

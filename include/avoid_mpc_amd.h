@@ -1208,6 +1208,64 @@ int amk_sim_vehicle_step(const double *h_ABc, const double *d_cmd, double *d_x, 
 int amk_sim_vehicle_step_host(const double *h_ABc, const double *h_cmd, double *h_x, double *h_Twb, int n_scenes,
                               double pose_quantum);
 
+/* amk_sim_render_world: amk_sim_render_depth in a world that also holds boxes -- walls, gates, lintels, beams.  Every argument it
+ * shares with amk_sim_render_depth means what it means there, and so do Twc, the ray d, the ground, the cylinders, max_range and
+ * both pixel types, word for word.
+ *   d_box         [S][max_box][8] double = (cx, cy, hx, hy, c, s, z0, z1): a box centred at (cx, cy) in the ground plane, with half
+ *                 extents hx, hy along its own axes, turned about the vertical by the yaw whose cosine and sine the CALLER computed
+ *                 (c, s): the device evaluates no transcendental and does not renormalise them.  [z0, z1] is the box's own vertical
+ *                 extent; it is not cut at z_top, and z0 > 0 is a floating box.  May be NULL when max_box == 0.
+ *   d_box_counts  [S] or NULL = max_box in every scene; a count outside [0, max_box] is clamped into it.
+ * Arithmetic, continuing the contract above (fp64, no contraction, left to right, IEEE division; avoid_mpc_amd/flight.py
+ * render_world_ordered restates it).  With o the camera position and d the ray, per box:
+ *   ox = o_x - cx, oy = o_y - cy;  olx = c ox + s oy, oly = c oy - s ox;  dlx = c d_x + s d_y, dly = c d_y - s d_x
+ *   three slabs (o, d, lo, hi), in this order: x (olx, dlx, -hx, hx), y (oly, dly, -hy, hy), z (o_z, d_z, z0, z1)
+ *   a slab with d != 0:  inv = 1.0 / d, t1 = (lo - o) inv, t2 = (hi - o) inv, near = t1 < t2 ? t1 : t2, far = t1 < t2 ? t2 : t1
+ *                        (one reciprocal per slab, no division per bound)
+ *   a slab with d == 0:  the ray is parallel to it.  near = -inf, far = +inf when lo <= o && o <= hi: the slab imposes no bound.
+ *                        Otherwise near = +inf, far = -inf: the box is missed.
+ *   tn = n_x > n_y ? n_x : n_y, then n_z > tn ? n_z : tn;  tf = f_x < f_y ? f_x : f_y, then f_z < tf ? f_z : tf
+ *   a hit at t = tn when  n_x <= f_x && n_y <= f_y && n_z <= f_z && tn > 0 && tn <= tf.
+ * A grazing ray counts (tn == tf is a hit, as disc == 0 is for a cylinder).  A camera inside a box gets no return from that box
+ * (tn <= 0), as a camera inside a cylinder gets none from it.  A NaN anywhere -- in a box entry, in the pose -- makes some slab's
+ * near or far a NaN, which fails that slab's near <= far: no hit from that box, and the other boxes are not affected.  A negative half
+ * extent gives the box of its absolute value to every ray that is not parallel to that slab (near and far are ordered by the
+ * comparison) and misses every ray that is (lo <= o <= hi cannot hold); z1 < z0 does the same for the z slab.
+ * Order: the ground, then the cylinders in index order, then the boxes in index order.  The pixel takes the least t under the same
+ * strict <, so on equal t the earlier one keeps it.
+ * AMK_ERR_INVALID_ARG: what amk_sim_render_depth refuses, max_box < 0, a NULL d_box with max_box > 0.  AMK_ERR_UNSUPPORTED: as there.
+ * Every error is returned before anything is launched.  The call is stream-ordered and allocates nothing.  With max_box == 0 it is
+ * amk_sim_render_depth's own launch.  amk_sim_render_world_host takes host pointers, stages them and synchronises.            */
+int amk_sim_render_world(const double *d_cyl, const int *d_cyl_counts, int max_cyl, const double *d_box, const int *d_box_counts,
+                         int max_box, int n_scenes, double z_top, double max_range, const amk_depth_params *params, int rows,
+                         int cols, const double *d_Twb, void *d_depth, int depth_type, void *stream);
+int amk_sim_render_world_host(const double *h_cyl, const int *h_cyl_counts, int max_cyl, const double *h_box,
+                              const int *h_box_counts, int max_box, int n_scenes, double z_top, double max_range,
+                              const amk_depth_params *params, int rows, int cols, const double *h_Twb, void *h_depth,
+                              int depth_type);
+
+/* amk_sim_vehicle_step_att: amk_sim_vehicle_step with a choice of the rotation written into d_Twb.  The state update, p' and every
+ * argument it shares with amk_sim_vehicle_step are that call's; only the rotation differs.
+ *   attitude  AMK_SIM_ATT_YAW: [Rz(yaw) | p'], amk_sim_vehicle_step bit for bit in x and Twb.
+ *             AMK_SIM_ATT_ACCEL: the vehicle tilts into its thrust, [acc2rotmat(a + (0, 0, gz), yaw) | p'] of the NEW state
+ *             (mpc_obstacle_casadi.py:253-264), so a forward camera looks at the ground while the vehicle accelerates.
+ *   gz        the caller's gravity (the generator's: 9.81), >= 0.
+ * Arithmetic of AMK_SIM_ATT_ACCEL: fp64, no contraction, left to right, IEEE division and square root.  cs, sn are exactly the yaw
+ * mode's, so 1 and 0 at yaw == 0 and the device's cos / sin otherwise:
+ *   T  = (a_0, a_1, a_2 + gz);  n = sqrt((T_0 T_0 + T_1 T_1) + T_2 T_2);  zb = T / n
+ *   y' = (0.0 - zb_2 sn, zb_2 cs, zb_0 sn - zb_1 cs);  m = sqrt((y'_0 y'_0 + y'_1 y'_1) + y'_2 y'_2);  yb = y' / m
+ *   xb = (yb_1 zb_2 - yb_2 zb_1, yb_2 zb_0 - yb_0 zb_2, yb_0 zb_1 - yb_1 zb_0);  R = [xb yb zb] (columns)
+ * Unless n > 0 && m > 0 the rotation falls back to Rz(yaw): free fall, a NaN, thrust along the heading.  At a == 0 and yaw == 0 the
+ * rotation is exactly the identity, and at yaw == 0 there is no transcendental in it.
+ * AMK_ERR_INVALID_ARG: what amk_sim_vehicle_step refuses, an unknown attitude, a NaN or negative gz -- returned before anything is
+ * launched.  Stream-ordered; allocates nothing.  amk_sim_vehicle_step_att_host takes host pointers.                           */
+#define AMK_SIM_ATT_YAW   0   /* [Rz(yaw) | p']: amk_sim_vehicle_step, bit for bit            */
+#define AMK_SIM_ATT_ACCEL 1   /* [acc2rotmat(a + (0,0,gz), yaw) | p'] of the NEW state       */
+int amk_sim_vehicle_step_att(const double *h_ABc, const double *d_cmd, double *d_x, double *d_Twb, int n_scenes, double pose_quantum,
+                             int attitude, double gz, void *stream);
+int amk_sim_vehicle_step_att_host(const double *h_ABc, const double *h_cmd, double *h_x, double *h_Twb, int n_scenes,
+                                  double pose_quantum, int attitude, double gz);
+
 #ifdef __cplusplus
 }
 #endif
