@@ -66,6 +66,8 @@ SYMBOLS = [
     "amk_depth_clouds_work_bytes", "amk_depth_to_clouds", "amk_depth_to_clouds_host",
     "amk_sim_render_depth", "amk_sim_render_depth_host", "amk_sim_vehicle_step", "amk_sim_vehicle_step_host",
     "amk_sim_render_world", "amk_sim_render_world_host", "amk_sim_vehicle_step_att", "amk_sim_vehicle_step_att_host",
+    "amk_sim_clearance", "amk_sim_clearance_host", "amk_sim_segment_cast", "amk_sim_segment_cast_host",
+    "amk_sim_path_cast", "amk_sim_path_cast_host",
 ]
 
 
@@ -305,6 +307,13 @@ def load():
         "amk_sim_render_world_host": (i, [vp, vp, i, vp, vp, i, i, d, d, C.POINTER(DepthParams), i, i, vp, vp, i]),
         "amk_sim_vehicle_step_att": (i, [vp, vp, vp, vp, i, d, i, d, vp]),
         "amk_sim_vehicle_step_att_host": (i, [vp, vp, vp, vp, i, d, i, d]),
+        # the world (cyl, cyl_counts, max_cyl, box, box_counts, max_box, n_scenes, z_top), then the points / path and the outputs
+        "amk_sim_clearance": (i, [vp, vp, i, vp, vp, i, i, d, vp, i, i, vp, vp, vp, vp]),
+        "amk_sim_clearance_host": (i, [vp, vp, i, vp, vp, i, i, d, vp, i, i, vp, vp, vp]),
+        "amk_sim_segment_cast": (i, [vp, vp, i, vp, vp, i, i, d, vp, i, i, d, vp, vp, vp, vp, vp]),
+        "amk_sim_segment_cast_host": (i, [vp, vp, i, vp, vp, i, i, d, vp, i, i, d, vp, vp, vp, vp]),
+        "amk_sim_path_cast": (i, [vp, vp, i, vp, vp, i, i, d, vp, i, i, d, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "amk_sim_path_cast_host": (i, [vp, vp, i, vp, vp, i, i, d, vp, i, i, d, vp, vp, vp, vp, vp, vp, vp]),
     }
     sig["amk__kd_set_mode"] = (i, [vp, i])  # internal: 0 bucketed index, 1 streaming scan
     sig["amk__sweep_set_target"] = (None, [i])  # internal (tests, A/B): the pool's sweep against 1 a fine hashed grid of the current frame (default), 0 the frame's own index
@@ -318,6 +327,8 @@ def load():
     sig["amk__sim_chunk"] = (i, [])  # internal (tests): cylinders per LDS round of the render kernel
     sig["amk__sim_render_world_t"] = (i, [vp, vp, i, vp, vp, i, i, d, d, C.POINTER(DepthParams), i, i, vp, vp, vp])  # internal (tests): amk_sim_render_world's fp64 ray parameter t
     sig["amk__sim_world_chunk"] = (i, [])  # internal (tests): boxes per LDS round of the world kernel
+    sig["amk__sim_truth_chunk"] = (i, [])  # internal (tests): solids per round of the ground-truth kernels, one per lane
+    sig["amk__sim_truth_waves"] = (i, [])  # internal (tests): points / legs in flight per block of the ground-truth kernels
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)
         if fn is None:

@@ -48,7 +48,7 @@ inline int planes_to_xyz(const float *d_x, const float *d_y, const float *d_z, i
 // never shrink; every call ends in its wait, so the next call of the handle may lay the block out anew.
 class HostStage {
 public:
-    static constexpr int kMaxSlots = 8;
+    static constexpr int kMaxSlots = 12;   // amk_sim_path_cast_host: the world's four arrays, the path and seven outputs
     // a slot's device pointer, taken as whatever pointer the launch's parameter is
     struct Dev { unsigned char *p = nullptr; template <class T> operator T *() const { return reinterpret_cast<T *>(p); } };
     HostStage() = default;

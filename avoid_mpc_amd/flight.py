@@ -19,6 +19,8 @@ GPU driver (tests/_flight.py, bench.py --workload flight) and the CPU-oracle dri
                               the *_ordered ones restate csrc/sim.hip (amk_sim_render_depth, amk_sim_vehicle_step) operation for operation
   render_world_ordered / vehicle_attitude_ordered / box_clearance / WallWorld   the same for amk_sim_render_world (cylinders and
                               boxes) and amk_sim_vehicle_step_att (the vehicle tilts into its thrust); a corridor with walls and gates
+  world_clearance_ordered / world_segment_cast_ordered / world_path_cast_ordered   csrc/sim_truth.hip (amk_sim_clearance, amk_sim_segment_cast,
+                              amk_sim_path_cast) restated operation for operation: a point or a plan against the world's TRUE solids
 
 Nothing here computes neighbours or solves anything: that is the step's job (amk_step_batch / the oracle's stepo_run).
 """
@@ -431,6 +433,192 @@ def box_clearance(p, box):
     out = np.sqrt(np.maximum(qx, 0.0) ** 2 + np.maximum(qy, 0.0) ** 2) + np.minimum(np.maximum(qx, qy), 0.0)
     level = (p[..., 2:3] >= box[:, 6]) & (p[..., 2:3] <= box[:, 7])
     return np.where(level, out, np.inf).min(axis=-1, initial=np.inf)
+
+
+# ---- ground truth against the world: amk_sim_clearance, amk_sim_segment_cast, amk_sim_path_cast ---------------------------------------
+KIND_NONE, KIND_GROUND, KIND_CYLINDER, KIND_BOX = -1, 0, 1, 2
+
+
+def _truth_world(cyl, box):
+    cyl = np.zeros((0, 3)) if cyl is None else np.asarray(cyl, np.float64).reshape(-1, 3)
+    box = np.zeros((0, 8)) if box is None else np.asarray(box, np.float64).reshape(-1, 8)
+    return cyl, box
+
+
+def cylinder_distance_ordered(p, cyl, z_top):
+    """Signed distance from points p [P, >= 3] to each solid cylinder {rho <= r, z <= z_top} of cyl [n, 3] -> [P, n], in the operation
+    order of amk_sim_clearance."""
+    p, cyl = np.asarray(p, np.float64), np.asarray(cyl, np.float64).reshape(-1, 3)
+    with np.errstate(invalid="ignore", over="ignore"):
+        ox, oy = p[:, 0:1] - cyl[:, 0], p[:, 1:2] - cyl[:, 1]
+        qr = np.sqrt(ox * ox + oy * oy) - cyl[:, 2]
+        qz = np.broadcast_to(p[:, 2:3] - z_top, qr.shape)
+        mr, mz = np.where(qr > 0, qr, 0.0), np.where(qz > 0, qz, 0.0)
+        m = np.where(qr > qz, qr, qz)
+        return np.sqrt(mr * mr + mz * mz) + np.where(m < 0, m, 0.0)
+
+
+def box_distance_ordered(p, box):
+    """Signed distance from points p [P, >= 3] to each box of box [n, 8] -> [P, n]: box_clearance in three dimensions, in the operation
+    order of amk_sim_clearance."""
+    p, box = np.asarray(p, np.float64), np.asarray(box, np.float64).reshape(-1, 8)
+    with np.errstate(invalid="ignore", over="ignore"):
+        ox, oy = p[:, 0:1] - box[:, 0], p[:, 1:2] - box[:, 1]
+        c, s = box[:, 4], box[:, 5]
+        olx, oly = c * ox + s * oy, c * oy - s * ox
+        qx, qy = np.abs(olx) - np.abs(box[:, 2]), np.abs(oly) - np.abs(box[:, 3])
+        lo, hi = box[:, 6] - p[:, 2:3], p[:, 2:3] - box[:, 7]
+        qz = np.where(lo > hi, lo, hi)
+        mx, my, mz = np.where(qx > 0, qx, 0.0), np.where(qy > 0, qy, 0.0), np.where(qz > 0, qz, 0.0)
+        m = np.where(qx > qy, qx, qy)
+        m = np.where(qz > m, qz, m)
+        return np.sqrt((mx * mx + my * my) + mz * mz) + np.where(m < 0, m, 0.0)
+
+
+def world_clearance_ordered(cyl, box, pts, z_top=4.0):
+    """amk_sim_clearance for ONE scene in numpy, operation for operation: cyl [n, 3] = (cx, cy, r), box [m, 8], pts [P, >= 3]
+    -> (dist float64 [P], kind int32 [P], index int32 [P]).  The scan starts at the ground (p_z, kind 0, index -1) and goes through the
+    cylinders and then the boxes in index order; a solid takes over under a strict <; a solid with a NaN entry is passed over."""
+    cyl, box = _truth_world(cyl, box)
+    pts = np.asarray(pts, np.float64)
+    best = pts[:, 2].copy()
+    kind, index = np.zeros(len(pts), np.int32), np.full(len(pts), -1, np.int32)
+    for code, solids, dist in ((KIND_CYLINDER, cyl, cylinder_distance_ordered(pts, cyl, z_top)), (KIND_BOX, box, box_distance_ordered(pts, box))):
+        for k in range(len(solids)):
+            if np.isnan(solids[k]).any():
+                continue
+            with np.errstate(invalid="ignore"):
+                win = dist[:, k] < best
+            best = np.where(win, dist[:, k], best)
+            kind[win] = code; index[win] = k
+    return best, kind, index
+
+
+def _truth_half_space(h, az, dz, inv_z):
+    """z <= h along a_z + t d_z -> (near, far): one bound, near or far by the sign of d_z; d_z == 0: all or nothing by the origin"""
+    bound = (h - az) * inv_z
+    near, far = np.where(dz < 0, bound, -np.inf), np.where(dz > 0, bound, np.inf)
+    par, inside = dz == 0, az <= h
+    return np.where(par, np.where(inside, -np.inf, np.inf), near), np.where(par, np.where(inside, np.inf, -np.inf), far)
+
+
+def _truth_slab(lo_o, hi_o, d, inv, inside):
+    """_box_slab with `inside` an array (one origin per leg)"""
+    t1, t2 = lo_o * inv, hi_o * inv
+    lt = t1 < t2
+    near, far = np.where(lt, t1, t2), np.where(lt, t2, t1)
+    par = d == 0
+    return np.where(par, np.where(inside, -np.inf, np.inf), near), np.where(par, np.where(inside, np.inf, -np.inf), far)
+
+
+def _truth_touched(ok, tn, tf):
+    return ok & (tn <= tf) & (tf >= 0) & (tn <= 1), np.where(tn > 0, tn, 0.0)
+
+
+def path_legs(path):
+    """path [n_points, >= 3] -> (a [L, 3], d = b - a [L, 3], judgeable [L]: every coordinate of a, b and d finite)"""
+    path = np.asarray(path, np.float64)
+    a, b = path[:-1, 0:3], path[1:, 0:3]
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = b - a
+    return a, d, np.isfinite(a).all(axis=1) & np.isfinite(b).all(axis=1) & np.isfinite(d).all(axis=1)
+
+
+def world_segment_cast_ordered(cyl, box, path, radius, z_top=4.0):
+    """amk_sim_segment_cast for ONE scene in numpy, operation for operation: path [n_points, >= 3] -> (hit int32 [L], t float64 [L],
+    kind int32 [L], index int32 [L]) per leg; t = 1.0, kind = index = -1 without contact.  The sphere's centre is cast against the
+    solids inflated by `radius`; every solid is an intersection of per-axis intervals [near, far] of the leg's parameter."""
+    cyl, box = _truth_world(cyl, box)
+    a, d, judgeable = path_legs(path)
+    L = len(a)
+    ax, ay, az, dx, dy, dz = a[:, 0], a[:, 1], a[:, 2], d[:, 0], d[:, 1], d[:, 2]
+    best, pos_kind, pos_index = np.full(L, np.inf), np.full(L, KIND_NONE, np.int32), np.full(L, -1, np.int32)
+    found = np.zeros(L, bool)
+
+    def take(hit, t, code, k):
+        nonlocal best, found
+        win = hit & (t < best)                                                       # strict <: the earlier solid keeps an equal t
+        best = np.where(win, t, best)
+        pos_kind[win] = code; pos_index[win] = k
+        found |= win
+
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        inv_z = 1.0 / dz
+        a2 = dx * dx + dy * dy
+        n0, f0 = _truth_half_space(radius, az, dz, inv_z)                            # the ground, inflated: z <= radius
+        take(*_truth_touched(n0 <= f0, n0, f0), KIND_GROUND, -1)
+        top = z_top + radius
+        n1, f1 = _truth_half_space(top, az, dz, inv_z)
+        for k, (cx, cy, r) in enumerate(cyl):
+            if np.isnan(cyl[k]).any():
+                continue
+            ox, oy, R = ax - cx, ay - cy, r + radius
+            b = ox * dx + oy * dy
+            c = (ox * ox + oy * oy) - R * R
+            disc = b * b - a2 * c
+            sq = np.sqrt(np.where(disc >= 0, disc, np.nan))
+            roots = (a2 != 0) & (disc >= 0)
+            n0 = np.where(roots, (-b - sq) / a2, np.where((a2 == 0) & (c <= 0), -np.inf, np.inf))
+            f0 = np.where(roots, (-b + sq) / a2, np.where((a2 == 0) & (c <= 0), np.inf, -np.inf))
+            tn, tf = np.where(n0 > n1, n0, n1), np.where(f0 < f1, f0, f1)
+            take(*_truth_touched((n0 <= f0) & (n1 <= f1), tn, tf), KIND_CYLINDER, k)
+        for k, (bx, by, hx, hy, c, s, z0, z1) in enumerate(box):
+            if np.isnan(box[k]).any():
+                continue
+            ox, oy = ax - bx, ay - by
+            hx, hy, z0, z1 = np.abs(hx) + radius, np.abs(hy) + radius, z0 - radius, z1 + radius
+            olx, oly = c * ox + s * oy, c * oy - s * ox
+            dlx, dly = c * dx + s * dy, c * dy - s * dx
+            n0, f0 = _truth_slab(-hx - olx, hx - olx, dlx, 1.0 / dlx, (-hx <= olx) & (olx <= hx))
+            n1b, f1b = _truth_slab(-hy - oly, hy - oly, dly, 1.0 / dly, (-hy <= oly) & (oly <= hy))
+            n2, f2 = _truth_slab(z0 - az, z1 - az, dz, inv_z, (z0 <= az) & (az <= z1))
+            tn, tf = np.where(n0 > n1b, n0, n1b), np.where(f0 < f1b, f0, f1b)
+            tn, tf = np.where(n2 > tn, n2, tn), np.where(f2 < tf, f2, tf)
+            take(*_truth_touched((n0 <= f0) & (n1b <= f1b) & (n2 <= f2), tn, tf), KIND_BOX, k)
+    found &= judgeable                                                               # a non-finite leg has no contact here
+    return (found.astype(np.int32), np.where(found, best, 1.0), np.where(found, pos_kind, KIND_NONE).astype(np.int32),
+            np.where(found, pos_index, -1).astype(np.int32))
+
+
+def path_cast_reduction(path, hit, t, kind, index):
+    """The reduction amk_sim_path_cast applies to amk_sim_segment_cast's per-leg answers on the same path: the first leg, in leg order,
+    that has a contact (stop 1) or is unjudgeable (stop 2) -> dict(stop, leg, t, free, pts [3], kind, index) of ONE scene;
+    free = ((len_0 + len_1) + ...) + t len_leg, the last term left out at stop 2; pts = a + t d at a contact, else zeros."""
+    a, d, judgeable = path_legs(path)
+    with np.errstate(invalid="ignore", over="ignore"):
+        length = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+    out = dict(stop=0, leg=-1, t=1.0, free=0.0, pts=np.zeros(3), kind=KIND_NONE, index=-1)
+    acc = np.float64(0.0)
+    for j in range(len(a)):
+        if not judgeable[j]:
+            out.update(stop=2, leg=j, t=0.0)
+            break
+        if hit[j]:
+            tj = np.float64(t[j])
+            acc = acc + tj * length[j]
+            out.update(stop=1, leg=j, t=float(tj), pts=a[j] + tj * d[j], kind=int(kind[j]), index=int(index[j]))
+            break
+        acc = acc + length[j]
+    out["free"] = float(acc)
+    return out
+
+
+def world_path_cast_ordered(cyl, box, path, radius, z_top=4.0):
+    """amk_sim_path_cast for ONE scene in numpy: the legs are cast one after the other, each on its own as a two-point path, and the
+    walk ends at the stop leg -- the legs behind it are never looked at.  -> path_cast_reduction's dict."""
+    path = np.asarray(path, np.float64)
+    L = len(path) - 1
+    hit, t = np.zeros(L, np.int32), np.ones(L)
+    kind, index = np.full(L, KIND_NONE, np.int32), np.full(L, -1, np.int32)
+    judgeable = path_legs(path)[2]
+    for j in range(L):
+        if not judgeable[j]:
+            break
+        h, tt, kd, ix = world_segment_cast_ordered(cyl, box, path[j:j + 2], radius, z_top)
+        hit[j], t[j], kind[j], index[j] = h[0], tt[0], kd[0], ix[0]
+        if h[0]:
+            break
+    return path_cast_reduction(path, hit, t, kind, index)
 
 
 class WallWorld(FlightWorld):

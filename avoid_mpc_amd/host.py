@@ -1164,6 +1164,76 @@ def sim_vehicle_step_att(ABc, cmd, x, Twb=None, pose_quantum=0.0, attitude=capi.
     return x
 
 
+def _sim_world_head(cyl, box, cyl_counts, box_counts, z_top):
+    """The leading arguments of the ground-truth queries: amk_sim_render_world's world, checked as sim_render_world checks it"""
+    assert cyl.dtype == torch.float64 and cyl.dim() == 3 and cyl.shape[2] == 3 and cyl.is_contiguous()
+    S, max_cyl, max_box = int(cyl.shape[0]), int(cyl.shape[1]), int(box.shape[1])
+    assert box.dtype == torch.float64 and tuple(box.shape) == (S, max_box, 8) and box.is_contiguous()
+    for counts in (cyl_counts, box_counts):
+        assert counts is None or (counts.dtype == torch.int32 and tuple(counts.shape) == (S,) and counts.is_contiguous())
+    return S, (capi.dptr(cyl) if max_cyl else None, capi.dptr(cyl_counts), max_cyl, capi.dptr(box) if max_box else None,
+               capi.dptr(box_counts), max_box, S, float(z_top))
+
+
+def _sim_points(pts, S):
+    assert pts.dtype == torch.float64 and pts.dim() == 3 and pts.shape[0] == S and pts.shape[2] >= 3 and pts.is_contiguous()
+    return int(pts.shape[1]), int(pts.shape[2])
+
+
+def sim_clearance(cyl, box, pts, cyl_counts=None, box_counts=None, z_top=4.0, out=None, stream=None):
+    """amk_sim_clearance: the signed distance from every point to the nearest TRUE solid of sim_render_world's world (negative: inside)
+    and which solid it is.  pts float64 [S, P, >= 3] (x, y, z lead every row; a [S, 1, 10] view of the odometry goes in as it is)
+    -> dict(dist float64 [S, P], kind int32 [S, P] 0 ground / 1 cylinder / 2 box, index int32 [S, P], -1 for the ground).
+    Stream-ordered on torch's current stream (or `stream`); `out` re-uses the buffers, an entry None is not written."""
+    S, head = _sim_world_head(cyl, box, cyl_counts, box_counts, z_top)
+    P, stride = _sim_points(pts, S)
+    if out is None:
+        out = {"dist": torch.empty((S, P), dtype=torch.float64, device=pts.device),
+               "kind": torch.empty((S, P), dtype=torch.int32, device=pts.device), "index": torch.empty((S, P), dtype=torch.int32, device=pts.device)}
+    capi.check(capi.load().amk_sim_clearance(*head, capi.dptr(pts), stride, P, capi.dptr(out["dist"]), capi.dptr(out["kind"]),
+                                             capi.dptr(out["index"]), capi.stream_ptr(stream)), "amk_sim_clearance")
+    return out
+
+
+def sim_segment_cast(cyl, box, path, radius, cyl_counts=None, box_counts=None, z_top=4.0, out=None, stream=None):
+    """amk_sim_segment_cast: per leg of path float64 [S, n_points >= 2, >= 3], the first contact of a sphere of `radius` with the world's
+    solids inflated by it -> dict(hit int32 [S, L], t float64 [S, L] (1.0 without contact), kind, index int32 [S, L], -1 / -1 without).
+    A leg that starts inside a solid touches it at t = 0."""
+    S, head = _sim_world_head(cyl, box, cyl_counts, box_counts, z_top)
+    P, stride = _sim_points(path, S)
+    L = P - 1
+    if out is None:
+        i32 = lambda: torch.empty((S, L), dtype=torch.int32, device=path.device)
+        out = {"hit": i32(), "t": torch.empty((S, L), dtype=torch.float64, device=path.device), "kind": i32(), "index": i32()}
+    capi.check(capi.load().amk_sim_segment_cast(*head, capi.dptr(path), stride, P, float(radius), capi.dptr(out["hit"]), capi.dptr(out["t"]),
+                                                capi.dptr(out["kind"]), capi.dptr(out["index"]), capi.stream_ptr(stream)),
+               "amk_sim_segment_cast")
+    return out
+
+
+def sim_path_cast_out(S, dev):
+    """outputs of sim_path_cast, one result per scene (the layout of KdBatch.path_cast's, pts in float64, kind and index for the id)"""
+    i32 = lambda: torch.empty((S,), dtype=torch.int32, device=dev)
+    f64 = lambda *shape: torch.empty((S, *shape), dtype=torch.float64, device=dev)
+    return {"stop": i32(), "leg": i32(), "t": f64(), "free": f64(), "pts": f64(3), "kind": i32(), "index": i32()}
+
+
+def sim_path_cast(cyl, box, path, radius, cyl_counts=None, box_counts=None, z_top=4.0, out=None, stream=None):
+    """amk_sim_path_cast: ONE verdict per scene for a whole path, laid out like KdBatch.path_cast's: stop [S] 0 free / 1 contact /
+    2 unjudgeable leg, leg (-1 when free), t, free (the free distance along the path), pts float64 [S, 3] the sphere's centre at the
+    contact, kind / index of the solid touched.  The reduction of sim_segment_cast's per-leg answers, bit for bit.  path must be a
+    contiguous [S, n_points, stride] tensor: Pipeline.output_tensors()["x0array"] itself (n_points = N), or a copy of its leading
+    n_legs + 1 rows per scene."""
+    S, head = _sim_world_head(cyl, box, cyl_counts, box_counts, z_top)
+    P, stride = _sim_points(path, S)
+    if out is None:
+        out = sim_path_cast_out(S, path.device)
+    capi.check(capi.load().amk_sim_path_cast(*head, capi.dptr(path), stride, P, float(radius), capi.dptr(out["stop"]), capi.dptr(out["leg"]),
+                                             capi.dptr(out["t"]), capi.dptr(out["free"]), capi.dptr(out["pts"]), capi.dptr(out["kind"]),
+                                             capi.dptr(out["index"]), capi.stream_ptr(stream)), "amk_sim_path_cast")
+    return out
+
+
 def plant_model(tau, con_dt, drag=(0.0, 0.0, 0.0)):
     """h_ABc of sim_vehicle_step: the MPC's own model at the control period con_dt (the library's host-side amk__mpc_dynamics; no
     device) -> numpy float64 [150] = A [10][10], B [10][4], c [10]."""

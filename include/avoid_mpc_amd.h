@@ -1266,6 +1266,107 @@ int amk_sim_vehicle_step_att(const double *h_ABc, const double *d_cmd, double *d
 int amk_sim_vehicle_step_att_host(const double *h_ABc, const double *h_cmd, double *h_x, double *h_Twb, int n_scenes,
                                   double pose_quantum, int attitude, double gz);
 
+/* Ground truth against the simulated world: clearance, segment cast and path cast against the TRUE solids.
+ * The map queries (amk_kd_segment_cast, amk_kd_path_cast, amk_pipeline_set_path_audit) judge a position or a plan against what the
+ * robot has seen.  These three judge it against the world amk_sim_render_world renders, on the device and in the same output shapes,
+ * so that a monitor holds both verdicts per robot and period without a host round trip.
+ * Every entry begins with the world arguments of amk_sim_render_world, in that order and with those meanings:
+ *   (d_cyl [S][max_cyl][3], d_cyl_counts | NULL, max_cyl, d_box [S][max_box][8], d_box_counts | NULL, max_box, n_scenes, z_top, ...)
+ * Counts are clamped into [0, max].  max_cyl == 0 and max_box == 0 are allowed with NULL lists; with both zero the world is the
+ * ground alone.  Points and paths are double [S][n_points][point_stride], point_stride >= 3, x y z leading each row, as the KD
+ * queries take them: d_odom (stride 10, one point) and x0array (stride 14, N rows) go in as they are.
+ * Arithmetic: fp64, no contraction, every sum left to right as written; division, reciprocal and square root are IEEE-correct, so a
+ * restatement in any IEEE language matches operation for operation (avoid_mpc_amd/flight.py world_clearance_ordered,
+ * world_segment_cast_ordered, world_path_cast_ordered are three).  "x > y ? x : y" below is that comparison and that select.
+ * NaN: a two-operand select drops a NaN, so no formula below is trusted to carry one.  A solid with a NaN in any of its entries (three
+ * for a cylinder, eight for a box) answers nothing, in the clearance and in the casts: every entry e is tested with e == e in front of
+ * the formulas and the solid is passed over.  Infinite entries and non-finite points are not special: they give what the formulas give.
+ * Order everywhere: the ground, then the cylinders in index order, then the boxes in index order; the least value wins under a
+ * strict <, so on equal values the earlier solid keeps it.
+ *
+ * amk_sim_clearance: for every point p the signed Euclidean distance to the nearest solid's surface (negative inside) and which
+ * solid that is.
+ *   d_dist   [S][P] double.   d_kind  [S][P] int: 0 ground, 1 cylinder, 2 box.   d_index  [S][P] int: -1 for the ground.
+ *   ground:    dist = p_z
+ *   cylinder:  the solid {rho <= r, z <= z_top}.  ox = p_x - cx, oy = p_y - cy;  qr = sqrt(ox ox + oy oy) - r;  qz = p_z - z_top;
+ *              mr = qr > 0 ? qr : 0, mz = qz > 0 ? qz : 0;  m = qr > qz ? qr : qz;  dist = sqrt(mr mr + mz mz) + (m < 0 ? m : 0)
+ *   box:       ox = p_x - cx, oy = p_y - cy;  olx = c ox + s oy, oly = c oy - s ox (exactly the render's);  qx = |olx| - |hx|,
+ *              qy = |oly| - |hy|;  lo = z0 - p_z, hi = p_z - z1, qz = lo > hi ? lo : hi;  mx, my, mz = q > 0 ? q : 0 of each;
+ *              m = qx > qy ? qx : qy, then qz > m ? qz : m;  dist = sqrt((mx mx + my my) + mz mz) + (m < 0 ? m : 0)
+ *              (flight.box_clearance in three dimensions: outside, the norm of the excess; inside, the largest face term)
+ *   The scan starts at the ground's p_z: a NaN height stays NaN with kind 0, since nothing is < NaN.  A distance that comes out NaN
+ *   never wins.  Each output may be NULL, but not all of them.
+ *
+ * amk_sim_segment_cast: per leg of a path, the first contact of a sphere of `radius` >= 0 whose centre moves from point j (a) to point
+ * j + 1 (b): d = b - a, t in [0, 1].  Outputs are [S][n_points - 1].  The sphere is judged as its CENTRE against the inflated solids:
+ *   ground:    z <= radius
+ *   cylinder:  radius R = r + radius, cut at z_top + radius
+ *   box:       half extents |hx| + radius, |hy| + radius, vertical extent [z0 - radius, z1 + radius]
+ * This is a superset of the true swept sphere (the rounded Minkowski sum): exact on faces and mantles, and over at edges and rims by
+ * at most (sqrt(3) - 1) radius.  radius == 0 is the centre line.
+ * Every solid is an intersection of per-axis intervals [near, far] of the leg's parameter; inv_z = 1.0 / d_z once per leg:
+ *   a half-space z <= h:  bound = (h - a_z) inv_z;  d_z < 0: [bound, +inf];  d_z > 0: [-inf, bound];  d_z == 0: [-inf, +inf] when
+ *                         a_z <= h, else [+inf, -inf]
+ *   a cylinder's mantle:  ox = a_x - cx, oy = a_y - cy;  a = d_x d_x + d_y d_y, b = ox d_x + oy d_y, c = (ox ox + oy oy) - R R (the
+ *                         render's, at the inflated radius);  disc = b b - a c.  a == 0: [-inf, +inf] when c <= 0, else [+inf, -inf].
+ *                         Otherwise, for disc >= 0: [(-b - sqrt(disc)) / a, (-b + sqrt(disc)) / a]; else [+inf, -inf]
+ *   a box's three slabs:  amk_sim_render_world's slab rule word for word -- x (olx, dlx, -HX, HX), y (oly, dly, -HY, HY),
+ *                         z (a_z, d_z, Z0, Z1) with the inflated HX, HY, Z0, Z1, one reciprocal per slab, d == 0 by "lo <= o && o <= hi"
+ *   the ground has one axis, a cylinder two (mantle, then z <= z_top + radius), a box three (x, y, z)
+ *   tn = the largest near and tf = the smallest far, by comparisons in axis order: tn = n_0 > n_1 ? n_0 : n_1, then n_2 > tn ? n_2 : tn;
+ *   tf = f_0 < f_1 ? f_0 : f_1, then f_2 < tf ? f_2 : tf
+ *   the solid is touched iff every axis has near <= far, and tn <= tf && tf >= 0 && tn <= 1;  its t is tn > 0 ? tn : 0.0
+ * A leg that starts inside a solid touches it at t = 0.  This is the one place the cast differs from the sensor, which returns nothing
+ * from inside.  A grazing leg counts (tn == tf), and so does a contact that begins exactly at b (t == 1).
+ * The leg's contact is the least t under the strict <, in the order above.  A degenerate leg (a == b) touches iff its start is inside.
+ * A leg with a non-finite endpoint coordinate, or a non-finite component of d, has no contact here.
+ *   d_hit    [S][L] int: 1 when the leg has a contact, else 0.
+ *   d_t      [S][L] double: the t of the contact; 1.0 without one -- free all the way -- so t |d| is the free distance in both cases.
+ *   d_kind   [S][L] int: 0 ground, 1 cylinder, 2 box; -1 without a contact.     d_index  [S][L] int: -1 for the ground and for none.
+ * Each output may be NULL, but not all of them.
+ *
+ * amk_sim_path_cast: one verdict per scene, laid out like amk_kd_path_cast's.  The stop leg is the first leg, in leg order, that has
+ * a contact by the segment cast's rule or is unjudgeable (the non-finite leg above: an audit must not read a NaN plan as free).
+ *   d_stop   [S] int: 0 free to the end, 1 contact, 2 unjudgeable leg.      d_leg  [S] int: the stop leg, -1 when free.
+ *   d_t      [S] double: t on the stop leg; 0.0 when d_stop is 2, 1.0 when free.
+ *   d_free   [S] double: ((len_0 + len_1) + ...) + t len_leg with len_j = sqrt((d_x d_x + d_y d_y) + d_z d_z), left to right; the last
+ *            term is left out when d_stop is 2; a free path gives its whole length.
+ *   d_pts    [S][3] double: the sphere's centre at the contact, a_i + t d_i; (0, 0, 0) unless d_stop is 1.
+ *   d_kind, d_index  [S] int: the solid touched, as the segment cast names it; -1, -1 unless d_stop is 1.
+ * Each output may be NULL, but not all of them.
+ * Identity: the answer equals this reduction applied to amk_sim_segment_cast's per-leg outputs on the same path, bit for bit; d_free
+ * and d_pts are rebuilt from the path by the formulas.  Legs behind the stop leg's round of legs are not walked.
+ *
+ * AMK_ERR_INVALID_ARG: NULL points or path, point_stride < 3, n_points < 1 (clearance) or < 2 (casts), radius < 0 or NaN, z_top not
+ * >= 0, a negative max, a NULL list with a positive max, every output NULL, n_scenes < 1.  AMK_ERR_UNSUPPORTED: a grid beyond the
+ * launch limits -- for the clearance and the segment cast more than 65 535 scenes (the scenes are the grid's second dimension) or
+ * more than 4 (2^24 - 1) points or legs per scene (four per block of 256 threads, and a grid dimension times the block size stays
+ * below 2^32); for the path cast more than 2^24 - 1 scenes (a block per scene) -- or max_cyl + max_box beyond 2^31 - 2.
+ * AMK_ERR_NO_DEVICE: no device.  Every error is returned before anything is staged or launched,
+ * the outputs untouched.  The three calls are stream-ordered and allocate nothing.  The _host forms take host pointers, stage them
+ * and synchronise.
+ * Not offered: the exact rounded Minkowski sum, per-scene radii, several contacts per leg, moving solids, the casts inside the
+ * pipeline (a caller enqueues them behind amk_pipeline_wait_stream on its own stream).                                       */
+int amk_sim_clearance(const double *d_cyl, const int *d_cyl_counts, int max_cyl, const double *d_box, const int *d_box_counts,
+                      int max_box, int n_scenes, double z_top, const double *d_pts, int point_stride, int n_points, double *d_dist,
+                      int *d_kind, int *d_index, void *stream);
+int amk_sim_clearance_host(const double *h_cyl, const int *h_cyl_counts, int max_cyl, const double *h_box, const int *h_box_counts,
+                           int max_box, int n_scenes, double z_top, const double *h_pts, int point_stride, int n_points,
+                           double *h_dist, int *h_kind, int *h_index);
+int amk_sim_segment_cast(const double *d_cyl, const int *d_cyl_counts, int max_cyl, const double *d_box, const int *d_box_counts,
+                         int max_box, int n_scenes, double z_top, const double *d_path, int point_stride, int n_points,
+                         double radius, int *d_hit, double *d_t, int *d_kind, int *d_index, void *stream);
+int amk_sim_segment_cast_host(const double *h_cyl, const int *h_cyl_counts, int max_cyl, const double *h_box,
+                              const int *h_box_counts, int max_box, int n_scenes, double z_top, const double *h_path,
+                              int point_stride, int n_points, double radius, int *h_hit, double *h_t, int *h_kind, int *h_index);
+int amk_sim_path_cast(const double *d_cyl, const int *d_cyl_counts, int max_cyl, const double *d_box, const int *d_box_counts,
+                      int max_box, int n_scenes, double z_top, const double *d_path, int point_stride, int n_points, double radius,
+                      int *d_stop, int *d_leg, double *d_t, double *d_free, double *d_pts, int *d_kind, int *d_index, void *stream);
+int amk_sim_path_cast_host(const double *h_cyl, const int *h_cyl_counts, int max_cyl, const double *h_box, const int *h_box_counts,
+                           int max_box, int n_scenes, double z_top, const double *h_path, int point_stride, int n_points,
+                           double radius, int *h_stop, int *h_leg, double *h_t, double *h_free, double *h_pts, int *h_kind,
+                           int *h_index);
+
 #ifdef __cplusplus
 }
 #endif
