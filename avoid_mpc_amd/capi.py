@@ -67,7 +67,7 @@ SYMBOLS = [
     "amk_sim_render_depth", "amk_sim_render_depth_host", "amk_sim_vehicle_step", "amk_sim_vehicle_step_host",
     "amk_sim_render_world", "amk_sim_render_world_host", "amk_sim_vehicle_step_att", "amk_sim_vehicle_step_att_host",
     "amk_sim_clearance", "amk_sim_clearance_host", "amk_sim_segment_cast", "amk_sim_segment_cast_host",
-    "amk_sim_path_cast", "amk_sim_path_cast_host",
+    "amk_sim_path_cast", "amk_sim_path_cast_host", "amk_sim_depth_noise", "amk_sim_depth_noise_host",
 ]
 
 
@@ -122,6 +122,13 @@ class FrameCamera(C.Structure):
     """amk_frame_camera: PtIsInFrame's camera model (FrameKDMap.cpp:215-231), intrinsics already divided by the resize scale."""
     _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
                 ("depth_max", C.c_double), ("width", C.c_int), ("height", C.c_int)]
+
+
+class SimNoiseParams(C.Structure):
+    """amk_sim_noise_params (host.sim_noise_params fills it)"""
+    _fields_ = [("seed", C.c_ulonglong), ("sigma0", C.c_double), ("sigma2", C.c_double), ("p_drop", C.c_double), ("edge_jump", C.c_double),
+                ("p_edge_drop", C.c_double), ("p_edge_fly", C.c_double), ("focal_baseline", C.c_double), ("disparity_quantum", C.c_double),
+                ("z_min", C.c_double), ("z_max", C.c_double)]
 
 
 AMK_DEPTH_U16, AMK_DEPTH_F32 = 0, 1
@@ -314,6 +321,9 @@ def load():
         "amk_sim_segment_cast_host": (i, [vp, vp, i, vp, vp, i, i, d, vp, i, i, d, vp, vp, vp, vp]),
         "amk_sim_path_cast": (i, [vp, vp, i, vp, vp, i, i, d, vp, i, i, d, vp, vp, vp, vp, vp, vp, vp, vp]),
         "amk_sim_path_cast_host": (i, [vp, vp, i, vp, vp, i, i, d, vp, i, i, d, vp, vp, vp, vp, vp, vp, vp]),
+        # (in, out, depth_type, rows, cols, scene_stride, n_scenes, pixel2meter, params, scene_id0, frame)
+        "amk_sim_depth_noise": (i, [vp, vp, i, i, i, C.c_longlong, i, d, C.POINTER(SimNoiseParams), C.c_longlong, C.c_ulonglong, vp]),
+        "amk_sim_depth_noise_host": (i, [vp, vp, i, i, i, C.c_longlong, i, d, C.POINTER(SimNoiseParams), C.c_longlong, C.c_ulonglong]),
     }
     sig["amk__kd_set_mode"] = (i, [vp, i])  # internal: 0 bucketed index, 1 streaming scan
     sig["amk__sweep_set_target"] = (None, [i])  # internal (tests, A/B): the pool's sweep against 1 a fine hashed grid of the current frame (default), 0 the frame's own index
@@ -329,6 +339,7 @@ def load():
     sig["amk__sim_world_chunk"] = (i, [])  # internal (tests): boxes per LDS round of the world kernel
     sig["amk__sim_truth_chunk"] = (i, [])  # internal (tests): solids per round of the ground-truth kernels, one per lane
     sig["amk__sim_truth_waves"] = (i, [])  # internal (tests): points / legs in flight per block of the ground-truth kernels
+    sig["amk__sim_noise_words"] = (i, [vp, i, i, i, C.c_ulonglong, C.c_longlong, C.c_ulonglong, vp])  # internal (tests): w_0..w_2 of every pixel of the depth noise's stream, uint64 [S][rows][cols][3]
     for name, (res, args) in sig.items():
         fn = getattr(lib, name, None)
         if fn is None:

@@ -21,6 +21,8 @@ GPU driver (tests/_flight.py, bench.py --workload flight) and the CPU-oracle dri
                               boxes) and amk_sim_vehicle_step_att (the vehicle tilts into its thrust); a corridor with walls and gates
   world_clearance_ordered / world_segment_cast_ordered / world_path_cast_ordered   csrc/sim_truth.hip (amk_sim_clearance, amk_sim_segment_cast,
                               amk_sim_path_cast) restated operation for operation: a point or a plan against the world's TRUE solids
+  noise_words / depth_noise_ordered   csrc/sim_noise.hip (amk_sim_depth_noise) restated operation for operation: the counter-based
+                              stream and what it does to a batch of depth frames (dropouts, flying pixels, axial noise, disparity steps)
 
 Nothing here computes neighbours or solves anything: that is the step's job (amk_step_batch / the oracle's stepo_run).
 """
@@ -619,6 +621,117 @@ def world_path_cast_ordered(cyl, box, path, radius, z_top=4.0):
         if h[0]:
             break
     return path_cast_reduction(path, hit, t, kind, index)
+
+
+# ---- sensor noise: amk_sim_depth_noise ------------------------------------------------------------------------------------------------
+NOISE_FIELDS = ("seed", "sigma0", "sigma2", "p_drop", "edge_jump", "p_edge_drop", "p_edge_fly", "focal_baseline", "disparity_quantum",
+                "z_min", "z_max")   # amk_sim_noise_params, in its order
+NOISE_SCALE = 2.6428997921303014e-05   # 1 / sqrt((65536^2 - 1) / 3): the sum of four 16-bit fields to variance 1
+_M64 = (1 << 64) - 1
+
+
+def noise_params(params=None, **fields):
+    """amk_sim_noise_params as a plain namespace: `params` (a dict or any object with some of NOISE_FIELDS) overridden by keywords;
+    what is not given is 0, which switches its stage off."""
+    got = {name: 0 if name == "seed" else 0.0 for name in NOISE_FIELDS}
+    for name in NOISE_FIELDS:
+        if isinstance(params, dict) and name in params:
+            got[name] = params[name]
+        elif params is not None and not isinstance(params, dict) and hasattr(params, name):
+            got[name] = getattr(params, name)
+    assert set(fields) <= set(NOISE_FIELDS), sorted(set(fields) - set(NOISE_FIELDS))
+    got.update(fields)
+    return type("NoiseParams", (), got)()
+
+
+def noise_mix(z):
+    """mix of amk_sim_depth_noise on np.uint64 (an array or a scalar), modulo 2^64"""
+    with np.errstate(over="ignore"):
+        z = np.asarray(z, np.uint64) + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
+def noise_words(seed, scene_id0, frame, n_scenes, rows, cols):
+    """The stream of amk_sim_depth_noise (amk__sim_noise_words): uint64 [n_scenes, rows, cols, 3] = w_0, w_1, w_2 of every pixel, with
+    k = mix(mix(mix(seed) ^ (scene_id0 + s)) ^ frame) and w_j = mix(k ^ (4 i + j)), i = v cols + u."""
+    scene = np.array([(int(scene_id0) + s) & _M64 for s in range(n_scenes)], np.uint64)
+    k = noise_mix(noise_mix(noise_mix(np.uint64(int(seed) & _M64)) ^ scene) ^ np.uint64(int(frame) & _M64))
+    ctr = np.uint64(4) * np.arange(rows * cols, dtype=np.uint64).reshape(1, rows, cols, 1) + np.arange(3, dtype=np.uint64)
+    return noise_mix(k.reshape(-1, 1, 1, 1) ^ ctr)
+
+
+def noise_threshold(p):
+    """T(p) of amk_sim_depth_noise: a draw of 32 bits succeeds when it is < T"""
+    return np.uint64(1 << 32 if p >= 1.0 else int(p * 4294967296.0))
+
+
+def _depth_z(pixels, pixel2meter):
+    """what depth.hip's inv_depth reads of a pixel, widened: (float)((double)(float)pixel * pixel2meter)"""
+    return (pixels.astype(np.float32).astype(np.float64) * float(pixel2meter)).astype(np.float32).astype(np.float64)
+
+
+def _noise_neighbours(z):
+    """z [S, rows, cols] -> the four neighbours of every pixel in the contract's order left, right, up, down: (z_n, inside the image)"""
+    S, rows, cols = z.shape
+    v, u = np.arange(rows).reshape(1, rows, 1), np.arange(cols).reshape(1, 1, cols)
+    full = lambda m: np.broadcast_to(m, z.shape)
+    return [(np.roll(z, 1, axis=2), full(u > 0)), (np.roll(z, -1, axis=2), full(u + 1 < cols)),
+            (np.roll(z, 1, axis=1), full(v > 0)), (np.roll(z, -1, axis=1), full(v + 1 < rows))]
+
+
+def depth_noise_ordered(depth, params, pixel2meter, frame, scene_id0=0, parts=None):
+    """amk_sim_depth_noise in numpy, operation for operation: depth uint16 or float32 [S, rows, cols] -> the noisy frames, same shape
+    and dtype.  `parts`, a dict, receives what the stages decided (valid, disc, partner, partner_z, flown, zero, z_in) for the tests."""
+    depth = np.ascontiguousarray(depth)
+    assert depth.ndim == 3 and depth.dtype in (np.uint16, np.float32)
+    p = noise_params(params)
+    S, rows, cols = depth.shape
+    w = noise_words(p.seed, scene_id0, frame, S, rows, cols)
+    w0, w1, w2 = w[..., 0], w[..., 1], w[..., 2]
+    with np.errstate(all="ignore"):
+        z0 = _depth_z(depth, pixel2meter)
+        valid = (z0 > 0.0) & (z0 < np.inf)                                           # 1. the others are copied as they are
+        z = z0.copy()
+        zero = np.zeros(z.shape, bool)
+        flown = np.zeros(z.shape, bool)
+        if p.edge_jump > 0.0:                                                        # 2. discontinuity
+            disc = np.zeros(z.shape, bool); have = np.zeros(z.shape, bool); zp = np.zeros(z.shape)
+            for zn, inside in _noise_neighbours(z0):
+                step = inside & (zn > 0.0) & (zn < np.inf) & (np.abs(zn - z0) > p.edge_jump)
+                disc |= (inside & ~(zn > 0.0)) | step
+                zp = np.where(step & ~have, zn, zp)
+                have |= step
+            r = w1 & np.uint64(0xffffffff)
+            t_drop, t_fly = noise_threshold(p.p_edge_drop), noise_threshold(p.p_edge_fly)
+            edge_drop = disc & (r < t_drop)
+            fly = disc & ~edge_drop & (r < t_drop + t_fly)
+            zero |= edge_drop | (fly & ~have)
+            flown = fly & have & valid
+            f = (w2 >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+            z = np.where(flown, z0 + f * (zp - z0), z0)
+            if parts is not None:
+                parts.update(disc=disc & valid, partner=have & valid, partner_z=zp)
+        zero |= (w1 >> np.uint64(32)) < noise_threshold(p.p_drop)                    # 3. dropout
+        axial, disparity = p.sigma0 > 0.0 or p.sigma2 > 0.0, p.disparity_quantum > 0.0
+        if axial:                                                                    # 4. axial noise
+            m = np.uint64(0xffff)
+            total = (w0 & m) + ((w0 >> np.uint64(16)) & m) + ((w0 >> np.uint64(32)) & m) + (w0 >> np.uint64(48))
+            g = (total.astype(np.int64) - 131070).astype(np.float64) * NOISE_SCALE
+            z = z + (p.sigma0 + (p.sigma2 * z) * z) * g
+        if disparity:                                                                # 5. disparity
+            dq = np.rint((p.focal_baseline / z) / p.disparity_quantum) * p.disparity_quantum
+            zero |= ~(dq > 0.0)
+            z = p.focal_baseline / dq
+        zero |= ~(z > 0.0) | (z < p.z_min) | ((z > p.z_max) if p.z_max > 0.0 else False)   # 6. range
+        touched = flown | axial | disparity                                          # 7. store
+        out = np.where(touched, quantise_depth(z, pixel2meter, depth.dtype), depth)
+        out = np.where(zero, np.zeros((), depth.dtype), out)
+        out = np.where(valid, out, depth).astype(depth.dtype)
+    if parts is not None:
+        parts.update(valid=valid, flown=flown, zero=zero & valid, z_in=z0)
+    return out
 
 
 class WallWorld(FlightWorld):

@@ -1150,6 +1150,33 @@ def sim_render_world(cyl, box, Twb, params, rows, cols, cyl_counts=None, box_cou
     return out
 
 
+def sim_noise_params(params=None, **fields):
+    """amk_sim_noise_params from flight.noise_params' fields (a dict, an object with those attributes, or keywords); everything
+    not given is off."""
+    from . import flight
+    p = flight.noise_params(params, **fields)
+    return capi.SimNoiseParams(int(p.seed), *[float(getattr(p, name)) for name in flight.NOISE_FIELDS[1:]])
+
+
+def sim_depth_noise(depth, params, pixel2meter, frame, scene_id0=0, out=None, stream=None):
+    """amk_sim_depth_noise: the frames a depth camera makes of perfect ones -- missing returns and flying pixels at depth
+    discontinuities, dropouts, axial noise, disparity steps, the sensor's range -- every draw a pure function of (params.seed,
+    scene_id0 + s, frame, pixel).  depth [S, rows, cols] uint16 / int16 / float32 device tensor (sim_render_world's) -> a tensor of the
+    same shape and dtype, never `depth` itself; it feeds depth_to_clouds and Pipeline.submit(depth=...).  params: capi.SimNoiseParams,
+    or what sim_noise_params takes.  Stream-ordered on torch's current stream (or `stream`); `out` re-uses a buffer."""
+    assert depth.dim() == 3 and depth.dtype in (torch.uint16, torch.int16, torch.float32) and depth.is_contiguous()
+    S, rows, cols = (int(v) for v in depth.shape)
+    if out is None:
+        out = torch.empty_like(depth)
+    assert tuple(out.shape) == (S, rows, cols) and out.is_contiguous() and out.dtype == depth.dtype
+    if not isinstance(params, capi.SimNoiseParams):
+        params = sim_noise_params(params)
+    kind = capi.AMK_DEPTH_F32 if depth.dtype == torch.float32 else capi.AMK_DEPTH_U16
+    capi.check(capi.load().amk_sim_depth_noise(capi.dptr(depth), capi.dptr(out), kind, rows, cols, rows * cols, S, float(pixel2meter),
+                                               C.byref(params), int(scene_id0), int(frame), capi.stream_ptr(stream)), "amk_sim_depth_noise")
+    return out
+
+
 def sim_vehicle_step_att(ABc, cmd, x, Twb=None, pose_quantum=0.0, attitude=capi.AMK_SIM_ATT_ACCEL, gz=9.81, stream=None):
     """amk_sim_vehicle_step_att: sim_vehicle_step, with Twb's rotation chosen by `attitude`: capi.AMK_SIM_ATT_YAW is sim_vehicle_step
     bit for bit, capi.AMK_SIM_ATT_ACCEL tilts the vehicle into its thrust a + (0, 0, gz) (acc2rotmat on the new state)."""

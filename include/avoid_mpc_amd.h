@@ -1367,6 +1367,72 @@ int amk_sim_path_cast_host(const double *h_cyl, const int *h_cyl_counts, int max
                            double radius, int *h_stop, int *h_leg, double *h_t, double *h_free, double *h_pts, int *h_kind,
                            int *h_index);
 
+/* Sensor noise on the simulated depth frames: dropouts, flying pixels, axial noise, disparity steps, the sensor's own range.
+ * amk_sim_render_depth / amk_sim_render_world give a perfect sensor: the exact planar depth of every first hit, silhouettes one
+ * pixel sharp.  amk_sim_depth_noise is one out-of-place pass over a batch of such frames (or any recorded ones), placed between
+ * the render and amk_pipeline_submit, that makes them the frames a depth camera gives.  It is DETERMINISTIC: every random number is
+ * a pure function of (seed, fleet-wide scene number, frame, pixel, draw) through a counter-based integer hash, so a noisy flight
+ * repeats on any machine and a host restatement matches bit for bit (avoid_mpc_amd/flight.py noise_words, depth_noise_ordered).
+ *   d_in, d_out  [n_scenes] images of rows x cols pixels of depth_type (AMK_DEPTH_U16 / AMK_DEPTH_F32), scene s at s * scene_stride
+ *                pixels in both; scene_stride >= rows cols, and the pixels between two images are neither read nor written.
+ *   scene_id0    the fleet-wide number of scene 0 of the call: a sharded or split fleet draws the same stream per robot.
+ *   frame        the period counter, by value.
+ * Arithmetic: fp64, no contraction, every sum left to right as written; division and rint (ties to even) are IEEE-correct.  Integer
+ * arithmetic is modulo 2^64.
+ *
+ * Stream.
+ *   mix(z):  z += 0x9E3779B97F4A7C15;  z = (z ^ z >> 30) 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) 0x94D049BB133111EB;  return z ^ z >> 31
+ *   per scene s and frame:  k = mix(mix(mix(seed) ^ (scene_id0 + s)) ^ frame)
+ *   per pixel i = v cols + u (the position in the image, not in memory, in 64 bits) and draw j in {0, 1, 2}:  w_j = mix(k ^ (4 i + j))
+ *   w_0 gives the variate g = (f0 + f1 + f2 + f3 - 131070) c, the f being the four 16-bit fields of w_0 and
+ *       c = 2.6428997921303014e-05 = 1 / sqrt((65536^2 - 1) / 3): mean 0, variance 1, |g| <= 3.4642 -- the noise is bounded
+ *   w_1: its high 32 bits decide the plain dropout, its low 32 bits what happens at a discontinuity
+ *   w_2 >> 11 times 2^-53 is the flying pixel's fraction f in [0, 1)
+ *   a probability p becomes the threshold T(p) = p >= 1 ? 2^32 : (u64)(p 4294967296.0), host arithmetic; a draw r succeeds when r < T
+ *
+ * Pixel.  z is read as amk_depth_to_clouds reads a pixel, (float)((double)(float)pixel pixel2meter), widened; it is written by
+ * amk_sim_render_depth's rule: AMK_DEPTH_F32 holds (float)z / (float)pixel2meter correctly rounded to float32, AMK_DEPTH_U16 that
+ * value under rintf, clamped to [0, 65535].  "The output is 0" ends the pixel.  The stages, in this order:
+ *   1. Invalid input.  A pixel that is not a finite z > 0 (0, NaN, +-inf, negative) is copied bit for bit; no stage sees it.
+ *   2. Discontinuity, only with edge_jump > 0.  The 4-neighbours inside the image, in the order left, right, up, down, are read from
+ *      the INPUT image.  The pixel is a discontinuity pixel when some neighbour has no return (z_n not > 0) or is a finite return
+ *      with |z_n - z| > edge_jump.  Then r = the low 32 bits of w_1:  r < T(p_edge_drop): the output is 0.  Otherwise
+ *      r < T(p_edge_drop) + T(p_edge_fly): the partner is the first neighbour in that order that is a finite return with
+ *      |z_n - z| > edge_jump; without one the output is 0, else z <- z + f (z_partner - z).
+ *   3. Dropout.  The high 32 bits of w_1 < T(p_drop): the output is 0.
+ *   4. Axial noise, only when sigma0 > 0 || sigma2 > 0:  z <- z + (sigma0 + (sigma2 z) z) g.
+ *   5. Disparity, only with disparity_quantum q > 0:  d = focal_baseline / z, dq = rint(d / q) q; dq not > 0: the output is 0;
+ *      else z <- focal_baseline / dq.
+ *   6. Range.  z not > 0, z < z_min, or (z_max > 0 and z > z_max): the output is 0.
+ *   7. Store.  A pixel that no enabled stage touched -- touched: flown, axial noise on, disparity on -- is copied bit for bit; every
+ *      other pixel goes through the store rule.  A call with everything off is a copy, for both pixel types.
+ * The result does not depend on the order in which pixels are processed, and a draw a pixel does not need is not part of any other.
+ *
+ * AMK_ERR_INVALID_ARG: a NULL pointer, d_in == d_out or overlapping ranges, rows, cols or n_scenes < 1, scene_stride < rows cols,
+ * pixel2meter not > 0, a probability outside [0, 1] or NaN, p_edge_drop + p_edge_fly > 1, a negative or NaN sigma, jump, quantum or
+ * range, disparity_quantum > 0 with focal_baseline not > 0, an unknown depth_type.  AMK_ERR_UNSUPPORTED: a grid beyond the launch
+ * limits -- more than 65 535 scenes (the scenes are the grid's second dimension) or more than 256 (2^24 - 1) pixels per image.
+ * AMK_ERR_NO_DEVICE: no device.  Every error is returned before anything is staged or launched, the output untouched.  The call is
+ * stream-ordered, allocates nothing and keeps no hidden state.  amk_sim_depth_noise_host takes host pointers, stages them and
+ * synchronises.
+ * Not offered: a calibrated model of any camera, spatially or temporally correlated noise, lateral (pixel-position) noise,
+ * multi-path and reflectance effects.                                                                                          */
+typedef struct amk_sim_noise_params {
+    unsigned long long seed;
+    double sigma0, sigma2;                    /* axial noise [m]: sigma(z) = sigma0 + sigma2 z z                  */
+    double p_drop;                            /* every valid pixel: probability of no return                       */
+    double edge_jump;                         /* [m] a depth step larger than this is a discontinuity; 0 = off     */
+    double p_edge_drop, p_edge_fly;           /* at a discontinuity pixel: no return / a flying pixel              */
+    double focal_baseline, disparity_quantum; /* z -> fb / (rint((fb / z) / q) q); q = 0 = off                     */
+    double z_min, z_max;                      /* the sensor's own working range; z_max = 0 = no upper gate         */
+} amk_sim_noise_params;
+int amk_sim_depth_noise(const void *d_in, void *d_out, int depth_type, int rows, int cols, long long scene_stride, int n_scenes,
+                        double pixel2meter, const amk_sim_noise_params *prm, long long scene_id0, unsigned long long frame,
+                        void *stream);
+int amk_sim_depth_noise_host(const void *h_in, void *h_out, int depth_type, int rows, int cols, long long scene_stride,
+                             int n_scenes, double pixel2meter, const amk_sim_noise_params *prm, long long scene_id0,
+                             unsigned long long frame);
+
 #ifdef __cplusplus
 }
 #endif
