@@ -68,6 +68,7 @@ SYMBOLS = [
     "amk_sim_render_world", "amk_sim_render_world_host", "amk_sim_vehicle_step_att", "amk_sim_vehicle_step_att_host",
     "amk_sim_clearance", "amk_sim_clearance_host", "amk_sim_segment_cast", "amk_sim_segment_cast_host",
     "amk_sim_path_cast", "amk_sim_path_cast_host", "amk_sim_depth_noise", "amk_sim_depth_noise_host",
+    "amk_sim_body_reset", "amk_sim_vehicle_step_body", "amk_sim_vehicle_step_body_host",
 ]
 
 
@@ -129,6 +130,16 @@ class SimNoiseParams(C.Structure):
     _fields_ = [("seed", C.c_ulonglong), ("sigma0", C.c_double), ("sigma2", C.c_double), ("p_drop", C.c_double), ("edge_jump", C.c_double),
                 ("p_edge_drop", C.c_double), ("p_edge_fly", C.c_double), ("focal_baseline", C.c_double), ("disparity_quantum", C.c_double),
                 ("z_min", C.c_double), ("z_max", C.c_double)]
+
+
+AMK_SIM_BODY_DOUBLES, AMK_SIM_COG_MAX = 64, 16
+
+
+class SimBodyParams(C.Structure):
+    """amk_sim_body_params (host.sim_body_params fills it)"""
+    _fields_ = [("h", C.c_double), ("n_sub", C.c_int), ("gz", C.c_double), ("k_att", C.c_double), ("rate_max", C.c_double),
+                ("k_rate", C.c_double), ("k_thrust", C.c_double), ("f_min", C.c_double), ("f_max", C.c_double), ("drag", C.c_double * 3),
+                ("yaw_cs", C.c_double), ("yaw_sn", C.c_double), ("cog_window", C.c_int), ("cog_weight", C.c_double * AMK_SIM_COG_MAX)]
 
 
 AMK_DEPTH_U16, AMK_DEPTH_F32 = 0, 1
@@ -324,6 +335,9 @@ def load():
         # (in, out, depth_type, rows, cols, scene_stride, n_scenes, pixel2meter, params, scene_id0, frame)
         "amk_sim_depth_noise": (i, [vp, vp, i, i, i, C.c_longlong, i, d, C.POINTER(SimNoiseParams), C.c_longlong, C.c_ulonglong, vp]),
         "amk_sim_depth_noise_host": (i, [vp, vp, i, i, i, C.c_longlong, i, d, C.POINTER(SimNoiseParams), C.c_longlong, C.c_ulonglong]),
+        "amk_sim_body_reset": (i, [vp, i, d, vp]),
+        "amk_sim_vehicle_step_body": (i, [C.POINTER(SimBodyParams), vp, vp, vp, vp, i, d, vp]),
+        "amk_sim_vehicle_step_body_host": (i, [C.POINTER(SimBodyParams), vp, vp, vp, vp, i, d]),
     }
     sig["amk__kd_set_mode"] = (i, [vp, i])  # internal: 0 bucketed index, 1 streaming scan
     sig["amk__sweep_set_target"] = (None, [i])  # internal (tests, A/B): the pool's sweep against 1 a fine hashed grid of the current frame (default), 0 the frame's own index

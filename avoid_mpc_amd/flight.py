@@ -23,6 +23,8 @@ GPU driver (tests/_flight.py, bench.py --workload flight) and the CPU-oracle dri
                               amk_sim_path_cast) restated operation for operation: a point or a plan against the world's TRUE solids
   noise_words / depth_noise_ordered   csrc/sim_noise.hip (amk_sim_depth_noise) restated operation for operation: the counter-based
                               stream and what it does to a batch of depth frames (dropouts, flying pixels, axial noise, disparity steps)
+  body_params / body_state0 / body_step_ordered   csrc/sim_body.hip (amk_sim_body_reset, amk_sim_vehicle_step_body) restated operation
+                              for operation: a rigid body flown by bfctrl's geometric attitude controller in sub-steps, and the node's COGFilter
 
 Nothing here computes neighbours or solves anything: that is the step's job (amk_step_batch / the oracle's stepo_run).
 """
@@ -732,6 +734,158 @@ def depth_noise_ordered(depth, params, pixel2meter, frame, scene_id0=0, parts=No
     if parts is not None:
         parts.update(valid=valid, flown=flown, zero=zero & valid, z_in=z0)
     return out
+
+
+# ---- the rigid-body vehicle: amk_sim_vehicle_step_body -------------------------------------------------------------------------------
+BODY_DOUBLES, COG_MAX = 64, 16   # AMK_SIM_BODY_DOUBLES, AMK_SIM_COG_MAX
+BODY_FIELDS = ("h", "n_sub", "gz", "k_att", "rate_max", "k_rate", "k_thrust", "f_min", "f_max", "drag", "yaw_cs", "yaw_sn", "cog_window",
+               "cog_weight")   # amk_sim_body_params, in its order
+BODY_Q, BODY_RATE, BODY_F, BODY_HELD, BODY_HEAD, BODY_RING = 0, 4, 7, 8, 9, 10   # where the hidden state lies in a scene's 64 doubles
+
+
+def cog_weights(decay=0.8):
+    """The node's COGFilter weights, [COG_MAX] float64: weight idx = float(std::pow(float decay, int idx)), which C++ evaluates in double
+    on the float32 decay and rounds to float32 (COGFilter.cpp:15)."""
+    d = float(np.float32(decay))
+    return np.array([float(np.float32(d ** idx)) for idx in range(COG_MAX)])
+
+
+def body_params(con_dt, params=None, tau_rate=0.03, tau_thrust=0.05, **fields):
+    """amk_sim_body_params as a plain namespace for a control period of con_dt seconds: `params` (a dict or an object with some of
+    BODY_FIELDS) overridden by keywords.  The defaults are THIS PROJECT'S CHOICES, calibrated against no vehicle: 33 sub-steps per
+    period, gravity 9.81, attitude gain 20 / s, body rates clamped at 10 rad/s, a 0.03 s rate lag and a 0.05 s thrust lag (as
+    k = min(1, h / tau)), collective thrust in [0, 4 gz], no drag, yaw 0, and the node's COGFilter (window 10, decay 0.8)."""
+    got = {}
+    for name in BODY_FIELDS:
+        if isinstance(params, dict) and name in params:
+            got[name] = params[name]
+        elif params is not None and not isinstance(params, dict) and hasattr(params, name):
+            got[name] = getattr(params, name)
+    assert set(fields) <= set(BODY_FIELDS), sorted(set(fields) - set(BODY_FIELDS))
+    got.update(fields)
+    n_sub = int(got.setdefault("n_sub", 33))
+    if "h" not in got:
+        got["h"] = float(con_dt) / n_sub
+    h = float(got["h"])
+    gz = float(got.setdefault("gz", GZ))
+    for name, value in (("k_att", 20.0), ("rate_max", 10.0), ("k_rate", min(1.0, h / tau_rate)), ("k_thrust", min(1.0, h / tau_thrust)),
+                        ("f_min", 0.0), ("f_max", 4.0 * gz), ("drag", (0.0, 0.0, 0.0)), ("yaw_cs", 1.0), ("yaw_sn", 0.0), ("cog_window", 10)):
+        got.setdefault(name, value)
+    w = np.zeros(COG_MAX)
+    given = np.asarray(got.get("cog_weight", cog_weights()), np.float64).reshape(-1)
+    w[:given.size] = given
+    got["cog_weight"] = w
+    got["drag"] = tuple(float(v) for v in got["drag"])
+    return type("BodyParams", (), got)()
+
+
+def body_state0(S, gz=GZ):
+    """amk_sim_body_reset: [S, BODY_DOUBLES] -- level (q = 1, 0, 0, 0), at rest, hovering (f = gz), an empty IMU window, the rest 0"""
+    body = np.zeros((int(S), BODY_DOUBLES))
+    body[:, BODY_Q] = 1.0
+    body[:, BODY_F] = gz
+    return body
+
+
+def _body_clamp(v, lo, hi):
+    """v < lo ? lo : (v > hi ? hi : v): a NaN fails both comparisons and passes through"""
+    return np.where(v < lo, lo, np.where(v > hi, hi, v))
+
+
+def _body_rotation(qw, qx, qy, qz):
+    """The nine polynomial entries of the rotation of a (nearly unit) quaternion, rows of [S] arrays"""
+    return ((1.0 - 2.0 * ((qy * qy) + (qz * qz)), 2.0 * ((qx * qy) - (qw * qz)), 2.0 * ((qx * qz) + (qw * qy))),
+            (2.0 * ((qx * qy) + (qw * qz)), 1.0 - 2.0 * ((qx * qx) + (qz * qz)), 2.0 * ((qy * qz) - (qw * qx))),
+            (2.0 * ((qx * qz) - (qw * qy)), 2.0 * ((qy * qz) + (qw * qx)), 1.0 - 2.0 * ((qx * qx) + (qy * qy))))
+
+
+def _body_index(v, hi):
+    """One of the two integers kept as doubles: truncated towards zero; a value outside [0, hi] (or a NaN) reads as 0"""
+    v = np.asarray(v, np.float64)
+    ok = (v >= 0.0) & (v <= hi)
+    return np.where(ok, np.trunc(np.where(ok, v, 0.0)), 0.0).astype(np.int64)
+
+
+def body_step_ordered(prm, x, body, cmd, pose_quantum=0.0):
+    """amk_sim_vehicle_step_body in numpy, operation for operation (include/avoid_mpc_amd.h, "The rigid-body vehicle"): a small rigid
+    body flown by bfctrl's geometric controller in acceleration mode through prm.n_sub sub-steps of prm.h seconds, and the node's
+    COGFilter over its body-frame specific force.  x [S, 10], body [S, BODY_DOUBLES], cmd [S, 3] -> (x+, body+, Twb [S, 4, 4]); the
+    inputs are not modified.  Every sum is written out left to right; no matrix product, no transcendental.  A NaN's sign and
+    payload are not part of the contract."""
+    x, body, cmd = (np.array(a, np.float64) for a in (x, body, cmd))
+    S = x.shape[0]
+    rows = np.arange(S)
+    h, hh, gz = float(prm.h), 0.5 * float(prm.h), float(prm.gz)
+    d0, d1, d2 = prm.drag
+    cs, sn = float(prm.yaw_cs), float(prm.yaw_sn)
+    p = [x[:, 0].copy(), x[:, 1].copy(), x[:, 2].copy()]
+    v = [x[:, 4].copy(), x[:, 5].copy(), x[:, 6].copy()]
+    qw, qx, qy, qz = (body[:, BODY_Q + i].copy() for i in range(4))
+    w = [body[:, BODY_RATE + i].copy() for i in range(3)]
+    f = body[:, BODY_F].copy()
+    held, head = _body_index(body[:, BODY_HELD], COG_MAX), _body_index(body[:, BODY_HEAD], COG_MAX - 1)
+    ring = body[:, BODY_RING:BODY_RING + 3 * COG_MAX].reshape(S, COG_MAX, 3)      # (a view: the pushes land in `body`)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        # once per call: the desired attitude R_d = [X Y Z] of acc2rotmat on the command itself (gravity is already in it)
+        T = (cmd[:, 0], cmd[:, 1], cmd[:, 2])
+        n = np.sqrt((T[0] * T[0] + T[1] * T[1]) + T[2] * T[2])
+        Z = (T[0] / n, T[1] / n, T[2] / n)
+        y = (0.0 - Z[2] * sn, Z[2] * cs, Z[0] * sn - Z[1] * cs)
+        m = np.sqrt((y[0] * y[0] + y[1] * y[1]) + y[2] * y[2])
+        Y = (y[0] / m, y[1] / m, y[2] / m)
+        X = (Y[1] * Z[2] - Y[2] * Z[1], Y[2] * Z[0] - Y[0] * Z[2], Y[0] * Z[1] - Y[1] * Z[0])
+        valid = (n > 0) & (m > 0)
+        col = lambda D, R, j: (D[0] * R[0][j] + D[1] * R[1][j]) + D[2] * R[2][j]
+        for _ in range(int(prm.n_sub)):
+            R = _body_rotation(qw, qx, qy, qz)
+            e = (0.5 * (col(Z, R, 1) - col(Y, R, 2)), 0.5 * (col(X, R, 2) - col(Z, R, 0)), 0.5 * (col(Y, R, 0) - col(X, R, 1)))   # 1.
+            wc = [np.where(valid, _body_clamp(-(prm.k_att * e[i]), -prm.rate_max, prm.rate_max), 0.0) for i in range(3)]         # 2.
+            fc = _body_clamp((T[0] * R[0][2] + T[1] * R[1][2]) + T[2] * R[2][2], prm.f_min, prm.f_max)                          # 3.
+            w = [w[i] + prm.k_rate * (wc[i] - w[i]) for i in range(3)]                                                            # 4.
+            f = f + prm.k_thrust * (fc - f)
+            vb = [(R[0][i] * v[0] + R[1][i] * v[1]) + R[2][i] * v[2] for i in range(3)]                                           # 5.
+            sb = (-(d0 * vb[0]), -(d1 * vb[1]), f - d2 * vb[2])
+            aw = [(R[i][0] * sb[0] + R[i][1] * sb[1]) + R[i][2] * sb[2] for i in range(3)]
+            aw[2] = aw[2] - gz
+            for i in range(3):
+                ring[rows, head, i] = sb[i]
+            head = (head + 1) % COG_MAX
+            held = np.minimum(held + 1, COG_MAX)
+            v = [v[i] + h * aw[i] for i in range(3)]                                                                              # 6.
+            p = [p[i] + h * v[i] for i in range(3)]
+            dw = -(((qx * w[0]) + (qy * w[1])) + (qz * w[2]))                                                                     # 7.
+            dx = ((qw * w[0]) + (qy * w[2])) - (qz * w[1])
+            dy = ((qw * w[1]) + (qz * w[0])) - (qx * w[2])
+            dz = ((qw * w[2]) + (qx * w[1])) - (qy * w[0])
+            qw, qx, qy, qz = qw + hh * dw, qx + hh * dx, qy + hh * dy, qz + hh * dz
+            nq = np.sqrt(((qw * qw + qx * qx) + qy * qy) + qz * qz)
+            qw, qx, qy, qz = qw / nq, qx / nq, qy / nq, qz / nq
+        R = _body_rotation(qw, qx, qy, qz)
+        newest = lambda idx: ring[rows, (head - 1 - idx) % COG_MAX]                # [S, 3], the idx-th newest sample
+        sbar = [newest(0)[:, i].copy() for i in range(3)]
+        if prm.cog_window >= 2:
+            cw = prm.cog_weight
+            take = np.minimum(held, int(prm.cog_window))
+            acc, wsum = [cw[0] * sbar[i] for i in range(3)], np.full(S, cw[0])
+            for idx in range(1, int(prm.cog_window)):
+                s, on = newest(idx), idx < take
+                acc = [np.where(on, acc[i] + cw[idx] * s[:, i], acc[i]) for i in range(3)]
+                wsum = np.where(on, wsum + cw[idx], wsum)
+            sbar = [acc[i] / wsum for i in range(3)]
+        a = [(R[i][0] * sbar[0] + R[i][1] * sbar[1]) + R[i][2] * sbar[2] for i in range(3)]
+        a[2] = a[2] - gz
+    for i in range(3):
+        x[:, i] = p[i]; x[:, 4 + i] = v[i]; x[:, 7 + i] = a[i]; body[:, BODY_RATE + i] = w[i]
+    for i, qi in enumerate((qw, qx, qy, qz)):
+        body[:, BODY_Q + i] = qi
+    body[:, BODY_F] = f; body[:, BODY_HELD] = held; body[:, BODY_HEAD] = head
+    Twb = np.zeros((S, 4, 4))
+    Twb[:, 3, 3] = 1.0
+    for i in range(3):
+        for j in range(3):
+            Twb[:, i, j] = R[i][j]
+        Twb[:, i, 3] = np.rint(p[i] * pose_quantum) / pose_quantum if pose_quantum > 0 else p[i]
+    return x, body, Twb
 
 
 class WallWorld(FlightWorld):

@@ -1191,6 +1191,44 @@ def sim_vehicle_step_att(ABc, cmd, x, Twb=None, pose_quantum=0.0, attitude=capi.
     return x
 
 
+def sim_body_params(con_dt=None, params=None, **fields):
+    """amk_sim_body_params from flight.body_params' fields (a dict, an object with those attributes, or keywords) for a control period of
+    con_dt seconds; what is not given takes flight.body_params' defaults.  con_dt may be None when `h` is given."""
+    from . import flight
+    if con_dt is None:
+        assert "h" in fields or (params is not None and (("h" in params) if isinstance(params, dict) else hasattr(params, "h")))
+        con_dt = 0.0
+    p = flight.body_params(con_dt, params, **fields)
+    return capi.SimBodyParams(float(p.h), int(p.n_sub), float(p.gz), float(p.k_att), float(p.rate_max), float(p.k_rate), float(p.k_thrust),
+                              float(p.f_min), float(p.f_max), (C.c_double * 3)(*p.drag), float(p.yaw_cs), float(p.yaw_sn), int(p.cog_window),
+                              (C.c_double * capi.AMK_SIM_COG_MAX)(*[float(v) for v in p.cog_weight]))
+
+
+def sim_body_reset(body, gz=9.81, stream=None):
+    """amk_sim_body_reset: body float64 [S, 64] <- level, at rest, hovering (f = gz), an empty IMU window (flight.body_state0)."""
+    S = int(body.shape[0])
+    assert body.dtype == torch.float64 and tuple(body.shape) == (S, capi.AMK_SIM_BODY_DOUBLES) and body.is_contiguous()
+    capi.check(capi.load().amk_sim_body_reset(capi.dptr(body), S, float(gz), capi.stream_ptr(stream)), "amk_sim_body_reset")
+    return body
+
+
+def sim_vehicle_step_body(params, cmd, x, body, Twb=None, pose_quantum=0.0, stream=None):
+    """amk_sim_vehicle_step_body: the rigid-body vehicle over one control period, in place -- cmd float64 [S, 3] (a thrust acceleration,
+    gravity inside), x float64 [S, 10] (p and v advance, x[:, 7:10] becomes the filtered IMU acceleration, the yaw is not written),
+    body float64 [S, 64] the hidden state (sim_body_reset), Twb float64 [S, 4, 4] or None <- [R | rint(p q) / q].  params:
+    capi.SimBodyParams, or what sim_body_params takes as `params` (then `h` must be among it).  Stream-ordered."""
+    S = int(x.shape[0])
+    assert x.dtype == torch.float64 and tuple(x.shape) == (S, 10) and cmd.dtype == torch.float64 and tuple(cmd.shape) == (S, 3)
+    assert body.dtype == torch.float64 and tuple(body.shape) == (S, capi.AMK_SIM_BODY_DOUBLES)
+    assert x.is_contiguous() and cmd.is_contiguous() and body.is_contiguous()
+    assert Twb is None or (Twb.dtype == torch.float64 and tuple(Twb.shape) == (S, 4, 4) and Twb.is_contiguous())
+    if not isinstance(params, capi.SimBodyParams):
+        params = sim_body_params(None, params)
+    capi.check(capi.load().amk_sim_vehicle_step_body(C.byref(params), capi.dptr(cmd), capi.dptr(x), capi.dptr(body), capi.dptr(Twb), S,
+                                                     float(pose_quantum), capi.stream_ptr(stream)), "amk_sim_vehicle_step_body")
+    return x
+
+
 def _sim_world_head(cyl, box, cyl_counts, box_counts, z_top):
     """The leading arguments of the ground-truth queries: amk_sim_render_world's world, checked as sim_render_world checks it"""
     assert cyl.dtype == torch.float64 and cyl.dim() == 3 and cyl.shape[2] == 3 and cyl.is_contiguous()

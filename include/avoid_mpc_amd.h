@@ -1433,6 +1433,102 @@ int amk_sim_depth_noise_host(const void *h_in, void *h_out, int depth_type, int 
                              int n_scenes, double pixel2meter, const amk_sim_noise_params *prm, long long scene_id0,
                              unsigned long long frame);
 
+/* The rigid-body vehicle: a body with an attitude loop, flown in sub-steps inside one control period.
+ * amk_sim_vehicle_step advances the plant with the MPC's own affine model, so the MPC's first predicted state is the next odometry
+ * exactly, and amk_sim_vehicle_step_att only paints a rotation onto that pose.  amk_sim_vehicle_step_body is a SECOND vehicle beside
+ * them (neither is changed): a small rigid body flown by bfctrl's GeometricController in acceleration mode -- the desired attitude from
+ * the commanded thrust vector, the thrust as the command projected on the current body z, the attitude error on SO(3) -- integrated in
+ * n_sub explicit sub-steps of h seconds, which reports its acceleration as the node does: the COGFilter's weighted mean of the
+ * body-frame accelerometer samples, rotated by the current attitude, minus gravity (AvoidanceStateMachine.cpp, the IMU callback).
+ * The plant no longer obeys the planner's model, and the camera's tilt lags its command.
+ *   d_cmd   [S][3], d_x [S][10], d_Twb [S][16] or NULL: amk_sim_vehicle_step's buffers.  x[0..2] = p and x[4..6] = v are read and
+ *           written; x[3], the yaw, is NOT written (what the affine plant does with it at u_3 = 0) and not read: the commanded yaw
+ *           comes as (yaw_cs, yaw_sn); x[7..9] is an OUTPUT only and never read.  Twb = [R_f | p'] of the new state, row-major, with
+ *           amk_sim_vehicle_step's own p': p' = rint(p q) / q for pose_quantum q > 0 (q = 1e6: the pose rounded to a micrometre,
+ *           numpy's round(p, 6)); q = 0: p' = p.
+ *   d_body  [S][AMK_SIM_BODY_DOUBLES] in/out, the hidden state of every scene as ONE array of doubles:
+ *           [0..3] the quaternion (w, x, y, z), [4..6] the body rates w, [7] the collective thrust acceleration f,
+ *           [8] held, the count of IMU samples in the ring, [9] head, the ring slot the NEXT sample goes to,
+ *           [10 + 3 k .. 12 + 3 k] slot k of the ring of the last AMK_SIM_COG_MAX body-frame specific-force samples, k = 0 .. 15;
+ *           [58..63] unused: the step leaves these words untouched (amk_sim_body_reset writes them as 0).
+ *           The two integers are stored as doubles.  Either is read truncated towards zero, and a value outside its range -- held
+ *           outside [0, AMK_SIM_COG_MAX], head outside [0, AMK_SIM_COG_MAX - 1], a NaN -- is read as 0, so that no state makes the
+ *           call touch memory that is not the scene's.  The quaternion is not renormalised on the way in.
+ * amk_sim_body_reset writes every scene's state: level (q = 1, 0, 0, 0), at rest, hovering (f = gz), an empty IMU window, all else 0.
+ *
+ * Arithmetic: fp64, no contraction, every sum left to right exactly as parenthesised below; division and square root are
+ * IEEE-correct; there is no transcendental on the device; -(a) is the negation (it flips the sign of a zero).  A NaN's sign and
+ * payload are not part of the contract.  avoid_mpc_amd/flight.py body_step_ordered restates it operation for operation.
+ *   clamp(v, lo, hi) = v < lo ? lo : (v > hi ? hi : v), so a NaN passes through.
+ *   R(q), "the usual nine polynomial entries" of q = (w, x, y, z):
+ *     R00 = 1.0 - 2.0 ((y y) + (z z))   R01 = 2.0 ((x y) - (w z))         R02 = 2.0 ((x z) + (w y))
+ *     R10 = 2.0 ((x y) + (w z))         R11 = 1.0 - 2.0 ((x x) + (z z))   R12 = 2.0 ((y z) - (w x))
+ *     R20 = 2.0 ((x z) - (w y))         R21 = 2.0 ((y z) + (w x))         R22 = 1.0 - 2.0 ((x x) + (y y))
+ * Once per call, from T = cmd.  T is already a thrust acceleration with gravity inside it (PubCmd; PubSlowDownCmd adds 9.8), so NO
+ * gz is added here, unlike AMK_SIM_ATT_ACCEL.  R_d = [X Y Z] (columns) is amk_sim_vehicle_step_att's acc2rotmat with
+ * cs, sn = yaw_cs, yaw_sn, the cosine and sine of the COMMANDED yaw as the caller computed them:
+ *   n = sqrt((T_0 T_0 + T_1 T_1) + T_2 T_2);  Z = T / n
+ *   y' = (0.0 - Z_2 sn, Z_2 cs, Z_0 sn - Z_1 cs);  m = sqrt((y'_0 y'_0 + y'_1 y'_1) + y'_2 y'_2);  Y = y' / m
+ *   X = (Y_1 Z_2 - Y_2 Z_1, Y_2 Z_0 - Y_0 Z_2, Y_0 Z_1 - Y_1 Z_0);  valid = n > 0 && m > 0
+ * Per sub-step, in this order, with R = R(q) built at the top of the sub-step and D . R_j = (D_0 R0j + D_1 R1j) + D_2 R2j:
+ *   1. Attitude error, M = R_d^T R:  e = (0.5 ((Z . R_1) - (Y . R_2)), 0.5 ((X . R_2) - (Z . R_0)), 0.5 ((Y . R_0) - (X . R_1)))
+ *      which is 0.5 (M21 - M12, M02 - M20, M10 - M01).
+ *   2. Rate command:  wc_i = valid ? clamp(-(k_att e_i), -rate_max, rate_max) : 0.0
+ *   3. Thrust command:  fc = clamp((T_0 R02 + T_1 R12) + T_2 R22, f_min, f_max) -- GetThrust(desired_acc.dot(zbody)) with a perfect
+ *      thrust map.
+ *   4. Lags:  w_i <- w_i + k_rate (wc_i - w_i);  f <- f + k_thrust (fc - f)
+ *   5. Specific force and acceleration:  vb_i = (R0i v_0 + R1i v_1) + R2i v_2  (v_b = R^T v);
+ *      sb = (-(drag_0 vb_0), -(drag_1 vb_1), f - drag_2 vb_2);  aw_i = (Ri0 sb_0 + Ri1 sb_1) + Ri2 sb_2, and aw_2 <- aw_2 - gz.
+ *      Push sb: ring[head] = sb, head <- (head + 1) mod AMK_SIM_COG_MAX, held <- min(held + 1, AMK_SIM_COG_MAX).
+ *   6. Translation:  v_i <- v_i + h aw_i, then p_i <- p_i + h v_i with the NEW v.
+ *   7. Attitude, with the NEW w and hh = 0.5 h:
+ *        dw = -(((x w_0) + (y w_1)) + (z w_2))      dx = ((w w_0) + (y w_2)) - (z w_1)      (on the right, w x y z are q's entries and
+ *        dy = ((w w_1) + (z w_0)) - (x w_2)         dz = ((w w_2) + (x w_1)) - (y w_0)       w_0 w_1 w_2 the body rates)
+ *      q_i <- q_i + hh d_i;  nq = sqrt(((w w + x x) + y y) + z z);  q_i <- q_i / nq.
+ * After the last sub-step, with R_f = R(q) of the final q and s_idx the idx-th newest sample, ring[(head - 1 - idx) mod 16]:
+ *   cog_window <= 1:  sbar = s_0, the newest sample itself, with no division.
+ *   otherwise:  over idx = 0 .. min(held, cog_window) - 1, newest first:  acc = cog_weight[0] s_0, W = cog_weight[0], then
+ *               acc <- acc + cog_weight[idx] s_idx, W <- W + cog_weight[idx];  sbar = acc / W.  This is the reference's filter over a
+ *               window that is still filling; cog_weight[idx] is the weight of the idx-th newest sample (the caller's decay^idx).
+ *   x[7 + i] = (Rf_i0 sbar_0 + Rf_i1 sbar_1) + Rf_i2 sbar_2, and x[9] <- x[9] - gz: the node's mAcc = R filtered - g.
+ *   x[0..2] = p, x[4..6] = v, Twb = [R_f | p'], its last row (0, 0, 0, 1).
+ * At hover -- level, at rest, cmd = (0, 0, gz) -- p, v, q, w and f are a fixed point bit for bit: R_d = I, e = 0 and aw = 0 without
+ * rounding.
+ * THE SIGN in step 2 is deliberate.  The reference's geometric_attcontroller has no minus in front of (2 / attctrl_tau_) error_att;
+ * it sits behind use_bodyrate_ctrl, which the reference ships false.  With e as defined here -- the reference's -- the attitude obeys
+ * theta' = +k_att sin(theta) under that sign and runs to pi; with the minus it decays.  k_att is the reference's 2 / attctrl_tau_.
+ * A non-finite command or state in one scene stays in that scene.
+ *
+ * AMK_ERR_INVALID_ARG: a NULL pointer (d_Twb excepted), n_scenes < 1, a negative or NaN pose_quantum, any parameter outside the range
+ * stated at its field or NaN (yaw_cs, yaw_sn: NaN), cog_window outside [0, AMK_SIM_COG_MAX], and for cog_window >= 2 a sum
+ * ((cog_weight[0] + cog_weight[1]) + ...) of the first cog_window weights that is not > 0; amk_sim_body_reset: a NULL pointer,
+ * n_scenes < 1, a negative or NaN gz.  AMK_ERR_NO_DEVICE: no device.  Every error is returned before anything is staged or launched,
+ * the outputs unwritten.  The calls are stream-ordered and allocate nothing.  amk_sim_vehicle_step_body_host takes host pointers,
+ * stages them and synchronises.
+ * Not offered: motor and rotor dynamics, moments and inertia (the body rates follow their command through a first-order lag), wind, a
+ * thrust-map estimator, odometry noise, the controller's position mode, calibrated parameters of any vehicle.                   */
+#define AMK_SIM_BODY_DOUBLES 64   /* doubles of hidden state per scene */
+#define AMK_SIM_COG_MAX      16
+typedef struct amk_sim_body_params {
+    double h;            /* sub-step, seconds, > 0 (the caller's con_dt / n_sub) */
+    int    n_sub;        /* sub-steps per call, 1 .. 4096 */
+    double gz;           /* gravity, >= 0 */
+    double k_att;        /* attitude gain, 1/s, >= 0 (bfctrl: 2 / attctrl_tau_) */
+    double rate_max;     /* |body rate command| clamp per axis, rad/s, > 0 (inf allowed) */
+    double k_rate;       /* rate lag per sub-step, in (0, 1]; 1 = the rates follow at once (caller: min(1, h / tau_rate)) */
+    double k_thrust;     /* thrust lag per sub-step, in (0, 1] */
+    double f_min, f_max; /* collective thrust acceleration clamp, f_min <= f_max */
+    double drag[3];      /* body-frame linear rotor drag, 1/s, >= 0 */
+    double yaw_cs, yaw_sn; /* cosine and sine of the COMMANDED yaw, as the caller computed them (flights: 1, 0) */
+    int    cog_window;   /* 0 or 1: no filter; 2 .. AMK_SIM_COG_MAX: the node's COGFilter */
+    double cog_weight[AMK_SIM_COG_MAX]; /* weight of the idx-th newest sample (caller: decay^idx) */
+} amk_sim_body_params;
+int amk_sim_body_reset(double *d_body, int n_scenes, double gz, void *stream);
+int amk_sim_vehicle_step_body(const amk_sim_body_params *prm, const double *d_cmd, double *d_x, double *d_body, double *d_Twb,
+                              int n_scenes, double pose_quantum, void *stream);
+int amk_sim_vehicle_step_body_host(const amk_sim_body_params *prm, const double *h_cmd, double *h_x, double *h_body, double *h_Twb,
+                                   int n_scenes, double pose_quantum);
+
 #ifdef __cplusplus
 }
 #endif
