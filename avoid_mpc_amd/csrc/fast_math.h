@@ -4,16 +4,31 @@
 // its exp is a degree-11 Horner chain behind a two-step reduction.  The solve is one wavefront per scene walking a
 // chain of dependent operations, so the length of these chains -- not the instruction count -- is
 // what an interior-point iteration pays: ten log and six exp latencies per iteration, ~7 of its ~30 us.  The versions
-// here have the SHORTEST dependency chain that still gives ~1 ulp (measured on the device against the host's libm,
-// tests/test_fast_math_gpu.py: max 1.5 ulp / 1.0 ulp):
+// here have the SHORTEST dependency chain that still gives ~1 ulp:
 //   fast_log  m in [sqrt(1/2), sqrt(2)), s = (m-1)/(m+1), the classical odd series in s with the 7-coefficient
 //             minimax fit of the FreeBSD/fdlibm e_log.c lineage (Lg1..Lg7), evaluated as two interleaved Horner
 //             chains in s^4; k ln2 added in hi/lo parts.  ~18 dependent operations.
 //   fast_exp  k = rint(x / ln2), r = x - k ln2 (hi/lo), e^r = 1 + r + r^2 Q(r) with Q the degree-11 Taylor tail
 //             evaluated by Estrin's scheme (depth 4), scaled by 2^k with v_ldexp.  ~11 dependent operations.
-// Domain: fast_log wants a positive, finite, normal argument (every call site passes products of positive slacks or
-// 1 + e^x >= 1); denormals are rescaled, 0 / inf / negative / NaN arguments get the IEEE answers by selects.  fast_exp clamps x to [-745.2, 709.7] (results 0 / inf
-// outside are not needed: the callers' arguments are bounded above by 32 x the drone radius).
+//
+// Contract (every sentence is asserted by tests/test_solve_math_gpu.py on the directed tables of tests/_solve_math_cases.py;
+// errors are TRUE errors, against a 160-bit reference, in ulp of the true value):
+//   fast_exp  any argument.  x is clamped to [-745.2, 709.7] first (results 0 / inf are not needed: the callers' arguments
+//             are bounded above by 32 x the drone radius), so +inf and anything above give fast_exp(709.7) = 1.65e308,
+//             finite; -inf and anything below give fast_exp(-745.2) = 0; and so does NaN, because fmax drops it -- a
+//             collision term with a NaN distance goes dormant, it does not poison the sum.  Bit-identical to the CPU
+//             restatement the tests use (sexp) on the whole table, the denormal results (v_ldexp_f64 rounds them) and
+//             the ties of rint at (k + 1/2) ln 2 included; the restatement's worst error there: 0.957 ulp, and 0.726 of a
+//             denormal quantum on denormal results.
+//   fast_log  any argument; the solver passes positive, finite, normal ones (products of positive slacks, 1 + e^x >= 1).
+//             log(1) = +0.  A denormal is rescaled by 2^54 into the series.  +-0 -> -inf, +inf -> +inf, negative, -inf and
+//             NaN -> NaN, by selects.  Worst error on the MI355X 0.784 ulp at the double below sqrt 2, 0.469 ulp on
+//             denormals; the same bits as the restatement slog (which divides where this multiplies by rcp_f64) on the whole
+//             table -- asserted: within 1 ulp of slog everywhere, the same bits on >= 99.9 %.
+//   rcp_f64   x and 1 / x both normal (2^-1022 <= |x| <= 2^1022).  <= 1 ulp; measured on the MI355X: correctly rounded (<= 1/2
+//             ulp) on all 681 632 table arguments.  Outside that domain (0, inf, a denormal x or a denormal 1 / x) nothing is
+//             promised: no call site goes there.  (The fp32 twin, mpc_device_impl.h fast_rcp: <= 1 ulp asserted on the same
+//             domain; measured on the MI355X: correctly rounded on every float of [1, 2) and at the extreme exponents.)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -228,6 +228,7 @@ def _decl_mpc(lib):
     lib.mpco_p_len.restype = i; lib.mpco_p_len.argtypes = [i, i]
     lib.mpco_rk4_step.argtypes = [_f64p, _f64p, _f64p, d, _f64p]
     lib.mpco_affine.argtypes = [_f64p, d, _f64p, _f64p, _f64p]
+    lib.mpco_fast_math.restype = None; lib.mpco_fast_math.argtypes = [vp, vp, vp, i]   # x, exp out, log out [n] doubles, n
     lib.mpco_nlp_f.restype = d; lib.mpco_nlp_f.argtypes = [_f64p, _f64p, i, i]
     lib.mpco_nlp_grad_f.argtypes = [_f64p, _f64p, i, i, _f64p]
     lib.mpco_nlp_hess_blocks.argtypes = [_f64p, _f64p, i, i, _f64p, _f64p, i]
